@@ -4,6 +4,8 @@
     python bench.py --gpus N --steps K --warmup W          # N > 1: starts its own N rank processes
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W      # or under a launcher (env RANK/WORLD_SIZE)
+    python bench.py --gpus 1 --steps K --warmup W --full   # + the untimed passes and the CPU baseline below
+    python bench.py ... --dump-outputs DIR                 # + the timed region's results as DIR/<name>.npy
 
 One "step" = one pass of the hot path over one batch of B synthetic 1024x2048 frames that are
 already resident in HBM as uint8 HWC (+ uint8 labels):
@@ -19,13 +21,25 @@ owns the contiguous block parallel.shard_range(160, r, N) and keeps it resident 
   * timed region (weak scaling): every rank runs K steps of B frames, cycling through its block; after the
     K steps the int64 counters are SUM-all-reduced over ranks (RCCL) and the mIoUs finished on the host,
     inside the timed region.  value = N*B*K / max-over-ranks time.
+A plain run sets up, warms up, times the K steps and prints the result line; its `miou` is the timed
+region's.  With --full it also runs, after the timed region:
   * parity pass (untimed): every global frame is evaluated exactly ONCE by its owner, counters all-reduced:
     the reported `miou` dict is therefore bit-identical at any N (integer sums are order-independent).
   * per-kernel pass (untimed): a few more steps with HIP event pairs around every C-ABI launch on the
     launching stream -> `roofline` (dominant hand-written kernel) and `kernels`.
   * fp32 pass (N=1): a few steps with every split-operand f16-MFMA kernel replaced by its float32-input
     counterpart -> `fp32_mfma`.
-`cpu_baseline` = the CPU oracle path timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+  * resident-frames pass: the same step without the host -> device ingestion -> `resident_frames`.
+  * `cpu_baseline` = the CPU oracle path timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+(--mode train: --full adds the per-kernel step, the CPU baseline and the replica parameter sums.)
+The explicit per-pass options (--kernel-steps, --fp32-steps, --resident-steps, --no-parity-pass,
+--no-cpu-baseline) still select or drop a single pass.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the timed path handed back to its caller,
+as float64 .npy files (eval: the all-reduced device counters — confusion per slot, ECE bins, disagreement
+histogram — and every scalar of the results dict; train: the losses and a fixed seeded sample of the
+updated parameters).  The inputs are a function of the arguments only, so two builds can be compared
+file for file.
 """
 from __future__ import annotations
 
@@ -435,14 +449,22 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=GLOBAL_FRAMES, help="size of the fixed global sample set")
     ap.add_argument("--no-depth", action="store_true", help="build the ensemble with include_depth=False")
     ap.add_argument("--no-stats", action="store_true", help="leave ECE + disagreement-AUROC accumulation (evaluate.py:230-255) out of the step")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the parity, per-kernel, float32-MFMA and resident-frames passes and the CPU baseline "
+                         "(a plain run times the steps and prints the headline line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned (counters and results of the timed region; train: losses and a seeded "
+                         "parameter sample) to DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--resident", action="store_true",
                     help="time the step on frames that are already resident in HBM (round-2 behaviour) instead of ingesting every batch from "
                          "pinned host memory on a side stream (REF/scripts/evaluate.py:172-173 starts each batch from host memory)")
-    ap.add_argument("--resident-steps", type=int, default=5, help="steps of the resident-frames comparison pass (0: skip)")
-    ap.add_argument("--no-parity-pass", action="store_true", help="skip the untimed pass over the whole global sample set (miou is then the timed region's)")
-    ap.add_argument("--kernel-steps", type=int, default=2, help="steps of the untimed per-kernel HIP-event pass (0: no roofline / kernels)")
-    ap.add_argument("--fp32-steps", type=int, default=3, help="steps of the float32-input-MFMA comparison pass at N=1 (0: skip)")
+    ap.add_argument("--resident-steps", type=int, default=None, help="steps of the resident-frames comparison pass (0: skip; default 5 with --full, else 0)")
+    ap.add_argument("--no-parity-pass", action="store_true", help="skip the untimed pass over the whole global sample set (miou is then the timed region's; "
+                                                                   "implied without --full)")
+    ap.add_argument("--kernel-steps", type=int, default=None, help="steps of the untimed per-kernel HIP-event pass (0: no roofline / kernels; "
+                                                                   "default 2 with --full, else 0)")
+    ap.add_argument("--fp32-steps", type=int, default=None, help="steps of the float32-input-MFMA comparison pass at N=1 (0: skip; default 3 with --full, else 0)")
     ap.add_argument("--fp32-mfma", action="store_true",
                     help="run the MAIN measurement on the float32-input MFMA kernels (own fp32 attention, hipBLASLt fp32, fp32 Winograd) "
                          "instead of the split-operand f16-MFMA ones (DESIGN.md 5b); same as AWSEG_ATTN_SPLIT=0 AWSEG_GEMM_SPLIT=0 AWSEG_WINO_SPLIT=0")
@@ -459,7 +481,26 @@ def parse_args(argv=None):
                     help="rendezvous only (gloo, CPU): every rank reports its block of the global sample set, rank 0 prints the pooled "
                          "frame count — exercises the self-launch / sharding path where there is no GPU (tests/)")
     ap.add_argument("--fail-rank", type=int, default=-1, help=argparse.SUPPRESS)      # tests: this rank exits 3 right after start-up
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    # the passes beside the headline figure run with --full only; an explicit step count still selects one of them
+    for name, full_default in (("resident_steps", 5), ("kernel_steps", 2), ("fp32_steps", 3)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    if not args.full:
+        args.no_parity_pass = args.no_cpu_baseline = True
+    return args
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """name -> array (or scalar): DIR/<name>.npy as float64 (the integer counters of the path stay far below 2**53: exact)."""
+    import numpy
+    arrays = {name: numpy.asarray(a, dtype=numpy.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 * 2 ** 20:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (at most 64 MB)")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        numpy.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def dry_run(args) -> None:
@@ -600,6 +641,15 @@ def train_main(args):
     if parallel.is_dist():
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # the losses train_epoch returned and a fixed seeded sample of the parameters the timed steps left
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1).double() for p in model.parameters()])
+            n_sample = min(flat.numel(), 1 << 22)
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:n_sample].sort().values
+            sample = flat[idx.to(dev)].cpu().numpy()
+            del flat
+        dump_outputs(args.dump_outputs, {**{f"loss_{k}": float(v) for k, v in res.items()}, "parameter_sample": sample})
     # ---- per-kernel pass (untimed): HIP event pairs around every C-ABI launch of ONE more step -> roofline of the dominant
     # hand-written kernel (the convolutions' forward / backward run on MIOpen: profiles/r03_train_step_kernels.csv lists them)
     from adverse_weather_semantic_segmentation_robustness_benchmark_amd import _native
@@ -642,17 +692,19 @@ def train_main(args):
         except Exception as e:  # noqa: BLE001
             cpu = {"value": None, "unit": "images/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e!r}"}
     # every replica must hold the same parameters after the timed steps (data-parallel averaging): the per-rank float64 sums of all
-    # parameters, gathered — rank 0 reports them and whether they are identical (tests/test_gpu_configs.py, RCCL-gated)
-    with torch.no_grad():
-        psum = torch.stack([p.detach().double().sum() for p in model.parameters()]).sum().reshape(1)
-        pabs = torch.stack([p.detach().double().abs().sum() for p in model.parameters()]).sum().reshape(1)
-    mine2 = torch.cat([psum, pabs]).to(dev)
-    if parallel.is_dist():
-        gathered = [torch.zeros_like(mine2) for _ in range(world)]
-        torch.distributed.all_gather(gathered, mine2)
-    else:
-        gathered = [mine2]
-    replica_sums = [[float(v) for v in g.cpu()] for g in gathered]
+    # parameters, gathered — rank 0 reports them and whether they are identical (tests/test_gpu_configs.py, RCCL-gated; --full)
+    replica_sums = None
+    if args.full:
+        with torch.no_grad():
+            psum = torch.stack([p.detach().double().sum() for p in model.parameters()]).sum().reshape(1)
+            pabs = torch.stack([p.detach().double().abs().sum() for p in model.parameters()]).sum().reshape(1)
+        mine2 = torch.cat([psum, pabs]).to(dev)
+        if parallel.is_dist():
+            gathered = [torch.zeros_like(mine2) for _ in range(world)]
+            torch.distributed.all_gather(gathered, mine2)
+        else:
+            gathered = [mine2]
+        replica_sums = [[float(v) for v in g.cpu()] for g in gathered]
     if rank == 0:
         line = {
             "metric": f"images/sec ({H}x{W}, AdverseWeatherTrainer train step: ensemble + FogDensityAwareLoss + depth heads)",
@@ -668,7 +720,8 @@ def train_main(args):
             "roofline": roofline, "cpu_baseline": cpu, "kernels": kernels,
             "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
             "losses": {k: round(float(v), 6) for k, v in res.items()},
-            "replica_parameter_sums": replica_sums, "replicas_identical": all(r == replica_sums[0] for r in replica_sums),
+            "replica_parameter_sums": replica_sums,
+            "replicas_identical": None if replica_sums is None else all(r == replica_sums[0] for r in replica_sums),
         }
         print(json.dumps(line), flush=True)
     if parallel.is_dist():
@@ -831,14 +884,23 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         if parallel.is_dist():
             torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
-        return float(tmax.item()), res
+        return float(tmax.item()), res, st
 
     with torch.no_grad():
         st = new_state()
         for i in range(args.warmup):
             step(st, i)
         finish(st)                                 # warm the host-side finalisation too (first-use costs of the CPU ops)
-        dt, timed_results = timed(args.steps, args.warmup)
+        dt, timed_results, timed_state = timed(args.steps, args.warmup)
+        if args.dump_outputs and rank == 0:
+            # the timed region's all-reduced counters and the results dict finish() computed from them
+            bins = ops.ece_bins_to_numpy(timed_state.ece)
+            out = {"confusion": timed_state.acc.counts.cpu().numpy(),
+                   "ece_bins": np.stack([bins["count"], bins["sum_conf"], bins["sum_correct"]], axis=-1)}
+            if timed_state.auroc is not None:
+                out["disagreement_histogram"] = timed_state.auroc.cpu().numpy()
+            out.update({f"result_{k}": float(v) for k, v in timed_results.items()})
+            dump_outputs(args.dump_outputs, out)
 
         # ---- parity pass: every global frame exactly once, by its owner ------------------------------------------
         results = timed_results
@@ -870,7 +932,7 @@ def main():
             st = new_state()
             for i in range(2):
                 step(st, i)
-            dt32, res32 = timed(args.fp32_steps, 2)
+            dt32, res32, _ = timed(args.fp32_steps, 2)
             ops.restore_split(saved)
             fp32 = {"value": round(B * args.fp32_steps / dt32, 3), "unit": "images/s", "ms_per_step": round(dt32 / args.fp32_steps * 1e3, 3),
                     "steps": args.fp32_steps, "what": "same step with attention / 1x1 GEMMs / Winograd on the float32-input MFMA kernels "
@@ -882,7 +944,7 @@ def main():
             staging_on[0] = False
             st = new_state()
             step(st, 0)
-            dtr, _ = timed(args.resident_steps, 1)
+            dtr, _, _ = timed(args.resident_steps, 1)
             staging_on[0] = True
             resident = {"value": round(B * args.resident_steps * world / dtr, 3), "unit": "images/s", "ms_per_step": round(dtr / args.resident_steps * 1e3, 3),
                         "steps": args.resident_steps, "what": "same step on frames already resident in HBM (no host -> device copy)"}

@@ -379,6 +379,42 @@ def test_bench_self_launches_its_ranks_and_shards_the_global_set():
     assert r.returncode == 3 and b"rank 1 exited" in r.stderr
 
 
+@pytest.fixture(scope="module")
+def bench():
+    """bench.py as a module (it imports numpy / torch only inside main())."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("awseg_bench", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_plain_run_leaves_the_extra_passes_to_full(bench):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the steps only; --full restores every untimed pass and the CPU
+    baseline at their old defaults; an explicit per-pass option still wins either way."""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.steps == 7 and plain.warmup == 2 and not plain.full and plain.dump_outputs is None
+    assert (plain.kernel_steps, plain.fp32_steps, plain.resident_steps) == (0, 0, 0)
+    assert plain.no_parity_pass and plain.no_cpu_baseline
+    full = bench.parse_args(["--full"])
+    assert (full.kernel_steps, full.fp32_steps, full.resident_steps) == (2, 3, 5)
+    assert not full.no_parity_pass and not full.no_cpu_baseline
+    mixed = bench.parse_args(["--full", "--kernel-steps", "0", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert mixed.kernel_steps == 0 and mixed.no_cpu_baseline and not mixed.no_parity_pass and mixed.dump_outputs == "out"
+    assert bench.parse_args(["--kernel-steps", "1"]).kernel_steps == 1
+
+
+def test_bench_dump_outputs_writes_float64_npy_and_refuses_more_than_64_mb(bench, tmp_path):
+    counts = np.arange(12, dtype=np.int64).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "d"), {"confusion": counts, "result_overall_miou": 0.25})
+    got = np.load(tmp_path / "d" / "confusion.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, counts)
+    assert np.load(tmp_path / "d" / "result_overall_miou.npy") == 0.25
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(64 * 2 ** 17 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
 def test_checkpoint_key_translation_between_transformers_spellings():
     """`segformer.segformer.*` keys are transformers-version dependent; a checkpoint in
     the legacy spelling (the releases REF/requirements.txt pins) must load into the live model."""

@@ -123,11 +123,35 @@ def _bench_line(*argv, timeout=1500):
     return json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_repeatable_outputs(native, tmp_path):
+    """A plain bench run (no --full) prints the headline line without the untimed passes; --steps sets the timed steps (the
+    dumped overall confusion counts exactly steps x batch x H x W labelled pixels); two runs with the same arguments dump
+    identical outputs."""
+    import numpy as np
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--frames", "8", "--height", "256", "--width", "512"]
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        lines.append(_bench_line(*argv, "--dump-outputs", str(d), timeout=600))
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "images/s"
+    assert line["value"] == pytest.approx(2 * 1e3 / line["ms_per_step"], rel=1e-2)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["fp32_mfma"] is None and line["kernels"] == []
+    assert line["miou_source"] == "timed region"
+    out = dumps[0]
+    assert {"confusion", "ece_bins", "disagreement_histogram", "result_overall_miou"} <= set(out)
+    assert all(a.dtype == np.float64 for a in out.values())
+    assert out["confusion"][0].sum() == 3 * 2 * 256 * 512
+    assert abs(out["result_overall_miou"] - line["timed_region_overall_miou"]) <= 1e-6          # (the line rounds to 6 places)
+    assert set(dumps[1]) == set(out) and all(np.array_equal(dumps[1][k], out[k]) for k in out), "two identical runs dumped different outputs"
+
+
 def test_c3_two_gpus_over_rccl_reproduce_the_single_gpu_miou(native):
     """BASELINE configs[2] on the smallest multi-GPU lease: two ranks, one device each, counters all-reduced over RCCL."""
     if torch.cuda.device_count() < 2:
         pytest.skip("one-GPU lease: RCCL needs one device per rank (the 2-rank gloo tests cover the sharding logic)")
-    common = ["--steps", "2", "--warmup", "1", "--frames", "20", "--batch", "2", "--no-cpu-baseline", "--fp32-steps", "0", "--kernel-steps", "0"]
+    common = ["--full", "--steps", "2", "--warmup", "1", "--frames", "20", "--batch", "2", "--no-cpu-baseline", "--fp32-steps", "0", "--kernel-steps", "0"]
     one = _bench_line("--gpus", "1", *common)
     two = _bench_line("--gpus", "2", *common)
     print("N=1:", one["value"], one["miou"]); print("N=2:", two["value"], two["miou"])
@@ -138,7 +162,7 @@ def test_c3_two_gpus_over_rccl_reproduce_the_single_gpu_miou(native):
 def test_c4_two_ranks_on_one_gpu_over_gloo_keep_the_replicas_identical(native):
     """The same check on a one-GPU lease: two ranks share the device, gradients averaged over gloo (bench.py falls back to it when
     there are more ranks than devices) — the trainer's bucketed all-reduce path end to end, minus RCCL itself."""
-    two = _bench_line("--gpus", "2", "--mode", "train", "--steps", "1", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "256",
+    two = _bench_line("--gpus", "2", "--full", "--mode", "train", "--steps", "1", "--warmup", "1", "--batch", "2", "--height", "128", "--width", "256",
                       "--no-cpu-baseline", "--kernel-steps", "0")
     print("N=2 train (gloo, one GPU):", two["value"], two["losses"], two["replica_parameter_sums"])
     assert two["n_gpus"] == 2 and two["config"]["dist_backend"] == "gloo" and two["rccl_ranks"] == 0
@@ -152,7 +176,7 @@ def test_c4_two_gpus_over_rccl_keep_the_replicas_identical(native):
     tests/test_abi_and_host.py::test_two_rank_gloo_counter_allreduce_matches_single_process)."""
     if torch.cuda.device_count() < 2:
         pytest.skip("one-GPU lease: RCCL needs one device per rank (the 2-rank gloo test covers the gradient buckets)")
-    two = _bench_line("--gpus", "2", "--mode", "train", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "256", "--width", "512",
+    two = _bench_line("--gpus", "2", "--full", "--mode", "train", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "256", "--width", "512",
                       "--no-cpu-baseline", "--kernel-steps", "0")
     print("N=2 train:", two["value"], two["losses"], two["replica_parameter_sums"])
     assert two["n_gpus"] == 2 and two["rccl_ranks"] == 2 and two["config"]["dist_backend"] == "nccl"
