@@ -109,7 +109,7 @@ SIGNATURES = {
     "awseg_bn_relu_dropout_backward": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p]),
     "awseg_dwconv3x3_wgrad_workspace": (c_i64, [c_i64, c_i, c_i, c_i]),
     "awseg_dwconv3x3_wgrad_nhwc": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
-    "awseg_mixffn_fused": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "awseg_mixffn_fused": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
     "awseg_maxpool3x3s2_nhwc": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_p, c_p]),
     "awseg_maxpool3x3s2_bias_relu_nhwc": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_p, c_p, c_p]),
     "awseg_upsample_bilinear": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),

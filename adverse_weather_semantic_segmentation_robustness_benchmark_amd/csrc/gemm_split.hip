@@ -28,6 +28,9 @@
 //     observed maximum: exact, power of two), multiplying 2^e back in the epilogue.  LayerNorm / BatchNorm-scaled
 //     activations never take the second pass; a tensor at 1e5 or 1e30 costs twice the time and is still float32-grade
 //     (tests/test_gpu_kernels.py::test_gemm_split_large_operands).  Inf / NaN propagate as in a float32 GEMM.
+//     The guard has a SMALL side too: a tile whose max|x| < 2^-7 (low parts f16 subnormals, the high parts too below 2^-14)
+//     takes the same scaled second pass (tests/test_gpu_split_magnitudes.py).  It is per tile, not per row: a row at 2^-12
+//     in a tile with O(1) rows keeps the optimistic split, accurate relative to the tile's largest products.
 #include "awseg_common.h"
 
 namespace {
@@ -122,6 +125,7 @@ struct gemm_args {
 };
 
 constexpr float kSplitLimit = 32768.0f;                          // |x| below this splits without loss (hi < 65504, lo * 2048 < 65504)
+constexpr float kSmallLimit = 0.0078125f;                        // a tile whose max|x| is below 2^-7 is redone scaled (small-side guard)
 
 __device__ __forceinline__ constexpr int acc_row(int r, int hk) { return (r & 3) + 8 * (r >> 2) + 4 * hk; }
 
@@ -160,7 +164,8 @@ void gemm_split_kernel(gemm_args a)
     constexpr int NB = BN / 64;                                  // 16-byte chunks of w per thread per K tile (hi and lo)
     __shared__ __attribute__((aligned(16))) _Float16 sA[2][BM * GROW];
     __shared__ __attribute__((aligned(16))) _Float16 sB[2][BN * GROW];
-    __shared__ unsigned sMax[2];                                 // max|x| bits seen by the block in a pass (if >= 2^15), by pass parity
+    __shared__ unsigned sMax[4];                                 // by pass parity: [par] max|x| bits reported in a pass, [2 + par] "some wave
+                                                                 // met |x| >= the small-side bound" (see the range guard)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hk = lane >> 5, li = lane & 31;
     const int wm = wave / WN, wn = wave % WN;                    // WM x WN waves, each (32 MT) rows x (32 NT) columns
@@ -283,7 +288,7 @@ void gemm_split_kernel(gemm_args a)
     if (slot >= ntiles) return;                                  // block-uniform, before any barrier
     point(m0, n0);
     fetch(0);
-    if (tid < 2) sMax[tid] = 0u;                                 // ordered before its first use by the barrier behind stage(0)
+    if (tid < 4) sMax[tid] = 0u;                                 // ordered before its first use by the barrier behind stage(0)
     int par = 0;                                                 // pass parity: which sMax word this pass reports into
     const int we = (int)a.trailer[1];                            // weights were stored as w * 2^-we
 
@@ -331,8 +336,15 @@ void gemm_split_kernel(gemm_args a)
             // range guard bookkeeping (two block-uniform branches per K tile).  First K tile: clear the OTHER parity's word
             // — its readers (previous pass) are behind this pass's first barrier, its writers (next pass) behind this
             // pass's last one.  Last K tile: everything this thread will stage in this pass has been staged; report.
-            if (t == 0 && tid == 0) sMax[par ^ 1] = 0u;
-            if (!BF16 && t == nkt - 1 && !scaled && amax >= kSplitLimit) atomicMax(&sMax[par], __builtin_bit_cast(unsigned, amax));
+            if (t == 0 && tid == 0) { sMax[par ^ 1] = 0u; sMax[2 + (par ^ 1)] = 0u; }
+            // Large side: a lane that met |x| >= 2^15 reports its maximum.  Small side: a wave with some lane at or above 2^-7 marks the
+            // tile "not small" (one lane, a plain LDS write); a wave all of whose lanes stayed below reports its lanes' maxima, so a block
+            // none of whose waves marked the tile knows its maximum.  O(1) tiles: one compare and one LDS write per wave, no atomics.
+            if (!BF16 && t == nkt - 1 && !scaled) {
+                const bool not_small = __ballot(amax >= kSmallLimit * kSx0) != 0ull;
+                if (amax >= kSplitLimit || !not_small) atomicMax(&sMax[par], __builtin_bit_cast(unsigned, amax));
+                if (not_small && lane == 0) sMax[2 + par] = 1u;
+            }
             if (t + 1 < nkt) {
                 if (t + 2 < nkt) fetch((t + 2) * GKT);
                 else if (has_next) { point(nm0, nn0); fetch(0); }
@@ -390,15 +402,19 @@ void gemm_split_kernel(gemm_args a)
         }
 #endif
 
-        // ---- range guard: some activation of this tile was too large for the optimistic split -> second pass, scaled
+        // ---- range guard: the activations of this tile were too large (|x| >= 2^15) or all too small (max|x| < 2^-7) for the
+        // optimistic split -> second pass, scaled
         {
             const unsigned mx = BF16 ? 0u : sMax[par];           // written before the K loop's last barrier; block-uniform
+            const bool small = !BF16 && sMax[2 + par] == 0u;
             par ^= 1;
-            if (mx != 0u && !scaled) {
+            constexpr unsigned kBig = __builtin_bit_cast(unsigned, kSplitLimit), kSmall = __builtin_bit_cast(unsigned, kSmallLimit * kSx0);
+            if (!scaled && (mx >= kBig || (small && mx >= 0x00800000u && mx < kSmall))) {    // (a subnormal or zero maximum stays as it is)
                 const int ex = (int)(mx >> 23) & 0xff;
                 if (ex != 0xff) {                                // Inf / NaN: nothing to rescue, let them propagate
                     xe = ex - 127 - 13 + kXe0;                   // max|x| * 2^-xe in [2^13, 2^14) (the maximum was taken after the x 2^-kXe0 staging scale)
-                    sx = pow2f(-xe);                             // xe in [2, 114]: one factor is enough
+                    xe = xe < -127 ? -127 : xe;                  // xe in [-127, 114]: one factor is enough
+                    sx = pow2f(-xe);
                     scaled = true;
                     point(m0, n0);                               // the registers hold the NEXT tile's first K tile: fetch this one again
                     fetch(0);

@@ -22,7 +22,8 @@
 //     before; raw-buffer accesses, rows past M dropped by the hardware range check) — a quarter of the store instructions;
 //   * persistent blocks, XCD-aware tile walk, the next tile's first K tile in flight during the epilogue (as before).
 // Operand range: as gemm_split.hip — weights normalised when they are split, activations split optimistically (x 2^4) while
-// the block tracks max|x|; a tile that met |x| >= 2^11 is recomputed with x 2^-e and rescaled in the epilogue.
+// the block tracks max|x|; a tile that met |x| >= 2^11, or whose max|x| < 2^-7 (low parts f16 subnormals: the small side), is
+// recomputed with x 2^-e and rescaled in the epilogue.  Per tile, not per row.
 #include "awseg_common.h"
 
 namespace {
@@ -33,11 +34,12 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int G3M_MAX = 256, G3K = 32;     // the tile has 32 WV rows (WV = 8 or 4 waves); one operand's stage: rows x 128 B
-// two stages of two operands + sMax[2]; the four-wave blocks pack the weight stages (64-column tiles: 48 KB a block, THREE blocks per CU)
+// two stages of two operands + sMax[4]; the four-wave blocks pack the weight stages (64-column tiles: 48 KB a block, THREE blocks per CU)
 constexpr int g3_lds(int wv, int nt) { return 2 * (32 * wv * 128) + 2 * (wv == 8 ? 32 * wv * 128 : 32 * nt * 128) + 64; }
 constexpr float kActScale0 = 16.0f;        // optimistic-pass activation scale (gemm_split.hip: split_pair_unscaled)
 constexpr int kActExp0 = -4;
 constexpr float kSplitLimit3 = 2048.0f;
+constexpr float kSmallLimit3 = 0.0078125f;  // a tile whose max|x| is below 2^-7 is redone scaled (small-side guard)
 #ifndef G3_TRANSPOSED
 #define G3_TRANSPOSED 0                    // 1: weights as the MFMA's row operand, lane = output row, 16-byte epilogue accesses (measured slower)
 #endif    // |x| below this splits without loss at scale 2^4 (|x s| < 2^15)
@@ -266,7 +268,7 @@ void gemm_split3_kernel(g3_args a)
     int64_t m0 = 0; int n0 = 0;
     while (slot < ntiles && !tile_of(slot, m0, n0)) slot += gridDim.x;
     if (slot >= ntiles) return;
-    if (tid < 2) sMax[tid] = 0u;
+    if (tid < 4) sMax[tid] = 0u;                                  // [par]: max|x| bits reported, [2 + par]: tile not small (range guard)
     int par = 0;
     const int we = (int)a.trailer[1];
     float amax = 0.f, sx = kActScale0;
@@ -316,7 +318,7 @@ void gemm_split3_kernel(g3_args a)
             G3_T(s1);
             if (t + 1 < nkt && ABL != 1 && !issue_late) issue(ktile(t + 1), st ^ 1);
             G3_T(s2);
-            if (t == 0 && tid == 0) sMax[par ^ 1] = 0u;
+            if (t == 0 && tid == 0) { sMax[par ^ 1] = 0u; sMax[2 + (par ^ 1)] = 0u; }
             const unsigned char* sa = smem + st * G3_STAGE;
             const unsigned char* sbw = smem + st * G3_BSTAGE;         // weight fragments (fb carries G3_B0)
 #pragma unroll
@@ -385,16 +387,25 @@ void gemm_split3_kernel(g3_args a)
         }
 
         // ---- range guard (gemm_split.hip): the block's max|x| of this pass, through LDS
-        if (!BF16 && !scaled && amax >= kSplitLimit3) atomicMax(&sMax[par], __builtin_bit_cast(unsigned, amax));
+        // (large side: lanes at |x| >= 2^11 report their maximum; small side as in gemm_split.hip: a wave with a lane at or above 2^-7
+        // marks the tile "not small", a wave entirely below reports its lanes' maxima — no atomics on O(1) tiles)
+        if (!BF16 && !scaled) {
+            const bool not_small = __ballot(amax >= kSmallLimit3) != 0ull;
+            if (amax >= kSplitLimit3 || !not_small) atomicMax(&sMax[par], __builtin_bit_cast(unsigned, amax));
+            if (not_small && (tid & 63) == 0) sMax[2 + par] = 1u;
+        }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();                              // also: every wave is done with the last K tile's stage
         const unsigned mx = sMax[par];
+        const bool small = !BF16 && sMax[2 + par] == 0u;
         par ^= 1;
         bool again = false;
-        if (mx != 0u && !scaled) {
+        constexpr unsigned kBig = __builtin_bit_cast(unsigned, kSplitLimit3), kSmall = __builtin_bit_cast(unsigned, kSmallLimit3);
+        if (!scaled && (mx >= kBig || (small && mx >= 0x00800000u && mx < kSmall))) {     // (a subnormal or zero maximum stays as it is)
             const int ex = (int)(mx >> 23) & 0xff;
             if (ex != 0xff) {                                      // Inf / NaN: nothing to rescue, let them propagate
                 xe = ex - 127 - 13;                                // max|x| * 2^-xe in [2^13, 2^14)
+                xe = xe < -127 ? -127 : xe;
                 sx = pow2f3(-xe);
                 scaled = true; again = true;
             }

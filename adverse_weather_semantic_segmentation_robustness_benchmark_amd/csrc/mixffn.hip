@@ -8,7 +8,10 @@
 // 2w, 2w + 1 of the tile as two 32-token column groups.  The two GEMMs run on v_mfma_f32_32x32x16_f16 with SPLIT float32 operands
 // (x = f16(x) + f16(x - f16(x)), three f16 products per float32-grade product, float32 accumulation: gemm_split.hip / DESIGN.md 5b)
 // — the float32-input MFMA (first version) spent 64 cycles per 32 x 32 x 2 product tile and bound the kernel: 1.6 ms for the four
-// launches of a step against 0.7 ms of vector work.  Weights arrive split ([hi | lo] f16 images from the host); LayerNorm outputs
+// launches of a step against 0.7 ms of vector work.  Weights arrive split and NORMALISED ([hi | lo] f16 images of w 2^-e, max|w 2^-e|
+// in [2^13, 2^14), e passed as an argument: the unscaled low parts of trained weights at std 0.01 .. 0.05 would otherwise be f16
+// subnormals, 2^-25 absolute instead of 2^-22 relative); 2^e is multiplied back in the fma that adds fc1's bias and in fc2's
+// epilogue (no extra instruction).  LayerNorm outputs
 // are bounded by |gamma| sqrt(C) + |beta| (the host checks it against the f16 range); the GELU outputs of a chunk are checked on the
 // device, and a chunk that meets |g| >= 2^15 runs its fc2 products on v_mfma_f32_32x32x2_f32 instead (float32 in: no range limit).
 // Lane = (token column, K half):
@@ -70,6 +73,7 @@ struct mf_args {
     const float* tok; const float* gamma; const float* beta; float eps;
     const _Float16* w1s; const float* b1; const float* w9; const float* bdw; const _Float16* w2s; const float* w2; const float* b2;
     float* out; int H, W, nbx, nby;
+    float s1, s2, s2inv;                     // 2^e1, 2^e2, 2^-e2: the weight images hold w1 2^-e1, w2 2^-e2
 };
 
 template <int C>
@@ -172,7 +176,8 @@ void mixffn_kernel(mf_args a)
 #pragma unroll
                 for (int g4 = 0; g4 < 4; ++g4) {
                     const float4 bb = *reinterpret_cast<const float4*>(a.b1 + hc * 32 + 8 * g4 + 4 * kh);
-                    float4 v = make_float4(acc[4 * g4] + bb.x, acc[4 * g4 + 1] + bb.y, acc[4 * g4 + 2] + bb.z, acc[4 * g4 + 3] + bb.w);
+                    float4 v = make_float4(fmaf(acc[4 * g4], a.s1, bb.x), fmaf(acc[4 * g4 + 1], a.s1, bb.y),
+                                           fmaf(acc[4 * g4 + 2], a.s1, bb.z), fmaf(acc[4 * g4 + 3], a.s1, bb.w));
                     if (!inimg[m]) v = make_float4(0.f, 0.f, 0.f, 0.f);          // the depthwise convolution's zero padding
                     *reinterpret_cast<float4*>(dst + 8 * g4) = v;
                 }
@@ -245,7 +250,8 @@ void mixffn_kernel(mf_args a)
                 }
             }
         } else {
-            // float32-input MFMA on the same operands (block-uniform branch): k = 0 <-> hidden channel 16 st + e, k = 1 <-> 16 st + 8 + e
+            // float32-input MFMA on the same operands (block-uniform branch): k = 0 <-> hidden channel 16 st + e, k = 1 <-> 16 st + 8 + e;
+            // the weights scaled as the split image's (exact: |w2| < 2^15, so e2 <= 1), so both paths add into the same accumulators
 #pragma unroll 1
             for (int st = 0; st < 2; ++st)
 #pragma unroll 1
@@ -256,7 +262,7 @@ void mixffn_kernel(mf_args a)
                         const float gv = s_g[((2 * wave + m) * MF_TW + col) * MF_HS + 16 * st + 8 * kh + e];
 #pragma unroll
                         for (int n = 0; n < NN; ++n)
-                            acc2[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w2[(int64_t)(n * 32 + col) * HD + hd], gv, acc2[m][n], 0, 0, 0);
+                            acc2[m][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w2[(int64_t)(n * 32 + col) * HD + hd] * a.s2inv, gv, acc2[m][n], 0, 0, 0);
                     }
                 }
         }
@@ -279,8 +285,8 @@ void mixffn_kernel(mf_args a)
                 const float4 bb = *reinterpret_cast<const float4*>(a.b2 + ch);
                 const float4 rs = *reinterpret_cast<const float4*>(tokb + base + ch);
                 float4 v;
-                v.x = (acc2[m][n][4 * g4] + bb.x) + rs.x; v.y = (acc2[m][n][4 * g4 + 1] + bb.y) + rs.y;
-                v.z = (acc2[m][n][4 * g4 + 2] + bb.z) + rs.z; v.w = (acc2[m][n][4 * g4 + 3] + bb.w) + rs.w;
+                v.x = fmaf(acc2[m][n][4 * g4], a.s2, bb.x) + rs.x; v.y = fmaf(acc2[m][n][4 * g4 + 1], a.s2, bb.y) + rs.y;
+                v.z = fmaf(acc2[m][n][4 * g4 + 2], a.s2, bb.z) + rs.z; v.w = fmaf(acc2[m][n][4 * g4 + 3], a.s2, bb.w) + rs.w;
                 *reinterpret_cast<float4*>(outb + base + ch) = v;
             }
     }
@@ -289,14 +295,15 @@ void mixffn_kernel(mf_args a)
 }  // namespace
 
 AWSEG_API int awseg_mixffn_fused(const float* tok, int batch, int height, int width, int channels, const float* ln_gamma, const float* ln_beta,
-                                 float ln_eps, const uint16_t* w1_split, const float* b1, const float* dw_taps, const float* dw_bias,
-                                 const uint16_t* w2_split, const float* w2, const float* b2, float* out, awseg_stream_t stream)
+                                 float ln_eps, const uint16_t* w1_split, int w1_exp, const float* b1, const float* dw_taps, const float* dw_bias,
+                                 const uint16_t* w2_split, int w2_exp, const float* w2, const float* b2, float* out, awseg_stream_t stream)
 {
     if (batch == 0) return 0;
     const void* w1 = w1_split;
     if (!tok || !ln_gamma || !ln_beta || !w1_split || !b1 || !dw_taps || !dw_bias || !w2_split || !w2 || !b2 || !out || batch < 0 || height < 1 || width < 1) return AWSEG_EINVAL;
     if (channels != 32 && channels != 64) return AWSEG_ERANGE;       // the two token widths whose hidden maps are worth the trouble (MiT-B0 stages 1, 2)
     if (out == tok) return AWSEG_EINVAL;                             // blocks read their neighbours' tokens: not in place
+    if (w1_exp < -126 || w1_exp > 1 || w2_exp < -126 || w2_exp > 1) return AWSEG_ERANGE;   // 2^e a normal float; |w| < 2^15
     const uintptr_t al = (uintptr_t)tok | (uintptr_t)ln_gamma | (uintptr_t)ln_beta | (uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)dw_taps |
                          (uintptr_t)dw_bias | (uintptr_t)w2 | (uintptr_t)w2_split | (uintptr_t)b2 | (uintptr_t)out;
     if (al & 15) return AWSEG_EALIGN;
@@ -304,6 +311,7 @@ AWSEG_API int awseg_mixffn_fused(const float* tok, int batch, int height, int wi
     a.tok = tok; a.gamma = ln_gamma; a.beta = ln_beta; a.eps = ln_eps; a.w1s = reinterpret_cast<const _Float16*>(w1_split); a.b1 = b1;
     a.w9 = dw_taps; a.bdw = dw_bias; a.w2s = reinterpret_cast<const _Float16*>(w2_split); a.w2 = w2; a.b2 = b2;
     a.out = out; a.H = height; a.W = width;
+    a.s1 = ldexpf(1.0f, w1_exp); a.s2 = ldexpf(1.0f, w2_exp); a.s2inv = ldexpf(1.0f, -w2_exp);
     a.nbx = (width + MF_IW - 1) / MF_IW; a.nby = (height + MF_IH - 1) / MF_IH;
     const int64_t blocks = (int64_t)batch * a.nbx * a.nby;
     if (blocks >= ((int64_t)1 << 31)) return AWSEG_ERANGE;

@@ -6,6 +6,7 @@ current torch stream, never synchronise, and raise if handed CPU tensors.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import ctypes as C
@@ -745,9 +746,18 @@ MIXFFN_FUSED = os.environ.get("AWSEG_MIXFFN_FUSED", "1") != "0"  # MiT Mix-FFN (
 
 
 def mixffn_split_weights(w: torch.Tensor) -> torch.Tensor:
-    """float32 [N,K] -> float16 [2,N,K]: f16(w) and f16(w - f16(w)) — the operand images awseg_mixffn_fused multiplies."""
-    hi = w.to(torch.float16)
-    return torch.stack([hi, (w - hi.float()).to(torch.float16)]).contiguous()
+    """float32 [N,K] -> float16 [2,N,K]: f16(v) and f16(v - f16(v)) of v = w 2^-e, e = floor(log2 max|w|) - 13 (clamped to
+    [-126, 1]), so the low parts of small weights are not f16 subnormals — the operand images awseg_mixffn_fused multiplies.
+    e rides on the tensor as `_awseg_exp` (awseg_mixffn_fused takes it as an argument); one host synchronisation (callers cache
+    the images per parameter version)."""
+    w = w.contiguous().float()
+    m = float(w.abs().max().item())
+    e = 0 if (m == 0.0 or not math.isfinite(m)) else min(1, max(-126, math.frexp(m)[1] - 14))
+    v = torch.ldexp(w, torch.tensor(float(-e), device=w.device))
+    hi = v.to(torch.float16)
+    img = torch.stack([hi, (v - hi.float()).to(torch.float16)]).contiguous()
+    img._awseg_exp = e
+    return img
 
 
 def mixffn_fused(tok: torch.Tensor, gamma, beta, eps: float, w1, b1, dw_taps, dw_bias, w2, b2, w1_split=None, w2_split=None,
@@ -765,9 +775,12 @@ def mixffn_fused(tok: torch.Tensor, gamma, beta, eps: float, w1, b1, dw_taps, dw
     out = torch.empty_like(tok)
     w1s = w1_split if w1_split is not None else mixffn_split_weights(w1)
     w2s = w2_split if w2_split is not None else mixffn_split_weights(w2)
+    e1, e2 = getattr(w1s, "_awseg_exp", None), getattr(w2s, "_awseg_exp", None)
+    if e1 is None or e2 is None:
+        raise N.AwsegError("mixffn weight images without their exponent: pass what mixffn_split_weights returned, not a copy")
     rc = N.try_call("awseg_mixffn_fused", N.ptr(tok), b, h, w, c, N.ptr(gamma.contiguous()), N.ptr(beta.contiguous()), float(eps),
-                    N.ptr(w1s), N.ptr(b1.contiguous()), N.ptr(dw_taps.contiguous()), N.ptr(dw_bias.contiguous()),
-                    N.ptr(w2s), N.ptr(w2.contiguous()), N.ptr(b2.contiguous()), N.ptr(out), N.stream())
+                    N.ptr(w1s), int(e1), N.ptr(b1.contiguous()), N.ptr(dw_taps.contiguous()), N.ptr(dw_bias.contiguous()),
+                    N.ptr(w2s), int(e2), N.ptr(w2.contiguous()), N.ptr(b2.contiguous()), N.ptr(out), N.stream())
     return out if rc == 0 else None
 
 

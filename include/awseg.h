@@ -402,8 +402,10 @@ int awseg_segformer_head_fused(const float* g9, int64_t batch, int cmid, int h, 
 
 /* The same head on v_mfma_f32_32x32x16_f16 with split operands (x = hi + lo in f16, three products per
  * float32-grade product, float32 accumulation): both contractions run at the f16 rate.  Rows in
- * which an operand reaches 2^15 are recomputed inside the kernel on the float32 instruction, so the result
- * is float32-grade for any finite input.  Same arguments; scale must be NULL (folded into g9), Cmid 128 or
+ * which an operand reaches 2^15 are recomputed inside the kernel on the float32 instruction.  Operand range: float32-grade
+ * for O(1) features and default-init weights; NOT at small magnitudes — W2, the tables and the hidden activations are split
+ * with unscaled low parts and there is no small-side guard, so features at 2^-6 or weights at std 0.01 / 2^-10 lose bits
+ * (up to ~800 x 2^-22 componentwise: tests/test_gpu_split_magnitudes.py; open).  Same arguments; scale must be NULL (folded into g9), Cmid 128 or
  * 256; AWSEG_ERANGE for a geometry or width the kernel does not cover (the caller then uses the entry above).
  * Replaces the same reference lines (PKG/models/model.py:209-214). */
 int awseg_segformer_head_fused_split(const float* g9, int64_t batch, int cmid, int h, int w,
@@ -506,7 +508,10 @@ int awseg_gemm_tune(const float* x, const float* w, const float* bias, int has_r
  * alias out), act 0 none / 1 ReLU, out float32 [M][N].  K % 8 == 0; x and w_split 16-byte aligned.  Operand range: any
  * finite float32.  Activations are split optimistically; a block that meets |x| >= 2^15 (2^11 in the single-accumulator
  * kernels) in its A tiles recomputes that output tile with x * 2^-e (exact) and multiplies 2^e back in the epilogue — twice
- * the time for that tile, same accuracy.  Inf / NaN propagate.  No workspace, no host state. */
+ * the time for that tile, same accuracy.  The same second pass runs for a block whose A tiles' max|x| < 2^-7 (small side: the
+ * low parts would be f16 subnormals); the decision is per output tile, not per row, so a row at 2^-12 in a tile with O(1) rows
+ * is accurate relative to the tile's largest products.  The two-source, piecewise, gathered-convolution and stem-rows entry
+ * points below share this guard.  Inf / NaN propagate.  No workspace, no host state. */
 int64_t awseg_gemm_split_weight_halfs(int n, int k);
 int awseg_gemm_split_weights(const float* w, int n, int k, uint16_t* w_split, awseg_stream_t stream);
 int awseg_gemm_split_bias_act(const float* x, const uint16_t* w_split, const float* bias, const float* residual, int act,
@@ -721,13 +726,15 @@ int awseg_dwconv3x3_wgrad_nhwc(const float* x, const float* dy, int64_t batch, i
  * as ONE tile kernel: out[b,y,x,:] = tok + w2 . gelu(dwconv(w1 . layernorm(tok) + b1) + dw_bias) + b2 on float32 NHWC tokens
  * [batch, height, width, channels]; the 4x-wide hidden map stays in LDS.  The two GEMMs run on the f16 matrix cores with SPLIT
  * float32 operands (three f16 products per float32-grade product, float32 accumulation): w1_split uint16 [2][4C][C], w2_split
- * uint16 [2][C][4C] = f16 bit patterns of f16(w) and of f16(w - f16(w)) (nn.Linear layouts [out][in]); w2 float32 [C][4C] as well
+ * uint16 [2][C][4C] = f16 bit patterns of f16(v) and of f16(v - f16(v)) for v = w 2^-e (nn.Linear layouts [out][in]), e = w1_exp /
+ * w2_exp = floor(log2 max|w|) - 13 clamped to [-126, 1] (AWSEG_ERANGE outside): the kernel multiplies 2^e back, so small weights
+ * keep 22 significant bits.  The LayerNorm / GELU operands have no small-side guard; w2 float32 [C][4C] as well
  * (a chunk whose GELU outputs reach 2^15 runs its fc2 products on the float32-input MFMA).  The caller guarantees |w| < 2^15 and
  * max|ln_gamma| sqrt(C) + max|ln_beta| < 2^15 (the LayerNorm outputs' bound); dw_taps [9][4C] tap-major (ky * 3 + kx); all
  * vectors 16-byte aligned.  channels 32 or 64 (AWSEG_ERANGE otherwise: the caller keeps its four launches); out must not alias tok. */
 int awseg_mixffn_fused(const float* tok, int batch, int height, int width, int channels, const float* ln_gamma, const float* ln_beta,
-                       float ln_eps, const uint16_t* w1_split, const float* b1, const float* dw_taps, const float* dw_bias,
-                       const uint16_t* w2_split, const float* w2, const float* b2, float* out, awseg_stream_t stream);
+                       float ln_eps, const uint16_t* w1_split, int w1_exp, const float* b1, const float* dw_taps, const float* dw_bias,
+                       const uint16_t* w2_split, int w2_exp, const float* w2, const float* b2, float* out, awseg_stream_t stream);
 
 /* nn.MaxPool2d(kernel 3, stride 2, padding 1) on a float32 NHWC tensor [batch, height, width, channels] (channels % 4 == 0)
  * -> [batch, (height - 1) / 2 + 1, (width - 1) / 2 + 1, channels]; padding does not take part in the maximum.  The ResNet stem
