@@ -612,7 +612,14 @@ int awseg_conv_rows_gemm_split_bias_act(const float* x, int64_t batch, int heigh
  * arguments, layouts, epilogues and error codes as the split-operand entry points they mirror; bfloat16 has float32's
  * exponent range, so there is no operand-range guard.  The reference has no counterpart (it cannot select these
  * backbones or a reduced precision: PKG/models/model.py:409-417); tolerance against the float32 path is stated in
- * tests/test_gpu_bf16.py.
+ * tests/test_gpu_bf16.py.  Asserted per kernel instance (tests/test_gpu_bf16_arith.py, models in tests/bf16_ref.py): the
+ * result equals a float64 model that rounds exactly where the kernel rounds (operands RNE to bf16; Winograd V after the
+ * float32 row-then-column transform; attention q after the float32 scale * log2e product, p relative to the running tile
+ * maximum, l over the unrounded p) within the float32-grade twin's own error, over activations 2^-40 .. 2^40.  GEMM and
+ * Winograd are also held to the unrounded float64 result within (2^-7 + 2^-16) sum |a||b| componentwise; attention has no
+ * such precision gate.  Where the kernel computes an operand in float32 that the model takes in float64 (attention's
+ * probabilities, the fused depth head's generated hidden map) a tie window T is allowed; it is as wide as bf16's rounding
+ * for the fused depth head and for attention logits near 10^3, so there only gross faults are seen.
  *   awseg_gemm_bf16_weights / awseg_gemm_bf16_bias_act  <->  awseg_gemm_split_weights / awseg_gemm_split_bias_act
  *       (w_bf16: uint16 [2][N][K] + 8 like w_split; plane 0 holds bf16(w), plane 1 is unused, trailer exponent 0)
  *   awseg_conv3x3_winograd_bf16_nhwc                    <->  awseg_conv3x3_winograd_split_nhwc
