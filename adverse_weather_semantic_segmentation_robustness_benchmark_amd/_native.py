@@ -121,6 +121,9 @@ SIGNATURES = {
     "awseg_combine_confusion_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_i,
                                            c_p, c_i, c_p, c_i, c_f, c_f, c_p, c_p]),
     "awseg_ece_accumulate": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
+    "awseg_temperature_grid_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
+    "awseg_ensemble_temperature_grid_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i,
+                                                   c_p, c_i, c_p]),
 }
 
 

@@ -55,6 +55,25 @@ template <int DT> __device__ __forceinline__ int64_t awseg_ld_label(const void* 
     return ((const int64_t*)p)[i];
 }
 
+// ECE confidence sums in FIXED POINT, units of 2^-30 (metrics.hip, calib.hip): a float32 confidence in [2^-7, 1] is a multiple
+// of 2^-30, so conf * 2^30 is an exact integer and integer sums do not depend on the order of the atomics.
+__device__ __forceinline__ unsigned long long awseg_conf_q30(float conf) { return (unsigned long long)(conf * 1073741824.0f); }
+
+// Bin of a confidence on the reference's float32 linspace, bins (lo, hi] (metrics.py:179-188): the uniform-grid guess is
+// checked against the staged edges with the reference's own comparisons and moved by one where rounding put it next door;
+// anything else (edges that are not a uniform grid) falls back to the linear scan.  -1 = in no bin.
+__device__ __forceinline__ int awseg_ece_find_bin(float conf, const float* s_edges, int n_bins)
+{
+    int b = (int)ceilf(conf * (float)n_bins) - 1;
+    b = b < 0 ? 0 : (b > n_bins - 1 ? n_bins - 1 : b);
+    if (!(conf > s_edges[b])) b = b > 0 ? b - 1 : 0;
+    else if (!(conf <= s_edges[b + 1])) b = b < n_bins - 1 ? b + 1 : b;
+    if (conf > s_edges[b] && conf <= s_edges[b + 1]) return b;
+    for (int k = 0; k < n_bins; ++k)
+        if (conf > s_edges[k] && conf <= s_edges[k + 1]) return k;
+    return -1;
+}
+
 // Philox4x32-7 counter-based generator (Salmon et al., Random123: 7 rounds pass BigCrush) for the
 // throughput-mode noise; parity mode takes host draws instead.  One call = four uint32.
 struct awseg_philox {

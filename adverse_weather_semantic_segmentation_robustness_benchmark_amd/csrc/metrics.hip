@@ -265,23 +265,10 @@ void confusion_kernel(const void* __restrict__ pred, const void* __restrict__ la
 // GPU count).  2^33 pixels fit.  Block partials: [nblk][n_bins] x {uint32 cnt, uint32 correct, uint64 sum_conf_q30}.
 // ---------------------------------------------------------------------------------------
 struct ece_cell { uint32_t cnt; uint32_t correct; unsigned long long sum_conf; };
-constexpr float kConfQ = 1073741824.0f;                          // 2^30
-__device__ __forceinline__ unsigned long long conf_q30(float conf) { return (unsigned long long)(conf * kConfQ); }
-
-// Bin of a confidence on the reference's float32 linspace, bins (lo, hi] (metrics.py:179-188): the uniform-grid guess is
-// checked against the staged edges with the reference's own comparisons and moved by one where rounding put it next door;
-// anything else (edges that are not a uniform grid) falls back to the linear scan.  -1 = in no bin.
-__device__ __forceinline__ int ece_find_bin(float conf, const float* s_edges, int n_bins)
-{
-    int b = (int)ceilf(conf * (float)n_bins) - 1;
-    b = b < 0 ? 0 : (b > n_bins - 1 ? n_bins - 1 : b);
-    if (!(conf > s_edges[b])) b = b > 0 ? b - 1 : 0;
-    else if (!(conf <= s_edges[b + 1])) b = b < n_bins - 1 ? b + 1 : b;
-    if (conf > s_edges[b] && conf <= s_edges[b + 1]) return b;
-    for (int k = 0; k < n_bins; ++k)
-        if (conf > s_edges[k] && conf <= s_edges[k + 1]) return k;
-    return -1;
-}
+// the 2^-30 fixed point and the (lo, hi] bin rule are shared with calib.hip (awseg_common.h), whose temperature grid
+// reproduces these bins bit for bit at t = 1
+__device__ __forceinline__ unsigned long long conf_q30(float conf) { return awseg_conf_q30(conf); }
+__device__ __forceinline__ int ece_find_bin(float conf, const float* s_edges, int n_bins) { return awseg_ece_find_bin(conf, s_edges, n_bins); }
 
 // C = 19, hw % 4 == 0: four pixels per lane, the 19 x 4 logits of a lane live in registers (one 16-byte load per class
 // plane instead of two 4-byte passes), fast exponentials.

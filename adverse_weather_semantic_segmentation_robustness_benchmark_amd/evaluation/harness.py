@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from .. import _native as N
 from .. import ops, parallel
-from .metrics import ConfidenceCalibration, RobustnessMetrics
+from .metrics import ConfidenceCalibration, RobustnessMetrics, calibration_from_stats
 
 logger = logging.getLogger(__name__)
 
@@ -47,10 +47,28 @@ def _cfg(config, key, default):
     return default if v is None else v
 
 
+def temperature_grid(spec):
+    """`evaluation.temperature_grid`: a list of temperatures, or {min, max, steps} = torch.linspace(min, max, steps) in float32
+    (the reference's grid is {min: 0.1, max: 10.0, steps: 100}).  None / absent: calibration off."""
+    if spec is None:
+        return None
+    if isinstance(spec, dict):
+        return torch.linspace(float(spec["min"]), float(spec["max"]), int(spec["steps"])).numpy()
+    return ops.calib_temperatures(list(spec))
+
+
+def check_calibration_budget(pixels: int) -> None:
+    """The NLL counters are int64 sums of per-pixel values up to 2^31 (include/awseg.h): raise before they could wrap."""
+    if pixels > ops.CALIB_PIXEL_BUDGET:
+        raise OverflowError(f"temperature calibration counters hold {ops.CALIB_PIXEL_BUDGET} pixels (summed over ranks); "
+                            f"{pixels} would exceed that")
+
+
 class EvalState:
     """All cross-batch state of one evaluation run (device resident, additive)."""
 
-    def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False):
+    def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
+                 temperature_grid=None, calibration_condition: str = "clean"):
         self.acc = metrics.new_accumulator(device)
         self.acc.conditions = list(conditions)
         self.acc.counts = ops.new_counts(metrics.num_classes, device, 1 + len(conditions))
@@ -58,6 +76,24 @@ class EvalState:
         self.edges = torch.linspace(0, 1, num_bins + 1).to(device)
         self.auroc = torch.zeros(2, AUROC_BINS, dtype=torch.int64, device=device) if ensemble else None
         self.samples = 0
+        # streamed temperature calibration (off unless a grid is given): NLL + ECE bins per (slot, grid temperature)
+        self.calib = None
+        if temperature_grid is not None:
+            temps = ops.calib_temperatures(temperature_grid)
+            self.calib = {"temps": temps, "condition": calibration_condition, "pixels": 0,
+                          "stats": ops.new_temperature_grid_stats(len(temps), num_bins, device, 1 + len(conditions))}
+
+    def update_calibration(self, labels: torch.Tensor, cond, logits=None, members=None) -> None:
+        """Grid NLL / ECE of this batch: from the two member maps (members = (seg1, seg2, mode, weights, T)) or materialised
+        logits.  Raises before the fixed-point pixel budget of the counters would be exceeded."""
+        c = self.calib
+        check_calibration_budget(c["pixels"] + labels.numel())
+        c["pixels"] += labels.numel()
+        if members is not None:
+            s1, s2, mode, w, T = members
+            ops.ensemble_temperature_grid_stats(s1, s2, mode, w, T, labels, c["stats"], c["temps"], self.edges, cond)
+        else:
+            ops.temperature_grid_stats(logits, labels, c["stats"], c["temps"], self.edges, cond)
 
     def update_auroc(self, seg1, seg2, labels):
         """Disagreement = mutual information (metrics.py:353-367); error = argmax of the MEAN
@@ -81,7 +117,14 @@ class EvalState:
         ts = [self.acc.counts, self.acc.oob, self.ece]
         if self.auroc is not None:
             ts.append(self.auroc)
+        pixels = None
+        if self.calib is not None:
+            # the ranks' pixel counts travel in the same message: the budget is that of the SUMMED counters
+            pixels = torch.tensor([self.calib["pixels"]], dtype=torch.int64, device=self.calib["stats"].device)
+            ts += [self.calib["stats"], pixels]
         parallel.all_reduce_sum_(ts)
+        if pixels is not None:
+            check_calibration_budget(int(pixels.item()))
 
     def auroc_value(self) -> float:
         neg, pos = self.auroc[0].double(), self.auroc[1].double()
@@ -108,9 +151,17 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     if st.auroc is not None:
         strategy = getattr(model, "ensemble_strategy", "weighted_average")
         fused_stats = metrics.num_classes == 19 and strategy != "max_confidence" and images[0, 0].numel() % 4 == 0
-        need_logits = with_stats and not fused_stats
+        need_logits = (with_stats or st.calib is not None) and not fused_stats
         one_pass = (st.edges, st.ece, st.auroc, AUROC_LO, AUROC_HI) if (with_stats and fused_stats and STATS_ONE_PASS) else None
         res = model.forward_eval(images, labels, st.acc.counts, st.acc.oob, cond, want_logits=need_logits, want_pred=False, stats=one_pass)
+        if st.calib is not None:
+            if fused_stats:                                       # grid statistics of combine(s1, s2)/T from the two member maps
+                mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
+                w = F.softmax(model.ensemble_weights, dim=0) if mode == N.COMBINE_WEIGHTED else None
+                T = model.temperature if getattr(model, "temperature_scaling", False) else None
+                st.update_calibration(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T))
+            else:
+                st.update_calibration(labels, cond, logits=res["segmentation"])
         if one_pass is not None and getattr(model, "_stats_fused", False):
             pass                                                  # confusion, ECE bins and the disagreement histogram came out of ONE pass
         elif with_stats and fused_stats:
@@ -130,6 +181,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
                                      oob=st.acc.oob, cond=cond)
         if with_stats:
             ops.ece_accumulate(logits, labels, st.ece, st.edges, cond)
+        if st.calib is not None:
+            st.update_calibration(labels, cond, logits=logits)
     st.samples += images.size(0)
 
 
@@ -139,7 +192,9 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
     conditions = list(_cfg(config, "data.weather_conditions", []))
     num_bins = int(_cfg(config, "evaluation.num_bins", 15))
     is_ensemble = hasattr(model, "segformer") and hasattr(model, "deeplabv3plus")
-    st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble)
+    st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
+                   temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
+                   calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -162,6 +217,9 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
     for k, name in enumerate(st.acc.conditions):
         if bins[1 + k]["count"].sum() > 0:
             results[f"ece_{name}"] = ConfidenceCalibration.ece_from_bins(bins[1 + k])
+    if st.calib is not None:
+        results.update(calibration_from_stats(ops.temperature_grid_stats_to_numpy(st.calib["stats"]), st.calib["temps"],
+                                              st.acc.conditions, st.calib["condition"]))
     if st.auroc is not None:
         results["ensemble_disagreement_auroc"] = st.auroc_value()
         results["ensemble_disagreement_auroc_bins"] = float(AUROC_BINS)             # rank histogram, not exact ranks:

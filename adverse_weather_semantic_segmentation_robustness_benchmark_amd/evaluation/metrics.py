@@ -177,6 +177,90 @@ class ConfidenceCalibration:
                 best, best_t = nll, t.item()
         return best_t
 
+    def fit_temperature(self, logits: torch.Tensor, targets: torch.Tensor, temperatures=None, return_details: bool = False):
+        """optimize_temperature's grid search as it was meant: the per-pixel NLL over the CLASS dimension of [B,C,H,W] logits,
+        every grid point in one device pass (no logit copied, no boolean mask).  Selection rule of the reference: the first
+        grid point with the smallest NLL, compared on the exact integer sums.  Raises IndexError on a label outside [0, C)
+        other than 255, where F.cross_entropy would."""
+        temps = ops.calib_temperatures(ops.DEFAULT_TEMPERATURE_GRID if temperatures is None else temperatures)
+        if targets.dtype not in (torch.uint8, torch.int64):
+            targets = targets.long()
+        device = logits.device
+        edges = torch.linspace(0, 1, self.num_bins + 1).to(device)
+        stats = ops.new_temperature_grid_stats(len(temps), self.num_bins, device)
+        ops.temperature_grid_stats(logits.float(), targets, stats, temps, edges)
+        s = ops.temperature_grid_stats_to_numpy(stats)
+        if int(s["out_of_range"][0]):
+            raise IndexError(f"Target out of bounds: {int(s['out_of_range'][0])} labels outside [0, {logits.size(1)}) other than 255")
+        k = first_min_index(s["nll_q"][0], s["count"][0])
+        if k is None:
+            t = 1.0                                                     # no pixel: the reference's loop keeps its start value
+            return {"temperature": t, "index": None, "nll": np.full(len(temps), np.nan), "ece": float("nan"),
+                    "temperatures": temps} if return_details else t
+        t = float(temps[k])
+        if not return_details:
+            return t
+        return {"temperature": t, "index": k, "temperatures": temps, "nll": mean_nll(s["nll_q"][0], s["count"][0]),
+                "ece": self.ece_from_bins(s["bins"][0, k]), "saturated": s["saturated"][0].copy(),
+                "nonfinite": s["nonfinite"][0].copy()}           # per grid point, pixels
+
+
+def mean_nll(nll_q: np.ndarray, count: np.ndarray) -> np.ndarray:
+    """Mean per-pixel NLL per grid point from the fixed-point sums (NaN where no pixel counted)."""
+    nll_q, count = np.asarray(nll_q), np.asarray(count)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.where(count > 0, nll_q.astype(np.float64) * ops.CALIB_NLL_UNIT / np.maximum(count, 1), np.nan)
+
+
+def first_min_index(nll_q, count) -> Optional[int]:
+    """Index of the first grid point with the smallest mean NLL, compared exactly (nll_q[i] * count[j] vs nll_q[j] * count[i]
+    in Python integers); None when no grid point counted a pixel."""
+    best = None
+    for i, (q, n) in enumerate(zip((int(v) for v in nll_q), (int(v) for v in count))):
+        if n <= 0:
+            continue
+        if best is None or q * best[1] < best[0] * n:
+            best = (q, n, i)
+    return None if best is None else best[2]
+
+
+def calibration_from_stats(stats: Dict[str, np.ndarray], temps, conditions, fit_condition: str = "clean") -> Dict[str, float]:
+    """Result keys of the streamed temperature calibration from the decoded counters (ops.temperature_grid_stats_to_numpy):
+    the temperature is fitted on `fit_condition`'s slot (slot 0 when that condition counted no pixel), the calibrated NLL and
+    ECE are reported at it overall and for every condition present, each condition also gets its own optimum.  Host only."""
+    temps = np.asarray(temps, dtype=np.float32)
+    conditions = list(conditions)
+    count, nll_q, bins = stats["count"], stats["nll_q"], stats["bins"]
+
+    def present(slot):
+        return int(bins[slot]["count"].sum()) > 0 or int(count[slot].sum()) > 0
+
+    fit = 1 + conditions.index(fit_condition) if fit_condition in conditions else 0
+    k = first_min_index(nll_q[fit], count[fit]) if present(fit) else None
+    if k is None:
+        fit, k = 0, first_min_index(nll_q[0], count[0])
+    if k is None:
+        return {}
+    nll = mean_nll(nll_q, count)
+    res = {"calibration_temperature": float(temps[k]), "nll_calibrated": float(nll[0, k]),
+           "ece_calibrated": ConfidenceCalibration.ece_from_bins(bins[0, k])}
+    for i, name in enumerate(conditions):
+        s = 1 + i
+        if s >= len(count) or not present(s):
+            continue
+        res[f"ece_calibrated_{name}"] = ConfidenceCalibration.ece_from_bins(bins[s, k])
+        if count[s, k] > 0:
+            res[f"nll_calibrated_{name}"] = float(nll[s, k])
+        own = first_min_index(nll_q[s], count[s])
+        if own is not None:
+            res[f"calibration_temperature_{name}"] = float(temps[own])
+    # pixels whose NLL was clamped at the cap, at the grid temperature that clamped the most of them (slot 0): a pixel count,
+    # not a sum over the grid; non-zero whenever the cap touched any grid point the fit compared
+    sat = int(stats["saturated"][0].max()) if stats["saturated"].size else 0
+    if sat:
+        res["calibration_saturated_pixels"] = float(sat)
+    return res
+
 
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""

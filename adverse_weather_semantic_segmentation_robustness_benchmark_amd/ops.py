@@ -164,6 +164,81 @@ def ece_bins_to_numpy(bins: torch.Tensor) -> np.ndarray:
     return out
 
 
+# ----------------------------------------------------------------------------- streaming temperature calibration
+CALIB_MAX_TEMPS = 128                  # include/awseg.h AWSEG_CALIB_MAX_TEMPS
+CALIB_NLL_UNIT = 2.0 ** -20            # per-pixel NLL fixed point (AWSEG_CALIB_NLL_FRAC_BITS)
+CALIB_NLL_CAP = 2048.0                 # per-pixel NLL clamp, counted as saturated (AWSEG_CALIB_NLL_CAP)
+CALIB_PIXEL_BUDGET = (1 << 32) - 1     # pixels one stats tensor holds, summed over ranks (AWSEG_CALIB_PIXEL_BUDGET: x 2^31 < 2^63)
+# the reference's grid (metrics.py:293) as the float32 values it iterates over; its tenth point is 0.99999994, not 1
+DEFAULT_TEMPERATURE_GRID = torch.linspace(0.1, 10.0, 100).numpy()
+
+
+def calib_temperatures(temps) -> np.ndarray:
+    """The grid as a host float32 array, checked before any launch (the C ABI refuses the same grids with AWSEG_EINVAL)."""
+    t = np.ascontiguousarray(np.asarray(temps, dtype=np.float32).reshape(-1))
+    if t.size < 1 or t.size > CALIB_MAX_TEMPS:
+        raise ValueError(f"a temperature grid has 1 .. {CALIB_MAX_TEMPS} points, got {t.size}")
+    if not (np.isfinite(t).all() and (t > 0).all()):
+        raise ValueError(f"every grid temperature must be finite and > 0, got {t.tolist()}")
+    return t
+
+
+def new_temperature_grid_stats(n_temps: int, n_bins: int, device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, n_temps + 1, 4 + 3 n_bins], the layout include/awseg.h documents (zeroed: the launches accumulate)."""
+    return torch.zeros(n_slots, n_temps + 1, 4 + 3 * n_bins, dtype=torch.int64, device=device)
+
+
+def _tgrid_args(logits: torch.Tensor, stats: torch.Tensor, temps, edges: torch.Tensor):
+    t = calib_temperatures(temps)
+    n_bins = edges.numel() - 1
+    if stats.dim() != 3 or stats.dtype != torch.int64 or stats.shape[1:] != (t.size + 1, 4 + 3 * n_bins):
+        raise ValueError(f"stats must be int64 [slots, {t.size + 1}, {4 + 3 * n_bins}] (new_temperature_grid_stats), got "
+                         f"{stats.dtype} {tuple(stats.shape)}")
+    if logits[:, 0].numel() > CALIB_PIXEL_BUDGET:
+        raise ValueError(f"{logits[:, 0].numel()} pixels exceed the {CALIB_PIXEL_BUDGET}-pixel budget of one stats tensor")
+    return t, n_bins
+
+
+def temperature_grid_stats(logits: torch.Tensor, label: torch.Tensor, stats: torch.Tensor, temps, edges: torch.Tensor,
+                           cond: Optional[torch.Tensor] = None) -> None:
+    """Per-pixel NLL and ECE bins of `logits` at every temperature of `temps`, accumulated into `stats` on device
+    (PKG/evaluation/metrics.py:266-321 streamed: no logit outlives the call)."""
+    t, n_bins = _tgrid_args(logits, stats, temps, edges)
+    logits, label = logits.contiguous(), label.contiguous()
+    b, c = logits.shape[0], logits.shape[1]
+    hw = logits[0, 0].numel()
+    N.call("awseg_temperature_grid_stats", N.ptr(logits), b, c, hw, N.ptr(label), N.label_dtype(label), N.ptr(cond), N.host(t),
+           t.size, N.ptr(edges), n_bins, N.ptr(stats), stats.shape[0], N.stream())
+
+
+def ensemble_temperature_grid_stats(seg1: torch.Tensor, seg2: torch.Tensor, mode: int, weights, temperature, label: torch.Tensor,
+                                    stats: torch.Tensor, temps, edges: torch.Tensor, cond: Optional[torch.Tensor] = None) -> None:
+    """temperature_grid_stats of r = combine(seg1, seg2)/T (WEIGHTED or MEAN, the roundings of ensemble_eval_stats) without
+    materialising r.  C = 19, H*W % 4 == 0."""
+    t, n_bins = _tgrid_args(seg1, stats, temps, edges)
+    seg1, seg2, label = seg1.contiguous(), seg2.contiguous(), label.contiguous()
+    b, c = seg1.shape[0], seg1.shape[1]
+    hw = seg1[0, 0].numel()
+    N.call("awseg_ensemble_temperature_grid_stats", N.ptr(seg1), N.ptr(seg2), b, c, hw, mode, N.ptr(weights), N.ptr(temperature),
+           N.ptr(label), N.label_dtype(label), N.ptr(cond), N.host(t), t.size, N.ptr(edges), n_bins, N.ptr(stats), stats.shape[0],
+           N.stream())
+
+
+def temperature_grid_stats_to_numpy(stats) -> dict:
+    """Decode the int64 counters (a device tensor or a numpy array) into exact integer arrays:
+    count / nll_q (units CALIB_NLL_UNIT) / saturated / nonfinite [slots, K], bins [slots, K, n_bins] as ece_bins_to_numpy,
+    out_of_range [slots]."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    k = raw.shape[1] - 1
+    n_bins = (raw.shape[2] - 4) // 3
+    rows = raw[:, :k]
+    b = rows[..., 4:].reshape(raw.shape[0], k, n_bins, 3)
+    bins = np.zeros(b.shape[:3], dtype=ECE_BIN_DTYPE)
+    bins["count"], bins["sum_conf"], bins["sum_correct"] = b[..., 0], b[..., 1].astype(np.float64) * ECE_CONF_UNIT, b[..., 2]
+    return {"count": rows[..., 0].copy(), "nll_q": rows[..., 1].copy(), "saturated": rows[..., 2].copy(),
+            "nonfinite": rows[..., 3].copy(), "bins": bins, "out_of_range": raw[:, k, 0].copy()}
+
+
 # ----------------------------------------------------------------------------- A7
 def normalize(imgs: torch.Tensor, out: Optional[torch.Tensor] = None, sel: Optional[torch.Tensor] = None,
               mean=None, std=None) -> torch.Tensor:

@@ -857,6 +857,63 @@ int awseg_combine_confusion_stats(const float* seg1, const float* seg2, int64_t 
                                   void* ece_bins, int ece_slots, int64_t* auroc_hist, int n_hist, float hist_lo,
                                   float hist_hi, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Streaming temperature calibration: per-pixel NLL and ECE bins at every temperature of a grid
+ *       replaces PKG/evaluation/metrics.py:266-321 (temperature_scale + optimize_temperature's grid search, which needs every
+ *       logit of the evaluation set in memory) at the place REF/scripts/evaluate.py:230-238 computes calibration
+ * ------------------------------------------------------------------------- *
+ * For every pixel with label != 255, r = the logits the ECE entry points see (the logits themselves, or combine(seg1, seg2)/T
+ * with the expressions and roundings of awseg_ensemble_eval_stats), pred = argmax r under the same rule, and every grid
+ * temperature t_k (k < n_temps):
+ *     z = r / t_k,  conf_k = 1 / sum_c exp(z_c - z_max),  nll_k = log sum_c exp(z_c - z_max) - (z_y - z_max)
+ * conf_k enters the ECE bin (lo, hi] of edges (device float32[n_bins+1], as awseg_ece_accumulate); nll_k (labels y in
+ * [0, C)) enters the NLL sums.
+ *
+ * Integer sums only: every accumulator is a sum of per-pixel integers, so results do not depend on launch geometry, batch
+ * split or rank count.  The per-pixel NLL is rounded to nearest in units of 2^-AWSEG_CALIB_NLL_FRAC_BITS (2^-20); a value
+ * above AWSEG_CALIB_NLL_CAP (2^11) is clamped to the cap and counted as saturated.  Pixel budget of one stats tensor:
+ * AWSEG_CALIB_PIXEL_BUDGET = 2^32 - 1 pixels ((2^32 - 1) x 2^31 < 2^63), about 2 048 frames at 1024 x 2048.  The budget holds for
+ * the tensor after any cross-rank sum: the Python accumulators raise before one rank exceeds it and again, before the results
+ * are read, when the ranks together do.  The confidence sums are in units of 2^-30 as in awseg_ece_accumulate.
+ *
+ * Bit-identity at t = 1: at a grid point equal to 1.0f the ECE bins equal those of awseg_ece_accumulate (single entry point)
+ * or awseg_ensemble_eval_stats / awseg_combine_confusion_stats (ensemble entry point) on the same inputs, bit for bit.
+ *
+ * Edge cases: a label outside [0, C) other than 255 enters the ECE bins as an error (as awseg_ece_accumulate) and is left out
+ * of the NLL; it is counted per slot.  A non-finite per-pixel NLL is left out of the NLL sums and counted.
+ *
+ * Output (accumulated, never cleared): stats int64 [n_slots][n_temps + 1][AWSEG_CALIB_ROW(n_bins)], slots as in
+ * awseg_ece_accumulate (slot 0 every image, slot 1 + cond[b] when cond[b] >= 0):
+ *     row k < n_temps:  {pixel count, NLL sum (units 2^-20), saturated, non-finite,
+ *                        n_bins x {count, sum conf (units 2^-30), sum correct}}
+ *     row n_temps:      {out-of-range labels, 0, ...}
+ * temps: HOST float32[n_temps] (they travel in the kernel arguments).  No workspace.  AWSEG_EINVAL when a temperature is not
+ * finite or not > 0, n_temps > AWSEG_CALIB_MAX_TEMPS, n_bins > 64, or C > AWSEG_CALIB_MAX_CLASSES.
+ */
+#define AWSEG_CALIB_MAX_TEMPS      128
+#define AWSEG_CALIB_MAX_CLASSES    64
+#define AWSEG_CALIB_NLL_FRAC_BITS  20
+#define AWSEG_CALIB_NLL_CAP        2048
+#define AWSEG_CALIB_PIXEL_BUDGET   ((1LL << 32) - 1)
+#define AWSEG_CALIB_ROW(n_bins)    (4 + 3 * (n_bins))
+
+/* Single logits [B, C, H, W] float32, any C <= 64 and any hw (C = 19, hw % 4 == 0 and 16-byte aligned logits: four pixels per
+ * lane, otherwise one).  Replaces metrics.py:266-321 on REF/scripts/evaluate.py:230-238's logits. */
+int awseg_temperature_grid_stats(const float* logits, int64_t batch, int num_classes, int64_t hw,
+                                 const void* label, int label_dtype, const int32_t* cond,
+                                 const float* temps, int n_temps, const float* edges, int n_bins,
+                                 int64_t* stats, int n_slots, awseg_stream_t stream);
+
+/* The two member logit maps, r = combine(seg1, seg2)/T (mode WEIGHTED or MEAN, weights device float32[2] for WEIGHTED,
+ * temperature device float32[1] or NULL) as awseg_ensemble_eval_stats; the ensemble logits are never materialised.
+ * C = 19, hw % 4 == 0, 16-byte aligned members (AWSEG_ERANGE / AWSEG_EALIGN otherwise).  Replaces metrics.py:266-321 on the
+ * ensemble logits of REF/scripts/evaluate.py:230-238. */
+int awseg_ensemble_temperature_grid_stats(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,
+                                          int mode, const float* weights, const float* temperature,
+                                          const void* label, int label_dtype, const int32_t* cond,
+                                          const float* temps, int n_temps, const float* edges, int n_bins,
+                                          int64_t* stats, int n_slots, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
