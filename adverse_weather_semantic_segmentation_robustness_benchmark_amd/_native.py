@@ -120,6 +120,10 @@ SIGNATURES = {
     "awseg_upsample_bilinear_strided": (c_i, [c_p, c_i64, c_i, c_i, c_i, c_i64, c_i64, c_i64, c_i64, c_i, c_i, c_i, c_p, c_p]),
     "awseg_combine_confusion_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_i,
                                            c_p, c_i, c_p, c_i, c_f, c_f, c_p, c_p]),
+    "awseg_combine_confusion_stats_pred": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p,
+                                                c_i, c_p, c_i, c_p, c_i, c_f, c_f, c_p, c_p, c_p]),
+    "awseg_consistency_workspace": (c_i64, [c_i64, c_i, c_i64]),
+    "awseg_prediction_consistency": (c_i, [c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
     "awseg_ece_accumulate": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p]),
     "awseg_temperature_grid_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "awseg_ensemble_temperature_grid_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i,

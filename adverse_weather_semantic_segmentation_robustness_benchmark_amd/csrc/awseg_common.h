@@ -55,6 +55,13 @@ template <int DT> __device__ __forceinline__ int64_t awseg_ld_label(const void* 
     return ((const int64_t*)p)[i];
 }
 
+// torch's argmax update rule (metrics.hip's combine and one-pass statistics kernels; their prediction maps are what
+// consistency.hip compares): take v when v > best, or v is NaN and best is not.
+__device__ __forceinline__ void awseg_amax_step(float v, int c, float& best, int& bi)
+{
+    if (!(v <= best) && !(best != best)) { best = v; bi = c; }
+}
+
 // ECE confidence sums in FIXED POINT, units of 2^-30 (metrics.hip, calib.hip): a float32 confidence in [2^-7, 1] is a multiple
 // of 2^-30, so conf * 2^30 is an exact integer and integer sums do not depend on the order of the atomics.
 __device__ __forceinline__ unsigned long long awseg_conf_q30(float conf) { return (unsigned long long)(conf * 1073741824.0f); }

@@ -1,0 +1,196 @@
+// consistency.hip — prediction consistency of a corrupted frame against the prediction of its clean frame (the paired severity
+// sweep): per condition slot, the C x C agreement matrix A[ref class][variant class] over every pixel and the four
+// correct / wrong transitions over the labelled pixels.
+//
+// A 2-3 B/px scan (two uint8 maps + the label map).  Each lane owns 16 consecutive pixels: one 16-byte load per map when every row
+// base is 16-byte aligned and hw % 16 == 0, byte loads otherwise (ragged frames).  Clean and corrupted predictions agree over large
+// connected regions, so the 16 agreement indices of a lane are merged into runs in registers before they touch the per-block LDS
+// histogram (one ds_add per run: one per 16 pixels in the common case); the four transition counters never touch LDS per pixel:
+// they live in registers, are summed over the wave and added once per wave.  Blocks write uint32 partials, a second launch folds
+// them into the int64 counters: integer sums only, so the counts do not depend on grid shape, batch split or rank count.
+#include "awseg_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPer = 16;                                                  // pixels per lane per step
+constexpr int kRowMax = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES + 4;
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+
+__device__ __forceinline__ void unpack16(const uint4 q, int (&v)[kPer])
+{
+    const uint32_t w[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) v[k] = (int)((w[k >> 2] >> ((k & 3) * 8)) & 0xFF);
+}
+
+// grid = (blocks_per_image, B); block x of image y writes partial[(y * gridDim.x + x)][C * C + 4].
+// VEC: hw % 16 == 0 and pred, ref_maps and label 16-byte aligned (every row base then is); else byte loads.
+template <int LDT, bool VEC>
+__global__ __launch_bounds__(kThreads)
+void consistency_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restrict__ ref_maps, int n_refs, int64_t hw,
+                        const int32_t* __restrict__ frame_ref, const void* __restrict__ label, int ignore_index, int C,
+                        uint32_t* __restrict__ partial, int64_t* __restrict__ oob)
+{
+    __shared__ uint32_t hist[kRowMax];
+    const int bins = C * C, row = bins + 4;
+    for (int i = threadIdx.x; i < row; i += kThreads) hist[i] = 0u;
+    __syncthreads();
+    const int64_t img = blockIdx.y;
+    const int r = frame_ref[img];
+    // transitions over labelled pixels: both correct, reference correct + variant wrong, reference wrong + variant correct, both wrong
+    uint32_t t_cc = 0, t_cw = 0, t_wc = 0, t_ww = 0, bad = 0;
+    if (r >= 0 && r < n_refs) {
+        const uint8_t* pp = pred + img * hw;
+        const uint8_t* rp = ref_maps + (int64_t)r * hw;
+        const int64_t lb = img * hw;
+        const int64_t nchunk = (hw + kPer - 1) / kPer;
+        for (int64_t ch = (int64_t)blockIdx.x * kThreads + threadIdx.x; ch < nchunk; ch += (int64_t)gridDim.x * kThreads) {
+            const int64_t base = ch * kPer;
+            int pv[kPer], rv[kPer];
+            int64_t lv[kPer];
+            if constexpr (VEC) {
+                unpack16(*reinterpret_cast<const uint4*>(pp + base), pv);
+                unpack16(*reinterpret_cast<const uint4*>(rp + base), rv);
+                if constexpr (LDT == AWSEG_U8) {
+                    int l8[kPer];
+                    unpack16(*reinterpret_cast<const uint4*>((const uint8_t*)label + lb + base), l8);
+#pragma unroll
+                    for (int k = 0; k < kPer; ++k) lv[k] = l8[k];
+                } else {
+                    const longlong2* lp = reinterpret_cast<const longlong2*>((const int64_t*)label + lb + base);
+#pragma unroll
+                    for (int k = 0; k < kPer / 2; ++k) { const longlong2 q = lp[k]; lv[2 * k] = q.x; lv[2 * k + 1] = q.y; }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < kPer; ++k) {
+                    const bool in = base + k < hw;
+                    pv[k] = in ? (int)pp[base + k] : 0;
+                    rv[k] = in ? (int)rp[base + k] : 0;
+                    lv[k] = in ? awseg_ld_label<LDT>(label, lb + base + k) : (int64_t)ignore_index;
+                }
+            }
+            int run_idx = -1;
+            uint32_t run = 0;
+#pragma unroll
+            for (int k = 0; k < kPer; ++k) {
+                if (!VEC && base + k >= hw) break;
+                const int pk = pv[k], rk = rv[k];
+                if (pk >= C || rk >= C) { ++bad; continue; }             // a map value no argmax over C classes produces
+                const int idx = rk * C + pk;
+                if (idx == run_idx) ++run;
+                else { if (run) atomicAdd(&hist[run_idx], run); run_idx = idx; run = 1; }
+                const int64_t t = lv[k];
+                if (t != ignore_index && t >= 0 && t < C) {
+                    const uint32_t rc = (int64_t)rk == t, vc = (int64_t)pk == t;
+                    t_cc += rc & vc; t_cw += rc & (vc ^ 1u); t_wc += (rc ^ 1u) & vc; t_ww += (rc ^ 1u) & (vc ^ 1u);
+                }
+            }
+            if (run) atomicAdd(&hist[run_idx], run);
+        }
+    } else if (r >= n_refs && blockIdx.x == 0 && threadIdx.x == 0) {
+        atomicAdd((unsigned long long*)oob, (unsigned long long)hw);    // a row index the reference maps do not have: frame not counted
+    }
+    t_cc = wave_sum_u32(t_cc); t_cw = wave_sum_u32(t_cw); t_wc = wave_sum_u32(t_wc); t_ww = wave_sum_u32(t_ww); bad = wave_sum_u32(bad);
+    if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0) {
+        if (t_cc) atomicAdd(&hist[bins + 0], t_cc);
+        if (t_cw) atomicAdd(&hist[bins + 1], t_cw);
+        if (t_wc) atomicAdd(&hist[bins + 2], t_wc);
+        if (t_ww) atomicAdd(&hist[bins + 3], t_ww);
+        if (bad) atomicAdd((unsigned long long*)oob, (unsigned long long)bad);
+    }
+    __syncthreads();
+    uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * row;
+    for (int i = threadIdx.x; i < row; i += kThreads) dst[i] = hist[i];
+}
+
+// Fold the per-block partials of one image into slot 0 and slot 1 + cond[img] (metrics.hip's fold_partials_kernel rule): a block
+// owns 64 counters, its 16 waves each sum a sixteenth of the partials, one LDS step combines them.
+constexpr int kFoldSlices = 16;
+__global__ __launch_bounds__(kFoldSlices * 64)
+void consistency_fold_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row,
+                             const int32_t* __restrict__ cond, int n_slots, int64_t* __restrict__ stats)
+{
+    __shared__ unsigned long long s_sum[kFoldSlices][64];
+    const int img = blockIdx.x;
+    const int kl = threadIdx.x & 63, slice = threadIdx.x >> 6;
+    const int k = blockIdx.y * 64 + kl;
+    const uint32_t* src = partial + (int64_t)img * blocks_per_image * row;
+    unsigned long long s = 0;
+    if (k < row) {
+#pragma unroll 8
+        for (int b = slice; b < blocks_per_image; b += kFoldSlices) s += src[(int64_t)b * row + k];
+    }
+    s_sum[slice][kl] = s;
+    __syncthreads();
+    if (slice == 0 && k < row) {
+        s = 0;
+#pragma unroll
+        for (int j = 0; j < kFoldSlices; ++j) s += s_sum[j][kl];
+        if (s) {
+            int slot = -1;
+            if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
+            atomicAdd((unsigned long long*)&stats[k], s);
+            if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * row + k], s);
+        }
+    }
+}
+
+int cons_blocks_per_image(int64_t hw, int64_t batch)
+{
+    // 256 CUs x 4 resident blocks over the whole batch (a 2-3 B/px scan), grid-stride beyond
+    int64_t want = ((hw + kPer - 1) / kPer + kThreads - 1) / kThreads;
+    int64_t cap = (AWSEG_CUS * 4 + batch - 1) / batch;
+    if (cap < 1) cap = 1;
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    return (int)want;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+AWSEG_API int64_t awseg_consistency_workspace(int64_t batch, int num_classes, int64_t hw)
+{
+    if (batch < 1) batch = 1;
+    if (hw < 1) hw = 1;
+    if (num_classes < 1 || num_classes > AWSEG_MAX_CLASSES) num_classes = AWSEG_MAX_CLASSES;
+    return (int64_t)cons_blocks_per_image(hw, batch) * batch * (num_classes * num_classes + 4) * (int64_t)sizeof(uint32_t);
+}
+
+AWSEG_API int awseg_prediction_consistency(const uint8_t* pred, const uint8_t* ref_maps, int n_refs, int64_t batch, int64_t hw,
+                                           const int32_t* frame_ref, const void* label, int label_dtype, int ignore_index,
+                                           int num_classes, const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob,
+                                           void* workspace, awseg_stream_t stream)
+{
+    if (!pred || !ref_maps || !frame_ref || !label || !stats || !oob || !workspace) return AWSEG_EINVAL;
+    if (n_refs < 1 || batch < 1 || hw < 1 || n_slots < 1) return AWSEG_EINVAL;
+    if (num_classes < 1 || num_classes > AWSEG_MAX_CLASSES) return AWSEG_EINVAL;
+    if (label_dtype != AWSEG_U8 && label_dtype != AWSEG_I64) return AWSEG_EINVAL;
+    if (batch > 65535 || hw > INT32_MAX) return AWSEG_ERANGE;                 // grid.y; uint32 per-block partials
+    hipStream_t s = awseg_s(stream);
+    const int bpi = cons_blocks_per_image(hw, batch);                          // same count the workspace query assumed
+    const int row = num_classes * num_classes + 4;
+    const bool vec = (hw % kPer == 0) && aligned16(pred) && aligned16(ref_maps) && aligned16(label);
+    uint32_t* partial = (uint32_t*)workspace;
+    dim3 grid(bpi, (unsigned)batch), block(kThreads);
+#define AWSEG_CONS(L, V) \
+    hipLaunchKernelGGL((consistency_kernel<L, V>), grid, block, 0, s, pred, ref_maps, n_refs, hw, frame_ref, label, ignore_index, \
+                       num_classes, partial, oob)
+    if (label_dtype == AWSEG_U8) { if (vec) AWSEG_CONS(AWSEG_U8, true); else AWSEG_CONS(AWSEG_U8, false); }
+    else { if (vec) AWSEG_CONS(AWSEG_I64, true); else AWSEG_CONS(AWSEG_I64, false); }
+#undef AWSEG_CONS
+    AWSEG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(consistency_fold_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kFoldSlices * 64), 0, s, partial, bpi, row,
+                       cond, n_slots, stats);
+    AWSEG_LAUNCH_CHECK();
+    return 0;
+}

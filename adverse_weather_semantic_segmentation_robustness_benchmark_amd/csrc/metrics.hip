@@ -20,13 +20,8 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kMaxBins = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES;
 
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-
-// torch argmax update rule: take v when v > best, or v is NaN and best is not.
-__device__ __forceinline__ void amax_step(float v, int c, float& best, int& bi)
-{
-    if (!(v <= best) && !is_nan(best)) { best = v; bi = c; }
-}
+// torch argmax update rule (awseg_common.h, shared with the prediction maps consistency.hip compares)
+__device__ __forceinline__ void amax_step(float v, int c, float& best, int& bi) { awseg_amax_step(v, c, best, bi); }
 
 template <int LDT>
 __device__ __forceinline__ void hist_add(uint32_t* hist, const void* label, int64_t li, int pred,
@@ -400,15 +395,18 @@ __global__ void ece_fold_kernel(const ece_cell* __restrict__ partial, int blocks
 // at 1024 x 2048) is not needed when neither the ensemble logits nor the prediction map are asked for.
 // TH threads x PX pixels per lane: the block's 64 KB score histogram allows two blocks per CU, so 256 threads are two waves per SIMD
 // whatever the register count; 512 threads with 2 pixels per lane (2 x 19 x 2 logits: < 128 registers) are four.
-template <int MODE, int LDT, bool CONF, int TH, int PX>
+// PRED = true (with CONF): the same pass also stores argmax(r) as uint8 for EVERY pixel, labelled 255 and out-of-range ones included
+// (awseg_combine_confusion_stats_pred: the clean prediction map of the paired severity sweep); PX bytes per lane in one store.
+template <int MODE, int LDT, bool CONF, int TH, int PX, bool PRED>
 __global__ __launch_bounds__(TH, TH / 128)   // waves per SIMD of two resident blocks
 void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restrict__ seg2, int64_t hw,
                            const float* __restrict__ weights, const float* __restrict__ temperature,
                            const void* __restrict__ label, const float* __restrict__ edges, int n_bins,
                            ece_cell* __restrict__ partial, unsigned long long* __restrict__ hist, int n_hist,
                            float h_lo, float h_scale, int ignore_index, int wrap, uint32_t* __restrict__ conf_partial,
-                           int64_t* __restrict__ oob)
+                           int64_t* __restrict__ oob, uint8_t* __restrict__ pred)
 {
+    static_assert(!PRED || CONF, "the prediction map comes out of the confusion pass");
     constexpr int C = 19;
     __shared__ uint32_t s_conf[CONF ? C * C : 1];
     if (CONF) { for (int i = threadIdx.x; i < C * C; i += TH) s_conf[i] = 0u; }
@@ -442,6 +440,7 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
 #pragma unroll
             for (int k = 0; k < PX; ++k) { x[c][k] = xv[k]; y[c][k] = yv[k]; }
         }
+        uint32_t pk = 0;                                          // PRED: the PX argmax bytes, packed as they are found (one register)
 #pragma unroll
         for (int k = 0; k < PX; ++k) {
             const int64_t t = awseg_ld_label<LDT>(label, img * hw + p + k);
@@ -461,6 +460,7 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
                 else if (c == 0 || rv > rmax) { rmax = rv; rarg = c; }
                 m1 = fmaxf(m1, x[c][k]); m2 = fmaxf(m2, y[c][k]);
             }
+            if (PRED) pk |= (uint32_t)rarg << (8 * k);
             if (CONF) {
                 hist_add<LDT>(s_conf, label, img * hw + p + k, rarg, C, ignore_index, wrap, oob);
                 if (t == 255) continue;                           // the calibration / disagreement statistics skip 255 (metrics.py:170, :426)
@@ -502,6 +502,10 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
             int hb = (int)((score - h_lo) * h_scale);
             hb = hb < 0 ? 0 : (hb >= n_hist ? n_hist - 1 : hb);
             atomicAdd(&s_hist[(marg != (int)t ? n_hist : 0) + hb], 1u);
+        }
+        if (PRED) {                                               // p = v * PX: PX-byte aligned (the launcher checks the base)
+            if constexpr (PX == 4) *reinterpret_cast<uint32_t*>(pred + img * hw + p) = pk;
+            else *reinterpret_cast<uint16_t*>(pred + img * hw + p) = (uint16_t)pk;
         }
     }
     __syncthreads();
@@ -700,7 +704,8 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
                       int label_dtype, const int32_t* cond, const float* edges, int n_bins, void* ece_bins,
                       int n_slots, int64_t* auroc_hist, int n_hist, float hist_lo, float hist_hi,
                       void* workspace, awseg_stream_t stream,
-                      bool conf, int ignore_index, int wrap, int64_t* counts, int count_slots, int64_t* oob)
+                      bool conf, int ignore_index, int wrap, int64_t* counts, int count_slots, int64_t* oob,
+                      uint8_t* pred = nullptr)
 {
     if (!seg1 || !seg2 || !label || !edges || !ece_bins || !auroc_hist || !workspace) return AWSEG_EINVAL;
     if (conf && (!counts || !oob || count_slots < 1)) return AWSEG_EINVAL;
@@ -709,6 +714,7 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
     if (mode == AWSEG_COMBINE_WEIGHTED && !weights) return AWSEG_EINVAL;
     if (n_bins < 1 || n_bins > 64 || n_slots < 1 || n_hist < 2 || n_hist > kHistMax || batch < 1 || batch > 65535 || hw < 4 || !(hist_hi > hist_lo)) return AWSEG_EINVAL;
     if ((hw & 3) || ((uintptr_t)seg1 & 15) || ((uintptr_t)seg2 & 15)) return AWSEG_EALIGN;
+    if (pred && (!conf || ((uintptr_t)pred & 3))) return pred && !conf ? AWSEG_EINVAL : AWSEG_EALIGN;
     hipStream_t s = awseg_s(stream);
     int bpi = blocks_per_image(hw, batch, 1);
     const int cap = (int)((AWSEG_CUS * 2 + batch - 1) / batch);   // 64 KB of LDS per block: two blocks per CU
@@ -721,12 +727,12 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
     unsigned long long* hist = (unsigned long long*)auroc_hist;
     // workspace: [batch][bpi][n_bins] ECE cells, then (conf) [batch][bpi][19 x 19] uint32 histogram partials
     uint32_t* conf_partial = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (size_t)batch * bpi * 64 * sizeof(ece_cell));
-#define AWSEG_ES_K(M, L, CF, TH, PX) { \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ensemble_stats_kernel<M, L, CF, TH, PX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL; \
-        hipLaunchKernelGGL((ensemble_stats_kernel<M, L, CF, TH, PX>), grid, dim3(TH), lds, s, seg1, seg2, hw, weights, temperature, label, \
-                           edges, n_bins, (ece_cell*)workspace, hist, n_hist, hist_lo, scale, ignore_index, wrap, conf_partial, oob); }
-#define AWSEG_ES(M, L, CF) { if (wide == 1) AWSEG_ES_K(M, L, CF, 512, 2) else if (wide == 2) AWSEG_ES_K(M, L, CF, 384, 2) else AWSEG_ES_K(M, L, CF, kThreads, 4) }
-#define AWSEG_ES2(M, L) { if (conf) AWSEG_ES(M, L, true) else AWSEG_ES(M, L, false) }
+#define AWSEG_ES_K(M, L, CF, TH, PX, PR) { \
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ensemble_stats_kernel<M, L, CF, TH, PX, PR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL; \
+        hipLaunchKernelGGL((ensemble_stats_kernel<M, L, CF, TH, PX, PR>), grid, dim3(TH), lds, s, seg1, seg2, hw, weights, temperature, label, \
+                           edges, n_bins, (ece_cell*)workspace, hist, n_hist, hist_lo, scale, ignore_index, wrap, conf_partial, oob, pred); }
+#define AWSEG_ES(M, L, CF, PR) { if (wide == 1) AWSEG_ES_K(M, L, CF, 512, 2, PR) else if (wide == 2) AWSEG_ES_K(M, L, CF, 384, 2, PR) else AWSEG_ES_K(M, L, CF, kThreads, 4, PR) }
+#define AWSEG_ES2(M, L) { if (pred) AWSEG_ES(M, L, true, true) else if (conf) AWSEG_ES(M, L, true, false) else AWSEG_ES(M, L, false, false) }
     if (mode == AWSEG_COMBINE_WEIGHTED) { if (label_dtype == AWSEG_U8) AWSEG_ES2(0, AWSEG_U8) else if (label_dtype == AWSEG_I64) AWSEG_ES2(0, AWSEG_I64) else return AWSEG_EINVAL; }
     else { if (label_dtype == AWSEG_U8) AWSEG_ES2(2, AWSEG_U8) else if (label_dtype == AWSEG_I64) AWSEG_ES2(2, AWSEG_I64) else return AWSEG_EINVAL; }
 #undef AWSEG_ES2
@@ -764,4 +770,17 @@ AWSEG_API int awseg_combine_confusion_stats(const float* seg1, const float* seg2
     return stats_impl(seg1, seg2, batch, num_classes, hw, mode, weights, temperature, label, label_dtype, cond, edges, n_bins,
                       ece_bins, ece_slots, auroc_hist, n_hist, hist_lo, hist_hi, workspace, stream, true, ignore_index,
                       label_wrap_u8, counts, count_slots, oob);
+}
+
+AWSEG_API int awseg_combine_confusion_stats_pred(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,
+                                                 int mode, const float* weights, const float* temperature, const void* label,
+                                                 int label_dtype, int ignore_index, int label_wrap_u8, const int32_t* cond,
+                                                 int64_t* counts, int count_slots, int64_t* oob, const float* edges, int n_bins,
+                                                 void* ece_bins, int ece_slots, int64_t* auroc_hist, int n_hist, float hist_lo,
+                                                 float hist_hi, uint8_t* pred, void* workspace, awseg_stream_t stream)
+{
+    if (!pred) return AWSEG_EINVAL;
+    return stats_impl(seg1, seg2, batch, num_classes, hw, mode, weights, temperature, label, label_dtype, cond, edges, n_bins,
+                      ece_bins, ece_slots, auroc_hist, n_hist, hist_lo, hist_hi, workspace, stream, true, ignore_index,
+                      label_wrap_u8, counts, count_slots, oob, pred);
 }

@@ -10,7 +10,8 @@ serves synthetic samples: 100 for 'train', 20 otherwise (:165-179), uint8 images
 from __future__ import annotations
 
 import logging
-from typing import Dict, Iterator, List, Optional, Tuple
+import math
+from typing import Dict, Iterator, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -19,6 +20,105 @@ from .. import ops
 from .preprocessing import DepthEstimationPreprocessor, WeatherDegradationTransforms
 
 logger = logging.getLogger(__name__)
+
+# `evaluation.severities: reference`: three levels per kind at the low end, middle and high end of the range the reference draws
+# each kind's intensity from (PKG/data/preprocessing.py:108, 128, 173, 207)
+REFERENCE_SEVERITIES = {"fog": [0.3, 0.6, 0.9], "rain": [0.2, 0.5, 0.8], "snow": [0.2, 0.45, 0.7], "night": [0.4, 0.6, 0.8]}
+
+
+class SeveritySweep(NamedTuple):
+    """A validated paired severity sweep: the adverse kinds in config order and each kind's S intensities."""
+    kinds: Tuple[str, ...]
+    intensities: Dict[str, Tuple[float, ...]]
+
+    @property
+    def levels(self) -> int:
+        return len(self.intensities[self.kinds[0]])
+
+    def slots(self) -> List[str]:
+        """Condition slot names of the sweep: 'clean', then '<kind>_s<j>' for every kind and level j = 1..S."""
+        return ["clean"] + [slot_name(k, j) for k in self.kinds for j in range(1, self.levels + 1)]
+
+
+def slot_name(kind: str, level: int) -> str:
+    return "clean" if level == 0 else f"{kind}_s{int(level)}"
+
+
+def resolve_severities(spec, weather_conditions: Sequence[str], rng: str = "philox") -> SeveritySweep:
+    """`evaluation.severities` -> SeveritySweep; pure, raises ValueError for a sweep that cannot be run.  spec: a list of
+    intensities for every adverse kind, a {kind: [...]} dict with one list per adverse kind (all of one length), or 'reference'.
+    The adverse kinds are the non-clean entries of `weather_conditions`, in that order."""
+    conds = [str(c) for c in weather_conditions]
+    if "clean" not in conds:
+        raise ValueError("a severity sweep compares with the clean frame: data.weather_conditions must contain 'clean'")
+    if rng != "philox":
+        raise ValueError("a severity sweep needs rng='philox': the variants of a source share its per-frame draws, which the "
+                         "shared numpy stream of parity mode cannot give")
+    kinds = tuple(c for c in conds if c != "clean")
+    if not kinds:
+        raise ValueError("a severity sweep needs at least one adverse kind in data.weather_conditions")
+    if isinstance(spec, str):
+        if spec != "reference":
+            raise ValueError(f"evaluation.severities: unknown preset {spec!r} (known: 'reference')")
+        missing = [k for k in kinds if k not in REFERENCE_SEVERITIES]
+        if missing:
+            raise ValueError(f"the 'reference' severities have no levels for {missing}")
+        table = {k: REFERENCE_SEVERITIES[k] for k in kinds}
+    elif isinstance(spec, dict):
+        extra = [k for k in spec if str(k) not in kinds]
+        if extra:
+            raise ValueError(f"evaluation.severities names {extra}, which are not adverse kinds of data.weather_conditions {list(kinds)}")
+        missing = [k for k in kinds if k not in spec]
+        if missing:
+            raise ValueError(f"evaluation.severities has no levels for {missing}")
+        table = {k: spec[k] for k in kinds}
+    else:
+        table = {k: spec for k in kinds}
+    out = {}
+    for k, levels in table.items():
+        if isinstance(levels, (str, bytes)) or not hasattr(levels, "__len__"):
+            raise ValueError(f"evaluation.severities[{k!r}] must be a list of intensities")
+        vals = tuple(float(v) for v in levels)
+        if not vals:
+            raise ValueError(f"evaluation.severities[{k!r}] is empty")
+        bad = [v for v in vals if not math.isfinite(v) or v < 0.0 or v > 1.0]
+        if bad:
+            raise ValueError(f"evaluation.severities[{k!r}]: intensities lie in [0, 1], got {bad}")
+        out[k] = vals
+    if len({len(v) for v in out.values()}) != 1:
+        raise ValueError(f"evaluation.severities: every kind needs the same number of levels, got { {k: len(v) for k, v in out.items()} }")
+    return SeveritySweep(kinds, out)
+
+
+class PairedBatch(NamedTuple):
+    """One batch of the paired plan: sources start .. start + n - 1 under (kind, level); level 0 is the clean frame."""
+    start: int
+    n: int
+    kind: str
+    level: int
+    intensity: Optional[float]
+
+
+def paired_plan(num_samples: int, batch_size: int, kinds: Sequence[str], severities, rank: int = 0, world_size: int = 1,
+                drop_last: bool = False) -> List[PairedBatch]:
+    """The batches one rank runs in a paired sweep.  Sources are sharded over ranks as `batches()` shards samples; each rank takes
+    its sources in groups of `batch_size` consecutive ones (the last may be smaller; dropped with drop_last) and yields, per group,
+    the clean batch and then one batch per (kind, level) in kind order, levels 1..S.  severities: a list for every kind or a
+    {kind: list} dict."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    table = severities if isinstance(severities, dict) else {k: severities for k in kinds}
+    per = (num_samples + world_size - 1) // world_size
+    lo, hi = min(rank * per, num_samples), min((rank + 1) * per, num_samples)
+    plan = []
+    for start in range(lo, hi, batch_size):
+        n = min(batch_size, hi - start)
+        if n < batch_size and drop_last:
+            break
+        plan.append(PairedBatch(start, n, "clean", 0, None))
+        for k in kinds:
+            plan += [PairedBatch(start, n, k, j + 1, float(v)) for j, v in enumerate(table[k])]
+    return plan
 
 
 class CityscapesKITTIDataset:
@@ -31,12 +131,16 @@ class CityscapesKITTIDataset:
     def __init__(self, data_root: str = "data", split: str = "train", image_size: Tuple[int, int] = (512, 1024),
                  weather_conditions: Optional[List[str]] = None, apply_augmentation: bool = True, include_depth: bool = True,
                  dataset_type: str = "combined", device="cuda", rng: str = "philox", weather_schedule: str = "random",
-                 num_samples: Optional[int] = None, seed: int = 42) -> None:
+                 num_samples: Optional[int] = None, seed: int = 42, severities=None) -> None:
         self.data_root, self.split, self.image_size = data_root, split, tuple(image_size)
         self.weather_conditions = weather_conditions or ["clean", "fog", "rain", "snow", "night"]
         self.apply_augmentation, self.include_depth, self.dataset_type = apply_augmentation, include_depth, dataset_type
         self.device = torch.device(device)
-        self.weather_schedule = weather_schedule          # 'random' (loader.py:265) or 'round_robin' (bench)
+        self.weather_schedule = weather_schedule          # 'random' (loader.py:265), 'round_robin' (bench) or 'paired' (severity sweep)
+        # paired: every source once clean and once per (adverse kind, severity), all variants of a source keyed by its index
+        self.sweep = resolve_severities(severities, self.weather_conditions, rng) if weather_schedule == "paired" else None
+        if self.sweep is None and severities is not None:
+            raise ValueError("severities are for weather_schedule='paired'")
         self.num_samples = num_samples if num_samples is not None else (100 if split == "train" else 20)
         self.seed = int(seed)
         # The reference redraws pixels, the weather choice and every corruption parameter on each __getitem__
@@ -104,8 +208,40 @@ class CityscapesKITTIDataset:
             batch["depth"] = self.depth_preprocessor.estimate_depth_batch(frames)
         return batch
 
+    def plan(self, batch_size: int, drop_last: bool = False, rank: int = 0, world_size: int = 1) -> List[PairedBatch]:
+        """The paired schedule of one rank (weather_schedule='paired')."""
+        return paired_plan(self.num_samples, batch_size, self.sweep.kinds, self.sweep.intensities, rank, world_size, drop_last)
+
+    def make_paired_batch(self, raw, item: PairedBatch) -> Dict[str, object]:
+        """One batch of the paired plan from the group's resident raw frames: every frame under item.kind at item.intensity, its
+        randomness drawn from the source's own stream (frame_stream(source)), so only the intensity differs between levels."""
+        imgs, labels = raw
+        n = item.n
+        conds = [item.kind] * n
+        ids = list(range(item.start, item.start + n))
+        h, w = self.image_size
+        image = torch.empty(n, 3, h, w, dtype=torch.float32, device=self.device)
+        batch = {"image": image, "label": labels, "weather_condition": conds, "dataset": ["synthetic"] * n, "source": ids,
+                 "severity": item.level}
+        intens = None if item.level == 0 else [item.intensity] * n
+        if self.depth_preprocessor is None:
+            self.weather_transforms.apply_batch(imgs, conds, intensities=intens, norm_out=image, frame_ids=ids)
+        else:
+            frames = torch.empty_like(imgs)
+            self.weather_transforms.apply_batch(imgs, conds, intensities=intens, out=frames, norm_out=image, frame_ids=ids)
+            batch["depth"] = self.depth_preprocessor.estimate_depth_batch(frames)
+        return batch
+
     def batches(self, batch_size: int, drop_last: bool = False, rank: int = 0, world_size: int = 1) -> Iterator[Dict[str, object]]:
-        """Contiguous block sharding of the sample index range over ranks."""
+        """Contiguous block sharding of the sample index range over ranks.  Paired schedule: the raw frames of a
+        group are generated once and stay resident while its clean batch and its K x S variant batches are rendered."""
+        if self.weather_schedule == "paired":
+            raw, key = None, None
+            for item in self.plan(batch_size, drop_last, rank, world_size):
+                if key != (item.start, item.n):
+                    raw, key = self.synth_raw(item.start, item.n), (item.start, item.n)
+                yield self.make_paired_batch(raw, item)
+            return
         per = (self.num_samples + world_size - 1) // world_size
         lo, hi = min(rank * per, self.num_samples), min((rank + 1) * per, self.num_samples)
         i = lo
@@ -196,6 +332,8 @@ class _Loader:
         return it
 
     def __len__(self):
+        if getattr(self.dataset, "weather_schedule", None) == "paired":
+            return len(self.dataset.plan(self.batch_size, self.drop_last, self.rank, self.world_size))
         per = (len(self.dataset) + self.world_size - 1) // self.world_size
         n = max(0, min((self.rank + 1) * per, len(self.dataset)) - self.rank * per)
         return n // self.batch_size if self.drop_last else (n + self.batch_size - 1) // self.batch_size

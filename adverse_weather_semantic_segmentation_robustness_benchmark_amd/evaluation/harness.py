@@ -27,7 +27,8 @@ import torch.nn.functional as F
 
 from .. import _native as N
 from .. import ops, parallel
-from .metrics import ConfidenceCalibration, RobustnessMetrics, calibration_from_stats
+from ..data.loader import resolve_severities, slot_name
+from .metrics import ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, iou_from_counts, severity_sweep_results
 
 logger = logging.getLogger(__name__)
 
@@ -68,7 +69,12 @@ class EvalState:
     """All cross-batch state of one evaluation run (device resident, additive)."""
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
-                 temperature_grid=None, calibration_condition: str = "clean"):
+                 temperature_grid=None, calibration_condition: str = "clean", sweep=None):
+        # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
+        # weather conditions; every counter below uses that one slot list
+        self.sweep = sweep
+        if sweep is not None:
+            conditions = sweep.slots()
         self.acc = metrics.new_accumulator(device)
         self.acc.conditions = list(conditions)
         self.acc.counts = ops.new_counts(metrics.num_classes, device, 1 + len(conditions))
@@ -82,6 +88,73 @@ class EvalState:
             temps = ops.calib_temperatures(temperature_grid)
             self.calib = {"temps": temps, "condition": calibration_condition, "pixels": 0,
                           "stats": ops.new_temperature_grid_stats(len(temps), num_bins, device, 1 + len(conditions))}
+        self.paired = None
+        if sweep is not None:
+            # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
+            # been counted yet; rows are reused once a source is done
+            self.paired = {"stats": ops.new_consistency_stats(metrics.num_classes, device, 1 + len(conditions)),
+                           "oob": torch.zeros(1, dtype=torch.int64, device=device), "rows": None, "free": [], "live": {},
+                           "done": set(), "variants": len(sweep.kinds) * sweep.levels, "scratch": None,
+                           "sources": torch.zeros(1, dtype=torch.int64, device=device)}
+
+    def _ref_rows(self, n: int, shape, device):
+        """n consecutive free rows of the clean-map buffer (grown when no run of n is free): the clean batch writes its maps there
+        directly."""
+        pd = self.paired
+        hw = int(np.prod(shape))
+        if pd["rows"] is not None and pd["rows"].shape[1] != hw:
+            raise ValueError("every frame of a severity sweep must have the same size")
+        free = sorted(pd["free"])
+        for i in range(len(free) - n + 1):
+            if free[i + n - 1] - free[i] == n - 1:
+                run = free[i:i + n]
+                pd["free"] = [r for r in pd["free"] if r not in run]
+                return run[0]
+        old = 0 if pd["rows"] is None else pd["rows"].shape[0]
+        new = torch.empty(max(2 * old, old + n), hw, dtype=torch.uint8, device=device)
+        if old:
+            new[:old].copy_(pd["rows"])
+        pd["free"] += list(range(old, new.shape[0]))
+        pd["rows"] = new
+        return self._ref_rows(n, shape, device)
+
+    def paired_pred_out(self, sources, severity, shape, device):
+        """Where this batch's prediction map goes: clean frames straight into fresh rows of the clean-map buffer, variants into
+        scratch.  Checks the order: a variant needs its source's clean frame first, and a clean frame comes once."""
+        pd, n = self.paired, len(sources)
+        if severity == 0:
+            for s in sources:
+                if s in pd["live"] or s in pd["done"]:
+                    raise ValueError(f"source {s}: its clean frame came twice")
+            r0 = self._ref_rows(n, shape, device)
+            for i, s in enumerate(sources):
+                pd["live"][s] = [r0 + i, pd["variants"]]
+            return pd["rows"][r0:r0 + n].view((n,) + tuple(shape))
+        for s in sources:
+            if s not in pd["live"]:
+                raise ValueError(f"source {s}: a corrupted frame came before its clean frame" if s not in pd["done"] else
+                                 f"source {s}: more corrupted frames than the sweep's {pd['variants']}")
+        numel = n * int(np.prod(shape))
+        if pd["scratch"] is None or pd["scratch"].numel() < numel:
+            pd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
+        return pd["scratch"][:numel].view((n,) + tuple(shape))
+
+    def update_consistency(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
+        """Count a variant batch's maps against its sources' clean maps (slot 0 + its condition slot); free the rows of sources whose
+        sweep is complete."""
+        pd = self.paired
+        if severity == 0:
+            return
+        rows = [pd["live"][s][0] for s in sources]
+        frame_ref = torch.tensor(rows, dtype=torch.int32).to(pred.device, non_blocking=True)
+        ops.prediction_consistency(pred, pd["rows"], frame_ref, labels, num_classes, pd["stats"], pd["oob"], cond)
+        for s in sources:
+            ent = pd["live"][s]
+            ent[1] -= 1
+            if ent[1] == 0:
+                del pd["live"][s]
+                pd["free"].append(ent[0])
+                pd["done"].add(s)
 
     def update_calibration(self, labels: torch.Tensor, cond, logits=None, members=None) -> None:
         """Grid NLL / ECE of this batch: from the two member maps (members = (seg1, seg2, mode, weights, T)) or materialised
@@ -122,6 +195,13 @@ class EvalState:
             # the ranks' pixel counts travel in the same message: the budget is that of the SUMMED counters
             pixels = torch.tensor([self.calib["pixels"]], dtype=torch.int64, device=self.calib["stats"].device)
             ts += [self.calib["stats"], pixels]
+        pd = getattr(self, "paired", None)
+        if pd is not None:
+            if pd["live"]:
+                raise ValueError(f"severity sweep incomplete: {len(pd['live'])} source(s) lack corrupted frames, "
+                                 f"e.g. source {min(pd['live'])}")
+            pd["sources"].fill_(len(pd["done"]))
+            ts += [pd["stats"], pd["oob"], pd["sources"]]
         parallel.all_reduce_sum_(ts)
         if pixels is not None:
             check_calibration_budget(int(pixels.item()))
@@ -141,10 +221,23 @@ STATS_ONE_PASS = os.environ.get("AWSEG_STATS_ONE_PASS", "1") != "0"
 
 @torch.no_grad()
 def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor, conds, metrics: RobustnessMetrics,
-               with_stats: bool = True) -> None:
+               with_stats: bool = True, *, sources=None, severity=None) -> None:
     """One batch of the evaluation loop (evaluate.py:166-200 + the per-batch share of :203-255): forward, argmax,
     confusion per condition, and (with_stats) the ECE bins and the disagreement histogram — all into `st`'s
-    device counters.  Nothing per-pixel survives the call."""
+    device counters.  Nothing per-pixel survives the call.
+    Severity sweep (st.sweep): `sources` (global indices) and `severity` (0 clean, 1..S) of the batch; conds are its kinds.  The
+    batch's prediction map is kept (clean) or compared with its sources' clean maps (variants)."""
+    pred_out = None
+    if st.sweep is not None:
+        if sources is None or severity is None:
+            raise ValueError("a severity sweep needs the paired loader's 'source' and 'severity' for every batch")
+        severity = int(severity[0] if isinstance(severity, (list, tuple)) else severity)
+        sources = [int(s) for s in sources]
+        conds = [slot_name(c, severity) for c in conds]
+        unknown = sorted({c for c in conds if c not in st.acc.conditions})
+        if unknown:
+            raise ValueError(f"batch conditions {unknown} are not slots of the severity sweep")
+        pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     if labels.dtype not in (torch.uint8, torch.int64):
         labels = labels.long()
@@ -153,7 +246,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         fused_stats = metrics.num_classes == 19 and strategy != "max_confidence" and images[0, 0].numel() % 4 == 0
         need_logits = (with_stats or st.calib is not None) and not fused_stats
         one_pass = (st.edges, st.ece, st.auroc, AUROC_LO, AUROC_HI) if (with_stats and fused_stats and STATS_ONE_PASS) else None
-        res = model.forward_eval(images, labels, st.acc.counts, st.acc.oob, cond, want_logits=need_logits, want_pred=False, stats=one_pass)
+        res = model.forward_eval(images, labels, st.acc.counts, st.acc.oob, cond, want_logits=need_logits, want_pred=False, stats=one_pass,
+                                 pred_out=pred_out)
         if st.calib is not None:
             if fused_stats:                                       # grid statistics of combine(s1, s2)/T from the two member maps
                 mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
@@ -178,11 +272,13 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     else:
         logits = model(images)["segmentation"].float().contiguous()
         ops.combine_argmax_confusion(logits, None, 3, want_logits=False, label=labels.contiguous(), counts=st.acc.counts,
-                                     oob=st.acc.oob, cond=cond)
+                                     oob=st.acc.oob, cond=cond, pred_out=pred_out)
         if with_stats:
             ops.ece_accumulate(logits, labels, st.ece, st.edges, cond)
         if st.calib is not None:
             st.update_calibration(labels, cond, logits=logits)
+    if pred_out is not None:
+        st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
 
 
@@ -192,13 +288,20 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
     conditions = list(_cfg(config, "data.weather_conditions", []))
     num_bins = int(_cfg(config, "evaluation.num_bins", 15))
     is_ensemble = hasattr(model, "segformer") and hasattr(model, "deeplabv3plus")
+    spec = _cfg(config, "evaluation.severities", None)
+    sweep = None
+    if spec is not None:
+        ds = getattr(test_loader, "dataset", None)
+        rng = getattr(getattr(ds, "weather_transforms", None), "rng", "philox")
+        sweep = resolve_severities(spec, conditions, rng)
     st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
-                   calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")))
+                   calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep)
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
-        eval_batch(model, st, images, labels, batch.get("weather_condition", ["clean"] * images.size(0)), metrics)
+        extra = {"sources": batch.get("source"), "severity": batch.get("severity")} if sweep is not None else {}
+        eval_batch(model, st, images, labels, batch.get("weather_condition", ["clean"] * images.size(0)), metrics, **extra)
     return finalize(st, metrics)
 
 
@@ -224,6 +327,28 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         results["ensemble_disagreement_auroc"] = st.auroc_value()
         results["ensemble_disagreement_auroc_bins"] = float(AUROC_BINS)             # rank histogram, not exact ranks:
         results["ensemble_disagreement_auroc_tolerance"] = AUROC_TOLERANCE           # |device - sklearn| bound the tests assert
+    if st.sweep is not None:
+        # per kind: its severity slots summed (the counters are additive), so miou_<kind> / ece_<kind> / robustness_degradation_<kind>
+        # keep their meaning over the kind's frames
+        pd = st.paired
+        if int(pd["oob"].item()):
+            raise IndexError("prediction map value outside [0, num_classes) in the consistency counters")
+        slots = st.acc.conditions
+        for kind in st.sweep.kinds:
+            idx = [1 + slots.index(slot_name(kind, j)) for j in range(1, st.sweep.levels + 1)]
+            cnt = st.acc.counts[idx].sum(0)
+            if int(cnt.sum().item()) > 0:
+                weather_mious[kind] = iou_from_counts(cnt, metrics.num_classes)["mean_iou"]
+                results[f"miou_{kind}"] = weather_mious[kind]
+            kb = bins[idx[0]].copy()
+            for i in idx[1:]:
+                for f in ("count", "sum_conf", "sum_correct"):
+                    kb[f] += bins[i][f]
+            if kb["count"].sum() > 0:
+                results[f"ece_{kind}"] = ConfidenceCalibration.ece_from_bins(kb)
+        results.update(severity_sweep_results(ops.consistency_stats_to_numpy(pd["stats"], metrics.num_classes), slots,
+                                              st.sweep.kinds, st.sweep.levels, st.sweep.intensities, int(pd["sources"].item()),
+                                              weather_mious, metrics.compute_robustness_degradation_ratio))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

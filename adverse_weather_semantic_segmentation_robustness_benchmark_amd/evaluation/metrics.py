@@ -262,6 +262,55 @@ def calibration_from_stats(stats: Dict[str, np.ndarray], temps, conditions, fit_
     return res
 
 
+def _agreement(a: np.ndarray) -> Optional[float]:
+    total = int(a.sum())
+    return None if total == 0 else float(np.trace(a)) / total
+
+
+def _corruption_error_rate(t: np.ndarray) -> float:
+    ref_correct = int(t[0]) + int(t[1])
+    return float(int(t[1]) / ref_correct) if ref_correct > 0 else 0.0
+
+
+def severity_sweep_results(cons: Dict[str, np.ndarray], slots: List[str], kinds, levels: int, intensities: Dict[str, Any],
+                           sources: int, mious: Dict[str, float], degradation=None) -> Dict[str, float]:
+    """Result keys of the paired severity sweep from the decoded consistency counters (ops.consistency_stats_to_numpy: slot 0 = every
+    corrupted frame, slot 1 + k = slots[k]) and the mIoUs already derived from the confusion counters (`mious`: 'clean', each
+    '<kind>_s<j>' present).  Host only; every value a float.
+      consistency            trace(A) / sum(A): pixel agreement of the corrupted prediction with the clean one
+      consistency_miou       mIoU of the corrupted prediction with the clean prediction as the target (iou_from_counts on A)
+      corruption_error_rate  labelled pixels the clean prediction gets right and the corrupted one wrong, over those it gets right
+    Pooled keys (per kind, over every kind) come from the summed counters, not from means of ratios."""
+    degradation = degradation or RobustnessMetrics().compute_robustness_degradation_ratio
+    A, T = np.asarray(cons["agreement"], np.int64), np.asarray(cons["transitions"], np.int64)
+    C = A.shape[-1]
+    res: Dict[str, float] = {"paired_sources": float(sources), "severity_levels": float(levels)}
+    for kind in kinds:
+        a_kind, t_kind = np.zeros((C, C), np.int64), np.zeros(4, np.int64)
+        for j in range(1, levels + 1):
+            name = f"{kind}_s{j}"
+            s = 1 + slots.index(name)
+            res[f"severity_intensity_{name}"] = float(intensities[kind][j - 1])
+            if "clean" in mious and name in mious:
+                res[f"robustness_degradation_{name}"] = float(degradation(mious["clean"], mious[name]))
+            agree = _agreement(A[s])
+            if agree is None:
+                continue
+            a_kind += A[s]
+            t_kind += T[s]
+            res[f"consistency_{name}"] = agree
+            res[f"consistency_miou_{name}"] = float(iou_from_counts(torch.from_numpy(A[s].reshape(-1).copy()), C)["mean_iou"])
+            res[f"corruption_error_rate_{name}"] = _corruption_error_rate(T[s])
+        agree = _agreement(a_kind)
+        if agree is not None:
+            res[f"consistency_{kind}"] = agree
+    agree = _agreement(A[0])
+    if agree is not None:
+        res["mean_consistency"] = agree
+        res["mean_corruption_error_rate"] = _corruption_error_rate(T[0])
+    return res
+
+
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""
 

@@ -32,7 +32,33 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += ["", "## Confidence Calibration", "", f"- **Expected Calibration Error**: {results['expected_calibration_error']:.3f}"]
     if "ensemble_disagreement_auroc" in results:
         lines += ["", "## Ensemble Performance", "", f"- **Disagreement AUROC**: {results['ensemble_disagreement_auroc']:.3f}"]
+    if "severity_levels" in results:
+        lines += severity_section(results)
     return "\n".join(lines)
+
+
+def severity_section(results: Dict[str, Any]) -> list:
+    """The paired severity sweep (evaluation.severities): one table per adverse kind, one row per level."""
+    levels = int(results["severity_levels"])
+    kinds = [k for k in dict.fromkeys(key[len("severity_intensity_"):].rsplit("_s", 1)[0] for key in results
+                                      if key.startswith("severity_intensity_"))]
+    lines = ["", "## Severity Sweep", "", f"{int(results.get('paired_sources', 0))} source frames, each also rendered under every "
+             f"kind at {levels} severity levels; consistency and corruption error rate compare with the clean frame's prediction."]
+    if "mean_consistency" in results:
+        lines.append(f"- **Mean Consistency**: {results['mean_consistency']:.3f}")
+    if "mean_corruption_error_rate" in results:
+        lines.append(f"- **Mean Corruption Error Rate**: {results['mean_corruption_error_rate']:.3f}")
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    for kind in kinds:
+        lines += ["", f"### {kind.title()}", "", "| Level | Intensity | mIoU | Degradation | Consistency | Corruption Error Rate |",
+                  "|-------|-----------|------|-------------|-------------|-----------------------|"]
+        for j in range(1, levels + 1):
+            n = f"{kind}_s{j}"
+            lines.append(f"| {j} | {cell('severity_intensity_' + n)} | {cell('miou_' + n)} | {cell('robustness_degradation_' + n)} | "
+                         f"{cell('consistency_' + n)} | {cell('corruption_error_rate_' + n)} |")
+    return lines
 
 
 def generate_evaluation_report(results: Dict[str, Any], output_dir, target_metrics: Optional[Dict[str, float]] = None) -> None:

@@ -391,10 +391,12 @@ class EnsembleModel(nn.Module):
     @torch.no_grad()
     def forward_eval(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
                      oob: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, want_logits: bool = True,
-                     want_pred: bool = True, pred_dtype=torch.int64, stats=None) -> Dict[str, torch.Tensor]:
+                     want_pred: bool = True, pred_dtype=torch.int64, stats=None, pred_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """members -> ONE pass: combine, /temperature, argmax, confusion (slots: overall + condition).
         stats = (edges, ece_bins, auroc_hist, lo, hi): also accumulate the calibration / disagreement statistics in that pass
-        when nothing per-pixel is asked for (`self._stats_fused` tells the caller whether it happened)."""
+        when nothing per-pixel is asked for (`self._stats_fused` tells the caller whether it happened).
+        pred_out (uint8 [B, H, W]): the prediction map is written there, by that one pass where it runs (no second read of the
+        member logits), else by the combine kernel; it is also returned as res['prediction']."""
         # (no channels-last copy of the frames here: both 7x7 stems read the zero-padded 4-channel image that fused._stem_rows builds
         # from the input in whatever layout it has — once per forward, shared through stem_scope; a member whose stem does not take
         # that path converts for itself)
@@ -431,14 +433,16 @@ class EnsembleModel(nn.Module):
                 and mode in (N.COMBINE_WEIGHTED, N.COMBINE_MEAN) and o1["segmentation"].shape[1] == 19
                 and o1["segmentation"][0, 0].numel() % 4 == 0):
             # confusion + ECE bins + disagreement histogram in ONE pass over the member logits (stats = (edges, ece, auroc, lo, hi))
-            ops.combine_confusion_stats(o1["segmentation"], o2["segmentation"], mode, w, T, labels, cond, counts, oob, *stats)
-            logits, pred = None, None
+            ops.combine_confusion_stats(o1["segmentation"], o2["segmentation"], mode, w, T, labels, cond, counts, oob, *stats,
+                                        pred_out=pred_out)
+            logits, pred = None, pred_out
             self._stats_fused = True
         else:
             self._stats_fused = False
             logits, pred = ops.combine_argmax_confusion(o1["segmentation"], o2["segmentation"], mode, w, T,
-                                                        want_logits=want_logits, want_pred=want_pred, pred_dtype=pred_dtype,
-                                                        label=labels, counts=counts, oob=oob, cond=cond)
+                                                        want_logits=want_logits, want_pred=want_pred or pred_out is not None,
+                                                        pred_dtype=torch.uint8 if pred_out is not None else pred_dtype,
+                                                        label=labels, counts=counts, oob=oob, cond=cond, pred_out=pred_out)
         res = {"segformer_seg": o1["segmentation"], "deeplabv3plus_seg": o2["segmentation"]}
         if logits is not None:
             res["segmentation"] = logits

@@ -75,14 +75,20 @@ def combine_argmax_confusion(seg1: torch.Tensor, seg2: Optional[torch.Tensor], m
                              want_logits: bool = True, want_pred: bool = False, pred_dtype=torch.int64,
                              label: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
                              oob: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None,
-                             ignore_index: int = 255, wrap_u8: Optional[bool] = None):
+                             ignore_index: int = 255, wrap_u8: Optional[bool] = None, pred_out: Optional[torch.Tensor] = None):
     """PKG/models/model.py:443-462 (+ argmax evaluate.py:179, + confusion metrics.py:54-71).
-    seg2 None -> single-model argmax(+confusion)."""
+    seg2 None -> single-model argmax(+confusion).  pred_out: the prediction map goes there (its dtype, uint8 or int64;
+    want_pred and pred_dtype are then implied)."""
     seg1 = seg1.contiguous()
     b, c = seg1.shape[0], seg1.shape[1]
     hw = seg1[0, 0].numel()
     out = torch.empty_like(seg1) if (want_logits and seg2 is not None) else None
-    pred = torch.empty((b,) + tuple(seg1.shape[2:]), dtype=pred_dtype, device=seg1.device) if want_pred else None
+    if pred_out is not None:
+        if pred_out.numel() != b * hw or pred_out.device != seg1.device:
+            raise ValueError(f"pred_out must hold {b} x {hw} predictions on {seg1.device}")
+        pred = pred_out
+    else:
+        pred = torch.empty((b,) + tuple(seg1.shape[2:]), dtype=pred_dtype, device=seg1.device) if want_pred else None
     ws = None
     ldt = N.U8
     if label is not None:
@@ -139,18 +145,56 @@ def ensemble_eval_stats(seg1: torch.Tensor, seg2: torch.Tensor, mode: int, weigh
 
 def combine_confusion_stats(seg1: torch.Tensor, seg2: torch.Tensor, mode: int, weights, temperature, label: torch.Tensor, cond,
                             counts: torch.Tensor, oob: torch.Tensor, edges: torch.Tensor, ece_bins: torch.Tensor,
-                            auroc_hist: torch.Tensor, lo: float, hi: float, ignore_index: int = 255, wrap_u8: Optional[bool] = None) -> None:
-    """combine_argmax_confusion (confusion counters only) + ensemble_eval_stats in one pass over the member logits."""
+                            auroc_hist: torch.Tensor, lo: float, hi: float, ignore_index: int = 255, wrap_u8: Optional[bool] = None,
+                            pred_out: Optional[torch.Tensor] = None) -> None:
+    """combine_argmax_confusion (confusion counters only) + ensemble_eval_stats in one pass over the member logits.
+    pred_out (uint8 [B, H, W]): the same pass also writes the prediction map there (awseg_combine_confusion_stats_pred)."""
     seg1, seg2, label = seg1.contiguous(), seg2.contiguous(), label.contiguous()
     b, c = seg1.shape[0], seg1.shape[1]
     hw = seg1[0, 0].numel()
     if wrap_u8 is None:
         wrap_u8 = label.dtype == torch.uint8
     ws = N.workspace.get(seg1.device, N.lib().awseg_metrics_workspace(b, c, hw))
-    N.call("awseg_combine_confusion_stats", N.ptr(seg1), N.ptr(seg2), b, c, hw, mode, N.ptr(weights), N.ptr(temperature), N.ptr(label),
-           N.label_dtype(label), int(ignore_index), int(bool(wrap_u8)), N.ptr(cond), N.ptr(counts), counts.shape[0], N.ptr(oob),
-           N.ptr(edges), ece_bins.shape[1], N.ptr(ece_bins), ece_bins.shape[0], N.ptr(auroc_hist), auroc_hist.shape[1], float(lo),
-           float(hi), N.ptr(ws), N.stream())
+    args = (N.ptr(seg1), N.ptr(seg2), b, c, hw, mode, N.ptr(weights), N.ptr(temperature), N.ptr(label), N.label_dtype(label),
+            int(ignore_index), int(bool(wrap_u8)), N.ptr(cond), N.ptr(counts), counts.shape[0], N.ptr(oob), N.ptr(edges),
+            ece_bins.shape[1], N.ptr(ece_bins), ece_bins.shape[0], N.ptr(auroc_hist), auroc_hist.shape[1], float(lo), float(hi))
+    if pred_out is None:
+        N.call("awseg_combine_confusion_stats", *args, N.ptr(ws), N.stream())
+        return
+    if pred_out.dtype != torch.uint8 or pred_out.numel() != b * hw:
+        raise ValueError(f"pred_out must be uint8 with {b} x {hw} elements")
+    N.call("awseg_combine_confusion_stats_pred", *args, N.ptr(pred_out), N.ptr(ws), N.stream())
+
+
+def new_consistency_stats(num_classes: int, device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, C*C + 4]: the agreement matrix A[ref class, variant class] and four transition counts per slot."""
+    return torch.zeros(n_slots, num_classes * num_classes + 4, dtype=torch.int64, device=device)
+
+
+def prediction_consistency(pred: torch.Tensor, ref_maps: torch.Tensor, frame_ref: torch.Tensor, label: torch.Tensor, num_classes: int,
+                           stats: torch.Tensor, oob: torch.Tensor, cond: Optional[torch.Tensor] = None, ignore_index: int = 255) -> None:
+    """Count the uint8 prediction maps `pred` [B, ...] against rows `frame_ref` (device int32 [B], < 0 skips a frame) of the clean
+    maps `ref_maps` [R, ...] into `stats` (new_consistency_stats; slot 0 + slot 1 + cond[b]); map values >= C go to `oob`."""
+    pred, ref_maps, label = pred.contiguous(), ref_maps.contiguous(), label.contiguous()
+    b, r = pred.shape[0], ref_maps.shape[0]
+    hw = pred[0].numel()
+    if pred.dtype != torch.uint8 or ref_maps.dtype != torch.uint8:
+        raise ValueError("prediction maps must be uint8")
+    if ref_maps[0].numel() != hw or label.numel() != b * hw or frame_ref.numel() != b or frame_ref.dtype != torch.int32:
+        raise ValueError("prediction_consistency: pred [B, HW], ref_maps [R, HW], label [B, HW], frame_ref int32 [B]")
+    if stats.shape[-1] != num_classes * num_classes + 4:
+        raise ValueError(f"consistency stats rows hold {num_classes}^2 + 4 counters")
+    ws = N.workspace.get(pred.device, N.lib().awseg_consistency_workspace(b, num_classes, hw), tag="consistency")
+    N.call("awseg_prediction_consistency", N.ptr(pred), N.ptr(ref_maps), r, b, hw, N.ptr(frame_ref), N.ptr(label), N.label_dtype(label),
+           int(ignore_index), int(num_classes), N.ptr(cond), N.ptr(stats), stats.shape[0], N.ptr(oob), N.ptr(ws), N.stream())
+
+
+def consistency_stats_to_numpy(stats, num_classes: int) -> dict:
+    """int64 [slots, C*C + 4] -> {'agreement' [slots, C, C] (rows: clean class, columns: variant class), 'transitions' [slots, 4]
+    (both correct, clean correct + variant wrong, clean wrong + variant correct, both wrong)}."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    c2 = num_classes * num_classes
+    return {"agreement": raw[..., :c2].reshape(raw.shape[:-1] + (num_classes, num_classes)), "transitions": raw[..., c2:c2 + 4]}
 
 
 ECE_CONF_UNIT = 2.0 ** -30     # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent

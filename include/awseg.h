@@ -857,6 +857,45 @@ int awseg_combine_confusion_stats(const float* seg1, const float* seg2, int64_t 
                                   void* ece_bins, int ece_slots, int64_t* auroc_hist, int n_hist, float hist_lo,
                                   float hist_hi, void* workspace, awseg_stream_t stream);
 
+/* awseg_combine_confusion_stats plus the prediction map: pred uint8 [B, hw] receives argmax(combine(seg1, seg2) / T) under the
+ * rule the confusion counts use (torch's: the first maximum, NaN wins) for EVERY pixel, labelled 255 or out of range included
+ * -- byte for byte what awseg_combine_argmax_confusion writes to a uint8 prediction map.  Counts, ECE bins and histogram are
+ * bit-identical to awseg_combine_confusion_stats'.  pred 4-byte aligned (AWSEG_EALIGN otherwise), NULL is AWSEG_EINVAL; every
+ * other argument, size limit and error code as awseg_combine_confusion_stats.  One uint8 store per pixel on top of that pass:
+ * the clean frames of the paired severity sweep (awseg_prediction_consistency) keep their map without a second read of the
+ * member logits. */
+int awseg_combine_confusion_stats_pred(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,
+                                       int mode, const float* weights, const float* temperature, const void* label,
+                                       int label_dtype, int ignore_index, int label_wrap_u8, const int32_t* cond,
+                                       int64_t* counts, int count_slots, int64_t* oob, const float* edges, int n_bins,
+                                       void* ece_bins, int ece_slots, int64_t* auroc_hist, int n_hist, float hist_lo,
+                                       float hist_hi, uint8_t* pred, void* workspace, awseg_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
+ *  Prediction consistency against the clean frame (paired severity sweep)
+ * ------------------------------------------------------------------------- *
+ * pred uint8 [B, hw]: the prediction maps of B corrupted frames.  ref_maps uint8 [n_refs, hw]: clean prediction maps;
+ * frame_ref device int32[B]: the row of ref_maps frame b is compared with (< 0: frame b is skipped; >= n_refs: frame b is not
+ * counted and adds hw to oob).  label uint8 / int64 [B, hw] (label_dtype), ignore_index; C = num_classes <= AWSEG_MAX_CLASSES.
+ * stats int64 [n_slots][C * C + 4], slot rule of the confusion counters: every frame into slot 0 and into slot 1 + cond[b] when
+ * 0 <= cond[b] < n_slots - 1 (cond NULL: slot 0 only).  Row layout:
+ *     [r * C + p]  r = reference (clean) class, p = variant class, over EVERY pixel, labelled or not
+ *     [C * C + 0]  labelled pixels where both maps equal the label
+ *     [C * C + 1]  reference correct, variant wrong
+ *     [C * C + 2]  reference wrong, variant correct
+ *     [C * C + 3]  both wrong
+ * A labelled pixel is one whose label is neither ignore_index nor outside [0, C).  A pixel whose map value (either map) is >= C
+ * adds 1 to oob (int64[1]) and nothing else.  Integer sums only: counts are independent of grid shape and batch split, and
+ * additive over launches and ranks.  Any hw < 2^31 (AWSEG_ERANGE beyond; batch <= 65535): 16 pixels per lane from 16-byte loads
+ * when hw % 16 == 0 and pred, ref_maps and label are 16-byte aligned, byte loads otherwise.  workspace:
+ * awseg_consistency_workspace(batch, num_classes, hw) bytes.  AWSEG_EINVAL for a NULL pointer (cond excepted), a size < 1 or an
+ * unknown label dtype. */
+int64_t awseg_consistency_workspace(int64_t batch, int num_classes, int64_t hw);
+int awseg_prediction_consistency(const uint8_t* pred, const uint8_t* ref_maps, int n_refs, int64_t batch, int64_t hw,
+                                 const int32_t* frame_ref, const void* label, int label_dtype, int ignore_index,
+                                 int num_classes, const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob,
+                                 void* workspace, awseg_stream_t stream);
+
 /* ------------------------------------------------------------------------- *
  *  Streaming temperature calibration: per-pixel NLL and ECE bins at every temperature of a grid
  *       replaces PKG/evaluation/metrics.py:266-321 (temperature_scale + optimize_temperature's grid search, which needs every

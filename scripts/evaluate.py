@@ -50,12 +50,25 @@ def load_model(config, checkpoint_path, device):
     return model.to(device).eval()
 
 
+def parse_severities(text: str):
+    """--severities: 'reference' or '0.3,0.6,0.9' (validated with the configuration by the dataset)."""
+    text = text.strip()
+    if text == "reference":
+        return text
+    try:
+        return [float(v) for v in text.split(",") if v.strip()]
+    except ValueError:
+        raise ValueError(f"--severities takes 'reference' or comma-separated intensities, got {text!r}") from None
+
+
 def main():
     ap = argparse.ArgumentParser(description="Evaluate adverse-weather segmentation model (MI355X-native path)")
     ap.add_argument("checkpoint", type=str)
     ap.add_argument("--config", type=str, default=None)
     ap.add_argument("--output-dir", type=str, default="evaluation_results")
     ap.add_argument("--device", type=str, default="auto")
+    ap.add_argument("--severities", type=str, default=None,
+                    help="paired severity sweep: 'reference' or comma-separated intensities (overrides evaluation.severities)")
     args = ap.parse_args()
     try:
         config = load_config(args.config) if args.config else create_default_config()
@@ -64,10 +77,14 @@ def main():
         dev = get_device_config(args.device if args.device != "auto" else config.get("device", "auto"))
         device = torch.device(dev, local) if dev.startswith("cuda") and ":" not in dev else torch.device(dev)
         model = load_model(config, args.checkpoint, device)
+        if args.severities is not None:
+            config.set("evaluation.severities", parse_severities(args.severities))
+        sev = config.get("evaluation.severities")
+        paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",
                                     image_size=tuple(config.get("data.image_size", [512, 1024])),
                                     weather_conditions=config.get("data.weather_conditions"), apply_augmentation=False,
-                                    include_depth=config.get("data.include_depth", True), device=device)
+                                    include_depth=config.get("data.include_depth", True), device=device, **paired)
         loader = create_dataloader(ds, batch_size=config.get("training.batch_size", 8), shuffle=False, rank=rank, world_size=world)
         metrics = RobustnessMetrics(num_classes=config.get("model.num_classes", 19), weather_conditions=config.get("data.weather_conditions"))
         results = evaluate_model(model, loader, metrics, device, config)

@@ -150,6 +150,24 @@ def main():
         lambda: ops.combine_confusion_stats(s1, s2, 0, wts, T, labels, cond, cnt6, oob1, edges, bins, hist, 0.0, 3.0), "hbm", (2 * C * 4 + 1) * px * B)
     cases["ensemble eval stats (ECE + disagreement hist)"] = (
         lambda: ops.ensemble_eval_stats(s1, s2, 0, wts, T, labels, cond, edges, bins, hist, 0.0, 3.0), "hbm", (2 * C * 4 + 1) * px * B)
+    pmap = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    cases["combine + confusion + ECE + disagreement + uint8 prediction map (one pass)"] = (
+        lambda: ops.combine_confusion_stats(s1, s2, 0, wts, T, labels, cond, cnt6, oob1, edges, bins, hist, 0.0, 3.0, pred_out=pmap), "hbm",
+        (2 * C * 4 + 2) * px * B)
+    # prediction consistency (paired severity sweep): clean maps of 16 x 16 blocks of one class, the variant agreeing on ~95 % of the
+    # pixels in coherent 32 x 32 patches (the hot diagonal: long runs of one agreement bin), and independent random maps
+    g = torch.Generator(device=dev).manual_seed(7)
+    ref_c = torch.randint(0, C, (B, H // 16, W // 16), device=dev, generator=g).to(torch.uint8).repeat_interleave(16, 1).repeat_interleave(16, 2)
+    flip = (torch.rand(B, H // 32, W // 32, device=dev, generator=g) < 0.05).repeat_interleave(32, 1).repeat_interleave(32, 2)
+    var_c = torch.where(flip, (ref_c + 1) % C, ref_c).contiguous()
+    ref_r = torch.randint(0, C, (B, H, W), device=dev, generator=g).to(torch.uint8)
+    var_r = torch.randint(0, C, (B, H, W), device=dev, generator=g).to(torch.uint8)
+    fref = torch.arange(B, dtype=torch.int32, device=dev)
+    cst, coob = ops.new_consistency_stats(C, dev, 6), torch.zeros(1, dtype=torch.int64, device=dev)
+    cases["prediction consistency, 95 % agreement in coherent regions"] = (
+        lambda: ops.prediction_consistency(var_c, ref_c, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
+    cases["prediction consistency, independent random maps"] = (
+        lambda: ops.prediction_consistency(var_r, ref_r, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
     for K in (100, 16):                      # streamed temperature calibration: K x C exponentials per pixel, issue-bound
         grid = ops.DEFAULT_TEMPERATURE_GRID if K == 100 else np.linspace(0.25, 4.0, K).astype(np.float32)
         tst = ops.new_temperature_grid_stats(K, 15, dev, 6)
