@@ -28,7 +28,8 @@ import torch.nn.functional as F
 from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
-from .metrics import ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, iou_from_counts, severity_sweep_results
+from .metrics import (ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, depth_metrics_from_stats, iou_from_counts,
+                      severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -65,11 +66,39 @@ def check_calibration_budget(pixels: int) -> None:
                             f"{pixels} would exceed that")
 
 
+def depth_options(config):
+    """`evaluation.depth_metrics` (bool, default off), `evaluation.depth_min` (finite, > 0, default 1e-3: the target is a [0, 1] map
+    that can touch 0, so the relative errors need a floor) and `evaluation.depth_target` ('frame': the loader's target, estimated
+    from the frame as rendered; 'clean': under a severity sweep every variant is scored against its clean frame's target).
+    -> None when off, else {'min': float, 'target': str}."""
+    on = _cfg(config, "evaluation.depth_metrics", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"evaluation.depth_metrics is true or false, got {on!r}")
+    target = _cfg(config, "evaluation.depth_target", "frame")
+    if target not in ("frame", "clean"):
+        raise ValueError(f"evaluation.depth_target is 'frame' or 'clean', got {target!r}")
+    md = _cfg(config, "evaluation.depth_min", 1e-3)
+    if isinstance(md, (bool, str)) or not isinstance(md, (int, float, np.floating, np.integer)) or not (np.isfinite(md) and md > 0):
+        raise ValueError(f"evaluation.depth_min must be a finite number > 0, got {md!r}")
+    if not on:
+        return None
+    if target == "clean" and _cfg(config, "evaluation.severities", None) is None:
+        raise ValueError("evaluation.depth_target: clean needs a severity sweep (evaluation.severities): without one a frame has no "
+                         "clean counterpart")
+    return {"min": float(md), "target": str(target)}
+
+
+def check_depth_budget(pixels: int) -> None:
+    """The depth counters are int64 sums of per-pixel terms up to 2^31 (include/awseg.h): raise before they could wrap."""
+    if pixels > ops.DEPTH_PIXEL_BUDGET:
+        raise OverflowError(f"depth error counters hold {ops.DEPTH_PIXEL_BUDGET} pixels (summed over ranks); {pixels} would exceed that")
+
+
 class EvalState:
     """All cross-batch state of one evaluation run (device resident, additive)."""
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
-                 temperature_grid=None, calibration_condition: str = "clean", sweep=None):
+                 temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -88,6 +117,15 @@ class EvalState:
             temps = ops.calib_temperatures(temperature_grid)
             self.calib = {"temps": temps, "condition": calibration_condition, "pixels": 0,
                           "stats": ops.new_temperature_grid_stats(len(temps), num_bins, device, 1 + len(conditions))}
+        # depth error sums (off unless depth = depth_options(config)): int64 [slot, series, AWSEG_DEPTH_ROW]
+        self.depth = None
+        if depth is not None:
+            if depth["target"] == "clean" and sweep is None:
+                raise ValueError("depth_target 'clean' needs a severity sweep")
+            # 'rows': under depth_target 'clean', the clean frames' targets, one float32 row per live source, at the row indices of
+            # the clean prediction maps (self.paired['rows']): allocated, reused and freed with them
+            self.depth = {"stats": ops.new_depth_eval_stats(device, 1 + len(conditions)), "min": float(depth["min"]),
+                          "target": depth["target"], "pixels": 0, "rows": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -156,6 +194,30 @@ class EvalState:
                 pd["free"].append(ent[0])
                 pd["done"].add(s)
 
+    def depth_target(self, target: torch.Tensor, sources, severity) -> torch.Tensor:
+        """The target this batch's depth maps are scored against, and the pixel budget check.  depth_target 'clean': a clean batch
+        (after paired_pred_out gave its sources their rows) leaves its targets in those rows, a variant batch gathers its sources'."""
+        d = self.depth
+        if target.dim() != 3 or target.dtype != torch.float32:
+            raise ValueError(f"the depth target is float32 [B, H, W], got {target.dtype} {tuple(target.shape)}")
+        check_depth_budget(d["pixels"] + target.numel())
+        d["pixels"] += target.numel()
+        if d["target"] != "clean":
+            return target
+        pd = self.paired
+        rows = [pd["live"][s][0] for s in sources]
+        n_rows, hw = pd["rows"].shape[0], target[0].numel()
+        if d["rows"] is None or d["rows"].shape[0] < n_rows:
+            new = torch.empty(n_rows, hw, dtype=torch.float32, device=target.device)
+            if d["rows"] is not None:
+                new[:d["rows"].shape[0]].copy_(d["rows"])
+            d["rows"] = new
+        idx = torch.tensor(rows, dtype=torch.int64).to(target.device, non_blocking=True)
+        if severity == 0:
+            d["rows"].index_copy_(0, idx, target.reshape(len(rows), hw))
+            return target
+        return d["rows"].index_select(0, idx).view(target.shape)
+
     def update_calibration(self, labels: torch.Tensor, cond, logits=None, members=None) -> None:
         """Grid NLL / ECE of this batch: from the two member maps (members = (seg1, seg2, mode, weights, T)) or materialised
         logits.  Raises before the fixed-point pixel budget of the counters would be exceeded."""
@@ -195,6 +257,10 @@ class EvalState:
             # the ranks' pixel counts travel in the same message: the budget is that of the SUMMED counters
             pixels = torch.tensor([self.calib["pixels"]], dtype=torch.int64, device=self.calib["stats"].device)
             ts += [self.calib["stats"], pixels]
+        depth_pixels = None
+        if getattr(self, "depth", None) is not None:
+            depth_pixels = torch.tensor([self.depth["pixels"]], dtype=torch.int64, device=self.depth["stats"].device)
+            ts += [self.depth["stats"], depth_pixels]
         pd = getattr(self, "paired", None)
         if pd is not None:
             if pd["live"]:
@@ -205,6 +271,8 @@ class EvalState:
         parallel.all_reduce_sum_(ts)
         if pixels is not None:
             check_calibration_budget(int(pixels.item()))
+        if depth_pixels is not None:
+            check_depth_budget(int(depth_pixels.item()))
 
     def auroc_value(self) -> float:
         neg, pos = self.auroc[0].double(), self.auroc[1].double()
@@ -221,12 +289,13 @@ STATS_ONE_PASS = os.environ.get("AWSEG_STATS_ONE_PASS", "1") != "0"
 
 @torch.no_grad()
 def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor, conds, metrics: RobustnessMetrics,
-               with_stats: bool = True, *, sources=None, severity=None) -> None:
+               with_stats: bool = True, *, sources=None, severity=None, depth=None) -> None:
     """One batch of the evaluation loop (evaluate.py:166-200 + the per-batch share of :203-255): forward, argmax,
     confusion per condition, and (with_stats) the ECE bins and the disagreement histogram — all into `st`'s
     device counters.  Nothing per-pixel survives the call.
     Severity sweep (st.sweep): `sources` (global indices) and `severity` (0 clean, 1..S) of the batch; conds are its kinds.  The
-    batch's prediction map is kept (clean) or compared with its sources' clean maps (variants)."""
+    batch's prediction map is kept (clean) or compared with its sources' clean maps (variants).
+    Depth metrics (st.depth): `depth` is the batch's target float32 [B, H, W]; the depth maps are scored in one pass and not kept."""
     pred_out = None
     if st.sweep is not None:
         if sources is None or severity is None:
@@ -239,6 +308,15 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             raise ValueError(f"batch conditions {unknown} are not slots of the severity sweep")
         pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
+    depth_kw = {}
+    if st.depth is not None:
+        if depth is None:
+            raise ValueError("evaluation.depth_metrics: the loader gives no depth target (batch['depth']; data.include_depth)")
+        if not getattr(model, "include_depth", True):
+            raise ValueError("evaluation.depth_metrics: the model has no depth head (model.include_depth)")
+        depth = st.depth_target(depth, sources, severity)
+        # the ensemble scores its three series in one pass and writes neither the upsampled nor the combined map
+        depth_kw = {"depth_stats": (depth, cond, st.depth["stats"], st.depth["min"]), "want_depth": False}
     if labels.dtype not in (torch.uint8, torch.int64):
         labels = labels.long()
     if st.auroc is not None:
@@ -247,7 +325,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         need_logits = (with_stats or st.calib is not None) and not fused_stats
         one_pass = (st.edges, st.ece, st.auroc, AUROC_LO, AUROC_HI) if (with_stats and fused_stats and STATS_ONE_PASS) else None
         res = model.forward_eval(images, labels, st.acc.counts, st.acc.oob, cond, want_logits=need_logits, want_pred=False, stats=one_pass,
-                                 pred_out=pred_out)
+                                 pred_out=pred_out, **depth_kw)
         if st.calib is not None:
             if fused_stats:                                       # grid statistics of combine(s1, s2)/T from the two member maps
                 mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
@@ -270,7 +348,12 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_auroc(res["segformer_seg"], res["deeplabv3plus_seg"], labels)
             ops.ece_accumulate(res["segmentation"], labels, st.ece, st.edges, cond)
     else:
-        logits = model(images)["segmentation"].float().contiguous()
+        out = model(images)
+        logits = out["segmentation"].float().contiguous()
+        if st.depth is not None:
+            if "depth" not in out:
+                raise ValueError("evaluation.depth_metrics: the model has no depth head (no 'depth' in its output)")
+            ops.depth_eval_stats(out["depth"].float(), None, None, depth, st.depth["stats"], st.depth["min"], cond)
         ops.combine_argmax_confusion(logits, None, 3, want_logits=False, label=labels.contiguous(), counts=st.acc.counts,
                                      oob=st.acc.oob, cond=cond, pred_out=pred_out)
         if with_stats:
@@ -296,11 +379,14 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
         sweep = resolve_severities(spec, conditions, rng)
     st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
-                   calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep)
+                   calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
+                   depth=depth_options(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
         extra = {"sources": batch.get("source"), "severity": batch.get("severity")} if sweep is not None else {}
+        if st.depth is not None:
+            extra["depth"] = None if batch.get("depth") is None else batch["depth"].to(device)
         eval_batch(model, st, images, labels, batch.get("weather_condition", ["clean"] * images.size(0)), metrics, **extra)
     return finalize(st, metrics)
 
@@ -349,6 +435,10 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         results.update(severity_sweep_results(ops.consistency_stats_to_numpy(pd["stats"], metrics.num_classes), slots,
                                               st.sweep.kinds, st.sweep.levels, st.sweep.intensities, int(pd["sources"].item()),
                                               weather_mious, metrics.compute_robustness_degradation_ratio))
+    if st.depth is not None:
+        results.update(depth_metrics_from_stats(st.depth["stats"].cpu().numpy(), st.acc.conditions,
+                                                kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                levels=st.sweep.levels if st.sweep is not None else 0))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

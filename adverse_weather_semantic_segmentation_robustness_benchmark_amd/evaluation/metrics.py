@@ -311,6 +311,69 @@ def severity_sweep_results(cons: Dict[str, np.ndarray], slots: List[str], kinds,
     return res
 
 
+DEPTH_METRICS = ("mae", "rmse", "abs_rel", "sq_rel", "rmse_log", "silog", "delta1", "delta2", "delta3")
+DEPTH_MEMBER_PREFIXES = ("", "segformer_", "deeplabv3plus_")      # series 0 / 1 / 2, the prefixes of the model's own depth keys
+
+
+def depth_row_metrics(row: np.ndarray) -> Optional[Dict[str, float]]:
+    """The depth metrics of one counter row (int64 [AWSEG_DEPTH_ROW], ops.DEPTH_FIELDS order); None when it has no valid pixel.
+    Means of the fixed-point sums over the valid count; silog's radicand is clamped at 0 (two separately rounded sums can leave it
+    a few units of 2^-20 negative where every pixel has the same log offset)."""
+    f = {name: int(row[i]) for i, name in enumerate(ops.DEPTH_FIELDS)}
+    n = f["valid"]
+    if n <= 0:
+        return None
+    mean = {k: f[k] * ops.DEPTH_UNIT / n for k in ("sum_abs", "sum_sq", "sum_abs_rel", "sum_sq_rel", "sum_log", "sum_log_sq")}
+    return {"mae": mean["sum_abs"], "rmse": float(np.sqrt(mean["sum_sq"])), "abs_rel": mean["sum_abs_rel"], "sq_rel": mean["sum_sq_rel"],
+            "rmse_log": float(np.sqrt(mean["sum_log_sq"])),
+            "silog": float(np.sqrt(max(mean["sum_log_sq"] - mean["sum_log"] ** 2, 0.0))),
+            "delta1": f["delta1"] / n, "delta2": f["delta2"] / n, "delta3": f["delta3"] / n}
+
+
+def depth_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0) -> Dict[str, float]:
+    """Result keys of the depth error counters (int64 [1 + len(conditions), 3, AWSEG_DEPTH_ROW]; slot 0 = every frame, slot 1 + k =
+    conditions[k]).  Host only; every value a float.
+      depth_<metric>[_<condition>]                          series 0: the ensemble, or the single model
+      segformer_depth_<metric>[_<condition>], deeplabv3plus_depth_<metric>[_<condition>]   the members (three-series counters)
+      depth_valid_fraction[_<condition>]                    valid / (valid + masked + non-finite) pixels
+      depth_saturated_terms, depth_masked_pixels, depth_nonfinite_pixels                  slot 0, only when non-zero
+      depth_degradation_<name> = (abs_rel_<name> - abs_rel_clean) / abs_rel_clean         when 'clean' has abs_rel > 0
+    Severity sweep (kinds, levels): conditions are its slots ('clean', '<kind>_s<j>'); each kind also gets keys from the summed
+    counters of its slots.  A slot without a valid pixel yields no keys."""
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.ndim != 3 or raw.shape[0] != 1 + len(conditions) or raw.shape[1:] != (len(ops.DEPTH_SERIES), ops.DEPTH_ROW):
+        raise ValueError(f"depth stats must be int64 [{1 + len(conditions)}, {len(ops.DEPTH_SERIES)}, {ops.DEPTH_ROW}], got {raw.shape}")
+    named = [("", raw[0])] + [("_" + name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        named.append(("_" + kind, raw[idx].sum(0)))
+    res: Dict[str, float] = {}
+    for suffix, slot in named:
+        got = False
+        for prefix, row in zip(DEPTH_MEMBER_PREFIXES, slot):
+            m = depth_row_metrics(row)
+            if m is None:
+                continue
+            got = True
+            for k in DEPTH_METRICS:
+                res[f"{prefix}depth_{k}{suffix}"] = float(m[k])
+        if got:
+            px = slot[0][:3].astype(np.float64)
+            res[f"depth_valid_fraction{suffix}"] = float(px[0] / px.sum())
+    i_sat, i_mask, i_bad = (ops.DEPTH_FIELDS.index(k) for k in ("saturated", "masked", "nonfinite"))
+    for key, v in (("depth_saturated_terms", int(raw[0, :, i_sat].sum())), ("depth_masked_pixels", int(raw[0, 0, i_mask])),
+                   ("depth_nonfinite_pixels", int(raw[0, 0, i_bad]))):
+        if v:
+            res[key] = float(v)
+    base = res.get("depth_abs_rel_clean", 0.0)
+    if base > 0:
+        for suffix, _ in named[1:]:
+            name = suffix[1:]
+            if name != "clean" and f"depth_abs_rel_{name}" in res:
+                res[f"depth_degradation_{name}"] = float((res[f"depth_abs_rel_{name}"] - base) / base)
+    return res
+
+
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""
 

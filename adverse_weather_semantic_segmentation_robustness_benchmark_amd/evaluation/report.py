@@ -34,7 +34,33 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += ["", "## Ensemble Performance", "", f"- **Disagreement AUROC**: {results['ensemble_disagreement_auroc']:.3f}"]
     if "severity_levels" in results:
         lines += severity_section(results)
+    if any(k.startswith("depth_abs_rel") for k in results):
+        lines += depth_section(results)
     return "\n".join(lines)
+
+
+def depth_section(results: Dict[str, Any]) -> list:
+    """Depth metrics (evaluation.depth_metrics): condition x metric for the ensemble (or the single model), one line per member."""
+    cols = ("abs_rel", "sq_rel", "mae", "rmse", "rmse_log", "silog", "delta1", "delta2", "delta3")
+    names = [""] + [k[len("depth_abs_rel_"):] for k in results if k.startswith("depth_abs_rel_")]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    lines = ["", "## Depth", "", "| Condition | " + " | ".join(cols) + " | Valid | Degradation |", "|---" * (len(cols) + 3) + "|"]
+    for n in names:
+        sfx = "_" + n if n else ""
+        lines.append(f"| {n or 'all'} | " + " | ".join(cell(f"depth_{c}{sfx}") for c in cols) +
+                     f" | {cell('depth_valid_fraction' + sfx)} | {cell('depth_degradation' + sfx) if n else '-'} |")
+    lines.append("")
+    for prefix, title in (("segformer_", "SegFormer"), ("deeplabv3plus_", "DeepLabV3+")):
+        if f"{prefix}depth_abs_rel" in results:
+            lines.append(f"- **{title}**: " + ", ".join(f"{c} = {results[f'{prefix}depth_{c}']:.3f}" for c in cols
+                                                        if f"{prefix}depth_{c}" in results))
+    for key, title in (("depth_masked_pixels", "Masked pixels (target below the floor)"), ("depth_nonfinite_pixels", "Non-finite pixels"),
+                       ("depth_saturated_terms", "Saturated terms")):
+        if key in results:
+            lines.append(f"- **{title}**: {int(results[key])}")
+    return lines
 
 
 def severity_section(results: Dict[str, Any]) -> list:

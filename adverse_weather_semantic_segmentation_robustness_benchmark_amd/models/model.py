@@ -391,12 +391,18 @@ class EnsembleModel(nn.Module):
     @torch.no_grad()
     def forward_eval(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
                      oob: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, want_logits: bool = True,
-                     want_pred: bool = True, pred_dtype=torch.int64, stats=None, pred_out: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                     want_pred: bool = True, pred_dtype=torch.int64, stats=None, pred_out: Optional[torch.Tensor] = None,
+                     depth_stats=None, want_depth: bool = True) -> Dict[str, torch.Tensor]:
         """members -> ONE pass: combine, /temperature, argmax, confusion (slots: overall + condition).
         stats = (edges, ece_bins, auroc_hist, lo, hi): also accumulate the calibration / disagreement statistics in that pass
         when nothing per-pixel is asked for (`self._stats_fused` tells the caller whether it happened).
         pred_out (uint8 [B, H, W]): the prediction map is written there, by that one pass where it runs (no second read of the
-        member logits), else by the combine kernel; it is also returned as res['prediction']."""
+        member logits), else by the combine kernel; it is also returned as res['prediction'].
+        depth_stats = (target [B, H, W], cond, stats, min_depth): the depth error sums of the ensemble and of both members against
+        `target` are added to `stats` (ops.new_depth_eval_stats) in one pass over the SegFormer map and DeepLab's stride-16 map.
+        want_depth=False: the upsampled and the combined depth map are not written and no depth key is returned."""
+        if depth_stats is not None and not self.include_depth:
+            raise ValueError("depth_stats needs a model with depth heads (include_depth)")
         # (no channels-last copy of the frames here: both 7x7 stems read the zero-padded 4-channel image that fused._stem_rows builds
         # from the input in whatever layout it has — once per forward, shared through stem_scope; a member whose stem does not take
         # that path converts for itself)
@@ -448,7 +454,12 @@ class EnsembleModel(nn.Module):
             res["segmentation"] = logits
         if pred is not None:
             res["prediction"] = pred
-        if self.include_depth:
+        if self.include_depth and depth_stats is not None:
+            target, dcond, dstats, min_depth = depth_stats
+            wd = fused.cached(self, "ens_softmax", [self.ensemble_weights], lambda: F.softmax(self.ensemble_weights, dim=0)) \
+                if self.ensemble_strategy == "weighted_average" else None
+            ops.depth_eval_stats(o1["depth"], o2["depth_low"] if "depth_low" in o2 else o2["depth"], wd, target, dstats, min_depth, dcond)
+        if self.include_depth and want_depth:
             if "depth_low" in o2:
                 wd = fused.cached(self, "ens_softmax", [self.ensemble_weights], lambda: F.softmax(self.ensemble_weights, dim=0)) \
                     if self.ensemble_strategy == "weighted_average" else None

@@ -283,6 +283,62 @@ def temperature_grid_stats_to_numpy(stats) -> dict:
             "nonfinite": rows[..., 3].copy(), "bins": bins, "out_of_range": raw[:, k, 0].copy()}
 
 
+# ----------------------------------------------------------------------------- depth error sums (include/awseg.h)
+DEPTH_UNIT = 2.0 ** -20                # fixed point of every real-valued term (AWSEG_DEPTH_FRAC_BITS)
+DEPTH_CAP = 2048.0                     # per-term clamp, counted as saturated (AWSEG_DEPTH_CAP)
+DEPTH_PIXEL_BUDGET = (1 << 32) - 1     # pixels one stats tensor holds, summed over ranks (AWSEG_DEPTH_PIXEL_BUDGET: x 2^31 < 2^63)
+DEPTH_SERIES = ("ensemble", "d1", "d2")            # AWSEG_DEPTH_SERIES_ENSEMBLE / _D1 / _D2; the one-series form fills row 0 only
+# AWSEG_DEPTH_VALID .. AWSEG_DEPTH_SATURATED, in row order (AWSEG_DEPTH_ROW = 13)
+DEPTH_FIELDS = ("valid", "masked", "nonfinite", "sum_abs", "sum_sq", "sum_abs_rel", "sum_sq_rel", "sum_log", "sum_log_sq",
+                "delta1", "delta2", "delta3", "saturated")
+DEPTH_ROW = len(DEPTH_FIELDS)
+DEPTH_THRESHOLDS = (1.25, 1.5625, 1.953125)        # 1.25, 1.25^2, 1.25^3: exact in float32
+
+
+def new_depth_eval_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, 3, 13], the layout include/awseg.h documents (zeroed: the launches accumulate)."""
+    return torch.zeros(n_slots, len(DEPTH_SERIES), DEPTH_ROW, dtype=torch.int64, device=device)
+
+
+def depth_eval_stats(d1: torch.Tensor, d2_low: Optional[torch.Tensor], weights: Optional[torch.Tensor], target: torch.Tensor,
+                     stats: torch.Tensor, min_depth: float = 1e-3, cond: Optional[torch.Tensor] = None) -> None:
+    """Depth error sums of d1 [B,(1,)H,W] (d2_low None: one series) or of the ensemble, d1 and the upsampled d2_low [B,(1,)h,w]
+    (three series; combined with weights [2], mean when None, exactly as depth_upsample_combine) against target [B,H,W],
+    accumulated into `stats` (new_depth_eval_stats; slot 0 + slot 1 + cond[b]).  No depth map is written."""
+    if stats.dim() != 3 or stats.dtype != torch.int64 or tuple(stats.shape[1:]) != (len(DEPTH_SERIES), DEPTH_ROW):
+        raise ValueError(f"stats must be int64 [slots, {len(DEPTH_SERIES)}, {DEPTH_ROW}] (new_depth_eval_stats), got "
+                         f"{stats.dtype} {tuple(stats.shape)}")
+    if d1.dtype != torch.float32 or target.dtype != torch.float32 or (d2_low is not None and d2_low.dtype != torch.float32):
+        raise ValueError("depth maps and the depth target must be float32")
+    H, W = d1.shape[-2:]
+    b = d1.shape[0] if d1.dim() > 2 else 1
+    if d1.numel() != b * H * W or tuple(target.shape[-2:]) != (H, W) or target.numel() != b * H * W:
+        raise ValueError(f"depth_eval_stats: d1 [B,(1,)H,W] and target [B,H,W] must agree, got {tuple(d1.shape)} and {tuple(target.shape)}")
+    h = w = 0
+    if d2_low is not None:
+        h, w = d2_low.shape[-2:]
+        if d2_low.numel() != b * h * w:
+            raise ValueError(f"depth_eval_stats: d2_low must be [B,(1,)h,w] with B = {b}, got {tuple(d2_low.shape)}")
+        d2_low = d2_low.contiguous()
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    if d1.numel() > DEPTH_PIXEL_BUDGET:
+        raise ValueError(f"{d1.numel()} pixels exceed the {DEPTH_PIXEL_BUDGET}-pixel budget of one stats tensor")
+    md = float(min_depth)
+    if not (np.isfinite(md) and md > 0):
+        raise ValueError(f"min_depth must be finite and > 0, got {min_depth}")
+    d1, target = d1.contiguous(), target.contiguous()
+    N.call("awseg_depth_eval_stats", N.ptr(d1), N.ptr(d2_low), b, h, w, H, W, N.ptr(None if weights is None else weights.contiguous()),
+           N.ptr(target), md, N.ptr(cond), N.ptr(stats), stats.shape[0], N.stream())
+
+
+def depth_eval_stats_to_numpy(stats) -> dict:
+    """Decode the int64 counters (a device tensor or a numpy array) into exact integer arrays [slots, series], one per name of
+    DEPTH_FIELDS (the sums in units of DEPTH_UNIT)."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    return {f: raw[..., i].copy() for i, f in enumerate(DEPTH_FIELDS)}
+
+
 # ----------------------------------------------------------------------------- A7
 def normalize(imgs: torch.Tensor, out: Optional[torch.Tensor] = None, sel: Optional[torch.Tensor] = None,
               mean=None, std=None) -> torch.Tensor:

@@ -953,6 +953,72 @@ int awseg_ensemble_temperature_grid_stats(const float* seg1, const float* seg2, 
                                           const float* temps, int n_temps, const float* edges, int n_bins,
                                           int64_t* stats, int n_slots, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Depth error sums of the evaluated depth maps against the depth target
+ *       scores what PKG/models/model.py:368-371, :471-478 predicts against the loader's batch["depth"]; the reference
+ *       evaluation (REF/scripts/evaluate.py) computes no depth metric, so the sums are the standard monocular set
+ * ------------------------------------------------------------------------- *
+ * d1 float32 [B,H,W]: a full-resolution depth map (SegFormer's, or a single model's).  d2_low float32 [B,h,w] or NULL: the
+ * second member's map (DeepLab's stride-16 map; h == H, w == W allowed).  target float32 [B,H,W].
+ *
+ * Series.  d2_low == NULL: one series, AWSEG_DEPTH_SERIES_ENSEMBLE = d1.  Otherwise three: AWSEG_DEPTH_SERIES_ENSEMBLE = the
+ * combined map, AWSEG_DEPTH_SERIES_D1 = d1, AWSEG_DEPTH_SERIES_D2 = d2_low upsampled bilinearly (align_corners=False) to [H,W].
+ * The upsampled and the combined value are formed in registers with the expressions and roundings of
+ * awseg_depth_upsample_combine (weights[0]*d1 + weights[1]*d2 with weights device float32[2], or (d1 + d2)/2 when weights is
+ * NULL): the one-series form on that entry point's d_out / d2_full gives the same rows bit for bit.  Neither map is written.
+ *
+ * Per pixel, t = target and p = a series' value:
+ *     non-finite  t or ANY series value is NaN or +-inf (d2_low: every output pixel whose four source texels include such a
+ *                 value, whatever their weights): counted, left out of everything else
+ *     masked      else t < min_depth: counted, left out
+ *     valid       else.  Per series  q = max(p, min_depth),  g = log(q) - log(t),  r = max(q / t, t / q),  and the terms
+ *                 |p-t|, (p-t)^2, |p-t|/t, (p-t)^2/t, g, g^2  plus the counts  r < 1.25f, r < 1.5625f, r < 1.953125f
+ *                 (strict; the three thresholds are exact in float32).  Every operation is float32 with IEEE division,
+ *                 except that the two logarithms of g are float64 and their difference is rounded to float32 once (a
+ *                 float32 logarithm's bias at a value many pixels share would enter the mean of g^2 times 2|g|).
+ *                 p below min_depth is clamped in g and r only, not in the differences.
+ *
+ * Integer sums only: every term is rounded to nearest in units of 2^-AWSEG_DEPTH_FRAC_BITS (2^-20) and clamped at
+ * AWSEG_DEPTH_CAP (2^11) in magnitude, each clamped term adding 1 to its series' saturated count (g is signed, its sum a
+ * two's-complement int64).  Results do not depend on launch geometry, batch split or rank count.  Pixel budget of one stats
+ * tensor: AWSEG_DEPTH_PIXEL_BUDGET = 2^32 - 1 pixels ((2^32 - 1) x 2^31 < 2^63), the bound and the reasoning of
+ * AWSEG_CALIB_PIXEL_BUDGET; it holds for the tensor after any cross-rank sum.
+ *
+ * Output (accumulated, never cleared): stats int64 [n_slots][AWSEG_DEPTH_SERIES][AWSEG_DEPTH_ROW], every frame into slot 0 and
+ * into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0 only).  The one-series form
+ * touches row AWSEG_DEPTH_SERIES_ENSEMBLE only.  Row layout (the three pixel counts are the same in every row of a call):
+ *     [AWSEG_DEPTH_VALID] [AWSEG_DEPTH_MASKED] [AWSEG_DEPTH_NONFINITE]                      pixels
+ *     [AWSEG_DEPTH_SUM_ABS] [.._SUM_SQ] [.._SUM_ABS_REL] [.._SUM_SQ_REL] [.._SUM_LOG] [.._SUM_LOG_SQ]   units of 2^-20
+ *     [AWSEG_DEPTH_DELTA1] [.._DELTA2] [.._DELTA3]                                          valid pixels under the threshold
+ *     [AWSEG_DEPTH_SATURATED]                                                               clamped terms
+ * Any H, W with H*W < 2^31 and batch <= 65535 (AWSEG_ERANGE beyond): four pixels per lane from 16-byte loads when W % 4 == 0
+ * and d1 and target are 16-byte aligned, one otherwise.  No workspace.  batch == 0 returns 0.  AWSEG_EINVAL for a NULL d1,
+ * target or stats, min_depth not finite or not > 0, or a size < 1 (low_height / low_width are read only with d2_low). */
+#define AWSEG_DEPTH_FRAC_BITS        20
+#define AWSEG_DEPTH_CAP              2048
+#define AWSEG_DEPTH_PIXEL_BUDGET     ((1LL << 32) - 1)
+#define AWSEG_DEPTH_SERIES           3
+#define AWSEG_DEPTH_SERIES_ENSEMBLE  0
+#define AWSEG_DEPTH_SERIES_D1        1
+#define AWSEG_DEPTH_SERIES_D2        2
+#define AWSEG_DEPTH_VALID            0
+#define AWSEG_DEPTH_MASKED           1
+#define AWSEG_DEPTH_NONFINITE        2
+#define AWSEG_DEPTH_SUM_ABS          3
+#define AWSEG_DEPTH_SUM_SQ           4
+#define AWSEG_DEPTH_SUM_ABS_REL      5
+#define AWSEG_DEPTH_SUM_SQ_REL       6
+#define AWSEG_DEPTH_SUM_LOG          7
+#define AWSEG_DEPTH_SUM_LOG_SQ       8
+#define AWSEG_DEPTH_DELTA1           9
+#define AWSEG_DEPTH_DELTA2           10
+#define AWSEG_DEPTH_DELTA3           11
+#define AWSEG_DEPTH_SATURATED        12
+#define AWSEG_DEPTH_ROW              13
+int awseg_depth_eval_stats(const float* d1, const float* d2_low, int batch, int low_height, int low_width, int height,
+                           int width, const float* weights, const float* target, float min_depth, const int32_t* cond,
+                           int64_t* stats, int n_slots, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ def main():
     ap.add_argument("--device", type=str, default="auto")
     ap.add_argument("--severities", type=str, default=None,
                     help="paired severity sweep: 'reference' or comma-separated intensities (overrides evaluation.severities)")
+    ap.add_argument("--depth-metrics", action="store_true",
+                    help="score the depth heads against the loader's depth target, per condition (sets evaluation.depth_metrics)")
     args = ap.parse_args()
     try:
         config = load_config(args.config) if args.config else create_default_config()
@@ -79,6 +81,8 @@ def main():
         model = load_model(config, args.checkpoint, device)
         if args.severities is not None:
             config.set("evaluation.severities", parse_severities(args.severities))
+        if args.depth_metrics:
+            config.set("evaluation.depth_metrics", True)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",

@@ -176,6 +176,19 @@ def main():
         cases[f"temperature grid stats ensemble K={K}"] = (
             lambda grid=grid, tst=tst: ops.ensemble_temperature_grid_stats(s1, s2, 0, wts, T, labels, tst, grid, edges, cond), "exp_issue",
             K * C * px * B)
+    # depth error sums (evaluation.depth_metrics): three series from the SegFormer map and DeepLab's stride-16 map against the target,
+    # 8 B/px (d1 + target; the low map is 1/256 of that).  Yardstick on the same tensors: the depth tail it replaces in the
+    # evaluation, which reads 4 B/px and writes two maps (12 B/px)
+    dd1 = torch.rand(B, 1, H, W, device=dev) * 0.98 + 0.02
+    dlo = torch.rand(B, 1, (H + 15) // 16, (W + 15) // 16, device=dev) * 0.98 + 0.02
+    dtg = torch.rand(B, H, W, device=dev) * 0.98 + 0.02
+    dwt = torch.softmax(torch.tensor([0.5, 0.5]), 0).to(dev)
+    dst = ops.new_depth_eval_stats(dev, 6)
+    cases["depth eval stats, three series (ensemble + members)"] = (
+        lambda: ops.depth_eval_stats(dd1, dlo, dwt, dtg, dst, 1e-3, cond), "hbm", 8 * px * B * (1 + 1 / 512))
+    cases["depth eval stats, one series"] = (lambda: ops.depth_eval_stats(dd1, None, None, dtg, dst, 1e-3, cond), "hbm", 8 * px * B)
+    cases["depth upsample + combine (the two maps depth eval stats does not write)"] = (
+        lambda: ops.depth_upsample_combine(dd1, dlo, dwt), "hbm", 12 * px * B * (1 + 1 / 768))
     xmp = torch.randn(B, H // 2, W // 2, 64, device=dev)
     cases["maxpool3x3s2 nhwc 64ch (resnet stem)"] = (lambda: ops.maxpool3x3s2_nhwc(xmp), "hbm", 64 * 4 * (H // 2) * (W // 2) * B * (1 + 1 / 4))
     lowl = torch.randn(B, C, H // 4, W // 4, device=dev)
