@@ -28,8 +28,8 @@ import torch.nn.functional as F
 from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
-from .metrics import (ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, depth_metrics_from_stats, iou_from_counts,
-                      severity_sweep_results)
+from .metrics import (ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, depth_metrics_from_stats,
+                      failure_metrics_from_stats, iou_from_counts, severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -88,6 +88,15 @@ def depth_options(config):
     return {"min": float(md), "target": str(target)}
 
 
+def failure_option(config) -> bool:
+    """`evaluation.failure_detection` (bool, default off): per-condition failure-detection counters (AUROC / AURC of four
+    uncertainty scores against the prediction's errors)."""
+    on = _cfg(config, "evaluation.failure_detection", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"evaluation.failure_detection is true or false, got {on!r}")
+    return bool(on)
+
+
 def check_depth_budget(pixels: int) -> None:
     """The depth counters are int64 sums of per-pixel terms up to 2^31 (include/awseg.h): raise before they could wrap."""
     if pixels > ops.DEPTH_PIXEL_BUDGET:
@@ -98,7 +107,7 @@ class EvalState:
     """All cross-batch state of one evaluation run (device resident, additive)."""
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
-                 temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None):
+                 temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -126,6 +135,11 @@ class EvalState:
             # the clean prediction maps (self.paired['rows']): allocated, reused and freed with them
             self.depth = {"stats": ops.new_depth_eval_stats(device, 1 + len(conditions)), "min": float(depth["min"]),
                           "target": depth["target"], "pixels": 0, "rows": None}
+        # failure-detection counters (off unless failure = failure_option(config)): int64 [slot, AWSEG_FAIL_ROW] over this run's slots
+        self.failure = None
+        if failure:
+            self.failure = {"stats": ops.new_failure_stats(device, 1 + len(conditions)), "conditions": list(conditions),
+                            "single": not ensemble}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -261,6 +275,8 @@ class EvalState:
         if getattr(self, "depth", None) is not None:
             depth_pixels = torch.tensor([self.depth["pixels"]], dtype=torch.int64, device=self.depth["stats"].device)
             ts += [self.depth["stats"], depth_pixels]
+        if getattr(self, "failure", None) is not None:
+            ts.append(self.failure["stats"])
         pd = getattr(self, "paired", None)
         if pd is not None:
             if pd["live"]:
@@ -285,6 +301,15 @@ class EvalState:
 
 # confusion + calibration + disagreement statistics in one pass over the member logits (AWSEG_STATS_ONE_PASS=0: two passes)
 STATS_ONE_PASS = os.environ.get("AWSEG_STATS_ONE_PASS", "1") != "0"
+
+
+def _combine_args(model, strategy):
+    """(mode, softmaxed weights, temperature) of r = combine(seg1, seg2)/T: one definition for every kernel that forms r from the
+    member maps (calibration grid, ECE + disagreement, failure detection), so that they describe the same logits."""
+    mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
+    w = F.softmax(model.ensemble_weights, dim=0) if mode == N.COMBINE_WEIGHTED else None
+    T = model.temperature if getattr(model, "temperature_scaling", False) else None
+    return mode, w, T
 
 
 @torch.no_grad()
@@ -323,25 +348,28 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         strategy = getattr(model, "ensemble_strategy", "weighted_average")
         fused_stats = metrics.num_classes == 19 and strategy != "max_confidence" and images[0, 0].numel() % 4 == 0
         need_logits = (with_stats or st.calib is not None) and not fused_stats
+        if st.failure is not None and strategy == "max_confidence":
+            need_logits = True                                    # the msp row reads the combined logits: the kernel does not know the rule
         one_pass = (st.edges, st.ece, st.auroc, AUROC_LO, AUROC_HI) if (with_stats and fused_stats and STATS_ONE_PASS) else None
         res = model.forward_eval(images, labels, st.acc.counts, st.acc.oob, cond, want_logits=need_logits, want_pred=False, stats=one_pass,
                                  pred_out=pred_out, **depth_kw)
         if st.calib is not None:
             if fused_stats:                                       # grid statistics of combine(s1, s2)/T from the two member maps
-                mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
-                w = F.softmax(model.ensemble_weights, dim=0) if mode == N.COMBINE_WEIGHTED else None
-                T = model.temperature if getattr(model, "temperature_scaling", False) else None
+                mode, w, T = _combine_args(model, strategy)
                 st.update_calibration(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T))
             else:
                 st.update_calibration(labels, cond, logits=res["segmentation"])
+        if st.failure is not None:
+            # max_confidence hands over its combined logits: the kernel does not know that rule
+            mode, w, T = _combine_args(model, strategy)
+            ops.ensemble_failure_stats(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T, labels, st.failure["stats"], cond,
+                                       combined=res["segmentation"] if strategy == "max_confidence" else None)
         if one_pass is not None and getattr(model, "_stats_fused", False):
             pass                                                  # confusion, ECE bins and the disagreement histogram came out of ONE pass
         elif with_stats and fused_stats:
             # ECE of the combined logits + disagreement histogram in ONE pass over the member logits:
             # the ensemble logits are never materialised
-            mode = N.COMBINE_WEIGHTED if strategy == "weighted_average" else N.COMBINE_MEAN
-            w = F.softmax(model.ensemble_weights, dim=0) if mode == N.COMBINE_WEIGHTED else None
-            T = model.temperature if getattr(model, "temperature_scaling", False) else None
+            mode, w, T = _combine_args(model, strategy)
             ops.ensemble_eval_stats(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T, labels, cond, st.edges, st.ece,
                                     st.auroc, AUROC_LO, AUROC_HI)
         elif with_stats:
@@ -360,6 +388,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             ops.ece_accumulate(logits, labels, st.ece, st.edges, cond)
         if st.calib is not None:
             st.update_calibration(labels, cond, logits=logits)
+        if st.failure is not None:
+            ops.failure_stats(logits, labels, st.failure["stats"], cond)
     if pred_out is not None:
         st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
@@ -380,7 +410,7 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
     st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
-                   depth=depth_options(config))
+                   depth=depth_options(config), failure=failure_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -439,6 +469,11 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         results.update(depth_metrics_from_stats(st.depth["stats"].cpu().numpy(), st.acc.conditions,
                                                 kinds=st.sweep.kinds if st.sweep is not None else None,
                                                 levels=st.sweep.levels if st.sweep is not None else 0))
+    if getattr(st, "failure", None) is not None:
+        results.update(failure_metrics_from_stats(st.failure["stats"].cpu().numpy(), st.failure["conditions"],
+                                                  kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                  levels=st.sweep.levels if st.sweep is not None else 0,
+                                                  single=st.failure["single"]))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -374,6 +374,86 @@ def depth_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: i
     return res
 
 
+FAILURE_METRICS = ("auroc", "auroc_halfwidth", "aurc", "eaurc")
+
+
+def failure_metrics_from_hist(right, wrong) -> Dict[str, float]:
+    """Failure-detection numbers of one score from its two histograms (counts per bin, bins in ascending score order; `right` /
+    `wrong` = pixels whose prediction was right / wrong).  Host only, float64.  Ties inside a bin count as uniformly interleaved.
+      auroc            P(score of a wrong pixel > score of a right one) + P(tie)/2 = sum_b wrong_b (right_<b + right_b/2) / (W R);
+                       0.5 when there is no wrong or no right pixel
+      auroc_halfwidth  sum_b wrong_b right_b / (2 W R): the exact-rank AUROC of the scores that were binned lies within
+                       auroc +- halfwidth whatever order the ties really have (0 without a wrong or a right pixel)
+      aurc             integral over the coverage c of risk(c) = errors among the c N least uncertain pixels / (c N).  With `a`
+                       wrong among the T pixels before a bin that holds w wrong of n, the bin adds w (T = 0) or
+                       w + (a - w T / n) ln((T + n) / T); the sum is divided by N
+      eaurc            aurc - (e + (1 - e) ln(1 - e)), e = error_rate: the excess over a ranking that puts every error last
+      error_rate       W / N (0 without a pixel)"""
+    r = np.asarray(right, dtype=np.float64).reshape(-1)
+    w = np.asarray(wrong, dtype=np.float64).reshape(-1)
+    if r.shape != w.shape:
+        raise ValueError(f"the two histograms must have one length, got {r.shape} and {w.shape}")
+    R, W = float(r.sum()), float(w.sum())
+    total = R + W
+    if total == 0:
+        return {"auroc": 0.5, "auroc_halfwidth": 0.0, "aurc": 0.0, "eaurc": 0.0, "error_rate": 0.0}
+    if W == 0 or R == 0:
+        auroc, half = 0.5, 0.0                                                      # metrics.py:430-431
+    else:
+        below = np.cumsum(r) - r
+        auroc = float((w * (below + 0.5 * r)).sum() / (W * R))
+        half = float((w * r).sum() / (2.0 * W * R))
+    n = r + w
+    keep = n > 0
+    nk, wk = n[keep], w[keep]
+    T = np.cumsum(nk) - nk                                                          # pixels kept before the bin
+    a = np.cumsum(wk) - wk                                                          # wrong ones among them
+    terms = wk.copy()
+    later = T > 0
+    terms[later] += (a[later] - wk[later] * T[later] / nk[later]) * np.log1p(nk[later] / T[later])
+    aurc = float(terms.sum() / total)
+    e = W / total
+    best = 1.0 if e >= 1.0 else float(e + (1.0 - e) * np.log1p(-e))
+    return {"auroc": auroc, "auroc_halfwidth": half, "aurc": aurc, "eaurc": float(aurc - best), "error_rate": float(e)}
+
+
+def failure_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0, single: bool = False) -> Dict[str, float]:
+    """Result keys of the failure-detection counters (int64 [1 + len(conditions), AWSEG_FAIL_ROW]; slot 0 = every frame, slot
+    1 + k = conditions[k]).  Host only; every value a float.
+      failure_<auroc|auroc_halfwidth|aurc|eaurc>_<score>[_<condition>]     score in ops.FAIL_SCORES (single: entropy, msp)
+      failure_error_rate[_<condition>]                    of the prediction mIoU scores (row msp: argmax of the combined logits)
+      failure_error_rate_mean_probability[_<condition>]   of argmax of the mean probability (rows mi, entropy, variance; not single)
+      failure_nonfinite_pixels, failure_out_of_range_labels               slot 0, only when non-zero
+    Severity sweep (kinds, levels): conditions are its slots ('clean', '<kind>_s<j>'); each kind also gets keys from the summed
+    counters of its slots.  A slot without a counted pixel yields no keys."""
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.ndim != 2 or raw.shape != (1 + len(conditions), ops.FAIL_ROW):
+        raise ValueError(f"failure stats must be int64 [{1 + len(conditions)}, {ops.FAIL_ROW}], got {raw.shape}")
+    dec = ops.failure_stats_to_numpy(raw)
+    named = [("", dec["hist"][0], int(dec["pixels"][0]))]
+    named += [("_" + name, dec["hist"][1 + k], int(dec["pixels"][1 + k])) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        named.append(("_" + kind, dec["hist"][idx].sum(0), int(dec["pixels"][idx].sum())))
+    scores = [(i, s) for i, s in enumerate(ops.FAIL_SCORES) if not single or s in ("entropy", "msp")]
+    res: Dict[str, float] = {}
+    for suffix, hist, pixels in named:
+        if pixels <= 0:
+            continue
+        for i, score in scores:
+            m = failure_metrics_from_hist(hist[i, 0], hist[i, 1])
+            for k in FAILURE_METRICS:
+                res[f"failure_{k}_{score}{suffix}"] = float(m[k])
+            if score == "msp":
+                res[f"failure_error_rate{suffix}"] = float(m["error_rate"])
+            elif score == "entropy" and not single:
+                res[f"failure_error_rate_mean_probability{suffix}"] = float(m["error_rate"])
+    for key, v in (("failure_nonfinite_pixels", int(dec["nonfinite"][0])), ("failure_out_of_range_labels", int(dec["out_of_range"][0]))):
+        if v:
+            res[key] = float(v)
+    return res
+
+
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""
 

@@ -36,7 +36,34 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += severity_section(results)
     if any(k.startswith("depth_abs_rel") for k in results):
         lines += depth_section(results)
+    if any(k.startswith("failure_auroc_") for k in results):
+        lines += failure_section(results)
     return "\n".join(lines)
+
+
+FAILURE_SCORES = ("mi", "entropy", "variance", "msp")
+
+
+def failure_section(results: Dict[str, Any]) -> list:
+    """Failure detection (evaluation.failure_detection): condition x score, AUROC +- its halfwidth and the excess AURC."""
+    scores = [s for s in FAILURE_SCORES if f"failure_auroc_{s}" in results]
+    first = f"failure_auroc_{scores[0]}_"
+    names = [""] + [k[len(first):] for k in results if k.startswith(first)]
+
+    def cell(score, sfx):
+        if f"failure_auroc_{score}{sfx}" not in results:
+            return "-"
+        return (f"{results[f'failure_auroc_{score}{sfx}']:.3f} ± {results[f'failure_auroc_halfwidth_{score}{sfx}']:.3f} / "
+                f"{results[f'failure_eaurc_{score}{sfx}']:.3f}")
+    lines = ["", "## Failure Detection", "", "AUROC ± halfwidth / E-AURC of each uncertainty score against the prediction's errors.", "",
+             "| Condition | " + " | ".join(scores) + " | Error rate |", "|---" * (len(scores) + 2) + "|"]
+    for n in names:
+        sfx = "_" + n if n else ""
+        err = f"{results['failure_error_rate' + sfx]:.3f}" if "failure_error_rate" + sfx in results else "-"
+        lines.append(f"| {n or 'all'} | " + " | ".join(cell(s, sfx) for s in scores) + f" | {err} |")
+    extra = [f"- **{title}**: {int(results[key])}" for key, title in (("failure_nonfinite_pixels", "Non-finite pixels"),
+                                                                     ("failure_out_of_range_labels", "Out-of-range labels")) if key in results]
+    return lines + ([""] + extra if extra else [])
 
 
 def depth_section(results: Dict[str, Any]) -> list:

@@ -339,6 +339,78 @@ def depth_eval_stats_to_numpy(stats) -> dict:
     return {f: raw[..., i].copy() for i, f in enumerate(DEPTH_FIELDS)}
 
 
+# ----------------------------------------------------------------------------- failure-detection counters (include/awseg.h)
+FAIL_SCORES = ("mi", "entropy", "variance", "msp")     # AWSEG_FAIL_MI / _ENTROPY / _VARIANCE / _MSP, in row order
+FAIL_BINS = 3072                                        # AWSEG_FAIL_BINS: 24 octaves from 2^-22 to 4.0, 128 steps each
+FAIL_ROW = len(FAIL_SCORES) * 2 * FAIL_BINS + 4         # AWSEG_FAIL_ROW: [score][flag][bin] + {counted, non-finite, out of range, 0}
+_FAIL_BIN_BASE = 105 << 23                              # bits of 2^-22
+
+
+def failure_bin(values) -> np.ndarray:
+    """Bin of each float32 score by the bit rule of include/awseg.h: clamp((int32(bits) - (105 << 23)) >> 16, 0, FAIL_BINS - 1).
+    The values are taken as float32 (a float64 input is rounded first, as a store to float32 would)."""
+    bits = np.ascontiguousarray(np.asarray(values, dtype=np.float32)).view(np.int32).astype(np.int64)
+    return np.clip((bits - _FAIL_BIN_BASE) >> 16, 0, FAIL_BINS - 1)
+
+
+def failure_bin_edges() -> np.ndarray:
+    """float32 [FAIL_BINS]: the lower edge of every bin (bin b holds edge[b] <= s < edge[b + 1]; bin 0 also everything below its
+    edge 2^-22, the last bin everything from its edge up)."""
+    return (_FAIL_BIN_BASE + (np.arange(FAIL_BINS, dtype=np.int64) << 16)).astype(np.int32).view(np.float32)
+
+
+def new_failure_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, FAIL_ROW], the layout include/awseg.h documents (zeroed: the launches accumulate)."""
+    return torch.zeros(n_slots, FAIL_ROW, dtype=torch.int64, device=device)
+
+
+def _failure_args(logits: torch.Tensor, label: torch.Tensor, stats: torch.Tensor, cond):
+    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[1] != FAIL_ROW:
+        raise ValueError(f"stats must be int64 [slots, {FAIL_ROW}] (new_failure_stats), got {stats.dtype} {tuple(stats.shape)}")
+    if logits.dim() < 3 or logits.dtype != torch.float32:
+        raise ValueError(f"logits must be float32 [B, C, ...], got {logits.dtype} {tuple(logits.shape)}")
+    b, c = logits.shape[0], logits.shape[1]
+    hw = logits[0, 0].numel() if b else int(np.prod(logits.shape[2:]))
+    if label.numel() != b * hw:
+        raise ValueError(f"label must hold {b} x {hw} elements, got {tuple(label.shape)}")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    return b, c, hw
+
+
+def ensemble_failure_stats(seg1: torch.Tensor, seg2: torch.Tensor, mode: int, weights, temperature, label: torch.Tensor,
+                           stats: torch.Tensor, cond: Optional[torch.Tensor] = None, combined: Optional[torch.Tensor] = None) -> None:
+    """Failure-detection counters of an ensemble batch: the four scores of FAIL_SCORES per pixel, histogrammed by "right / wrong"
+    into `stats` (new_failure_stats; slot 0 + slot 1 + cond[b]) in one pass over the member logits.  `combined` [B, C, ...]: the
+    msp row reads the combined logits from it (mode, weights, temperature are then ignored), else forms them as
+    ensemble_eval_stats does (mode WEIGHTED or MEAN)."""
+    b, c, hw = _failure_args(seg1, label, stats, cond)
+    if seg2.shape != seg1.shape or seg2.dtype != torch.float32 or (combined is not None and (combined.shape != seg1.shape or
+                                                                                              combined.dtype != torch.float32)):
+        raise ValueError("ensemble_failure_stats: seg1, seg2 (and combined) must be float32 of one shape")
+    seg1, seg2, label = seg1.contiguous(), seg2.contiguous(), label.contiguous()
+    N.call("awseg_ensemble_failure_stats", N.ptr(seg1), N.ptr(seg2), N.ptr(None if combined is None else combined.contiguous()), b, c, hw,
+           int(mode), N.ptr(None if weights is None else weights.contiguous()), N.ptr(temperature), N.ptr(label), N.label_dtype(label),
+           N.ptr(cond), N.ptr(stats), stats.shape[0], N.stream())
+
+
+def failure_stats(logits: torch.Tensor, label: torch.Tensor, stats: torch.Tensor, cond: Optional[torch.Tensor] = None) -> None:
+    """Failure-detection counters of one model's logits: rows 'entropy' and 'msp' of `stats` (the other two are not touched)."""
+    b, c, hw = _failure_args(logits, label, stats, cond)
+    logits, label = logits.contiguous(), label.contiguous()
+    N.call("awseg_failure_stats", N.ptr(logits), b, c, hw, N.ptr(label), N.label_dtype(label), N.ptr(cond), N.ptr(stats), stats.shape[0],
+           N.stream())
+
+
+def failure_stats_to_numpy(stats) -> dict:
+    """int64 [slots, FAIL_ROW] (a device tensor or a numpy array) -> {'hist' [slots, 4, 2, FAIL_BINS] (score, 0 right / 1 wrong,
+    bin), 'pixels', 'nonfinite', 'out_of_range' [slots]}."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    n = len(FAIL_SCORES) * 2 * FAIL_BINS
+    return {"hist": raw[:, :n].reshape(raw.shape[0], len(FAIL_SCORES), 2, FAIL_BINS).copy(), "pixels": raw[:, n].copy(),
+            "nonfinite": raw[:, n + 1].copy(), "out_of_range": raw[:, n + 2].copy()}
+
+
 # ----------------------------------------------------------------------------- A7
 def normalize(imgs: torch.Tensor, out: Optional[torch.Tensor] = None, sel: Optional[torch.Tensor] = None,
               mean=None, std=None) -> torch.Tensor:

@@ -1019,6 +1019,59 @@ int awseg_depth_eval_stats(const float* d1, const float* d2_low, int batch, int 
                            int width, const float* weights, const float* target, float min_depth, const int32_t* cond,
                            int64_t* stats, int n_slots, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Failure-detection counters: does the uncertainty point at the mistakes?  
+ *       per condition what REF/evaluation/metrics.py:565-605 computes per weather condition (the disagreement AUROC), for the
+ *       four uncertainty scores the reference ships (:353-367, :385-389, :161-162); AUROC / AURC are host math on these counts
+ * ------------------------------------------------------------------------- *
+ * Per pixel whose label is neither 255 nor outside [0, C), four float32 scores, each "higher = less certain":
+ *     [AWSEG_FAIL_MI]        H(m) - (H(p1) + H(p2))/2, m = (p1 + p2)/2, p_i = softmax(seg_i): the expression
+ *                            awseg_ensemble_eval_stats histograms, operation for operation       error: argmax(m) != label
+ *     [AWSEG_FAIL_ENTROPY]   H(m) = -sum m log(m + 1e-8)                                           error: argmax(m) != label
+ *     [AWSEG_FAIL_VARIANCE]  sum_c (p1_c - p2_c)^2 / 2 (torch.var over the two members, summed)    error: argmax(m) != label
+ *     [AWSEG_FAIL_MSP]       1 - conf, conf = 1.0f / sum exp(r - max r), r = combine(seg1, seg2)/T exactly as
+ *                            awseg_ensemble_eval_stats forms it                                     error: argmax(r) != label
+ * (first maximum in both).  A score ranks the errors of the prediction it was computed from: rows 0-2 describe the mean
+ * probability, row 3 the combined logits that mIoU and ECE are scored on.
+ *
+ * Bins come from the float32 bit pattern of a score s:
+ *     bin = clamp((int32(bits(s)) - (105 << 23)) >> 16, 0, AWSEG_FAIL_BINS - 1)        (105 = 127 - 22; exact integers)
+ * 24 octaves from 2^-22 to 2^2 with 128 steps each.  Everything at or below 2^-22 lands in bin 0 (zero and negative rounding
+ * noise included: a negative float is a negative int32), everything from 4.0 up in the last bin.  Every bin edge is an exact
+ * float32, so a host model that holds the same float32 score agrees on the bin.  Every score is at most ln C, below 4 for
+ * C <= 54; the entropy of awseg_failure_stats at C > 54 (ln 64 = 4.16) can reach the last bin.
+ *
+ * Output (accumulated, never cleared): stats int64 [n_slots][AWSEG_FAIL_ROW], a row laid out [score][flag: 0 right, 1 wrong][bin]
+ * followed by {counted pixels, non-finite pixels, out-of-range labels, 0}.  Every frame goes into slot 0 and into slot
+ * 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0 only).  A label of 255 is skipped; any other
+ * label outside [0, C) is counted as out of range and enters no histogram; else a pixel with any non-finite input logit (a
+ * member's, or `combined`'s) is counted as non-finite and enters none; else it is counted and enters every row once.  Integer
+ * sums only: the result does not depend on launch geometry, batch split or rank count, and counts never exceed the pixel count.
+ *
+ * awseg_ensemble_failure_stats: seg1, seg2 float32 [B,C,hw].  combined == NULL: r from mode AWSEG_COMBINE_WEIGHTED (weights device
+ * float32[2]) or AWSEG_COMBINE_MEAN, divided by temperature[0] when temperature != NULL, as awseg_ensemble_eval_stats
+ * (AWSEG_COMBINE_MAXCONF without `combined` is AWSEG_EINVAL).  combined != NULL (float32 [B,C,hw]): r is read from it and mode,
+ * weights and temperature are ignored; this serves the max_confidence strategy and any other.  C <= AWSEG_MAX_CLASSES.
+ * awseg_failure_stats: one model's logits [B,C,hw]; rows AWSEG_FAIL_ENTROPY (of softmax(logits), the same + 1e-8) and
+ * AWSEG_FAIL_MSP only, both flagged by argmax(logits) != label; the other two rows are not touched.  C <= AWSEG_CALIB_MAX_CLASSES.
+ * Both: any hw < 2^31 (a ragged frame such as 17 x 23 works) and batch <= 65535 (the frame is the grid's second dimension);
+ * AWSEG_ERANGE beyond those limits.  C = 19 runs with the class walk unrolled: the ensemble form one pixel per lane whatever hw
+ * and the alignment (measured faster than two or four pixels per lane), the single form four pixels per lane from
+ * 16-byte loads when hw % 4 == 0 and logits is 16-byte aligned.  No workspace.  batch == 0
+ * returns 0.  AWSEG_EINVAL for a NULL seg1 / seg2 / logits / label / stats, a size < 1, n_slots < 1, an unknown label dtype or mode. */
+#define AWSEG_FAIL_SCORES    4
+#define AWSEG_FAIL_MI        0
+#define AWSEG_FAIL_ENTROPY   1
+#define AWSEG_FAIL_VARIANCE  2
+#define AWSEG_FAIL_MSP       3
+#define AWSEG_FAIL_BINS      3072
+#define AWSEG_FAIL_ROW       (AWSEG_FAIL_SCORES * 2 * AWSEG_FAIL_BINS + 4)
+int awseg_ensemble_failure_stats(const float* seg1, const float* seg2, const float* combined, int64_t batch, int num_classes,
+                                 int64_t hw, int mode, const float* weights, const float* temperature, const void* label,
+                                 int label_dtype, const int32_t* cond, int64_t* stats, int n_slots, awseg_stream_t stream);
+int awseg_failure_stats(const float* logits, int64_t batch, int num_classes, int64_t hw, const void* label, int label_dtype,
+                        const int32_t* cond, int64_t* stats, int n_slots, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -71,6 +71,9 @@ def main():
                     help="paired severity sweep: 'reference' or comma-separated intensities (overrides evaluation.severities)")
     ap.add_argument("--depth-metrics", action="store_true",
                     help="score the depth heads against the loader's depth target, per condition (sets evaluation.depth_metrics)")
+    ap.add_argument("--failure-detection", action="store_true",
+                    help="AUROC / AURC of four uncertainty scores against the prediction's errors, per condition "
+                         "(sets evaluation.failure_detection)")
     args = ap.parse_args()
     try:
         config = load_config(args.config) if args.config else create_default_config()
@@ -83,6 +86,8 @@ def main():
             config.set("evaluation.severities", parse_severities(args.severities))
         if args.depth_metrics:
             config.set("evaluation.depth_metrics", True)
+        if args.failure_detection:
+            config.set("evaluation.failure_detection", True)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",

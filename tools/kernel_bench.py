@@ -189,6 +189,28 @@ def main():
     cases["depth eval stats, one series"] = (lambda: ops.depth_eval_stats(dd1, None, None, dtg, dst, 1e-3, cond), "hbm", 8 * px * B)
     cases["depth upsample + combine (the two maps depth eval stats does not write)"] = (
         lambda: ops.depth_upsample_combine(dd1, dlo, dwt), "hbm", 12 * px * B * (1 + 1 / 768))
+    # failure-detection counters (evaluation.failure_detection): four scores x right / wrong histograms in one pass over the member
+    # logits.  Yardstick on the same tensors: the one-pass ECE + disagreement statistics, which reads the same bytes and evaluates
+    # the same exponentials and logarithms.  Random logits spread the scores; "trained-like" ones (a shared one-hot evidence, right
+    # 85 % of the time, margin log-uniform over 1..20, plus member noise) pile most of a wave into bin 0 of three rows.
+    fst = ops.new_failure_stats(dev, 6)
+    lab_l = labels.long()
+    right = torch.rand(B, H, W, device=dev) < 0.85
+    cls = torch.where(right, lab_l, (lab_l + torch.randint(1, C, (B, H, W), device=dev)) % C)
+    margin = torch.exp(torch.rand(B, H, W, device=dev) * float(np.log(20.0)))
+    margin = torch.where(right, margin, 1.0 + 0.3 * (margin - 1.0))
+    t1 = torch.zeros(B, C, H, W, device=dev).scatter_(1, cls[:, None], margin[:, None])
+    t2 = t1 + 0.7 * torch.randn(B, C, H, W, device=dev)
+    t1 += 0.7 * torch.randn(B, C, H, W, device=dev)
+    del lab_l, right, cls, margin
+    for tag, (m1, m2) in (("random", (s1, s2)), ("trained-like", (t1, t2))):
+        cases[f"failure stats ensemble, {tag} logits"] = (
+            lambda m1=m1, m2=m2: ops.ensemble_failure_stats(m1, m2, 0, wts, T, labels, fst, cond), "hbm", (2 * C * 4 + 1) * px * B)
+        cases[f"failure stats ensemble, combined logits given, {tag} logits"] = (
+            lambda m1=m1, m2=m2: ops.ensemble_failure_stats(m1, m2, 1, None, None, labels, fst, cond, combined=m2), "hbm", (3 * C * 4 + 1) * px * B)
+        cases[f"ensemble eval stats (the yardstick of failure stats), {tag} logits"] = (
+            lambda m1=m1, m2=m2: ops.ensemble_eval_stats(m1, m2, 0, wts, T, labels, cond, edges, bins, hist, -1e-3, 0.70), "hbm", (2 * C * 4 + 1) * px * B)
+        cases[f"failure stats single model, {tag} logits"] = (lambda m1=m1: ops.failure_stats(m1, labels, fst, cond), "hbm", (C * 4 + 1) * px * B)
     xmp = torch.randn(B, H // 2, W // 2, 64, device=dev)
     cases["maxpool3x3s2 nhwc 64ch (resnet stem)"] = (lambda: ops.maxpool3x3s2_nhwc(xmp), "hbm", 64 * 4 * (H // 2) * (W // 2) * B * (1 + 1 / 4))
     lowl = torch.randn(B, C, H // 4, W // 4, device=dev)
