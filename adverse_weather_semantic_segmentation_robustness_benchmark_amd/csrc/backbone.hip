@@ -447,8 +447,23 @@ void maxpool3x3s2_nhwc_kernel(const float* __restrict__ x, int64_t batch, int H,
     }
 }
 
+// torch's upsample_bilinear2d writes  scale * (dst + 0.5) - 0.5  and  h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11);  its build
+// contracts them (measured against F.interpolate on gfx950: the forms below differ at 0 of 10^5 values for either corner convention,
+// every other choice of fused operand at thousands; the uncontracted expressions — this file is built with -ffp-contract=off — at a
+// third of them, by one ulp).  The fused operands are therefore spelled out.
+__device__ __forceinline__ float bilinear_src(float scale, int dst, int align)
+{
+    const float f = align ? scale * (float)dst : fmaf(scale, (float)dst + 0.5f, -0.5f);
+    return f < 0.f ? 0.f : f;
+}
+
+__device__ __forceinline__ float bilinear_blend(float ly0, float ly1, float lx0, float lx1, float v00, float v01, float v10, float v11)
+{
+    return fmaf(ly0, fmaf(lx0, v00, lx1 * v01), ly1 * fmaf(lx0, v10, lx1 * v11));
+}
+
 // Bilinear upsampling of [planes, h, w] float32 maps to [planes, H, W] with torch's upsample_bilinear2d arithmetic (source index,
-// weights and the order h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11)), either corner convention.  DeepLabV3+'s
+// weights and blend as above: bit-identical), either corner convention.  DeepLabV3+'s
 // segmentation head ends in UpsamplingBilinear2d(x4) on the 19 logit planes (1.27 GB written per batch of 8 at 1024x2048):
 // 4 output pixels per lane, one 16-byte store, the <= 2 x 4 source values from L2 (the low-resolution maps are 64x smaller).
 __global__ __launch_bounds__(kThreads)
@@ -462,8 +477,7 @@ void upsample_bilinear_kernel(const float* __restrict__ low, int h, int w, int H
         int64_t t = i / wq;
         const int y = (int)(t % H);
         const int64_t pl = t / H;
-        float fy = align ? sy * (float)y : sy * ((float)y + 0.5f) - 0.5f;
-        fy = fy < 0.f ? 0.f : fy;
+        const float fy = bilinear_src(sy, y, align);
         const int y0 = (int)fy, y1 = y0 + (y0 < h - 1 ? 1 : 0);
         const float ly1 = fy - (float)y0, ly0 = 1.0f - ly1;
         const float* r0 = low + (pl * h + y0) * (int64_t)w;
@@ -473,31 +487,27 @@ void upsample_bilinear_kernel(const float* __restrict__ low, int h, int w, int H
             // upsampling by more than 3: the four pixels' source columns lie in [a, a + 2] — six loads instead of sixteen
             // (the sixteen-load form is bound by the vector-memory pipe: 0.51 ms for 1.27 GB, torch's kernel the same)
             int xa = xq * 4; xa = xa < W ? xa : W - 1;
-            float fa = align ? sx * (float)xa : sx * ((float)xa + 0.5f) - 0.5f;
-            fa = fa < 0.f ? 0.f : fa;
-            const int a = (int)fa;
+            const int a = (int)bilinear_src(sx, xa, align);
             const int c1 = a + 1 < w ? a + 1 : w - 1, c2 = a + 2 < w ? a + 2 : w - 1;
             const float t0 = r0[a], t1 = r0[c1], t2 = r0[c2], b0 = r1[a], b1 = r1[c1], b2 = r1[c2];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 int x = xq * 4 + k; x = x < W ? x : W - 1;
-                float fx = align ? sx * (float)x : sx * ((float)x + 0.5f) - 0.5f;
-                fx = fx < 0.f ? 0.f : fx;
+                const float fx = bilinear_src(sx, x, align);
                 const int x0 = (int)fx;
                 const float lx1 = fx - (float)x0, lx0 = 1.0f - lx1;
                 const bool first = x0 == a;                        // else x0 == a + 1; x1 = x0 + 1 clamped = the next staged column
                 const float v00 = first ? t0 : t1, v01 = first ? t1 : t2, v10 = first ? b0 : b1, v11 = first ? b1 : b2;
-                v[k] = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 + lx1 * v11);
+                v[k] = bilinear_blend(ly0, ly1, lx0, lx1, v00, v01, v10, v11);
             }
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 int x = xq * 4 + k; x = x < W ? x : W - 1;
-                float fx = align ? sx * (float)x : sx * ((float)x + 0.5f) - 0.5f;
-                fx = fx < 0.f ? 0.f : fx;
+                const float fx = bilinear_src(sx, x, align);
                 const int x0 = (int)fx, x1 = x0 + (x0 < w - 1 ? 1 : 0);
                 const float lx1 = fx - (float)x0, lx0 = 1.0f - lx1;
-                v[k] = ly0 * (lx0 * r0[x0] + lx1 * r0[x1]) + ly1 * (lx0 * r1[x0] + lx1 * r1[x1]);
+                v[k] = bilinear_blend(ly0, ly1, lx0, lx1, r0[x0], r0[x1], r1[x0], r1[x1]);
             }
         }
         float* o = out + (pl * H + y) * (int64_t)W + xq * 4;
@@ -520,7 +530,7 @@ void upsample_bilinear_4x4_kernel(const float* __restrict__ low, int h, int w, i
         int64_t t = i / wq;
         const int yq = (int)(t % hq);
         const int64_t pl = t / hq;
-        auto src = [&](int d, float sc) { float f = align ? sc * (float)d : sc * ((float)d + 0.5f) - 0.5f; return f < 0.f ? 0.f : f; };
+        auto src = [&](int d, float sc) { return bilinear_src(sc, d, align); };
         const int ya = (int)src(yq * 4, sy), xa = (int)src(xq * 4, sx);
         float c[3][3];
         // the low-resolution map through its strides (floats): planar NCHW, or the NHWC rows a GEMM wrote — it is small and stays in L2
@@ -555,7 +565,7 @@ void upsample_bilinear_4x4_kernel(const float* __restrict__ low, int h, int w, i
                 const float t01 = fy_first ? (fx_first[k] ? c[0][1] : c[0][2]) : (fx_first[k] ? c[1][1] : c[1][2]);
                 const float t10 = fy_first ? (fx_first[k] ? c[1][0] : c[1][1]) : (fx_first[k] ? c[2][0] : c[2][1]);
                 const float t11 = fy_first ? (fx_first[k] ? c[1][1] : c[1][2]) : (fx_first[k] ? c[2][1] : c[2][2]);
-                v[k] = ly0 * (lx0[k] * t00 + lx1[k] * t01) + ly1 * (lx0[k] * t10 + lx1[k] * t11);
+                v[k] = bilinear_blend(ly0, ly1, lx0[k], lx1[k], t00, t01, t10, t11);
             }
             *reinterpret_cast<float4*>(out + (pl * H + y) * (int64_t)W + xq * 4) = make_float4(v[0], v[1], v[2], v[3]);
         }

@@ -37,6 +37,20 @@ def _versions(*tensors):
     return tuple((t.data_ptr(), t._version) for t in tensors if t is not None)
 
 
+# Entries whose key is a tensor of ANOTHER entry's value (the GEMM operand images of a folded / packed / im2col matrix, of the
+# stacked k/v weights, of the ASPP projection slices, of ResNet's folded stem), not a parameter.  Such a key cannot tell a
+# re-derived tensor from the one it replaces: the new one is freshly allocated, version 0, and may land on the old one's address.
+# So they die with their parent: a rebuild of any other entry on a module deletes every one of these on that module.  A new entry
+# keyed on a cache value belongs in this list, on the module that owns its parent.
+DERIVED = ("wsplit", "wbf16", "wsplit_small", "kvsplit", "proj_pieces", "stemrows")
+
+
+def _drop_derived(module: nn.Module) -> None:
+    for dep in DERIVED:
+        if hasattr(module, "_awseg_" + dep):
+            delattr(module, "_awseg_" + dep)
+
+
 def folded_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
     """(weight * bn_scale in channels_last, shift) for eval-mode Conv -> BN; cached on the modules
     and recomputed whenever a parameter / running stat changes (in-place version counters)."""
@@ -51,11 +65,7 @@ def folded_conv_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d):
         shift = shift + conv.bias * scale
     w = (conv.weight * scale.view(-1, 1, 1, 1)).contiguous(memory_format=CL)
     conv._awseg_fold = (key, w, shift.contiguous())
-    # everything derived from the folded weights dies with them: the split-operand image is keyed on the folded tensor's
-    # (address, version), and a re-folded tensor can land on the same address with the same version
-    for dep in ("_awseg_wsplit", "_awseg_wbf16"):
-        if hasattr(conv, dep):
-            delattr(conv, dep)
+    _drop_derived(conv)
     return w, shift.contiguous()
 
 
@@ -66,11 +76,17 @@ def cached(module: nn.Module, name: str, tensors, fn):
         return cache[1]
     val = fn()
     setattr(module, "_awseg_" + name, (key, val))
-    if name not in ("wsplit", "wbf16"):
-        for dep in ("_awseg_wsplit", "_awseg_wbf16"):
-            if hasattr(module, dep):
-                delattr(module, dep)              # operand images are keyed on the tensor just replaced
+    if name not in DERIVED:
+        _drop_derived(module)                     # they are keyed on (a tensor of) the value just replaced
     return val
+
+
+def drop_prepared(model: nn.Module) -> None:
+    """Forget every prepared weight image (`_awseg_*`) on `model` and its sub-modules; the next eval forward rebuilds them from the
+    parameters as they are then.  Needed after an edit the keys cannot see: a write through `param.data` leaves `_version` alone."""
+    for m in model.modules():
+        for k in [k for k in vars(m) if k.startswith("_awseg_")]:
+            delattr(m, k)
 
 
 def split_weights(owner: nn.Module, w2: torch.Tensor, m: int):

@@ -418,10 +418,14 @@ class EnsembleModel(nn.Module):
                     if fused.stem_image_ok(x):
                         fused.stem_image(x)
                     side.wait_stream(cur)
-                    with torch.cuda.stream(side):
-                        o2 = self.deeplabv3plus(x)
-                    o1 = self.segformer(x)
-                    cur.wait_stream(side)
+                    try:
+                        with torch.cuda.stream(side):
+                            o2 = self.deeplabv3plus(x)
+                        o1 = self.segformer(x)
+                    finally:
+                        # also when a member raises: whatever the side stream was given still reads the shared stem image and cached
+                        # weights, which the next forward refills / frees on this stream
+                        cur.wait_stream(side)
                     for t in o2.values():
                         t.record_stream(cur)
                 else:

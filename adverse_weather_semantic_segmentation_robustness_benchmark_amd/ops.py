@@ -1461,7 +1461,9 @@ def upsample_bilinear(x: torch.Tensor, size, align_corners: bool) -> torch.Tenso
     if not (x.is_contiguous() or (STRIDED_UPSAMPLE and W % 4 == 0 and 3 * w < W and 3 * h < H and all(s_ >= 0 for s_ in x.stride()))):
         x = x.contiguous()
     out = torch.empty(b, c, H, W, dtype=torch.float32, device=x.device)
-    sb, sc, sy, sx = x.stride()
+    # (torch ignores the stride of a size-1 dimension: a [B,1,h,w] channels_last map or a one-image view is_contiguous() with
+    # strides the launcher's planar test would reject — what is contiguous is passed with the canonical strides)
+    sb, sc, sy, sx = (c * h * w, h * w, w, 1) if x.is_contiguous() else x.stride()
     N.call("awseg_upsample_bilinear_strided", N.ptr_strided(x), b, c, h, w, sb, sc, sy, sx, H, W, int(bool(align_corners)), N.ptr(out), N.stream())
     return out
 

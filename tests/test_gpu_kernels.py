@@ -1592,6 +1592,40 @@ def test_upsample_bilinear_reads_nhwc_rows_through_strides(ops):
                                                       ops.N.ptr(torch.empty(2, 19, 48, 80, device="cuda")), None) == -2     # AWSEG_ERANGE
 
 
+@pytest.mark.parametrize("align", [True, False])
+@pytest.mark.parametrize("cfg", [
+    # (layout, B, C, h, w, H, W): inputs torch calls contiguous although their strides are not the canonical ones — it ignores the stride
+    # of a size-1 dimension.  "c1_channels_last": a one-channel NHWC product permuted back, strides (h w, 1, w, 1); "b1_view": a
+    # one-image view with an arbitrary batch stride.  Ragged W (W % 4 != 0) and scales >= 1/3 take the row-at-a-time kernel, which
+    # reads planar maps only; the x4 cases take the 4 x 4 kernel, which reads through the strides.
+    ("c1_channels_last", 2, 1, 5, 9, 33, 70), ("c1_channels_last", 2, 1, 8, 8, 16, 16), ("c1_channels_last", 3, 1, 4, 8, 64, 128),
+    ("c1_channels_last", 2, 1, 6, 6, 5, 4), ("c1_channels_last", 1, 1, 7, 5, 28, 21),
+    ("b1_view", 1, 2, 5, 9, 33, 70), ("b1_view", 1, 4, 8, 8, 16, 16), ("b1_view", 1, 3, 7, 5, 28, 20), ("b1_view", 1, 19, 9, 12, 18, 24),
+    ("b1_c1_view", 1, 1, 6, 10, 17, 30)])
+def test_upsample_bilinear_takes_what_torch_calls_contiguous(ops, cfg, align):
+    """is_contiguous() inputs with non-canonical strides: the same values as F.interpolate, bit for bit (both run torch's expression
+    on the same numbers; the canonical copy of the input goes through the same kernel and must give the same bits too)."""
+    layout, B, C, h, w, H, W = cfg
+    g = torch.Generator(device="cuda").manual_seed(h * w + H)
+    base = torch.randn(B, C, h, w, device="cuda", generator=g)
+    if layout == "c1_channels_last":
+        rows = torch.empty(B, h, w, C, device="cuda")                      # what an NHWC kernel writes
+        rows.copy_(base.permute(0, 2, 3, 1))
+        x = rows.permute(0, 3, 1, 2)
+        assert x.stride() == (h * w, 1, w, 1)
+    else:
+        buf = torch.zeros(5 * C * h * w + 64, device="cuda")
+        sc = (7 * h * w) if layout == "b1_c1_view" else h * w
+        x = buf.as_strided((1, C, h, w), (3 * C * h * w + 12, sc, w, 1), 4)
+        x.copy_(base)
+    assert x.is_contiguous() and x.stride() != base.stride() and torch.equal(x, base)
+    ref = torch.nn.functional.interpolate(base, size=(H, W), mode="bilinear", align_corners=align)
+    got = ops.upsample_bilinear(x, (H, W), align)
+    print(f"{cfg} align={align}: max |got - F.interpolate| = {(got - ref).abs().max().item():.3e}")
+    assert torch.equal(got, ops.upsample_bilinear(base, (H, W), align))
+    assert torch.equal(got, ref)
+
+
 @pytest.mark.parametrize("shape", [(2, 1, 200, 64), (1, 2, 128, 32), (2, 5, 300, 2048)])
 def test_attention_d32_packed_keys_and_values(ops, shape):
     """Keys and values packed per token ([key | value] rows, as one GEMM over the stacked projection weights writes them): the
