@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 #include "../../include/awseg.h"
 
 #define AWSEG_API extern "C" __attribute__((visibility("default")))
@@ -17,6 +18,19 @@
     } while (0)
 
 static inline hipStream_t awseg_s(awseg_stream_t s) { return (hipStream_t)s; }
+
+// CU count of the CURRENT device (a process may drive several): asked once per ordinal, AWSEG_CUS where the runtime cannot say.
+inline int awseg_cu_count()
+{
+    static std::atomic<int> cached[16];                       // zero-initialised; ordinals past the array ask every time
+    int dev = 0, n_cu = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return AWSEG_CUS;
+    const bool slot = dev >= 0 && dev < 16;
+    if (slot && (n_cu = cached[dev].load(std::memory_order_relaxed)) > 0) return n_cu;
+    if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) return AWSEG_CUS;
+    if (slot) cached[dev].store(n_cu, std::memory_order_relaxed);
+    return n_cu;
+}
 
 // Memory-bound grids: cap at 8 resident 256-thread blocks per CU and grid-stride the rest
 // (cdna_hip_programming.md Guideline 11).
@@ -123,7 +137,7 @@ __device__ __forceinline__ void awseg_box_muller16(uint32_t a, float& n0, float&
 }
 __device__ __forceinline__ float awseg_u01(uint32_t a) { return (float)(a >> 8) * (1.0f / 16777216.0f); }
 
-// gemm_split3.hip (the LDS-DMA split-operand GEMM for N % 256 == 0, K % 32 == 0), called from gemm_split.hip
+// gemm_split3.hip (the LDS-DMA split-operand GEMM), called from gemm_split.hip
 int awseg_gemm_split3_weights(const float* w, int n, int k, uint16_t* w3, const unsigned* trailer, hipStream_t stream);
 bool awseg_gemm_split3_eligible(int64_t m, int n, int k, const void* x, const void* out, const void* residual, const void* bias);
 // dual: the A operand continues in a second source behind column k1 (gemm_split3.hip g3_args: x2, K1, x2H, x2W, x2s, x2Ho, x2Wo)

@@ -31,7 +31,7 @@ def header_hash() -> int:
     return int(hashlib.sha256(HEADER.read_bytes()).hexdigest()[:15], 16)
 
 
-EXTRA_FLAGS = {"attn.hip": ["-DAWSEG_ATTN_SPLIT_WAVES=" + os.environ.get("AWSEG_ATTN_SPLIT_WAVES", "2")], "wino.hip": ["-fno-slp-vectorize"], "wino_split.hip": ["-fno-slp-vectorize", "-DAWSEG_WS_ASM_PK"],
+EXTRA_FLAGS = {"attn.hip": ["-DAWSEG_ATTN_SPLIT_WAVES=" + os.environ.get("AWSEG_ATTN_SPLIT_WAVES", "2")], "wino.hip": ["-fno-slp-vectorize"], "wino_split.hip": ["-fno-slp-vectorize"],
                "core.hip": ["-DAWSEG_HEADER_HASH=0x%xULL" % header_hash()]}
 
 

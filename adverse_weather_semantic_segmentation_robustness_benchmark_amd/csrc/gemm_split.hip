@@ -56,17 +56,6 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsig
     lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
 }
 
-// Unscaled form: hi = f16(x) (round toward zero), lo = f16(x - hi) — three instructions per pair (v_cvt_pkrtz + two v_fma_mix).
-// The low part keeps its 11 bits while |lo| >= 2^-14, i.e. |x| >= 2^-3; the single-accumulator kernel stages x * 2^4, which
-// moves that bound to 2^-7 (below it the absolute error is 2^-29 of a unit: far inside float32 grade for O(1) tensors).
-__device__ __forceinline__ void split_pair_unscaled(float a, float b, unsigned& hi, unsigned& lo)
-{
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(lo) : "v"(a), "v"(b), "v"(hi));
-}
-
 // power-of-two scale that brings a maximum magnitude with float bits `maxbits` into [2^13, 2^14): returns e with
 // scaled = v * 2^-e.  Zero / subnormal maxima (and Inf / NaN) leave the tensor unscaled.
 __device__ __forceinline__ int norm_exponent(unsigned maxbits)
@@ -147,17 +136,10 @@ __device__ __forceinline__ unsigned pack_bf16(float a, float b)
 // path): activations are rounded to bf16 when they are staged, weights come as one bf16 plane (awseg_gemm_bf16_weights
 // writes it where the split form keeps its high parts), float32 accumulation and epilogue.  bf16 has float32's exponent
 // range: no range guard, no second pass.
-// ONE = true: ONE accumulator per product tile.  The weights' low plane is brought back to its unscaled value when it is staged
-// (x 2^-11, exact: v_pk_mul_f16), the activations are split into unscaled parts, and the three products of a tile add into the
-// same registers — half the accumulator registers, which is what lets a wave own 128 x 64 (MT 4, NT 2: 12 KB of LDS fragment
-// reads per 24 MFMAs instead of 8 KB per 12) in a 256 x 256 block tile.
-template <int MT, int NT, int WM, int WN, bool KTAIL, bool BF16, bool ONE = false>
+template <int MT, int NT, int WM, int WN, bool KTAIL, bool BF16>
 __global__ __launch_bounds__(GT, (MT * NT <= 2 ? 4 : 2))
 void gemm_split_kernel(gemm_args a)
 {
-    static_assert(!(ONE && BF16), "single-accumulator form is for split operands");
-    constexpr float kSx0 = ONE ? 16.0f : 1.0f;                   // optimistic-pass activation scale (ONE: see split_pair_unscaled)
-    constexpr int kXe0 = ONE ? -4 : 0;
     static_assert(WM * WN == 8, "eight waves");
     constexpr int BM = 32 * MT * WM, BN = 32 * NT * WN;
     constexpr int NA = BM / 64;                                  // float4 of x per thread per K tile
@@ -213,8 +195,8 @@ void gemm_split_kernel(gemm_args a)
     float4 areg[NA]; u32x4 breg[NB];
     float amax = 0.f;                                            // max|x| this thread staged in the current pass
     bool scaled = false;                                         // second pass over a tile whose activations left the split range
-    float sx = kSx0;                                             // activation scale of the pass (2^-e)
-    int xe = kXe0;
+    float sx = 1.0f;                                             // activation scale of the pass (2^-e)
+    int xe = 0;
     auto fetch = [&](int k0) {
         if (a.conv) {                                            // block-uniform: the K tile's tap and its channel offset
             const int tap = k0 / a.cC, c0 = k0 - tap * a.cC + 4 * ac;
@@ -251,28 +233,17 @@ void gemm_split_kernel(gemm_args a)
                 *reinterpret_cast<u32x2*>(d) = H;
                 continue;
             }
-            if (ONE || scaled) { v.x *= sx; v.y *= sx; v.z *= sx; v.w *= sx; }       // block-uniform branch
+            if (scaled) { v.x *= sx; v.y *= sx; v.z *= sx; v.w *= sx; }       // block-uniform branch
             amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));   // v_max3_f32 with |.| modifiers
             amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v.z)), __builtin_fabsf(v.w));
-            if (ONE) {
-                split_pair_unscaled(v.x, v.y, hh, ll); H[0] = hh; L[0] = ll;
-                split_pair_unscaled(v.z, v.w, hh, ll); H[1] = hh; L[1] = ll;
-            } else {
-                split_pair(v.x, v.y, hh, ll); H[0] = hh; L[0] = ll;
-                split_pair(v.z, v.w, hh, ll); H[1] = hh; L[1] = ll;
-            }
+            split_pair(v.x, v.y, hh, ll); H[0] = hh; L[0] = ll;
+            split_pair(v.z, v.w, hh, ll); H[1] = hh; L[1] = ll;
             *reinterpret_cast<u32x2*>(d) = H;
             *reinterpret_cast<u32x2*>(d + 32) = L;
         }
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             if (BF16 && (i & 1)) continue;
-            if (ONE && (i & 1)) {                                // low plane: stored as (w - hi) * 2^11 -> back to w - hi
-                // one vector multiply (element-wise writes through breg[i][q] in a loop were compiled into a chain reading the
-                // element just written: hipcc / clang-22, checked in the ISA)
-                const h8 lo8 = __builtin_bit_cast(h8, breg[i]) * (_Float16)0.00048828125f;
-                breg[i] = __builtin_bit_cast(u32x4, lo8);
-            }
             *reinterpret_cast<u32x4*>(&sB[buf][bdst0 + (i >> 1) * 128 * GROW + 32 * (i & 1)]) = breg[i];
         }
     };
@@ -341,7 +312,7 @@ void gemm_split_kernel(gemm_args a)
             // tile "not small" (one lane, a plain LDS write); a wave all of whose lanes stayed below reports its lanes' maxima, so a block
             // none of whose waves marked the tile knows its maximum.  O(1) tiles: one compare and one LDS write per wave, no atomics.
             if (!BF16 && t == nkt - 1 && !scaled) {
-                const bool not_small = __ballot(amax >= kSmallLimit * kSx0) != 0ull;
+                const bool not_small = __ballot(amax >= kSmallLimit) != 0ull;
                 if (amax >= kSplitLimit || !not_small) atomicMax(&sMax[par], __builtin_bit_cast(unsigned, amax));
                 if (not_small && lane == 0) sMax[2 + par] = 1u;
             }
@@ -377,11 +348,6 @@ void gemm_split_kernel(gemm_args a)
                             continue;
                         }
                         am[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i], Bh[j], am[i][j], 0, 0, 0);
-                        if (ONE) {
-                            am[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i], Bl[j], am[i][j], 0, 0, 0);
-                            am[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[i], Bh[j], am[i][j], 0, 0, 0);
-                            continue;
-                        }
                         ac2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah[i], Bl[j], ac2[i][j], 0, 0, 0);
                         ac2[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al[i], Bh[j], ac2[i][j], 0, 0, 0);
                     }
@@ -408,11 +374,11 @@ void gemm_split_kernel(gemm_args a)
             const unsigned mx = BF16 ? 0u : sMax[par];           // written before the K loop's last barrier; block-uniform
             const bool small = !BF16 && sMax[2 + par] == 0u;
             par ^= 1;
-            constexpr unsigned kBig = __builtin_bit_cast(unsigned, kSplitLimit), kSmall = __builtin_bit_cast(unsigned, kSmallLimit * kSx0);
+            constexpr unsigned kBig = __builtin_bit_cast(unsigned, kSplitLimit), kSmall = __builtin_bit_cast(unsigned, kSmallLimit);
             if (!scaled && (mx >= kBig || (small && mx >= 0x00800000u && mx < kSmall))) {    // (a subnormal or zero maximum stays as it is)
                 const int ex = (int)(mx >> 23) & 0xff;
                 if (ex != 0xff) {                                // Inf / NaN: nothing to rescue, let them propagate
-                    xe = ex - 127 - 13 + kXe0;                   // max|x| * 2^-xe in [2^13, 2^14) (the maximum was taken after the x 2^-kXe0 staging scale)
+                    xe = ex - 127 - 13;                          // max|x| * 2^-xe in [2^13, 2^14)
                     xe = xe < -127 ? -127 : xe;                  // xe in [-127, 114]: one factor is enough
                     sx = pow2f(-xe);
                     scaled = true;
@@ -424,7 +390,7 @@ void gemm_split_kernel(gemm_args a)
         }
         // result scale: 2^(we + xe), applied as two factors (each a normal float; their product may legitimately overflow
         // to Inf exactly where the float32 GEMM would)
-        const int oe = we + xe;                                  // xe = kXe0 on the optimistic pass
+        const int oe = we + xe;                                  // xe = 0 on the optimistic pass
         const int oe1 = oe / 2, oe2 = oe - oe1;
         const float os1 = pow2f(oe1 < -126 ? -126 : (oe1 > 127 ? 127 : oe1)), os2 = pow2f(oe2 < -126 ? -126 : (oe2 > 127 ? 127 : oe2));
         const bool rescale = oe != 0;
@@ -468,7 +434,7 @@ void gemm_split_kernel(gemm_args a)
 #pragma unroll
                         for (int r8 = 0; r8 < 8; ++r8) {
                             const int r = 8 * half + r8;
-                            float vv = ONE ? am[i][j][r] : fmaf(ac2[i][j][r], kLoInv, am[i][j][r]);
+                            float vv = fmaf(ac2[i][j][r], kLoInv, am[i][j][r]);
                             if (rescale) vv = vv * os1 * os2;                                  // block-uniform branch
                             vv = vv + bv + rv[r8];
                             if (a.act == 1) vv = fmaxf(vv, 0.f);
@@ -480,7 +446,7 @@ void gemm_split_kernel(gemm_args a)
         }
         if (!has_next) break;
         slot = nslot; m0 = nm0; n0 = nn0;
-        scaled = false; sx = kSx0; xe = kXe0;
+        scaled = false; sx = 1.0f; xe = 0;
     }
 }
 
@@ -530,17 +496,10 @@ int gemm_launch(bool bf16, const float* x, const uint16_t* w_split, const float*
     a.conv = cv ? 1 : 0;
     if (cv) { a.cH = cv->H; a.cW = cv->W; a.cC = cv->C; a.cHo = cv->Ho; a.cWo = cv->Wo; a.ckw = cv->kw; a.cs = cv->stride; a.cp = cv->pad; a.cd = cv->dil; }
     else { a.cH = a.cW = a.cC = a.cHo = a.cWo = a.ckw = a.cs = 1; a.cp = 0; a.cd = 1; }
-    static int cus = 0;                                          // CU count of the (single, per-process) device, read once
-    if (cus == 0) {
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-        cus = n_cu;
-    }
-    static int v3_on = -1;                                       // AWSEG_GEMM_SPLIT_V3=0: keep the register-staged kernels of round 2 (A/B measurements)
-    if (v3_on < 0) { const char* e = getenv("AWSEG_GEMM_SPLIT_V3"); v3_on = e ? atoi(e) : 1; }
+    const int cus = awseg_cu_count();
     // (bf16: only the 256-wide tile — on B5 + R101's N = 64 / 128 / 320 projections the narrow tiles measured slower than the
-    // round-2 bf16 kernel: 105.0 against 98.7 ms per step)
-    if (v3_on && awseg_gemm_split3_eligible(m, n, k, cv ? nullptr : x, out, residual, bias) && !(bf16 && (cv || n % 256)) &&
+    // register-staged bf16 kernel: 105.0 against 98.7 ms per step)
+    if (awseg_gemm_split3_eligible(m, n, k, cv ? nullptr : x, out, residual, bias) && !(bf16 && (cv || n % 256)) &&
         (!cv || (cv->C % 32 == 0 && (int64_t)cv->batch * cv->H * cv->W * (cv->pitch > 0 ? cv->pitch : cv->C) * 4 <= 0x7fffffff)) &&
         (((m + 255) / 256) * (int64_t)((n + awseg_gemm_split3_bn(n) - 1) / awseg_gemm_split3_bn(n)) >= (int64_t)cus / 2 ||
          (!bf16 && ((m + 127) / 128) * (int64_t)((n + 127) / 128) >= (int64_t)cus / 2))) {     // few rows: 128-row tiles (gemm_split3.hip picks them)
@@ -550,29 +509,16 @@ int gemm_launch(bool bf16, const float* x, const uint16_t* w_split, const float*
                                         cv ? cdesc : nullptr, bf16);
     }
     if (cv && cv->pitch > 0) return AWSEG_ERANGE;                // the ROWS form exists in the LDS-DMA kernel only
-    static int tile_mode = -1;                                   // AWSEG_GEMM_SPLIT_TILE = 128 / 256 / 512 forces the block tile (measurements; 512 = 256 x 256)
-    if (tile_mode < 0) { const char* e = getenv("AWSEG_GEMM_SPLIT_TILE"); tile_mode = !e ? 0 : (atoi(e) == 512 ? 3 : (atoi(e) == 256 ? 2 : (atoi(e) == 128 ? 1 : 0))); }
-    // 256 x 256 (single accumulator) when N fills it and there is at least one tile per CU (AWSEG_GEMM_SPLIT_HUGE_MIN_TILES per CU); else the 128 x 256 tile when N
-    // fills it and there are enough tiles for every CU; else 128 x 128
-    static int huge_min = -1;
-    if (huge_min < 0) { const char* e = getenv("AWSEG_GEMM_SPLIT_HUGE_MIN_TILES"); huge_min = e ? atoi(e) : 1; }
-    const bool huge = (tile_mode == 3 || (tile_mode == 0 && n % 256 == 0 && k >= 128 && ((m + 255) / 256) * (int64_t)(n / 256) >= (int64_t)huge_min * cus));   // K = 64: two K tiles per 256 x 256 epilogue, measured 6 % slower
-    const bool wide = !huge && (tile_mode == 2 || (tile_mode == 0 && n % 256 == 0 && ((m + 127) / 128) * (int64_t)(n / 256) >= cus));
-    // 256 x 128 (single accumulator, 64 x 64 wave tiles: 8 KB of LDS fragment reads per 12 MFMAs where the 128 x 128 tile's 32 x 64
-    // wave tiles read 6 KB per 6) for the N % 128 == 0 shapes that cannot fill 256-wide tiles; AWSEG_GEMM_SPLIT_TALL=0 turns it off
-    static int tall_on = -1;
-    if (tall_on < 0) { const char* e = getenv("AWSEG_GEMM_SPLIT_TALL"); tall_on = e ? atoi(e) : 1; }
-    const bool tall = !huge && !wide && !bf16 && tile_mode == 0 && tall_on && n % 128 == 0 && k >= 128 &&
-                      ((m + 255) / 256) * (int64_t)(n / 128) >= cus;
-    const int bn = (wide || huge) ? 256 : 128;
-    const int bm = (huge || tall) ? 256 : 128;
+    // 128 x 256 when N fills it and there are enough tiles for every CU; else 128 x 128
+    const bool wide = n % 256 == 0 && ((m + 127) / 128) * (int64_t)(n / 256) >= cus;
+    const int bn = wide ? 256 : 128, bm = 128;
     const int64_t ntm = (m + bm - 1) / bm;
     a.ntn = (n + bn - 1) / bn;
     const int64_t ntm8 = (ntm + 7) / 8 * 8;                      // 8 m-tiles (one per XCD) x all n-tiles per group
     if (ntm8 * a.ntn > 0x7fffffff || (int64_t)bm * n > 0x7fffffff) return AWSEG_ERANGE;
     a.ntm = (int)ntm; a.ntm8 = (int)ntm8;
     const int64_t slots = ntm8 * a.ntn;
-    int64_t blocks = (int64_t)cus * ((wide || huge || tall) ? 1 : 2) / 8 * 8;      // persistent: one (128 x 256 / 256 x 256 / 256 x 128) or two (128 x 128) blocks per CU
+    int64_t blocks = (int64_t)cus * (wide ? 1 : 2) / 8 * 8;      // persistent: one (128 x 256) or two (128 x 128) blocks per CU
     if (blocks < 8) blocks = 8;
     if (blocks > slots) blocks = slots;                          // slots is a multiple of 8
     const dim3 grid((unsigned)blocks), block(GT);
@@ -586,19 +532,7 @@ int gemm_launch(bool bf16, const float* x, const uint16_t* w_split, const float*
             else hipLaunchKernelGGL((gemm_split_kernel<MT_, NT_, WM_, WN_, false, false>), grid, block, 0, awseg_s(stream), a);        \
         }                                                                                                             \
     } while (0)
-    if (huge && bf16) {                                          // one product per tile anyway: the same 128 x 64 wave tiles
-        if (k % GKT) hipLaunchKernelGGL((gemm_split_kernel<4, 2, 2, 4, true, true, false>), grid, block, 0, awseg_s(stream), a);
-        else hipLaunchKernelGGL((gemm_split_kernel<4, 2, 2, 4, false, true, false>), grid, block, 0, awseg_s(stream), a);
-    }
-    else if (huge) {
-        if (k % GKT) hipLaunchKernelGGL((gemm_split_kernel<4, 2, 2, 4, true, false, true>), grid, block, 0, awseg_s(stream), a);
-        else hipLaunchKernelGGL((gemm_split_kernel<4, 2, 2, 4, false, false, true>), grid, block, 0, awseg_s(stream), a);
-    }
-    else if (tall) {
-        if (k % GKT) hipLaunchKernelGGL((gemm_split_kernel<2, 2, 4, 2, true, false, true>), grid, block, 0, awseg_s(stream), a);
-        else hipLaunchKernelGGL((gemm_split_kernel<2, 2, 4, 2, false, false, true>), grid, block, 0, awseg_s(stream), a);
-    }
-    else if (wide) GEMM_GO(2, 2, 2, 4); else GEMM_GO(1, 2, 4, 2);
+    if (wide) GEMM_GO(2, 2, 2, 4); else GEMM_GO(1, 2, 4, 2);
 #undef GEMM_GO
     AWSEG_LAUNCH_CHECK();
     return 0;
@@ -643,14 +577,8 @@ AWSEG_API int awseg_gemm_split_dual_bias_act(const float* x, int k1, const float
         d.bytes = m * (int64_t)k2 * 4;
     }
     if (d.bytes > 0x7fffffff) return AWSEG_ERANGE;                // 32-bit offsets into the second source
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-        cus = n_cu;
-    }
     return awseg_gemm_split3_launch(x, w_split + 2 * (int64_t)n * k + 8, reinterpret_cast<const unsigned*>(w_split + 2 * (int64_t)n * k), bias, residual,
-                                    act, out, m, n, k, cus, awseg_s(stream), nullptr, false, &d);
+                                    act, out, m, n, k, awseg_cu_count(), awseg_s(stream), nullptr, false, &d);
 }
 
 AWSEG_API int awseg_gemm_split_pieces_bias_act(const float* const* pieces, int n_pieces, int k_piece, const uint16_t* w_split, const float* bias,
@@ -671,14 +599,8 @@ AWSEG_API int awseg_gemm_split_pieces_bias_act(const float* const* pieces, int n
     d.bytes = m * (int64_t)k_piece * 4;
     d.x3 = n_pieces > 2 ? pieces[2] : nullptr; d.x4 = n_pieces > 3 ? pieces[3] : nullptr;
     if (d.bytes > 0x7fffffff) return AWSEG_ERANGE;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n_cu = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
-        cus = n_cu;
-    }
     return awseg_gemm_split3_launch(pieces[0], w_split + 2 * (int64_t)n * k + 8, reinterpret_cast<const unsigned*>(w_split + 2 * (int64_t)n * k), bias, residual,
-                                    act, out, m, n, k, cus, awseg_s(stream), nullptr, false, &d);
+                                    act, out, m, n, k, awseg_cu_count(), awseg_s(stream), nullptr, false, &d);
 }
 
 AWSEG_API int awseg_conv_gemm_split_bias_act(const float* x, int64_t batch, int height, int width, int channels, int kernel_h,

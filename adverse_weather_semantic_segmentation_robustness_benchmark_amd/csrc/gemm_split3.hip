@@ -1,7 +1,7 @@
 // gemm_split3.hip — the operator of gemm_split.hip (out[M,N] = act(x[M,K] . w[N,K]^T + bias (+ residual)), float32 grade on
 // the f16 matrix cores with split operands; the 1x1 convolutions behind PKG/models/model.py:349 and the MiT Linear layers
 // behind :193-197) rebuilt around the LDS-DMA pipeline of cdna_hip_programming.md §5 for the shapes that fill 256-wide tiles
-// (N % 256 == 0, K % 32 == 0).  Round 2's kernel staged both operands through registers (global load -> split -> ds_write)
+// (N % 256 == 0, K % 32 == 0).  gemm_split.hip's kernel stages both operands through registers (global load -> split -> ds_write)
 // with every wave of the block in the same phase: cycle stamps put a third of a K tile into the barrier and a third into
 // staging, with the matrix pipe idle in both.  Here NO operand passes through a staging phase:
 //   * x (raw float32) and the weights (a k-blocked image [N][K/32][32 hi | 32 lo] f16, unscaled low parts, written once by
@@ -9,18 +9,17 @@
 //     operands) ahead, two stages of 64 KB; 16-byte chunks XOR-swizzled on the SOURCE address (chunk ^ ((row >> 1) & 7)), so
 //     the linear LDS-DMA image is conflict-free for ds_read_b128 fragment reads;
 //   * ONE barrier per K tile; a wave's only vector work in the loop is splitting the activation fragment it has just read
-//     (4 v_fma_mix per pair: hi = f16(x s), lo = f16(x s - hi); s = 2^4 as in gemm_split.hip's single-accumulator form) and
-//     the running max|x| of the range guard;
+//     (4 v_fma_mix per pair: hi = f16(x s), lo = f16(x s - hi); s = 2^4, see kActScale0) and the running max|x| of the
+//     range guard;
 //   * block = 256 x 256, 8 waves as 8 x 1: a wave owns 32 ROWS x all 256 columns (1 x 8 MFMA tiles, ONE accumulator each:
 //     128 registers), so every activation fragment is split by exactly one wave — 20 vector instructions beside 24 MFMAs
 //     per 16-deep step.  (The first build had 2 x 4 waves of 128 x 64: each activation fragment was split by the four waves
 //     that share its rows, 80 vector instructions per 24 MFMAs, and the ablation build without the split ran 25 % faster:
 //     v_fma_mix does not hide behind MFMAs at that density.)  The weight fragments — no vector work — are what the waves
 //     share: 36 ds_read_b128 per wave and K tile, 37 % of the LDS read rate at the MFMA-bound pace;
-//   * the product is computed TRANSPOSED (weights as the MFMA's row operand): a lane owns one output ROW and its registers
-//     4 consecutive COLUMNS, so the epilogue moves 16 bytes per lane and instruction (bias / residual / ReLU / rescale as
-//     before; raw-buffer accesses, rows past M dropped by the hardware range check) — a quarter of the store instructions;
-//   * persistent blocks, XCD-aware tile walk, the next tile's first K tile in flight during the epilogue (as before).
+//   * lanes own output COLUMNS as in gemm_split.hip (bias / residual / ReLU / rescale in the epilogue; raw-buffer accesses,
+//     rows past M dropped by the hardware range check);
+//   * persistent blocks, XCD-aware tile walk, the next tile's first K tile in flight during the epilogue (as gemm_split.hip).
 // Operand range: as gemm_split.hip — weights normalised when they are split, activations split optimistically (x 2^4) while
 // the block tracks max|x|; a tile that met |x| >= 2^11, or whose max|x| < 2^-7 (low parts f16 subnormals: the small side), is
 // recomputed with x 2^-e and rescaled in the epilogue.  Per tile, not per row.
@@ -36,13 +35,13 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int G3M_MAX = 256, G3K = 32;     // the tile has 32 WV rows (WV = 8 or 4 waves); one operand's stage: rows x 128 B
 // two stages of two operands + sMax[4]; the four-wave blocks pack the weight stages (64-column tiles: 48 KB a block, THREE blocks per CU)
 constexpr int g3_lds(int wv, int nt) { return 2 * (32 * wv * 128) + 2 * (wv == 8 ? 32 * wv * 128 : 32 * nt * 128) + 64; }
-constexpr float kActScale0 = 16.0f;        // optimistic-pass activation scale (gemm_split.hip: split_pair_unscaled)
+// Optimistic-pass activation scale.  One accumulator per product tile means the low parts are used UNSCALED: lo = f16(x s - hi)
+// keeps its 11 bits while |lo| >= 2^-14, i.e. |x s| >= 2^-3.  Staging x * 2^4 moves that bound to |x| >= 2^-7 (below it the
+// absolute error is 2^-29 of a unit: far inside float32 grade for O(1) tensors) at the price of the large side: 2^11 instead of 2^15.
+constexpr float kActScale0 = 16.0f;
 constexpr int kActExp0 = -4;
-constexpr float kSplitLimit3 = 2048.0f;
+constexpr float kSplitLimit3 = 2048.0f;     // |x| below this splits without loss at scale 2^4 (|x s| < 2^15)
 constexpr float kSmallLimit3 = 0.0078125f;  // a tile whose max|x| is below 2^-7 is redone scaled (small-side guard)
-#ifndef G3_TRANSPOSED
-#define G3_TRANSPOSED 0                    // 1: weights as the MFMA's row operand, lane = output row, 16-byte epilogue accesses (measured slower)
-#endif    // |x| below this splits without loss at scale 2^4 (|x s| < 2^15)
 
 __device__ __forceinline__ float pow2f3(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }
 
@@ -84,9 +83,6 @@ struct g3_args {
     const unsigned* trailer;               // {max|w| bits, weight exponent ew, 0, 0}
     int64_t M; int N, K, act, ntm, ntm8, ntn;
     int img_bn;                            // rows of an n-tile of the weight image (>= the block tile's width)
-    int rot;                               // measurement switch (AWSEG_G3_ROT): block b starts its K loop at K tile (b * rot) % nkt
-    int prio;                              // AWSEG_G3_PRIO (default 0): waves 4-7 at raised priority during the first 16-deep step of a K tile
-    int stagger;                           // AWSEG_G3_STAGGER (default 1): waves 4-7 issue their LDS-DMA between the two 16-deep steps of a K tile
     // CONV: x is an NHWC image batch [B, cH, cW, cC] (cC % 32 == 0: a K tile lies inside one tap) and row m = (b, oy, ox) of the
     // A operand is gathered from it by the LDS-DMA's per-lane source address — column k = (ky * ckw + kx) * cC + c is
     // x[b, oy * cs - cp + ky * cd, ox * cs - cp + kx * cd, c], zero outside (awseg_conv_gemm_split_bias_act)
@@ -105,8 +101,6 @@ struct g3_args {
     const float* x3; const float* x4; int K2;
 };
 
-// ABL != 0: ablation builds for measurements (wrong results, valid times; AWSEG_G3_ABL): 1 no LDS-DMA in the K loop, 2 no MFMAs,
-// 3 no operand split, 4 no activation fragment reads, 5 no weight fragment reads
 // BF16: BASELINE config 5 — ONE v_mfma_f32_32x32x16_bf16 per product tile: the activation fragment is rounded to bf16 (RNE) by the
 // wave that multiplies it, the weights come as a bf16 image [N/256][KB][256][32] (64-byte rows: a 16 KB stage), float32
 // accumulation and epilogue; bf16 has float32's exponent range: no range guard, no scaling.
@@ -121,7 +115,8 @@ __device__ __forceinline__ unsigned pack_bf16_3(float x, float y) { return __bui
 // 64 KB — TWO blocks per CU, so that one block's epilogue (its stores leave a CU at ~15 B/clk: 17 k cycles for a 256 x 256 tile,
 // a third of a K = 256 tile's time) runs beside the other block's K loop; the price is NT <= 4 (every activation
 // fragment is split once per 128 columns instead of 256) and twice the weight traffic from L2 per product.
-template <bool CONV, int ABL = 0, bool BF16 = false, int NT = 8, int WV = 8, bool DUAL = false>
+// (the unnamed second parameter is unused: bench.py finds these kernels by the prefix of their six-argument names)
+template <bool CONV, int = 0, bool BF16 = false, int NT = 8, int WV = 8, bool DUAL = false>
 __global__ __launch_bounds__(64 * WV, 2)
 void gemm_split3_kernel(g3_args a)
 {
@@ -276,14 +271,12 @@ void gemm_split3_kernel(g3_args a)
     bool scaled = false;
     bool stores_pending = false;                                  // an epilogue's stores may still be in flight
     int g = 0;                                                    // running K-tile counter: stage = g & 1 across output tiles
-    const int kt0 = a.rot ? (int)(((unsigned)blockIdx.x * (unsigned)a.rot) % (unsigned)nkt) : 0;
-    auto ktile = [&](int t) { const int u = t + kt0; return u >= nkt ? u - nkt : u; };
 #ifdef AWSEG_G3_STAMP
     unsigned long long g3s[6] = {0, 0, 0, 0, 0, 0};
     G3_T(sb0);
 #endif
     point(m0, n0);
-    issue(ktile(0), 0);
+    issue(0, 0);
 
     while (true) {
         int nslot = slot + gridDim.x;
@@ -302,46 +295,39 @@ void gemm_split3_kernel(g3_args a)
             const int st = g & 1;
             // K tile t (issued one tile ago) has landed for this wave; behind the barrier for every wave — and every wave has
             // finished the MFMAs of tile t-1, whose fragments came from the other stage: it may be refilled now.
-            // (first K tile behind an epilogue: the epilogue's stores — 128, or 32 in the transposed form — are the youngest
-            // vector-memory operations and the 8 LDS-DMA of this K tile are older than all of them: "at most 63 (32)
-            // outstanding" means the DMA have landed, without waiting out the stores' write latency)
+            // (first K tile behind an epilogue: the epilogue's stores are the youngest vector-memory operations and the 8 LDS-DMA
+            // of this K tile are older than all of them: "at most as many outstanding as there are stores" means the DMA have
+            // landed, without waiting out the stores' write latency)
             G3_T(s0);
             // (per template: the epilogue issues 16 NT stores — 128 / 64 / 32 — so "all but the min(63, 16 NT) youngest" covers the DMA
             // explicitly; with vmcnt(63) the 32-store tiles would lean on the compiler's wait for the bias loads issued behind the DMA)
-            if (t == 0 && stores_pending) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(G3_TRANSPOSED ? 32 : (16 * NT < 63 ? 16 * NT : 63)) : "memory");
+            if (t == 0 && stores_pending) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(16 * NT < 63 ? 16 * NT : 63) : "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             // (the next output tile's first K tile is issued behind the guard check.)  Issuing its eight LDS-DMA instructions keeps a
             // wave away from its MFMAs for ~800 cycles (tools/probe_wino_stamps.hip: ~100 per instruction): waves 0-3 do it here, their
-            // SIMD partners 4-7 between the two 16-deep steps, so a SIMD always has one wave multiplying (AWSEG_G3_STAGGER=0: all here)
-            const bool issue_late = a.stagger && wave_u >= 4;
+            // SIMD partners 4-7 between the two 16-deep steps, so a SIMD always has one wave multiplying
+            const bool issue_late = wave_u >= 4;
             G3_T(s1);
-            if (t + 1 < nkt && ABL != 1 && !issue_late) issue(ktile(t + 1), st ^ 1);
+            if (t + 1 < nkt && !issue_late) issue(t + 1, st ^ 1);
             G3_T(s2);
             if (t == 0 && tid == 0) { sMax[par ^ 1] = 0u; sMax[2 + (par ^ 1)] = 0u; }
             const unsigned char* sa = smem + st * G3_STAGE;
             const unsigned char* sbw = smem + st * G3_BSTAGE;         // weight fragments (fb carries G3_B0)
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                // The arbiter favours the older wave of a SIMD: the stamps show waves 0-3 done with a K tile after 2 400 cycles and waiting
-                // 1 100 at the barrier for their partners, which finish the last third alone (one wave cannot keep the matrix pipe
-                // busy).  AWSEG_G3_PRIO=1 runs the FIRST 16-deep step of waves 4-7 at raised priority: 1-4 % on the long-K shapes in
-                // isolation (l4 conv1 0.381 -> 0.367 ms), -0.3 % on the whole step in an A/B on one box: off by default.
-                if (a.prio && wave_u >= 4) { if (ks == 0) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+                // (The arbiter favours the older wave of a SIMD: the stamps show waves 0-3 done with a K tile after 2 400 cycles and waiting
+                // 1 100 at the barrier for their partners.  Measured and dropped: the first 16-deep step of waves 4-7 at raised priority —
+                // 1-4 % on the long-K shapes in isolation, -0.3 % on the whole step.)
 #ifdef AWSEG_G3_STAMP
                 if (ks == 1) { G3_T(s3); g3s[2] += s3 - s2; g3s[5] = s3; }
 #endif
-                if (ks == 1 && t + 1 < nkt && ABL != 1 && issue_late) issue(ktile(t + 1), st ^ 1);
-                f32x4 p, q;
-                if (ABL == 4) { p = f32x4{(float)t, 1.f, 2.f, 3.f}; q = f32x4{(float)ks, 1.f, 2.f, 3.f}; }
-                else {
-                    p = *reinterpret_cast<const f32x4*>(sa + fa[ks][0]);
-                    q = *reinterpret_cast<const f32x4*>(sa + fa[ks][1]);
-                }
+                if (ks == 1 && t + 1 < nkt && issue_late) issue(t + 1, st ^ 1);
+                const f32x4 p = *reinterpret_cast<const f32x4*>(sa + fa[ks][0]);
+                const f32x4 q = *reinterpret_cast<const f32x4*>(sa + fa[ks][1]);
                 h8 Bh[NT], Bl[NT];
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    if (ABL == 5) { Bh[j] = h8{(_Float16)t, (_Float16)j, 1, 2, 3, 4, 5, 6}; Bl[j] = h8{(_Float16)ks, (_Float16)j, 1, 2, 3, 4, 5, 6}; continue; }
                     if (BF16) { Bh[j] = *reinterpret_cast<const h8*>(sbw + fb[ks][0] + j * 2048); Bl[j] = Bh[j]; continue; }
                     Bh[j] = *reinterpret_cast<const h8*>(sbw + fb[ks][0] + j * 4096);
                     Bl[j] = *reinterpret_cast<const h8*>(sbw + fb[ks][1] + j * 4096);
@@ -358,27 +344,16 @@ void gemm_split3_kernel(g3_args a)
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(p[2])), __builtin_fabsf(p[3]));
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(q[0])), __builtin_fabsf(q[1]));
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(q[2])), __builtin_fabsf(q[3]));
-                if (ABL == 3) { H = __builtin_bit_cast(u32x4, p); L = __builtin_bit_cast(u32x4, q); }
-                else {
-                    split2(p[0], p[1], sx, h, l); H[0] = h; L[0] = l;
-                    split2(p[2], p[3], sx, h, l); H[1] = h; L[1] = l;
-                    split2(q[0], q[1], sx, h, l); H[2] = h; L[2] = l;
-                    split2(q[2], q[3], sx, h, l); H[3] = h; L[3] = l;
-                }
+                split2(p[0], p[1], sx, h, l); H[0] = h; L[0] = l;
+                split2(p[2], p[3], sx, h, l); H[1] = h; L[1] = l;
+                split2(q[0], q[1], sx, h, l); H[2] = h; L[2] = l;
+                split2(q[2], q[3], sx, h, l); H[3] = h; L[3] = l;
                 const h8 Ah = __builtin_bit_cast(h8, H), Al = __builtin_bit_cast(h8, L);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
-                    if (ABL == 2) { asm volatile("" : : "v"(Ah), "v"(Al), "v"(Bh[j]), "v"(Bl[j])); continue; }
-                    if (G3_TRANSPOSED) {
-                        // transposed product: rows of the accumulator tile = weight rows n, columns (lanes) = activation rows m
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bh[j], Ah, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl[j], Ah, acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bh[j], Al, acc[j], 0, 0, 0);
-                    } else {
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[j], acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[j], acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[j], acc[j], 0, 0, 0);
-                    }
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bh[j], acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Ah, Bl[j], acc[j], 0, 0, 0);
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Al, Bh[j], acc[j], 0, 0, 0);
                 }
             }
 #ifdef AWSEG_G3_STAMP
@@ -412,58 +387,17 @@ void gemm_split3_kernel(g3_args a)
         }
         if (again) {                                               // same tile again, scaled: its first K tile into the free stage
             stores_pending = false;
-            issue(ktile(0), g & 1);
+            issue(0, g & 1);
             continue;
         }
         // the next output tile's first K tile travels during the epilogue (stage g & 1 was last read two K tiles ago)
         const int64_t em0 = m0; const int en0 = n0;
-        if (has_next) { point(nm0, nn0); issue(ktile(0), g & 1); }
+        if (has_next) { point(nm0, nn0); issue(0, g & 1); }
 
         const int oe = BF16 ? 0 : we + xe;
         const int oe1 = oe / 2, oe2 = oe - oe1;
         const float os1 = pow2f3(oe1 < -126 ? -126 : (oe1 > 127 ? 127 : oe1)), os2 = pow2f3(oe2 < -126 ? -126 : (oe2 > 127 ? 127 : oe2));
 
-#if G3_TRANSPOSED
-        // ---- epilogue: lane = output row m (32 wave + li), registers 4 g4 .. 4 g4 + 3 of tile j = four consecutive columns
-        // 32 j + 8 g4 + 4 hk ..: 16-byte accesses.  BRANCH-FREE on purpose: a missing bias / residual is read through a
-        // zero-record descriptor (the hardware returns zeros).  With `has_res ? load : 0` the loads sat in their own basic
-        // blocks and hipcc (clang-22) placed a `v_mov v, 0` of a store-data register directly behind a 16-byte store across
-        // the block boundary — the store then wrote the zero (seen as exact zeros in column 8 g4 + 2 of some rows, run-dependent).
-        {
-            const int64_t tile_off = em0 * a.N + en0;
-            const int64_t rem = ((int64_t)a.M * a.N - tile_off) * 4;
-            const int nrec = rem > 0x7fffffff ? 0x7fffffff : (int)rem;
-            const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + tile_off), 0, nrec, 0x00020000);
-            const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((a.residual ? a.residual : a.out) + tile_off), 0, a.residual ? nrec : 0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t b_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)((a.bias ? a.bias : a.out) + en0), 0, a.bias ? BN * 4 : 0, 0x00020000);
-            const int voff = ((wave * 32 + li) * a.N + 4 * hk) * 4;
-            const float relu_floor = a.act == 1 ? 0.f : -__builtin_inff();
-#pragma unroll
-            for (int j = 0; j < NT; ++j) {
-                f32x4 bv[4], rv[4];
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    bv[g4] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(b_rsrc, 16 * hk + (j * 32 + 8 * g4) * 4, 0, 0));
-                    rv[g4] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r_rsrc, voff + (j * 32 + 8 * g4) * 4, 0, 0));
-                }
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4) {
-                    f32x4 v;
-#pragma unroll
-                    for (int qq = 0; qq < 4; ++qq) {
-                        float vv = acc[j][4 * g4 + qq] * os1 * os2;
-                        vv = vv + bv[g4][qq] + rv[g4][qq];
-                        v[qq] = __builtin_fmaxf(vv, relu_floor);
-                    }
-                    // the column offset rides in the instruction's IMMEDIATE offset (vector offset + constant, scalar offset 0), not in
-                    // a scalar register: with an SGPR offset hipcc pads no wait state between a 16-byte store and the next vector
-                    // write of its data registers (LLVM's rule: that hazard exists only without an soffset register) — on gfx950
-                    // the store then picked up the NEXT group's value in its first dword (wrong, run-dependent outputs)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), o_rsrc, voff + (j * 32 + 8 * g4) * 4, 0, 0);
-                }
-            }
-        }
-#else
         // ---- epilogue: lane = output column n (32 j + li), registers = rows m (32 wave + 8 (r >> 2) + 4 hk + (r & 3)): a store
         // instruction writes two full 128-byte lines.  (The transposed form — lane = row, 16-byte accesses, a quarter of the
         // instructions — was measured SLOWER wherever the epilogue dominates (K = 64: 0.62 against 0.48 ms): each of its
@@ -534,7 +468,6 @@ void gemm_split3_kernel(g3_args a)
                 for (int g = 0; g < 2 * NT; ++g) group_store(g, none, false);
             }
         }
-#endif
         if (!has_next) break;
         stores_pending = true;
         slot = nslot; m0 = nm0; n0 = nn0;
@@ -648,15 +581,6 @@ int awseg_gemm_split3_launch(const float* x, const uint16_t* w3, const unsigned*
         a.x_bytes = (int64_t)conv[9] * a.cH * a.cW * a.cpitch * 4;
         if (a.cC % G3K || a.x_bytes > 0x7fffffff) return AWSEG_ERANGE;    // checked by the caller (eligibility)
     }
-    static int rot = -1;
-    if (rot < 0) { const char* e = getenv("AWSEG_G3_ROT"); rot = e ? atoi(e) : 0; }
-    a.rot = rot;
-    static int stagger = -1;
-    if (stagger < 0) { const char* e = getenv("AWSEG_G3_STAGGER"); stagger = e ? atoi(e) : 1; }
-    a.stagger = stagger;
-    static int prio = -1;
-    if (prio < 0) { const char* e = getenv("AWSEG_G3_PRIO"); prio = e ? atoi(e) : 0; }
-    a.prio = prio;
     a.x = x; a.w3 = w3; a.bias = bias; a.residual = residual; a.out = out; a.trailer = trailer;
     a.M = m; a.N = n; a.K = k; a.act = act;
     const int img_bn = awseg_gemm_split3_bn(n);
@@ -665,14 +589,12 @@ int awseg_gemm_split3_launch(const float* x, const uint16_t* w3, const unsigned*
     // little — measured per shape (kernel_bench, one box, 256-row -> 128-row): K = 64 N = 256 0.498 -> 0.442 ms, K = 128 N = 512
     // 0.269 -> 0.245, N = 64 K = 256 0.253 -> 0.238, N = 128 K = 512 0.152 -> 0.142; against it K = 256 / 304 N = 256 0.513 -> 0.59 /
     // 0.625 -> 0.70 (the activation split per 128 instead of 256 columns and twice the weight reads outweigh the overlap) and every
-    // long-K shape (K = 2048: +20 %).  AWSEG_G3_HALF=0 turns it off, =2 forces it on every shape (tests).
-    static int half_mode = -1;
-    if (half_mode < 0) { const char* e = getenv("AWSEG_G3_HALF"); half_mode = e ? atoi(e) : 1; }
+    // long-K shape (K = 2048: +20 %).
     const int bn_half = img_bn >= 128 ? 128 : 64;
     // ... and, whatever K, where 256-row tiles would leave CUs without a block (M = 16 384: MiT stage 4, the key / value projections)
     const bool few = ((m + 255) / 256) * (int64_t)((n + img_bn - 1) / img_bn) < (int64_t)cus;
-    const bool half = !bf16 && (half_mode == 2 || (half_mode == 1 && (few || ((k <= 128 || (img_bn <= 128 && k <= 512)) &&
-                                                   ((m + 127) / 128) * (int64_t)((n + bn_half - 1) / bn_half) >= 4 * (int64_t)cus))));
+    const bool half = !bf16 && (few || ((k <= 128 || (img_bn <= 128 && k <= 512)) &&
+                                        ((m + 127) / 128) * (int64_t)((n + bn_half - 1) / bn_half) >= 4 * (int64_t)cus));
     const int rows = half ? 128 : 256;
     const int bn = half ? bn_half : img_bn;
     const int64_t ntm = (m + rows - 1) / rows;
@@ -681,54 +603,26 @@ int awseg_gemm_split3_launch(const float* x, const uint16_t* w3, const unsigned*
     if (ntm8 * a.ntn > 0x7fffffff) return AWSEG_ERANGE;
     a.ntm = (int)ntm; a.ntm8 = (int)ntm8;
     const int64_t slots = ntm8 * a.ntn;
-    static int three = -1;                                          // AWSEG_G3_THREE=0: two four-wave blocks per CU for the 64-column tiles too
-    if (three < 0) { const char* e = getenv("AWSEG_G3_THREE"); three = e ? atoi(e) : 1; }
-    int64_t blocks = (int64_t)cus * (half ? ((bn == 64 && three) ? 3 : 2) : 1) / 8 * 8;
+    // one eight-wave block per CU (128 KB of LDS), two four-wave blocks, three where the 64-column tiles pack their weight stages (48 KB)
+    int64_t blocks = (int64_t)cus * (half ? (bn == 64 ? 3 : 2) : 1) / 8 * 8;
     if (blocks < 8) blocks = 8;
     if (blocks > slots) blocks = slots;
-    static int abl = -1;
-    if (abl < 0) { const char* e = getenv("AWSEG_G3_ABL"); abl = e ? atoi(e) : 0; }
-    if (abl && !conv && !bf16 && !dual && bn == 256) {
-#define G3_ABL(n) case n: { auto kf = gemm_split3_kernel<false, n>; (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds(8, 8)); hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(512), g3_lds(8, 8), stream, a); break; }
-        switch (abl) { G3_ABL(1) G3_ABL(2) G3_ABL(3) G3_ABL(4) G3_ABL(5) default: break; }
-#undef G3_ABL
-        AWSEG_LAUNCH_CHECK();
-        return 0;
-    }
-#define G3_GO(CONV_, BF_, NT_, WV_)                                                                                                    \
+    // (the > 64 KB dynamic-LDS attribute is set on every launch: it belongs to the current device, and a process may use several)
+#define G3_GO(CONV_, BF_, NT_, WV_, DUAL_)                                                                                             \
     do {                                                                                                                              \
-        auto kf = gemm_split3_kernel<CONV_, 0, BF_, NT_, WV_>;                                                                        \
-        static bool attr = false;                                                                                                     \
-        if (!attr) {                                                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds(WV_, NT_)); \
-            if (e != hipSuccess) return (int)e;                                                                                       \
-            attr = true;                                                                                                              \
-        }                                                                                                                             \
-        hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(64 * WV_), g3_lds(WV_, NT_), stream, a);                                       \
+        auto kf = gemm_split3_kernel<CONV_, 0, BF_, NT_, WV_, DUAL_>;                                                                 \
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds(WV_, NT_)); \
+        if (e != hipSuccess) return (int)e;                                                                                           \
+        hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(64 * WV_), g3_lds(WV_, NT_), stream, a);                                   \
     } while (0)
-#define G3_BY_NT(CONV_, BF_) do { if (bn == 256) G3_GO(CONV_, BF_, 8, 8); else if (bn == 128) G3_GO(CONV_, BF_, 4, 8); else G3_GO(CONV_, BF_, 2, 8); } while (0)
-#define G3_HALF(CONV_) do { if (bn == 128) G3_GO(CONV_, false, 4, 4); else G3_GO(CONV_, false, 2, 4); } while (0)
-#define G3_GO_DUAL(NT_, WV_)                                                                                                            \
-    do {                                                                                                                              \
-        auto kf = gemm_split3_kernel<false, 0, false, NT_, WV_, true>;                                                                \
-        static bool attr = false;                                                                                                     \
-        if (!attr) {                                                                                                                  \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kf), hipFuncAttributeMaxDynamicSharedMemorySize, g3_lds(WV_, NT_)); \
-            if (e != hipSuccess) return (int)e;                                                                                       \
-            attr = true;                                                                                                              \
-        }                                                                                                                             \
-        hipLaunchKernelGGL(kf, dim3((unsigned)blocks), dim3(64 * WV_), g3_lds(WV_, NT_), stream, a);                                       \
-    } while (0)
-    if (dual) {
-        if (half) { if (bn == 128) G3_GO_DUAL(4, 4); else G3_GO_DUAL(2, 4); }
-        else if (bn == 256) G3_GO_DUAL(8, 8); else if (bn == 128) G3_GO_DUAL(4, 8); else G3_GO_DUAL(2, 8);
-    }
-    else if (bf16) G3_BY_NT(false, true);
-    else if (half && conv) G3_HALF(true);
-    else if (half) G3_HALF(false);
-    else if (conv) G3_BY_NT(true, false);
-    else G3_BY_NT(false, false);
-#undef G3_GO_DUAL
+#define G3_BY_NT(CONV_, BF_, DUAL_) do { if (bn == 256) G3_GO(CONV_, BF_, 8, 8, DUAL_); else if (bn == 128) G3_GO(CONV_, BF_, 4, 8, DUAL_); else G3_GO(CONV_, BF_, 2, 8, DUAL_); } while (0)
+#define G3_HALF(CONV_, DUAL_) do { if (bn == 128) G3_GO(CONV_, false, 4, 4, DUAL_); else G3_GO(CONV_, false, 2, 4, DUAL_); } while (0)
+    if (dual) { if (half) G3_HALF(false, true); else G3_BY_NT(false, false, true); }
+    else if (bf16) G3_BY_NT(false, true, false);
+    else if (half && conv) G3_HALF(true, false);
+    else if (half) G3_HALF(false, false);
+    else if (conv) G3_BY_NT(true, false, false);
+    else G3_BY_NT(false, false, false);
 #undef G3_HALF
 #undef G3_BY_NT
 #undef G3_GO

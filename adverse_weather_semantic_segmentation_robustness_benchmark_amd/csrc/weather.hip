@@ -1645,11 +1645,8 @@ AWSEG_API int awseg_weather_batch(const uint8_t* imgs, int height, int width, co
     gauss_taps_f32 tf;
     for (int i = 0; i < 2 * FR + 1; ++i) tf.w[i] = (float)taps_host[i];
     const size_t lds = n_fog ? (size_t)kFogRing * 256 * sizeof(float4) : 0;
-    static bool attr_set = false;
-    if (lds && !attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(weather_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)kFogRing * 256 * sizeof(float4))) != hipSuccess) return AWSEG_EINVAL;
-        attr_set = true;
-    }
+    // (set on every launch: the attribute belongs to the current device, and a process may use several)
+    if (lds && hipFuncSetAttribute(reinterpret_cast<const void*>(weather_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL;
     hipLaunchKernelGGL(weather_batch_kernel, dim3((unsigned)next_block), dim3(256), lds, s, imgs, H, W, tab, tf, make_blur(3, 0.5), make_blur(3, 1.0),
                        gains_host[0], gains_host[1], gains_host[2], out, norm_out, make_nc(mean_host, std_host), bits, wd);
     AWSEG_LAUNCH_CHECK();
@@ -1724,11 +1721,7 @@ static int fog_common(int mode, const uint8_t* imgs, int H, int W, const awseg_f
             const int strips = strip_ok ? (H + strip_rows - 1) / strip_rows : 0;
             if (strip_ok && (strips + 3) / 4 <= 65535) {
                 const size_t lds = (size_t)kFogRing * 256 * sizeof(float4);
-                static bool attr_set = false;
-                if (!attr_set) {
-                    if (hipFuncSetAttribute(reinterpret_cast<const void*>(fog_strip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL;
-                    attr_set = true;
-                }
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(fog_strip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL;   // per launch: per device
                 dim3 sgrid(((W >> 2) + kFogStripQuads - 1) / kFogStripQuads, (strips + 3) / 4, cnt);
                 hipLaunchKernelGGL(fog_strip_kernel, sgrid, dim3(256), lds, s, imgs, H, W, pk, j0, tf, out, norm_out, depth_out, nc, strip_rows);
             }

@@ -14,19 +14,19 @@
 //     < 2^-4 (low parts would go subnormal) runs its tile again with x * 2^sx, sx from the observed maximum, and the
 //     epilogue multiplies 2^(eu - sx) back.  Same guard as gemm_split.hip / attn.hip.
 //
-// Block = 8x8 tiles (16x16 outputs) x 64 output channels, 4 waves, input channels in chunks of 16 (one K step of the
-// MFMA).  Wave (nt, ph) owns ALL 64 tiles x 32 couts x 8 of the 16 positions (V rows 2ph, 2ph+1): 2 m-tiles x 8
-// positions = 256 accumulator registers.  With this split every U fragment is loaded by exactly ONE wave of the block,
-// straight from L2 into registers (64 KB per chunk per CU; sharing U through LDS would need 64 KB of LDS per chunk, a
-// second wave pair loading the same fragments 128 KB of L2 traffic), and a wave's U fragment of a position feeds two
-// m-tiles.  The partial inverse transforms of the two position halves meet through LDS once, in the epilogue.
-//   * raw 18x18-pixel patch of a chunk: LDS-DMA, three chunks ahead, ring of three 21 KB slots;
+// Block = 8x8 tiles (16x16 outputs) x 64 output channels, 8 waves, input channels in chunks of 16 (one K step of the
+// MFMA).  A wave owns ALL 64 tiles x 32 couts x 4 of the 16 positions: 2 m-tiles x 4 positions = 128 accumulator
+// registers, two waves per SIMD.  With this split every U fragment is loaded by exactly ONE wave of the block, straight
+// from L2 into registers (64 KB per chunk per CU; sharing U through LDS would need 64 KB of LDS per chunk), and a wave's
+// U fragment of a position feeds two m-tiles.  The partial inverse transforms meet through LDS once, in the epilogue.
+//   * raw 18x18-pixel patch of a chunk: LDS-DMA, ring of three 21 KB slots;
 //   * V (f16 high | low parts, [position][tile][16 hi | 16 lo], 16-byte chunks XOR-swizzled by (tile >> 2) & 3:
 //     conflict-free ds_read_b128 A fragments) is SINGLE-buffered in 64 KB and refilled in halves behind the MFMAs that
 //     consumed them: a chunk is two slots — slot A: MFMAs on V rows {0, 2} while rows {1, 3} of the same chunk are
-//     written and the next chunk's patch is read and row-transformed; slot B: MFMAs on rows {1, 3} while rows {0, 2}
-//     of the next chunk are written — one barrier per slot;
-//   * transform item of a thread = (tile, 4 channels): ds_read_b64 of the patch, packed f32 adds, split, ds_write_b64.
+//     written; slot B: MFMAs on rows {1, 3} while rows {0, 2} of the next chunk are written — one barrier per slot;
+//   * transform item of a thread = (tile, 4 channels, one V row): one 16-byte read per patch pixel, float32 adds, split,
+//     ds_write_b64.
+// wino8s_kernel is one block per tile; wino8p_kernel the same block made persistent (launch_ws picks by map size).
 #include "awseg_common.h"
 
 namespace {
@@ -38,7 +38,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
-constexpr int WT = 256;                    // threads per block
 constexpr int TB = 8;                      // 8 x 8 tiles per block
 constexpr int NTILE = TB * TB;             // 64
 constexpr int KC = 16;                     // input channels per chunk = one K step of v_mfma_f32_32x32x16_f16
@@ -50,21 +49,17 @@ constexpr int P_BYTES = P_INSTR * 1024;    // 21504
 constexpr int P_RING = 3;
 constexpr int V_POS = NTILE * 64;          // bytes of one position: 64 tiles x (16 hi + 16 lo halfs)
 constexpr int V_BYTES = 16 * V_POS;        // 65536
-constexpr int LDS_BYTES = V_BYTES + P_RING * P_BYTES + 64;
 
 struct ws_args {
     const float* x; const uint16_t* U; const float* shift; const float* residual; const float* w2; const float* b2;
     float* out;
     int H, W, Cin, Cout, dil, act, nbx, nby, ngroups, batch;
     int nblocks, tpb;                      // wino8p_kernel: linear block indices in all, tiles per (persistent) block
-    int span;                              // wino8_kernel: spatial tiles of one XCD that run the same cout group back to back (block order)
     int64_t u_halfs;                       // halfs of U in front of the trailer {2^eu as float}
     // MODE 2 (wino8p_kernel only): the input map is not read but GENERATED per block from the bilinear forms of
     // awseg_upconv_forms (depthfuse.hip): forms [batch][F4 | F2] float32, fh x fw = the low-resolution grid (H = 32 fh, W = 32 fw)
     const float* forms; int fh, fw;
 };
-
-__device__ __forceinline__ float act_apply(float v, int act) { return (act == AWSEG_ACT_RELU) ? (v > 0.f ? v : 0.f) : v; }
 
 // LDS-DMA of 16 bytes per lane through a buffer descriptor (see wino.hip: inline asm on purpose, hardware range check
 // supplies the zero padding)
@@ -73,27 +68,10 @@ __device__ __forceinline__ void bufdma16(__amdgpu_buffer_rsrc_t rsrc, uint32_t v
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base) : "m0");
 }
 __device__ __forceinline__ void vm_wait_all() { asm volatile("s_waitcnt vmcnt(0)" : : : "memory"); }
-// everything but the six youngest vector-memory operations (the U fragments of the next three positions, fetched last)
-__device__ __forceinline__ void vm_wait_keep6() { asm volatile("s_waitcnt vmcnt(6)" : : : "memory"); }
 __device__ __forceinline__ uint32_t lds_addr(const void* p)
 {
     return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
 }
-
-#ifdef AWSEG_WS_ASM_PK
-__device__ __forceinline__ v2f pk_add(v2f a, v2f b) { v2f d; asm("v_pk_add_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
-__device__ __forceinline__ v2f pk_sub(v2f a, v2f b)
-{
-    v2f d;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-#else
-// plain vector arithmetic: the scheduler can classify these (sched_group_barrier) and, next to f16 MFMAs, whether hipcc
-// keeps them packed matters less than where they are placed
-__device__ __forceinline__ v2f pk_add(v2f a, v2f b) { return a + b; }
-__device__ __forceinline__ v2f pk_sub(v2f a, v2f b) { return a - b; }
-#endif
 
 // (a, b) -> packed f16 high parts and packed f16 low parts (a - f16(a), b - f16(b): exact in float32, then rounded to f16)
 // Three instructions: v_cvt_pkrtz_f16_f32, then one mixed-precision FMA per value — v_fma_mixlo/mixhi_f16 computes
@@ -119,13 +97,8 @@ __device__ __forceinline__ void split_pair_mfma(float x, float y, unsigned& hi, 
 }
 
 #ifdef AWSEG_WS_STAMP
-// tools/probe_wino_stamps.hip: s_memtime stamps of block 0, wave 0: [slot A work, barrier A, slot B work, barrier B,
-// chunks, prologue, epilogue, whole block]
-__device__ unsigned long long g_ws_stamp[8];
-__device__ unsigned long long g_ws_stamp2[8];                      // slot A in detail: [wait, DMA issue, group 0, group 1, group 2]
-#define WS_T(var) const unsigned long long var = __builtin_readcyclecounter()
-#else
-#define WS_T(var)
+// tools/probe_wino_stamps.hip: s_memtime stamps of block 0
+__device__ unsigned long long g_w8_stamp[2][8];                       // [wave 0 | wave 4][slot A work, barrier A, slot B work, barrier B, chunks, slot A: first half, second half]
 #endif
 
 struct awseg_false { static constexpr bool value = false; };
@@ -146,850 +119,19 @@ __device__ __forceinline__ unsigned pack_bf16(v2f v)
 // rounded to bf16 after the float32 input transform, U comes as bf16 in the "high part" slots of the same image (the low
 // slots are neither stored nor fetched: half the U traffic), float32 accumulation, transforms and epilogue.  bf16 has
 // float32's exponent range: no range guard.
-template <int MODE, bool BF16>
-__global__ __launch_bounds__(WT, 1)
-void wino_split_kernel(ws_args a)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sV = smem;
-    unsigned char* sP = smem + V_BYTES;
-    unsigned* sMax = reinterpret_cast<unsigned*>(smem + V_BYTES + P_RING * P_BYTES);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hk = lane >> 5, li = lane & 31;
-    // 1-D grid, XCD-aware (wino.hip): spatial tile t -> XCD t % 8, its cout groups back to back there
-    const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-    const int ng = jj % a.ngroups, t = (jj / a.ngroups) * 8 + xcd;
-    const int gx = a.nbx * a.dil, gy = a.nby * a.dil;
-    if (t >= gx * gy * a.batch) return;
-    const int b = t / (gx * gy), txy = t - b * (gx * gy), tyy = txy / gx, txx = txy - tyy * gx;
-    const int bx = txx % a.nbx, rx = txx / a.nbx;
-    const int by = tyy % a.nby, ry = tyy / a.nby;
-    const int Hs = (a.H - ry + a.dil - 1) / a.dil, Ws = (a.W - rx + a.dil - 1) / a.dil;   // sub-grid extent of this residue
-    if (by * 2 * TB >= Hs || bx * 2 * TB >= Ws) return;
-    const float* xb = a.x + (int64_t)b * a.H * a.W * a.Cin;
-    const int n0 = ng * NB;
-    const int nchunks = a.Cin / KC;
-
-    // ---- raw patch DMA, pixel-major: slot = 4 * g + quad (16 bytes = 4 channels), pixel group g = py * 18 + pos with the
-    // even columns of a patch row first (pos = px / 2 for even px, 9 + px / 2 for odd px): the four lanes of a group
-    // read 64 contiguous bytes of global memory (one request instead of four), and the eight tiles of a tile row — two
-    // pixels apart — sit in consecutive 64-byte records, which halves the bank conflicts of the transform's reads.
-    // Slots >= 4 * 324 fetch out of range (zeros).
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((size_t)a.H * a.W * a.Cin * 4), 0x00020000);
-    uint32_t pvoff[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int q = (wave + 4 * j) * 64 + lane;
-        const int g = q >> 2, h = q & 3;
-        const int py = g / PW, pos = g - py * PW;
-        const int px = pos < PW / 2 ? 2 * pos : 2 * (pos - PW / 2) + 1;
-        const int sy = by * 2 * TB - 1 + py, sx = bx * 2 * TB - 1 + px;
-        const int y = ry + a.dil * sy, x = rx + a.dil * sx;
-        const bool ok = g < NPIX && sy >= 0 && sx >= 0 && y < a.H && x < a.W;
-        pvoff[j] = ok ? (uint32_t)(((y * a.W + x) * a.Cin + h * 4) * 4) : 0x80000000u;
-    }
-    const int n_pinstr = wave == 0 ? 6 : 5;                         // 21 instructions over 4 waves
-    const uint32_t p_lds = __builtin_amdgcn_readfirstlane(lds_addr(sP) + wave * 1024);
-    auto glds_patch = [&](int chunk, int slot) {
-        const uint32_t soff = (uint32_t)((chunk < nchunks ? chunk : nchunks - 1) * KC * 4);
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-            if (j < n_pinstr) bufdma16(x_rsrc, pvoff[j], soff, p_lds + (uint32_t)(slot * P_BYTES + j * 4096));
-    };
-
-    // ---- transform role: tile xtile, channel quad xq (4 channels = two packed pairs)
-    const int xtile = tid >> 2, xq = tid & 3;
-    const int xty = xtile >> 3, xtx = xtile & 7;
-    const int prd = (2 * xty * PW + xtx) * 64 + xq * 16;            // patch byte offset of the tile's pixel (0,0), this quad
-    const int xsw = (xtile >> 2) & 3;
-    const int vw_hi = xtile * 64 + (((xq >> 1) ^ xsw) * 16) + (xq & 1) * 8;          // hi chunk = quad >> 1 (channels 0-7 | 8-15)
-    const int vw_lo = xtile * 64 + (((2 + (xq >> 1)) ^ xsw) * 16) + (xq & 1) * 8;
-
-    // ---- MFMA role: wave (nt, ph): couts n0 + 32 nt .., positions 8 ph .. 8 ph + 7, both m-tiles
-    const int nt = wave & 1, ph = wave >> 1;
-    int a_hi[2], a_lo[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int tile = m * 32 + li, sw = (tile >> 2) & 3;
-        a_hi[m] = tile * 64 + ((hk ^ sw) * 16);
-        a_lo[m] = tile * 64 + (((2 + hk) ^ sw) * 16);
-    }
-    // U: [chunk][position][cout block of 32][hi h0 | hi h1 | lo h0 | lo h1][32 couts][8 halfs]: 2 KB per (chunk, p, cb)
-    const int ncb = a.Cout / 32, cb = (n0 >> 5) + nt;
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.U, 0, (int)(a.u_halfs * 2), 0x00020000);
-    const uint32_t ulane = (uint32_t)(hk * 512 + li * 16);
-    const uint32_t u_p = (uint32_t)ncb * 2048u, u_c = 16u * u_p;
-    const uint32_t u_w = (uint32_t)(__builtin_amdgcn_readfirstlane(8 * ph) * (int)u_p + __builtin_amdgcn_readfirstlane(cb) * 2048);
-    const float uscale = *reinterpret_cast<const float*>(a.U + a.u_halfs);              // 2^eu
-
-    WS_T(blk0);
-    f32x16 acc[8][2];
-    float amax = 0.f;
-    float xs = 1.0f;                                                 // activation scale of a second pass (2^sx)
-    int sx = 0;
-    if (tid == 0) sMax[0] = 0u;
-
-    // One pass over the input channels.  SC::value: activations are multiplied by xs (second pass of the range guard);
-    // the first pass tracks max|x| instead.
-    auto run = [&](auto SC) {
-        constexpr bool SCALED = decltype(SC)::value;
-        v2f tA[16], tB[16];                                          // B^T d of the item's two channel pairs, alive across a slot boundary
-        // ---- transform pieces ----------------------------------------------------------------------------------------
-        auto patch_rows = [&](int slot, int e, v2f (&tt)[16]) {
-            const unsigned char* pp = sP + slot * P_BYTES + prd + e * 8;
-            v2f r[16];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) r[i * 4 + j] = *reinterpret_cast<const v2f*>(pp + (i * PW + (j & 1) * (PW / 2) + (j >> 1)) * 64);
-            if (BF16) {
-            } else if (!SCALED) {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(r[i].x)), __builtin_fabsf(r[i].y));
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) r[i] = r[i] * v2f{xs, xs};
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                tt[0 * 4 + j] = pk_sub(r[0 * 4 + j], r[2 * 4 + j]);
-                tt[1 * 4 + j] = pk_add(r[1 * 4 + j], r[2 * 4 + j]);
-                tt[2 * 4 + j] = pk_sub(r[2 * 4 + j], r[1 * 4 + j]);
-                tt[3 * 4 + j] = pk_sub(r[1 * 4 + j], r[3 * 4 + j]);
-            }
-        };
-        // row i of (t B) -> positions 4i .. 4i+3, split, stored as {hi pair A, hi pair B} and {lo pair A, lo pair B}
-        auto cols_store = [&](int i) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v2f va, vb;
-                if (j == 0) { va = pk_sub(tA[i * 4 + 0], tA[i * 4 + 2]); vb = pk_sub(tB[i * 4 + 0], tB[i * 4 + 2]); }
-                else if (j == 1) { va = pk_add(tA[i * 4 + 1], tA[i * 4 + 2]); vb = pk_add(tB[i * 4 + 1], tB[i * 4 + 2]); }
-                else if (j == 2) { va = pk_sub(tA[i * 4 + 2], tA[i * 4 + 1]); vb = pk_sub(tB[i * 4 + 2], tB[i * 4 + 1]); }
-                else { va = pk_sub(tA[i * 4 + 1], tA[i * 4 + 3]); vb = pk_sub(tB[i * 4 + 1], tB[i * 4 + 3]); }
-                u32x2 H, L; unsigned h, l;
-                if (BF16) {
-                    H[0] = pack_bf16(va); H[1] = pack_bf16(vb);
-                    *reinterpret_cast<u32x2*>(sV + (i * 4 + j) * V_POS + vw_hi) = H;
-                    continue;
-                }
-                split_pair(va, h, l); H[0] = h; L[0] = l;
-                split_pair(vb, h, l); H[1] = h; L[1] = l;
-                *reinterpret_cast<u32x2*>(sV + (i * 4 + j) * V_POS + vw_hi) = H;
-                *reinterpret_cast<u32x2*>(sV + (i * 4 + j) * V_POS + vw_lo) = L;
-            }
-        };
-        // ---- MFMA pieces -----------------------------------------------------------------------------------------------
-        auto u_load = [&](int c, int lp, h8& uh, h8& ul) {
-            const uint32_t so = (uint32_t)c * u_c + u_w + (uint32_t)lp * u_p;
-            uh = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ulane, so, 0));
-            if (!BF16) ul = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ulane + 1024u, so, 0));
-        };
-        auto a_load = [&](int lp, h8 (&vh)[2], h8 (&vl)[2]) {
-            const unsigned char* vp = sV + (8 * ph + lp) * V_POS;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                vh[m] = *reinterpret_cast<const h8*>(vp + a_hi[m]);
-                if (!BF16) vl[m] = *reinterpret_cast<const h8*>(vp + a_lo[m]);
-            }
-        };
-        auto mfma6 = [&](int lp, const h8 (&vh)[2], const h8 (&vl)[2], const h8& uh, const h8& ul) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                f32x16 z = acc[lp][m];
-                if (BF16) {
-                    if (MODE == 1) z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, uh), __builtin_bit_cast(bf8, vh[m]), z, 0, 0, 0);
-                    else z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, vh[m]), __builtin_bit_cast(bf8, uh), z, 0, 0, 0);
-                } else if (MODE == 1) {                              // couts on the accumulator rows (in-register sum over couts)
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh, vh[m], z, 0, 0, 0);
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(ul, vh[m], z, 0, 0, 0);
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh, vl[m], z, 0, 0, 0);
-                } else {
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[m], uh, z, 0, 0, 0);
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[m], ul, z, 0, 0, 0);
-                    z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl[m], uh, z, 0, 0, 0);
-                }
-                acc[lp][m] = z;
-            }
-        };
-        // instruction-mix recipe for one position group: each of the 6 MFMAs is followed by a share of the group's
-        // companion work (mask 0x008 MFMA, 0x002 VALU, 0x020 VMEM read, 0x100 DS read, 0x200 DS write)
-#define WS_MIX(NVALU, NDSR, NDSW)                                                                \
-        _Pragma("unroll") for (int mm = 0; mm < 6; ++mm) {                                       \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                   \
-            if (mm < 2) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                       \
-            if (NDSR) __builtin_amdgcn_sched_group_barrier(0x100, NDSR, 0);                      \
-            if (NVALU) __builtin_amdgcn_sched_group_barrier(0x002, NVALU, 0);                    \
-            if (NDSW) __builtin_amdgcn_sched_group_barrier(0x200, NDSW, 0);                      \
-        }
-
-        // ---- prologue ----------------------------------------------------------------------------------------------------
-#pragma unroll
-        for (int lp = 0; lp < 8; ++lp)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[lp][m][r] = 0.f;
-        glds_patch(0, 0);
-        glds_patch(1, 1);
-        glds_patch(2, 2);
-        // U fragments are fetched THREE positions ahead of their MFMAs into a ring of four register pairs (8 positions per
-        // chunk: the ring phase is the same in every chunk).  The kernel is bound by what a CU can pull from L2 (U: 64 KB
-        // per chunk, patch: 21 KB; measured 12-14 B/clk/CU with two positions in flight): bytes in flight are what raises it.
-        h8 u0h, u0l, u1h, u1l, u2h, u2l, u3h, u3l;
-        // only patch 0 has to be there to start: the DMAs of patches 1 and 2 (this wave's 2 x 5 or 2 x 6 youngest operations —
-        // the U loads are issued behind the wait, so the count is exact) stay in flight through the first transform
-        if (wave == 0) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        __syncthreads();                                             // (also orders sMax[0] = 0 / the previous pass's V reads)
-        u_load(0, 0, u0h, u0l);
-        u_load(0, 1, u1h, u1l);
-        u_load(0, 2, u2h, u2l);
-        patch_rows(0, 0, tA);
-        patch_rows(0, 1, tB);
-        cols_store(0);
-        cols_store(2);
-        __syncthreads();
-
-        // ---- main loop: two slots per chunk ------------------------------------------------------------------------------
-#ifdef AWSEG_WS_STAMP
-        unsigned long long fa[5] = {0, 0, 0, 0, 0};
-#define WS_ACC2(t0, t1, t2, t3, t4, t5) { fa[0] += t1 - t0; fa[1] += t2 - t1; fa[2] += t3 - t2; fa[3] += t4 - t3; fa[4] += t5 - t4; }
-        unsigned long long sa = 0, ba = 0, sb = 0, bb = 0, nn = 0;
-#define WS_ACC(t0, t1, t2, t3, t4) { sa += t1 - t0; ba += t2 - t1; sb += t3 - t2; bb += t4 - t3; nn += 1; }
-#else
-#define WS_ACC2(t0, t1, t2, t3, t4, t5)
-#define WS_ACC(t0, t1, t2, t3, t4)
-#endif
-        WS_T(loop0);
-        for (int c = 0; c < nchunks; ++c) {
-            h8 vh0[2], vl0[2], vh1[2], vl1[2];
-            const int cn = c + 1 < nchunks ? c + 1 : c;              // chunk of the U prefetches behind position 4 (clamped)
-            // slot A: MFMAs on V rows {0, 2} of chunk c | rows {1, 3} of chunk c written, pair A of patch c+1 read and row-transformed
-            WS_T(st0);
-            vm_wait_keep6();                                         // the DMA issued a chunk ago (long landed)
-            WS_T(sa1);
-            glds_patch(c + 3, c % 3);                                // that ring slot held patch c (read a slot ago, behind a barrier)
-            WS_T(sa2);
-            a_load(0, vh0, vl0);
-            u_load(c, 3, u3h, u3l); a_load(1, vh1, vl1);
-            __builtin_amdgcn_sched_barrier(0);
-            cols_store(1);
-            mfma6(0, vh0, vl0, u0h, u0l);
-            WS_MIX(6, 0, 2)
-            __builtin_amdgcn_sched_barrier(0);
-            WS_T(sa3);
-            u_load(c, 4, u0h, u0l); a_load(2, vh0, vl0);
-            __builtin_amdgcn_sched_barrier(0);
-            cols_store(3);
-            mfma6(1, vh1, vl1, u1h, u1l);
-            WS_MIX(6, 0, 2)
-            __builtin_amdgcn_sched_barrier(0);
-            WS_T(sa4);
-            u_load(c, 5, u1h, u1l); a_load(3, vh1, vl1);
-            __builtin_amdgcn_sched_barrier(0);
-            mfma6(2, vh0, vl0, u2h, u2l);
-            __builtin_amdgcn_sched_barrier(0);
-            WS_T(sa5);
-            WS_ACC2(st0, sa1, sa2, sa3, sa4, sa5)
-            u_load(c, 6, u2h, u2l);
-            patch_rows((c + 1) % 3, 0, tA);
-            mfma6(3, vh1, vl1, u3h, u3l);
-            WS_MIX(6, 3, 0)
-            __builtin_amdgcn_sched_barrier(0);
-            WS_T(st1);
-            __syncthreads();
-            WS_T(st2);
-            // slot B: MFMAs on rows {1, 3} of chunk c | pair B of patch c+1, rows {0, 2} of chunk c+1 written
-            a_load(4, vh0, vl0);
-            u_load(c, 7, u3h, u3l); a_load(5, vh1, vl1);
-            __builtin_amdgcn_sched_barrier(0);
-            patch_rows((c + 1) % 3, 1, tB);
-            mfma6(4, vh0, vl0, u0h, u0l);
-            WS_MIX(6, 3, 0)
-            __builtin_amdgcn_sched_barrier(0);
-            u_load(cn, 0, u0h, u0l); a_load(6, vh0, vl0);
-            __builtin_amdgcn_sched_barrier(0);
-            cols_store(0);
-            mfma6(5, vh1, vl1, u1h, u1l);
-            WS_MIX(6, 0, 2)
-            __builtin_amdgcn_sched_barrier(0);
-            u_load(cn, 1, u1h, u1l); a_load(7, vh1, vl1);
-            __builtin_amdgcn_sched_barrier(0);
-            cols_store(2);
-            mfma6(6, vh0, vl0, u2h, u2l);
-            WS_MIX(6, 0, 2)
-            __builtin_amdgcn_sched_barrier(0);
-            u_load(cn, 2, u2h, u2l);
-            mfma6(7, vh1, vl1, u3h, u3l);
-            __builtin_amdgcn_sched_barrier(0);
-            WS_T(st3);
-            __syncthreads();
-            WS_T(st4);
-            WS_ACC(st0, st1, st2, st3, st4)
-        }
-        vm_wait_all();
-#ifdef AWSEG_WS_STAMP
-        if (blockIdx.x == 0 && tid == 0) {
-            g_ws_stamp[0] += sa; g_ws_stamp[1] += ba; g_ws_stamp[2] += sb; g_ws_stamp[3] += bb; g_ws_stamp[4] += nn;
-            g_ws_stamp[5] += loop0 - blk0;
-            for (int i = 0; i < 5; ++i) g_ws_stamp2[i] += fa[i];
-        }
-#endif
-#undef WS_ACC
-#undef WS_ACC2
-#undef WS_MIX
-    };
-
-    run(awseg_false{});
-    if (!BF16) {
-        // ---- range guard: one more pass with scaled activations? --------------------------------------------------------
-        if (amax > 0.f) atomicMax(&sMax[0], __builtin_bit_cast(unsigned, amax));
-        __syncthreads();
-        const unsigned mx = sMax[0];
-        const int ex = (int)(mx >> 23) & 0xff;
-        const float mf = __builtin_bit_cast(float, mx);
-        if (!(mx == 0u || ex == 0xff || (mf < 8192.0f && mf >= 0.0625f))) {     // out of range (and not all zero / Inf / NaN)
-            sx = 11 - (ex - 127);                                    // max|x| * 2^sx in [2^11, 2^12): 4 max|x| < 2^14
-            sx = sx > 126 ? 126 : sx;
-            xs = pow2f(sx);
-            run(awseg_true{});
-        }
-    }
-
-    // ---- output transform.  Wave (nt, ph) holds M rows 2ph, 2ph+1 (positions 8ph + 4 i' + j); Y = A^T M A is linear in M:
-    // each half computes its partial 2x2 and the halves meet through LDS — m-tile ph is finished by wave ph.
-    //   tmp[0][j] = M0j + M1j + M2j, tmp[1][j] = M1j - M2j - M3j;  Y[a][0] = tmp[a][0] + tmp[a][1] + tmp[a][2],
-    //   Y[a][1] = tmp[a][1] - tmp[a][2] - tmp[a][3]
-    float* xch = reinterpret_cast<float*>(sV);                        // [nt][dest ph][4 outputs][16 regs][64 lanes]
-    // (register by register: the whole-tile form keeps eight 16-register temporaries alive and spills — scratch loads in the
-    // epilogue cost the big depth-head launch, 8 chunks per block, a fifth of its time)
-    auto partial = [&](int m, f32x16 (&yp)[4]) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float t0[4], t1[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float lo = acc[j][m][r], hi = acc[4 + j][m][r];
-                if (ph == 0) { t0[j] = lo + hi; t1[j] = hi; }
-                else { t0[j] = lo; t1[j] = -lo - hi; }
-            }
-            yp[0][r] = t0[0] + t0[1] + t0[2]; yp[1][r] = t0[1] - t0[2] - t0[3];
-            yp[2][r] = t1[0] + t1[1] + t1[2]; yp[3][r] = t1[1] - t1[2] - t1[3];
-        }
-    };
-    f32x16 y[4];
-    {
-        // the m-tile the partner finishes goes to LDS first (frees its accumulators), then this wave's own
-        float* dst = xch + ((nt * 2 + (1 - ph)) * 4) * 16 * 64 + lane;
-        if (ph == 0) partial(1, y); else partial(0, y);
-#pragma unroll
-        for (int o = 0; o < 4; ++o)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dst[(o * 16 + r) * 64] = y[o][r];
-        if (ph == 0) partial(0, y); else partial(1, y);
-    }
-    __syncthreads();
-    const float ysc = uscale * pow2f(-sx);                            // 2^(eu - sx)
-    {
-        const float* src = xch + ((nt * 2 + ph) * 4) * 16 * 64 + lane;
-#pragma unroll
-        for (int o = 0; o < 4; ++o)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) y[o][r] = (y[o][r] + src[(o * 16 + r) * 64]) * ysc;
-    }
-    const int mt = ph;                                               // this wave's m-tile in the epilogue
-
-    if (MODE == 0) {
-        // rows = tiles of m-tile mt (tile row 4 mt + (r >> 2), tile column 4 hk + (r & 3)), columns = couts (see wino.hip)
-        const int n = n0 + nt * 32 + li;
-        const float sh = a.shift[n];
-        const size_t img = (size_t)a.H * a.W * a.Cout;
-        const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)b * img), 0, (int)(img * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.residual ? a.residual + (size_t)b * img : a.out), 0, (int)(img * 4), 0x00020000);
-        const bool has_res = a.residual != nullptr;
-        const int mt_u = __builtin_amdgcn_readfirstlane(mt);
-        const uint32_t kOob = 0x80000000u;
-        uint32_t vsel[4][2];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const int xs0 = rx + a.dil * (bx * 2 * TB + 2 * c + bb);
-                const int xl = a.dil * 8 * hk;
-                vsel[c][bb] = (xs0 + xl < a.W) ? (uint32_t)((xl * a.Cout + n) * 4) : kOob;
-            }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ty = mt_u * 4 + (r >> 2), c = r & 3;
-#pragma unroll
-            for (int aa = 0; aa < 2; ++aa) {
-                const int yy = ry + a.dil * (by * 2 * TB + 2 * ty + aa);
-                if (yy >= a.H) continue;                             // wave-uniform
-#pragma unroll
-                for (int bb = 0; bb < 2; ++bb) {
-                    const int xs0 = rx + a.dil * (bx * 2 * TB + 2 * c + bb);
-                    const uint32_t soff = (uint32_t)((yy * a.W + xs0) * a.Cout * 4);
-                    float v = y[aa * 2 + bb][r] + sh;
-                    if (has_res) v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, vsel[c][bb], soff, 0));
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, act_apply(v, a.act)), o_rsrc, vsel[c][bb], soff, 0);
-                }
-            }
-        }
-    } else {
-        // rows = couts n0 + 32 nt + (r & 3) + 8 (r >> 2) + 4 hk, columns = tiles of m-tile mt (tile = 32 mt + li)
-        float z[4] = {0.f, 0.f, 0.f, 0.f};
-        // rows 4g .. 4g+3 of a lane are four consecutive couts: one 16-byte load each for the shift and the 1x1 weights
-        float shv[16], wv[16];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int co = n0 + nt * 32 + 8 * g4 + 4 * hk;
-            const float4 s4 = *reinterpret_cast<const float4*>(a.shift + co), w4 = *reinterpret_cast<const float4*>(a.w2 + co);
-            shv[4 * g4] = s4.x; shv[4 * g4 + 1] = s4.y; shv[4 * g4 + 2] = s4.z; shv[4 * g4 + 3] = s4.w;
-            wv[4 * g4] = w4.x; wv[4 * g4 + 1] = w4.y; wv[4 * g4 + 2] = w4.z; wv[4 * g4 + 3] = w4.w;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-#pragma unroll
-            for (int o = 0; o < 4; ++o) z[o] += fmaxf(y[o][r] + shv[r], 0.f) * wv[r];
-        }
-#pragma unroll
-        for (int o = 0; o < 4; ++o) z[o] += __shfl_xor(z[o], 32, 64);   // the other half-wave holds rows + 4 of the same tile
-        __syncthreads();                                             // every wave has read its exchange data
-        float* red = reinterpret_cast<float*>(sV);                   // [nt][tile][4]
-        if (hk == 0) *reinterpret_cast<float4*>(red + (nt * NTILE + mt * 32 + li) * 4) = make_float4(z[0], z[1], z[2], z[3]);
-        __syncthreads();
-        const int tile = tid >> 2, q = tid & 3;
-        const int uy = by * 2 * TB + 2 * (tile >> 3) + (q >> 1), ux = bx * 2 * TB + 2 * (tile & 7) + (q & 1);
-        const int yy = ry + a.dil * uy, xx = rx + a.dil * ux;
-        if (yy < a.H && xx < a.W) {
-            const float zz = red[tile * 4 + q] + red[(NTILE + tile) * 4 + q] + a.b2[0];
-            a.out[((int64_t)b * a.H + yy) * a.W + xx] = 1.0f / (1.0f + expf(-zz));
-        }
-    }
-#ifdef AWSEG_WS_STAMP
-    { WS_T(blk1); if (blockIdx.x == 0 && tid == 0) g_ws_stamp[7] += blk1 - blk0; }
-#endif
-}
-
+constexpr int W8T = 512;                   // threads per block (8 waves)
+constexpr int X_BYTES = 8 * 64 * 64 * 4;   // epilogue exchange: 8 waves x 64 lanes x 64 floats (V and the patches are dead by then)
+constexpr int LDS8S_BYTES = X_BYTES;       // wino8s_kernel: V + the patch ring + sMax, reused as the exchange buffer
+static_assert(V_BYTES + P_RING * P_BYTES + 64 <= X_BYTES, "the chunk loop's LDS image fits the exchange buffer");
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Round 3: the same operator with EIGHT waves per block that ALTERNATE between two roles.  The four-wave kernel above keeps one
-// wave per SIMD: its ~280 transform instructions, 64 LDS accesses and 48 MFMAs per chunk share ONE instruction stream, and the
-// stamps show 5 100 ticks per chunk against 1 536 of matrix time.  Here a wave owns ONE V row (4 positions) x all
-// 64 tiles x 32 couts — 128 accumulator registers, two waves per SIMD — and every U fragment is still fetched by exactly one wave:
-//   * waves 0-3 own V rows {0, 2} ("even"), waves 4-7 rows {1, 3} ("odd"); wave w and w + 4 share a SIMD;
-//   * slot A of chunk c: the even waves run their 24 MFMAs on rows {0, 2} while the odd waves turn patch c into rows {1, 3} of
-//     the same chunk (they need only rows 1..3 of the 4x4 input tile: B^T rows 1 and 3), fetch their U fragments of chunk c and
-//     issue the LDS-DMA of patch c + 2; slot B: the odd waves run their MFMAs, the even waves build rows {0, 2} of chunk c + 1
-//     (input rows 0..2) and fetch their U of chunk c + 1.  One barrier per slot.  On every SIMD one wave feeds the matrix pipe
-//     while its partner does vector / LDS work, and the roles swap each slot — no wave is ever a dedicated loader;
-//   * the partial inverse transforms of the four V rows meet through LDS in the epilogue (V and the patches are dead by then):
-//     wave (nt, row) finishes m-tile row >> 1, output row row & 1.
-constexpr int W8T = 512;
-#ifdef AWSEG_WS_STAMP
-__device__ unsigned long long g_w8_stamp[2][8];                       // [wave 0 | wave 4][slot A work, barrier A, slot B work, barrier B, chunks, whole block]
-#endif
-#ifndef AWSEG_W8_ABL
-#define AWSEG_W8_ABL 0
-#endif
-constexpr int X_BYTES = 8 * 64 * 64 * 4;                              // epilogue exchange: 8 waves x 64 lanes x 64 floats
-
-template <int MODE, bool BF16>
-__global__ __launch_bounds__(W8T, 2)
-void wino8_kernel(ws_args a)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned char* sV = smem;
-    unsigned char* sP = smem + V_BYTES;
-    unsigned* sMax = reinterpret_cast<unsigned*>(smem + V_BYTES + P_RING * P_BYTES);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int hk = lane >> 5, li = lane & 31;
-    const int grp = wave >> 2;                                       // 0: V rows {0, 2}; 1: rows {1, 3}
-    const int gw = wave & 3;                                         // wave within its group
-    const int nt = wave & 1;
-    const int vrow = 2 * ((wave >> 1) & 1) + grp;                    // this wave's V row (positions 4 vrow .. 4 vrow + 3)
-    // Block order.  Blocks b, b + 8, ... share an XCD (and its L2).  U of a layer with many channels does not fit an L2
-    // (2048 -> 256: 33 MB) and streams from the Infinity Cache at ~8.6 TB/s chip-wide — the measured pace of both kernels —
-    // unless the CUs of an XCD read the SAME cout group's U at about the same time: `span` consecutive spatial tiles of the
-    // XCD run cout group 0, then the same tiles group 1, ... (span = 1: a tile's groups back to back, the round-2 order).
-    const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
-    const int per = a.span * a.ngroups, sg = jj / per, rr = jj - sg * per;
-    const int ng = rr / a.span, t = (sg * a.span + (rr - ng * a.span)) * 8 + xcd;
-    const int gx = a.nbx * a.dil, gy = a.nby * a.dil;
-    if (t >= gx * gy * a.batch) return;
-    const int b = t / (gx * gy), txy = t - b * (gx * gy), tyy = txy / gx, txx = txy - tyy * gx;
-    const int bx = txx % a.nbx, rx = txx / a.nbx;
-    const int by = tyy % a.nby, ry = tyy / a.nby;
-    const int Hs = (a.H - ry + a.dil - 1) / a.dil, Ws = (a.W - rx + a.dil - 1) / a.dil;
-    if (by * 2 * TB >= Hs || bx * 2 * TB >= Ws) return;
-    const float* xb = a.x + (int64_t)b * a.H * a.W * a.Cin;
-    const int n0 = ng * NB;
-    const int nchunks = a.Cin / KC;
-    constexpr int abl = AWSEG_W8_ABL;                                // timing experiments only: compile-time switches that REMOVE one ingredient of the chunk loop
-
-    // ---- patch LDS-DMA (issued by the odd group at the start of its transform slot: 21 instructions over its 4 waves), layout as
-    // in the kernel above.  (Measured and dropped: every wave issuing its share and its next U fragments from its MFMA slot — that
-    // slot went from 1 060 to 2 750 ticks for 10 vector-memory instructions, the chunk from 4 950 to 5 700.)
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((size_t)a.H * a.W * a.Cin * 4), 0x00020000);
-    uint32_t pvoff[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int q = (gw + 4 * j) * 64 + lane;
-        const int g = q >> 2, h = q & 3;
-        const int py = g / PW, pos = g - py * PW;
-        const int px = pos < PW / 2 ? 2 * pos : 2 * (pos - PW / 2) + 1;
-        const int sy = by * 2 * TB - 1 + py, sx = bx * 2 * TB - 1 + px;
-        const int y = ry + a.dil * sy, x = rx + a.dil * sx;
-        const bool ok = g < NPIX && sy >= 0 && sx >= 0 && y < a.H && x < a.W;
-        pvoff[j] = ok ? (uint32_t)(((y * a.W + x) * a.Cin + h * 4) * 4) : 0x80000000u;
-    }
-    const int gw_u = __builtin_amdgcn_readfirstlane(gw);
-    const int n_pinstr = gw_u == 0 ? 6 : 5;
-    const uint32_t p_lds = __builtin_amdgcn_readfirstlane(lds_addr(sP)) + (uint32_t)gw_u * 1024u;
-    auto glds_patch = [&](int chunk, int slot) {
-        const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane((chunk < nchunks ? chunk : nchunks - 1) * KC * 4);
-        const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p_lds + (uint32_t)(slot * P_BYTES)));
-#pragma unroll
-        for (int j = 0; j < 6; ++j)
-            if (j < n_pinstr) bufdma16(x_rsrc, pvoff[j], soff, base + (uint32_t)(j * 4096));
-    };
-
-    // ---- transform role: item (tile, channel quad) of the group's 256 threads
-    const int it = tid & 255;
-    const int xtile = it >> 2, xq = it & 3;
-    const int xty = xtile >> 3, xtx = xtile & 7;
-    const int prd = (2 * xty * PW + xtx) * 64 + xq * 16;
-    const int xsw = (xtile >> 2) & 3;
-    const int vw_hi = xtile * 64 + (((xq >> 1) ^ xsw) * 16) + (xq & 1) * 8;
-    const int vw_lo = xtile * 64 + (((2 + (xq >> 1)) ^ xsw) * 16) + (xq & 1) * 8;
-
-    // ---- MFMA role.  (Measured and dropped: V as float32 in LDS, split by the multiplying wave beside its MFMAs — the MFMA slot
-    // went from 1 060 to 2 000 - 2 270 ticks, the transform slot from 2 100 to 1 400, the chunk stayed at 4 950.)
-    int a_hi[2], a_lo[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int tile = m * 32 + li, sw = (tile >> 2) & 3;
-        a_hi[m] = tile * 64 + ((hk ^ sw) * 16);
-        a_lo[m] = tile * 64 + (((2 + hk) ^ sw) * 16);
-    }
-    const int ncb = a.Cout / 32, cb = (n0 >> 5) + nt;
-    const __amdgpu_buffer_rsrc_t u_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.U, 0, (int)(a.u_halfs * 2), 0x00020000);
-    const uint32_t ulane = (uint32_t)(hk * 512 + li * 16);
-    const uint32_t u_p = (uint32_t)ncb * 2048u, u_c = 16u * u_p;
-    const uint32_t u_w = (uint32_t)(__builtin_amdgcn_readfirstlane(4 * vrow) * (int)u_p + __builtin_amdgcn_readfirstlane(cb) * 2048);
-    const float uscale = *reinterpret_cast<const float*>(a.U + a.u_halfs);
-
-    f32x16 acc[4][2];
-    float amax = 0.f, xs = 1.0f;
-    int sx = 0;
-    if (tid == 0) sMax[0] = 0u;
-
-    auto run = [&](auto SC) {
-        constexpr bool SCALED = decltype(SC)::value;
-        h8 uh[4], ul[4];
-        auto u_fetch = [&](int c) {
-#pragma unroll
-            for (int lp = 0; lp < 4; ++lp) {
-                const uint32_t so = (uint32_t)c * u_c + u_w + (uint32_t)lp * u_p;
-                uh[lp] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ulane, so, 0));
-                if (!BF16) ul[lp] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(u_rsrc, ulane + 1024u, so, 0));
-            }
-        };
-        // patch `slot` -> the group's two V rows (grp, grp + 2).  B^T rows:  0: d0 - d2   1: d1 + d2   2: d2 - d1   3: d1 - d3, so the
-        // even group reads input rows 0, 1, 2 (shared: d2) and the odd group rows 1, 2, 3 (shared: d1).  One V row at a time — the
-        // second row's private input row is loaded after the first row's four positions are stored — keeps 32 registers of patch
-        // data alive instead of 80 (the wave's 128 accumulators and 32 U registers leave ~70 for either role).
-        auto transform = [&](int slot) {
-            const unsigned char* pp = sP + slot * P_BYTES + prd;
-            auto load_row = [&](int i, v2f (&d)[2][4]) {               // input row i of the tile's 4 x 4 patch, both channel pairs
-                // ONE 16-byte read per pixel (the quad's four channels are contiguous in the pixel-major patch): the four lanes of
-                // a tile cover 64 contiguous bytes and 16 lanes 256 — conflict-free, where the two 8-byte reads per pixel of the
-                // four-wave kernel are 2-way conflicted (a fifth of its LDS cycles)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float4 q = make_float4(uscale, xs, uscale, xs);
-                    if (!(abl & 32)) q = *reinterpret_cast<const float4*>(pp + (i * PW + (j & 1) * (PW / 2) + (j >> 1)) * 64);
-                    v2f v0 = {q.x, q.y}, v1 = {q.z, q.w};
-                    if (BF16) {
-                    } else if (!SCALED) {
-                        if (!(abl & 1)) {
-                        amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v0.x)), __builtin_fabsf(v0.y));
-                        amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v1.x)), __builtin_fabsf(v1.y));
-                        }
-                    } else { v0 = v0 * v2f{xs, xs}; v1 = v1 * v2f{xs, xs}; }
-                    d[0][j] = v0; d[1][j] = v1;
-                }
-            };
-            auto cols_store = [&](int vr, const v2f (&tt)[2][4]) {     // row vr of (B^T d) -> positions 4 vr .. 4 vr + 3, split, stored
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    v2f va, vb;
-                    if (j == 0) { va = pk_sub(tt[0][0], tt[0][2]); vb = pk_sub(tt[1][0], tt[1][2]); }
-                    else if (j == 1) { va = pk_add(tt[0][1], tt[0][2]); vb = pk_add(tt[1][1], tt[1][2]); }
-                    else if (j == 2) { va = pk_sub(tt[0][2], tt[0][1]); vb = pk_sub(tt[1][2], tt[1][1]); }
-                    else { va = pk_sub(tt[0][1], tt[0][3]); vb = pk_sub(tt[1][1], tt[1][3]); }
-                    u32x2 H, L; unsigned h, l;
-                    if (BF16) {
-                        H[0] = pack_bf16(va); H[1] = pack_bf16(vb);
-                        *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
-                        continue;
-                    }
-                    if (abl & 4) { H[0] = __builtin_bit_cast(unsigned, va.x); L[0] = __builtin_bit_cast(unsigned, va.y); H[1] = __builtin_bit_cast(unsigned, vb.x); L[1] = __builtin_bit_cast(unsigned, vb.y); }
-                    else {
-                    split_pair(va, h, l); H[0] = h; L[0] = l;
-                    split_pair(vb, h, l); H[1] = h; L[1] = l;
-                    }
-                    if (abl & 2) { if (H[0] == 0x12345678u && L[1] == 0x9abcdef0u) *reinterpret_cast<u32x2*>(sV + vw_hi) = H; continue; }
-                    *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
-                    *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_lo) = L;
-                }
-            };
-            v2f sh_[2][4], pr[2][4];                                   // shared input row, private input row -> B^T d row (in place)
-            if (grp == 0) {
-                load_row(2, sh_); load_row(0, pr);
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pr[e][j] = pk_sub(pr[e][j], sh_[e][j]);            // row 0: d0 - d2
-                cols_store(0, pr);
-                load_row(1, pr);
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pr[e][j] = pk_sub(sh_[e][j], pr[e][j]);            // row 2: d2 - d1
-                cols_store(2, pr);
-            } else {
-                load_row(1, sh_); load_row(2, pr);
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pr[e][j] = pk_add(sh_[e][j], pr[e][j]);            // row 1: d1 + d2
-                cols_store(1, pr);
-                load_row(3, pr);
-#pragma unroll
-                for (int e = 0; e < 2; ++e)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) pr[e][j] = pk_sub(sh_[e][j], pr[e][j]);            // row 3: d1 - d3
-                cols_store(3, pr);
-            }
-        };
-        auto mma = [&]() {
-#pragma unroll
-            for (int lp = 0; lp < 4; ++lp) {
-                const unsigned char* vp = sV + (4 * vrow + lp) * V_POS;
-                h8 vh[2], vl[2];
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    vh[m] = *reinterpret_cast<const h8*>(vp + a_hi[m]);
-                    if (!BF16) vl[m] = *reinterpret_cast<const h8*>(vp + a_lo[m]);
-                }
-#pragma unroll
-                for (int m = 0; m < 2; ++m) {
-                    f32x16 z = acc[lp][m];
-                    if (BF16) {
-                        if (MODE == 1) z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, uh[lp]), __builtin_bit_cast(bf8, vh[m]), z, 0, 0, 0);
-                        else z = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, vh[m]), __builtin_bit_cast(bf8, uh[lp]), z, 0, 0, 0);
-                    } else if (MODE == 1) {
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[lp], vh[m], z, 0, 0, 0);
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(ul[lp], vh[m], z, 0, 0, 0);
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(uh[lp], vl[m], z, 0, 0, 0);
-                    } else {
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[m], uh[lp], z, 0, 0, 0);
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[m], ul[lp], z, 0, 0, 0);
-                        z = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl[m], uh[lp], z, 0, 0, 0);
-                    }
-                    acc[lp][m] = z;
-                }
-            }
-        };
-
-#pragma unroll
-        for (int lp = 0; lp < 4; ++lp)
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[lp][m][r] = 0.f;
-        // ---- prologue: patches 0 and 1 in flight, patch 0 landed; the even waves build rows {0, 2} of chunk 0
-        if (grp == 1) {
-            glds_patch(0, 0);
-            glds_patch(1, 1);
-            if (gw_u == 0) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        }
-        __syncthreads();                                             // (also orders sMax[0] = 0 and the previous pass's V reads)
-        if (grp == 0) { u_fetch(0); transform(0); }
-        __syncthreads();
-#ifdef AWSEG_WS_STAMP
-        unsigned long long w8s[5] = {0, 0, 0, 0, 0};
-#define W8_T(v) const unsigned long long v = __builtin_readcyclecounter()
-#define W8_ACC(t0, t1, t2, t3, t4) { w8s[0] += t1 - t0; w8s[1] += t2 - t1; w8s[2] += t3 - t2; w8s[3] += t4 - t3; w8s[4] += 1; }
-#else
-#define W8_T(v)
-#define W8_ACC(t0, t1, t2, t3, t4)
-#endif
-        for (int c = 0; c < nchunks; ++c) {
-            W8_T(q0);
-            // slot A: even waves multiply rows {0, 2} of chunk c | odd waves: DMA of patch c + 2, U of chunk c, patch c -> rows {1, 3}
-            if (grp == 0) { if (!(abl & 64)) mma(); }
-            else {
-                if (!(abl & 16)) glds_patch(c + 2, (c + 2) % 3);     // that ring slot held patch c - 1 (last read in slot A of chunk c - 1)
-                if (!(abl & 8)) u_fetch(c);
-                transform(c % 3);
-                // patch c + 1 (DMA issued a chunk ago, older than this slot's n_pinstr + 8 operations) has landed
-                if (BF16) { if (gw_u == 0) asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(9)" ::: "memory"); }
-                else { if (gw_u == 0) asm volatile("s_waitcnt vmcnt(14)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); }
-            }
-            W8_T(q1);
-            __syncthreads();
-            W8_T(q2);
-            // slot B: odd waves multiply rows {1, 3} of chunk c | even waves: patch c + 1 -> rows {0, 2} of chunk c + 1, U of chunk c + 1
-            if (grp == 1) { if (!(abl & 64)) mma(); }
-            else if (c + 1 < nchunks) { if (!(abl & 8)) u_fetch(c + 1); transform((c + 1) % 3); }
-            W8_T(q3);
-            __syncthreads();
-            W8_T(q4);
-            W8_ACC(q0, q1, q2, q3, q4)
-        }
-        vm_wait_all();
-#ifdef AWSEG_WS_STAMP
-        if (blockIdx.x == 0 && (tid == 0 || tid == 256)) for (int i = 0; i < 5; ++i) g_w8_stamp[tid >> 8][i] += w8s[i];
-#endif
-#undef W8_T
-#undef W8_ACC
-    };
-
-    run(awseg_false{});
-    if (!BF16) {
-        if (amax > 0.f) atomicMax(&sMax[0], __builtin_bit_cast(unsigned, amax));
-        __syncthreads();
-        const unsigned mx = sMax[0];
-        const int ex = (int)(mx >> 23) & 0xff;
-        const float mf = __builtin_bit_cast(float, mx);
-        if (!(mx == 0u || ex == 0xff || (mf < 8192.0f && mf >= 0.0625f))) {
-            sx = 11 - (ex - 127);
-            sx = sx > 126 ? 126 : sx;
-            xs = pow2f(sx);
-            run(awseg_true{});
-        }
-    }
-
-    // ---- output transform.  This wave holds M[vrow][0..3] (its four positions); Y = A^T M A:
-    //   R_0 = M_i0 + M_i1 + M_i2, R_1 = M_i1 - M_i2 - M_i3 (column factor, in registers), then over the V rows i
-    //   Y[0][b] = R_b(0) + R_b(1) + R_b(2),  Y[1][b] = R_b(1) - R_b(2) - R_b(3)  — through LDS.
-    // exchange layout: float4 [nt][V row][m][b][r >> 2][lane]
-    float* xch = reinterpret_cast<float*>(smem);
-    {
-        float* dst = xch + ((size_t)(nt * 4 + vrow) * 16 * 64 + lane) * 4;
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                float4 q0, q1;
-                float* p0 = &q0.x; float* p1 = &q1.x;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int r = 4 * r4 + q;
-                    p0[q] = acc[0][m][r] + acc[1][m][r] + acc[2][m][r];
-                    p1[q] = acc[1][m][r] - acc[2][m][r] - acc[3][m][r];
-                }
-                *reinterpret_cast<float4*>(dst + ((m * 2 + 0) * 4 + r4) * 64 * 4) = q0;
-                *reinterpret_cast<float4*>(dst + ((m * 2 + 1) * 4 + r4) * 64 * 4) = q1;
-            }
-    }
-    __syncthreads();
-    const int mt = vrow >> 1, oa = vrow & 1;                          // this wave finishes m-tile mt, output row oa
-    const float ysc = uscale * pow2f(-sx);
-    f32x16 y[2];                                                      // [output column b]
-    {
-#pragma unroll
-        for (int bcol = 0; bcol < 2; ++bcol)
-#pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) {
-                float4 s0, s1, s2;
-                auto ld = [&](int i) {
-                    return *reinterpret_cast<const float4*>(xch + (((size_t)(nt * 4 + i) * 16 + (mt * 2 + bcol) * 4 + r4) * 64 + lane) * 4);
-                };
-                s0 = ld(oa); s1 = ld(oa + 1); s2 = ld(oa + 2);       // oa = 0: rows 0, 1, 2 (+ + +); oa = 1: rows 1, 2, 3 (+ - -)
-                const float* f0 = &s0.x; const float* f1 = &s1.x; const float* f2 = &s2.x;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) y[bcol][4 * r4 + q] = (oa == 0 ? f0[q] + f1[q] + f2[q] : f0[q] - f1[q] - f2[q]) * ysc;
-            }
-    }
-
-    if (MODE == 0) {
-        // rows = tiles of m-tile mt (tile row 4 mt + (r >> 2), tile column 4 hk + (r & 3)), columns (lanes) = couts; output row 2 ty + oa
-        const int n = n0 + nt * 32 + li;
-        const float sh = a.shift[n];
-        const size_t img = (size_t)a.H * a.W * a.Cout;
-        const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.out + (size_t)b * img), 0, (int)(img * 4), 0x00020000);
-        const __amdgpu_buffer_rsrc_t r_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)(a.residual ? a.residual + (size_t)b * img : a.out), 0, a.residual ? (int)(img * 4) : 0, 0x00020000);
-        const int mt_u = __builtin_amdgcn_readfirstlane(mt), oa_u = __builtin_amdgcn_readfirstlane(oa);
-        const uint32_t kOob = 0x80000000u;
-        uint32_t vsel[4][2];
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const int xs0 = rx + a.dil * (bx * 2 * TB + 2 * c + bb);
-                const int xl = a.dil * 8 * hk;
-                vsel[c][bb] = (xs0 + xl < a.W) ? (uint32_t)((xl * a.Cout + n) * 4) : kOob;
-            }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int ty = mt_u * 4 + (r >> 2), c = r & 3;
-            const int yy = ry + a.dil * (by * 2 * TB + 2 * ty + oa_u);
-            if (yy >= a.H) continue;                                 // wave-uniform
-#pragma unroll
-            for (int bb = 0; bb < 2; ++bb) {
-                const int xs0 = rx + a.dil * (bx * 2 * TB + 2 * c + bb);
-                const uint32_t soff = (uint32_t)((yy * a.W + xs0) * a.Cout * 4);
-                float v = y[bb][r] + sh;
-                v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r_rsrc, vsel[c][bb], soff, 0));   // zero-record descriptor without a residual
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, act_apply(v, a.act)), o_rsrc, vsel[c][bb], soff, 0);
-            }
-        }
-    } else {
-        // rows = couts n0 + 32 nt + (r & 3) + 8 (r >> 2) + 4 hk, columns (lanes) = tiles of m-tile mt (tile = 32 mt + li); output row oa
-        float z[2] = {0.f, 0.f};
-        float shv[16], wv[16];
-#pragma unroll
-        for (int g4 = 0; g4 < 4; ++g4) {
-            const int co = n0 + nt * 32 + 8 * g4 + 4 * hk;
-            const float4 s4 = *reinterpret_cast<const float4*>(a.shift + co), w4 = *reinterpret_cast<const float4*>(a.w2 + co);
-            shv[4 * g4] = s4.x; shv[4 * g4 + 1] = s4.y; shv[4 * g4 + 2] = s4.z; shv[4 * g4 + 3] = s4.w;
-            wv[4 * g4] = w4.x; wv[4 * g4 + 1] = w4.y; wv[4 * g4 + 2] = w4.z; wv[4 * g4 + 3] = w4.w;
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-#pragma unroll
-            for (int o = 0; o < 2; ++o) z[o] += fmaxf(y[o][r] + shv[r], 0.f) * wv[r];
-        }
-#pragma unroll
-        for (int o = 0; o < 2; ++o) z[o] += __shfl_xor(z[o], 32, 64);
-        __syncthreads();                                             // every wave has read its exchange data
-        float* red = reinterpret_cast<float*>(smem);                 // [nt][tile][output row][2]
-        if (hk == 0) *reinterpret_cast<float2*>(red + ((nt * NTILE + mt * 32 + li) * 2 + oa) * 2) = make_float2(z[0], z[1]);
-        __syncthreads();
-        if (tid < 256) {
-            const int tile = tid >> 2, q = tid & 3;                  // q = 2 * output row + output column
-            const int uy = by * 2 * TB + 2 * (tile >> 3) + (q >> 1), ux = bx * 2 * TB + 2 * (tile & 7) + (q & 1);
-            const int yy = ry + a.dil * uy, xx = rx + a.dil * ux;
-            if (yy < a.H && xx < a.W) {
-                const float zz = red[tile * 4 + q] + red[(NTILE + tile) * 4 + q] + a.b2[0];
-                a.out[((int64_t)b * a.H + yy) * a.W + xx] = 1.0f / (1.0f + expf(-zz));
-            }
-        }
-    }
-}
-
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// The eight-wave block with SYMMETRIC slots.  wino8_kernel gives the two waves of a SIMD opposite roles per slot, but the roles
-// are not equally long: the stamps (tools/probe_wino_stamps.hip) read 1 060 cycles for a wave's 24 MFMAs and 2 100 - 2 600 for
-// its partner's transform of two V rows, so the multiplying group waits at the barrier for half of every slot and a chunk costs
-// two transform slots (~4 950 cycles).  tools/scratch/pipe_overlap.hip shows the pipes themselves DO run side by side when
-// different waves of a SIMD feed them (MFMA + LDS + vector work of two waves: both at their stand-alone pace), with two
-// exceptions this kernel avoids: v_pk_*_f32 waits for the matrix pipe to go idle (7x slower beside MFMAs), and MFMAs that
-// depend on their predecessor hold the SIMD's vector issue.  Here EVERY wave does half of both jobs in every slot:
+// The eight-wave block with SYMMETRIC slots.  Two waves share a SIMD, and a wave's 24 MFMAs per chunk (1 060 cycles by the stamps
+// of tools/probe_wino_stamps.hip) are much shorter than the transform of two V rows (2 100 - 2 600): with one wave of a SIMD
+// multiplying while its partner transforms, the multiplying wave waits at the barrier for half of every slot.
+// tools/scratch/pipe_overlap.hip shows the pipes themselves DO run side by side when different waves of a SIMD feed them (MFMA +
+// LDS + vector work of two waves: both at their stand-alone pace), with two exceptions this kernel avoids: v_pk_*_f32 waits for
+// the matrix pipe to go idle (7x slower beside MFMAs), and MFMAs that depend on their predecessor hold the SIMD's vector issue.
+// So EVERY wave does half of both jobs in every slot:
 //   * wave (nt, j) owns V COLUMN j — positions j, 4 + j, 8 + j, 12 + j — x all 64 tiles x 32 couts (128 accumulators);
 //   * slot A of chunk c: 12 MFMAs on its positions of V rows {0, 2}, and ONE V row of the transform (threads 0-255: row 1,
 //     256-511: row 3, of the same chunk); slot B: 12 MFMAs on rows {1, 3}, and row 0 / row 2 of chunk c + 1;
@@ -999,8 +141,9 @@ void wino8_kernel(ws_args a)
 //   * U: the two rows' fragments are re-fetched right behind the MFMAs that consumed them (for the next chunk): 4 loads per slot;
 //   * epilogue: the inverse transform over the V rows happens in registers (a wave holds all four rows of its column), the
 //     columns meet through LDS: wave (nt, j) finishes m-tile j >> 1, output COLUMN j & 1, both output rows.
-// Stamps: 3 700 cycles per chunk (wino8_kernel: 4 950), both slots ~1 500-1 900 with ~150 at each barrier; the clock under the
-// kernel drops with it (2.13 -> 1.77 GHz from time / cycles), so the launch times fall by 7-10 %, not 25 %.
+// Stamps: 3 700 cycles per chunk (4 950 with whole-slot roles), both slots ~1 500-1 900 with ~150 at each barrier; the clock under
+// the kernel drops with it (2.13 -> 1.77 GHz from time / cycles), so the launch times fell by 7-10 %, not 25 %.
+// Block order: blocks b, b + 8, ... share an XCD (and its L2); spatial tile t runs on XCD t % 8, its cout groups back to back there.
 // (Measured and dropped: (1) issuing the slot's LDS reads for BOTH jobs up front — 256 registers, 3-4 spilled, 2 % slower;
 // (2) ONE instruction stream per slot, a piece of the transform pinned behind each MFMA with scheduling barriers — an MFMA leaves
 // the issue port after 8 of its 32 cycles, so the vector work would ride for free: needs ~270 registers next to 128 accumulators
@@ -1027,7 +170,7 @@ void wino8s_kernel(ws_args a)
     const int nt = wave & 1, vcol = wave >> 1;                       // cout half, V column
     const int xcd = blockIdx.x & 7, jj = blockIdx.x >> 3;
     int ng, b, bx, by, rx, ry;
-    if (a.dil == 1 && a.span == 1) {
+    if (a.dil == 1) {
         // the common case with three integer divisions instead of ten (the stamps put 1 900 cycles of a block's 6 700-cycle prologue
         // into the index arithmetic in front of the first DMA request)
         const int sg = jj / a.ngroups;
@@ -1039,9 +182,9 @@ void wino8s_kernel(ws_args a)
         by = txy / a.nbx; bx = txy - by * a.nbx; rx = 0; ry = 0;
         if (by * 2 * TB >= a.H || bx * 2 * TB >= a.W) return;
     } else {
-        const int per = a.span * a.ngroups, sg = jj / per, rr = jj - sg * per;
-        ng = rr / a.span;
-        const int t = (sg * a.span + (rr - ng * a.span)) * 8 + xcd;
+        const int sg = jj / a.ngroups;
+        ng = jj - sg * a.ngroups;
+        const int t = sg * 8 + xcd;
         const int gx = a.nbx * a.dil, gy = a.nby * a.dil;
         if (t >= gx * gy * a.batch) return;
         b = t / (gx * gy);
@@ -1056,8 +199,12 @@ void wino8s_kernel(ws_args a)
     const int nchunks = a.Cin / KC;
 
     // ---- patch LDS-DMA: the 21 wave-wide instructions of a patch are dealt over ALL eight waves (instruction wave + 8 k: three for
-    // waves 0-4, two for 5-7) — issuing one costs a wave ~100 cycles, and the six per wave of wino8_kernel made slot A 700 cycles
-    // longer for the issuing group than for its partners.  Layout as in wino8_kernel.
+    // waves 0-4, two for 5-7) — issuing one costs a wave ~100 cycles, and six per wave of one half of the block made slot A 700 cycles
+    // longer for the issuing waves than for their partners.
+    // Pixel-major layout: slot = 4 * g + quad (16 bytes = 4 channels), pixel group g = py * 18 + pos with the even columns of a
+    // patch row first (pos = px / 2 for even px, 9 + px / 2 for odd px): the four lanes of a group read 64 contiguous bytes of
+    // global memory (one request instead of four), and the eight tiles of a tile row — two pixels apart — sit in consecutive
+    // 64-byte records, which halves the bank conflicts of the transform's reads.  Slots >= 4 * 324 fetch out of range (zeros).
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xb, 0, (int)((size_t)a.H * a.W * a.Cin * 4), 0x00020000);
     uint32_t pvoff[3];
 #pragma unroll
@@ -1098,7 +245,7 @@ void wino8s_kernel(ws_args a)
     const int vw_hi = xtile * 64 + (((xq >> 1) ^ xsw) * 16) + (xq & 1) * 8;
     const int vw_lo = xtile * 64 + (((2 + (xq >> 1)) ^ xsw) * 16) + (xq & 1) * 8;
 
-    // ---- MFMA operands
+    // ---- MFMA operands.  U: [chunk][position][cout block of 32][hi h0 | hi h1 | lo h0 | lo h1][32 couts][8 halfs]: 2 KB per (chunk, p, cb)
     int a_hi[2], a_lo[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -1538,7 +685,7 @@ void wino8p_kernel(ws_args a)
     auto decode = [&](int bidx, int& ng, int& b, int& bx, int& by, int& rx, int& ry) -> bool {
         if (bidx >= a.nblocks) return false;
         const int xcd = bidx & 7, jj = bidx >> 3;
-        if (a.dil == 1 && a.span == 1) {
+        if (a.dil == 1) {
             // the common case with three integer divisions instead of ten (the stamps put 1 900 cycles of a block's 6 700-cycle prologue
             // into the index arithmetic in front of the first DMA request)
             const int sg = jj / a.ngroups;
@@ -1550,9 +697,9 @@ void wino8p_kernel(ws_args a)
             by = txy / a.nbx; bx = txy - by * a.nbx; rx = 0; ry = 0;
             if (by * 2 * TB >= a.H || bx * 2 * TB >= a.W) return false;
         } else {
-            const int per = a.span * a.ngroups, sg = jj / per, rr = jj - sg * per;
-            ng = rr / a.span;
-            const int t = (sg * a.span + (rr - ng * a.span)) * 8 + xcd;
+            const int sg = jj / a.ngroups;
+            ng = jj - sg * a.ngroups;
+            const int t = sg * 8 + xcd;
             const int gx = a.nbx * a.dil, gy = a.nby * a.dil;
             if (t >= gx * gy * a.batch) return false;
             b = t / (gx * gy);
@@ -1568,8 +715,7 @@ void wino8p_kernel(ws_args a)
     const int nchunks = a.Cin / KC;
 
     // ---- patch LDS-DMA: the 21 wave-wide instructions of a patch are dealt over ALL eight waves (instruction wave + 8 k: three for
-    // waves 0-4, two for 5-7) — issuing one costs a wave ~100 cycles, and the six per wave of wino8_kernel made slot A 700 cycles
-    // longer for the issuing group than for its partners.  Layout as in wino8_kernel.
+    // waves 0-4, two for 5-7), layout as in wino8s_kernel.
     __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, 0, 0x00020000);
     uint32_t pvoff[3] = {0x80000000u, 0x80000000u, 0x80000000u};
     auto patch_addr = [&](int tb, int tbx, int tby, int trx, int try_, __amdgpu_buffer_rsrc_t& rsrc, uint32_t (&pv)[3]) {
@@ -2120,57 +1266,45 @@ void wino8p_kernel(ws_args a)
 }
 
 
-// (Measured and dropped in round 3: the same block on SIXTEEN waves of 128 registers — wave = 2 positions x 64 tiles x 32 couts, every
+// (Measured and dropped: the same block on SIXTEEN waves of 128 registers — wave = 2 positions x 64 tiles x 32 couts, every
 // slot all 1 024 threads share the transform (item = tile x channel pair x one V row), eight waves multiply.  Correct on the first
 // run and 5-10 % slower than this kernel on every shape: 4, 8 and 16 waves all land at ~5 000 cycles per chunk, with MFMA 32 %,
 // LDS 40-48 % and vector ALU 28 % busy (profiles/r03_pmc_winograd_lds.csv) — the pipes take turns instead of overlapping.)
 
-template <int MODE, bool BF16>
-int launch_ws(const ws_args& a, hipStream_t s)
+// tiles per persistent block: two persistent blocks per CU in sequence where the map has that many tiles (measured flat from 2 to 4
+// per CU, and 1.7x slower once the grid no longer covers the 256 CUs); at most 64 tiles a block.  AWSEG_WINO8_TPB overrides the
+// rule: it is the only way to put ragged last blocks (3) and whole-map blocks (64) of the persistent kernel on a map that takes
+// milliseconds (the tests do).
+int ws_tiles_per_block(int64_t nblocks)
 {
-    static int w8 = -1;                                              // AWSEG_WINO8=0: the four-wave kernel of round 2, 1: eight waves with alternating roles, 2: symmetric slots, 3: symmetric slots in persistent blocks (A/B measurements)
-    if (w8 < 0) { const char* e = getenv("AWSEG_WINO8"); w8 = e ? atoi(e) : 3; }
+    static int tpb_env = -1;
+    if (tpb_env < 0) { const char* e = getenv("AWSEG_WINO8_TPB"); tpb_env = e ? atoi(e) : 0; }
+    const int tpb = tpb_env > 0 ? tpb_env : (int)((nblocks + 511) / 512);
+    return tpb < 1 ? 1 : (tpb > 64 ? 64 : tpb);
+}
+
+template <int MODE, bool BF16>
+int launch_ws(ws_args a, hipStream_t s)
+{
     const int64_t tiles = (int64_t)a.nbx * a.dil * a.nby * a.dil * a.batch;
     const int64_t nblocks = ((tiles + 7) / 8) * a.ngroups * 8;
     if (nblocks >= ((int64_t)1 << 31)) return AWSEG_ERANGE;
-    if (w8) {
-        static int span_env = -1;
-        if (span_env < 0) { const char* e = getenv("AWSEG_WINO8_SPAN"); span_env = e ? atoi(e) : 0; }
-        ws_args a8 = a;
-        const int64_t tiles_x = (tiles + 7) / 8;                        // spatial tiles per XCD
-        int span = span_env > 0 ? span_env : 1;
-        if (span > tiles_x) span = (int)tiles_x;
-        while (tiles_x % span) --span;                                   // whole spans only (the grid stays a rectangle)
-        a8.span = span;
-        static int tpb_env = -1;
-        if (tpb_env < 0) { const char* e = getenv("AWSEG_WINO8_TPB"); tpb_env = e ? atoi(e) : 0; }
-        // two persistent blocks per CU in sequence where the map has that many tiles (measured flat from 2 to 4 per CU, and
-        // 1.7x slower once the grid no longer covers the 256 CUs); at most 64 tiles a block.  A map of <= 512 blocks gains
-        // nothing from persistence and runs the plain kernel.
-        int tpb = tpb_env > 0 ? tpb_env : (int)((nblocks + 511) / 512);
-        tpb = tpb < 1 ? 1 : (tpb > 64 ? 64 : tpb);
-        if (w8 == 3 && tpb > 1) {
-            a8.nblocks = (int)nblocks; a8.tpb = tpb;
-            const int64_t grid = ((nblocks + tpb - 1) / tpb + 7) / 8 * 8;
-            auto kp = wino8p_kernel<MODE, BF16>;
-            hipError_t ep = hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8P_BYTES);
-            if (ep != hipSuccess) return (int)ep;
-            hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(W8T), LDS8P_BYTES, s, a8);
-            AWSEG_LAUNCH_CHECK();
-            return 0;
-        }
-        auto k8 = w8 >= 2 ? wino8s_kernel<MODE, BF16> : wino8_kernel<MODE, BF16>;
-        constexpr int LDS8 = (LDS_BYTES > X_BYTES ? LDS_BYTES : X_BYTES);
-        hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8);
-        if (e8 != hipSuccess) return (int)e8;
-        hipLaunchKernelGGL(k8, dim3((unsigned)nblocks), dim3(W8T), LDS8, s, a8);
+    const int tpb = ws_tiles_per_block(nblocks);
+    if (tpb > 1) {
+        a.nblocks = (int)nblocks; a.tpb = tpb;
+        const int64_t grid = ((nblocks + tpb - 1) / tpb + 7) / 8 * 8;
+        auto kp = wino8p_kernel<MODE, BF16>;
+        hipError_t ep = hipFuncSetAttribute(reinterpret_cast<const void*>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8P_BYTES);
+        if (ep != hipSuccess) return (int)ep;
+        hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(W8T), LDS8P_BYTES, s, a);
         AWSEG_LAUNCH_CHECK();
         return 0;
     }
-    auto kern = wino_split_kernel<MODE, BF16>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblocks), dim3(WT), LDS_BYTES, s, a);
+    // a map of <= 512 blocks gains nothing from persistence and runs the plain kernel
+    auto k8 = wino8s_kernel<MODE, BF16>;
+    hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, LDS8S_BYTES);
+    if (e8 != hipSuccess) return (int)e8;
+    hipLaunchKernelGGL(k8, dim3((unsigned)nblocks), dim3(W8T), LDS8S_BYTES, s, a);
     AWSEG_LAUNCH_CHECK();
     return 0;
 }
@@ -2204,7 +1338,7 @@ int ws_entry(bool bf16, const float* x, int batch, int height, int width, int ci
     const int hs = (height + dilation - 1) / dilation, ws = (width + dilation - 1) / dilation;
     a.nbx = (ws + 2 * TB - 1) / (2 * TB); a.nby = (hs + 2 * TB - 1) / (2 * TB); a.ngroups = cout / NB; a.batch = batch;
     a.u_halfs = (int64_t)16 * cin * cout * 2;
-    a.span = 1; a.nblocks = 0; a.tpb = 1;
+    a.nblocks = 0; a.tpb = 1;
     a.forms = nullptr; a.fh = 0; a.fw = 0;
     if (bf16) return w2 ? launch_ws<1, true>(a, awseg_s(stream)) : launch_ws<0, true>(a, awseg_s(stream));
     return w2 ? launch_ws<1, false>(a, awseg_s(stream)) : launch_ws<0, false>(a, awseg_s(stream));
@@ -2217,10 +1351,7 @@ int launch_gen(ws_args a, hipStream_t s)
     const int64_t tiles = (int64_t)a.nbx * a.nby * a.batch;
     const int64_t nblocks = ((tiles + 7) / 8) * 8;
     if (nblocks >= ((int64_t)1 << 31)) return AWSEG_ERANGE;
-    static int tpb_env = -1;
-    if (tpb_env < 0) { const char* e = getenv("AWSEG_WINO8_TPB"); tpb_env = e ? atoi(e) : 0; }
-    int tpb = tpb_env > 0 ? tpb_env : (int)((nblocks + 511) / 512);
-    tpb = tpb < 1 ? 1 : (tpb > 64 ? 64 : tpb);
+    const int tpb = ws_tiles_per_block(nblocks);
     a.nblocks = (int)nblocks; a.tpb = tpb;
     const int64_t grid = ((nblocks + tpb - 1) / tpb + 7) / 8 * 8;
     auto kp = wino8p_kernel<2, BF16>;
@@ -2246,7 +1377,7 @@ AWSEG_API int awseg_depth_head_fused(const float* forms, int batch, int h, int w
     a.H = 32 * h; a.W = 32 * w; a.Cin = cmid; a.Cout = NB; a.dil = 1; a.act = AWSEG_ACT_RELU;
     a.nbx = a.W / (2 * TB); a.nby = a.H / (2 * TB); a.ngroups = 1; a.batch = batch;
     a.u_halfs = (int64_t)16 * cmid * NB * 2;
-    a.span = 1; a.nblocks = 0; a.tpb = 1;
+    a.nblocks = 0; a.tpb = 1;
     a.forms = forms; a.fh = h; a.fw = w;
     return u_is_bf16 ? launch_gen<true>(a, awseg_s(stream)) : launch_gen<false>(a, awseg_s(stream));
 }

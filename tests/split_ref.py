@@ -16,9 +16,9 @@ max(4 * (largest e of its float32 twin on the same inputs), 2^-20); 2^-20 is fou
 (b) The three split forms, as the kernels compute them:
   * SCALED low part (gemm_split.hip split_pair, kLoScale): lo = f16_rtz((x - hi) * 2^11), the cross products in a
     second accumulator multiplied by 2^-11 in the epilogue;
-  * UNSCALED low part (gemm_split.hip split_pair_unscaled, mixffn.hip mf_split_pair, heads.hip head_split_pair):
+  * UNSCALED low part (attn.hip split_pair_unscaled, mixffn.hip mf_split_pair, heads.hip head_split_pair):
     lo = f16_rn(x - hi), one accumulator for all three products;
-  * UNSCALED after x 2^4 staging (gemm_split.hip's single-accumulator kernel, gemm_split3.hip): the unscaled form of
+  * UNSCALED after x 2^4 staging (gemm_split3.hip, kActScale0): the unscaled form of
     x * 2^4, the result multiplied by 2^-4.
 f16 subnormals are kept (the MFMA does not flush them), products of two f16 numbers are exact in float32, accumulation is
 float32.  Weights may be NORMALISED (w * 2^-e with max |w| in [2^13, 2^14), gemm_split_weights) and activations may take

@@ -4,8 +4,7 @@ Two gates per case (tests/bf16_ref.py): ARITHMETIC, max(|got - model| - T)_+ / D
 exactly where the kernel rounds; and PRECISION (GEMM, Winograd, depth head), |got - exact64| / D_unrounded <= 2^-7 + 2^-16 +
 gate_bound(e_twin).  e_twin is the float32-grade twin kernel's error on the same inputs against exact float64.  Every shape
 is labelled with the kernel instance the dispatcher really picks (a restatement of the launchers' rules, below); the
-switch variants (AWSEG_WINO8, AWSEG_WINO8_TPB, AWSEG_GEMM_SPLIT_V3), which the launchers read once per process, run in
-child processes.  Errors print in units of 2^-22."""
+AWSEG_WINO8_TPB variants, which the launcher reads once per process, run in child processes.  Errors print in units of 2^-22."""
 import os
 import subprocess
 import sys
@@ -39,30 +38,25 @@ def _env(name, default):
 
 def wino_instance(B, H, W, cin, cout, d, mode):
     """launch_ws / launch_gen of csrc/wino_split.hip: 8x8-tile blocks, nblocks = ceil(tiles / 8) (Cout / 64) 8; the persistent
-    kernel when AWSEG_WINO8 = 3 (default) and tpb = AWSEG_WINO8_TPB or ceil(nblocks / 512), clamped to [1, 64], exceeds 1"""
-    w8, tpb_env = _env("AWSEG_WINO8", 3), _env("AWSEG_WINO8_TPB", 0)
+    kernel when tpb = AWSEG_WINO8_TPB or ceil(nblocks / 512), clamped to [1, 64], exceeds 1, else wino8s_kernel"""
+    tpb_env = _env("AWSEG_WINO8_TPB", 0)
     hs, ws = -(-H // d), -(-W // d)
     tiles = -(-ws // 16) * d * -(-hs // 16) * d * B
     nblocks = -(-tiles // 8) * (cout // 64) * 8
     tpb = min(64, max(1, tpb_env if tpb_env > 0 else -(-nblocks // 512)))
     if mode == 2:
         return f"wino8p_kernel<2, bf16> tpb {tpb}"
-    if w8 == 0:
-        return f"wino_split_kernel<{mode}, bf16>"
-    if w8 == 3 and tpb > 1:
+    if tpb > 1:
         return f"wino8p_kernel<{mode}, bf16> tpb {tpb}"
-    return f"{'wino8s' if w8 >= 2 else 'wino8'}_kernel<{mode}, bf16>"
+    return f"wino8s_kernel<{mode}, bf16>"
 
 
 def gemm_instance(m, n, k):
-    """gemm_launch of csrc/gemm_split.hip (bf16, 256 CUs): gemm_split3 when AWSEG_GEMM_SPLIT_V3 (default 1), K >= 32, N % 256 == 0
-    and ceil(M / 256) N / 256 >= CUs / 2; else 256x256 when N % 256 == 0, K >= 128 and ceil(M / 256) N / 256 >= CUs; else 128x256
-    when N % 256 == 0 and ceil(M / 128) N / 256 >= CUs; else 128x128.  K % 32 != 0: the K-tail instance."""
+    """gemm_launch of csrc/gemm_split.hip (bf16, 256 CUs): gemm_split3 when K >= 32, N % 256 == 0 and ceil(M / 256) N / 256 >=
+    CUs / 2; else 128x256 when N % 256 == 0 and ceil(M / 128) N / 256 >= CUs; else 128x128.  K % 32 != 0: the K-tail instance."""
     tail = " K tail" if k % 32 else ""
-    if _env("AWSEG_GEMM_SPLIT_V3", 1) and k >= 32 and n % 256 == 0 and -(-m // 256) * (n // 256) >= CUS // 2:
+    if k >= 32 and n % 256 == 0 and -(-m // 256) * (n // 256) >= CUS // 2:
         return "gemm_split3 bf16" + tail
-    if n % 256 == 0 and k >= 128 and -(-m // 256) * (n // 256) >= CUS:
-        return "gemm_split 256x256 bf16" + tail
     if n % 256 == 0 and -(-m // 128) * (n // 256) >= CUS:
         return "gemm_split 128x256 bf16" + tail
     return "gemm_split 128x128 bf16" + tail + (" N<64" if n < 64 else "")
@@ -94,7 +88,6 @@ GEMM_TABLE = [                       # (M, N, K); instance from gemm_instance at
     (38400, 256, 128), (70000, 256, 136), (300, 256, 128), (300, 256, 136), (129, 64, 64), (4100, 40, 72), (32768, 256, 16),
     (66000, 320, 320),
 ]
-GEMM_V3_OFF = [(65600, 512, 128), (65600, 512, 136), (38400, 256, 128), (38400, 256, 136)]
 
 
 def gemm_case(ops, failures, shape, wk="inv_sqrt_k", s=0, bias=True, res=True, act=1, seed=0):
@@ -184,8 +177,7 @@ def test_winograd_bf16_magnitude_sweep(ops, case):
 
 
 # ------------------------------------------------------------------ switch variants, one child process each
-VARIANTS = [("AWSEG_WINO8", "0"), ("AWSEG_WINO8", "1"), ("AWSEG_WINO8", "2"), ("AWSEG_WINO8_TPB", "3"), ("AWSEG_WINO8_TPB", "64"),
-            ("AWSEG_GEMM_SPLIT_V3", "0")]
+VARIANTS = [("AWSEG_WINO8_TPB", "3"), ("AWSEG_WINO8_TPB", "64")]
 VARIANT_WINO = [WINO_TABLE[1], WINO_TABLE[2], WINO_TABLE[6]]
 
 
@@ -198,24 +190,16 @@ def test_bf16_switch_variants(name, value):
     print(out)
     assert r.returncode == 0, out[-3000:]
     rows = out.count("ok   [") + out.count("FAIL [")
-    if name == "AWSEG_GEMM_SPLIT_V3":
-        assert rows == len(GEMM_V3_OFF) and "256x256" in out and "128x256" in out
-    else:
-        assert rows == len(VARIANT_WINO)
-        want = {"0": "wino_split_kernel", "1": "wino8_kernel", "2": "wino8s_kernel"}.get(value, "wino8p_kernel") if name == "AWSEG_WINO8" else "wino8p_kernel"
-        assert out.count(want) == len(VARIANT_WINO), want
+    assert rows == len(VARIANT_WINO)
+    assert out.count("wino8p_kernel") == len(VARIANT_WINO)
 
 
 def _variant_main():
     from adverse_weather_semantic_segmentation_robustness_benchmark_amd import _native, ops
     _native.lib()
     failures = []
-    if os.environ.get("AWSEG_GEMM_SPLIT_V3") == "0":
-        for shape in GEMM_V3_OFF:
-            gemm_case(ops, failures, shape)
-    else:
-        for case in VARIANT_WINO:
-            wino_case(ops, failures, case)
+    for case in VARIANT_WINO:
+        wino_case(ops, failures, case)
     if failures:
         print("\n".join(failures))
         sys.exit(1)

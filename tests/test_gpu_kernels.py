@@ -1066,15 +1066,17 @@ def test_attention_d32_split_flat_softmax(ops):
 
 @pytest.mark.parametrize("shape", [(300, 256, 128), (1000, 19, 304), (257, 2048, 512), (128, 128, 2048), (4100, 320, 72), (200, 160, 264), (1100, 384, 1024), (38400, 256, 128), (38500, 512, 104),
                                    (131100, 256, 128), (65600, 512, 104), (65700, 128, 512), (70000, 384, 136), (66000, 64, 256), (40000, 320, 96),
-                                   (270100, 48, 256), (300000, 19, 256), (262200, 32, 128), (262300, 32, 32), (262400, 56, 40), (66000, 160, 160), (65600, 160, 640), (131000, 200, 72)])
+                                   (270100, 48, 256), (300000, 19, 256), (262200, 32, 128), (262300, 32, 32), (262400, 56, 40), (66000, 160, 160), (65600, 160, 640), (131000, 200, 72),
+                                   (65600, 64, 544), (65600, 128, 544)])
 @pytest.mark.parametrize("res_act", [(False, 0), (True, 1)])
 def test_gemm_split_float32_grade(ops, shape, res_act):
     """Split-operand f16-MFMA GEMM against float64, next to the hipBLASLt float32 GEMM on the same inputs: ragged M and
-    N, K not a multiple of the 32-wide K tile, bias / residual / ReLU epilogue, residual aliasing the output; the last
-    two shapes before the end have enough tiles for the 128 x 256 block-tile configuration (N % 256 == 0, >= one tile per CU),
-    the next two for the 256 x 256 single-accumulator one (ragged M, K tail), the next two for the 256 x 128 one (N % 128 == 0); the
-    last eight are N < 64 on 2^18+ rows and N % 64 != 0 above it (160 = 2.5 tiles, 200): masked 64-column tiles of the LDS-DMA kernel (columns past N never stored, a single K tile
-    for K = 32, a K tail for K = 40), with the element behind the last column of every row checked untouched."""
+    N, K not a multiple of the 32-wide K tile, bias / residual / ReLU epilogue, residual aliasing the output.  The shapes with
+    fewer than half a tile per CU (the first seven) run the register-staged 128 x 128 kernel of gemm_split.hip, with and without
+    a K tail; the others the LDS-DMA kernel of gemm_split3.hip: 256-row and 128-row tiles at 256, 128 and 64 columns (ragged M,
+    K tails), then N < 64 on 2^18+ rows and N % 64 != 0 above it (160 = 2.5 tiles, 200): masked 64-column tiles (columns past
+    N never stored, a single K tile for K = 32, a K tail for K = 40), with the element behind the last column of every row
+    checked untouched.  The last two (K > 512, a 256-row tile per CU) are the 256-row tiles at 64 and 128 columns."""
     M, Nn, K = shape
     has_res, act = res_act
     g = torch.Generator(device="cuda").manual_seed(M + Nn + K)
@@ -1155,11 +1157,13 @@ def test_stem_pad_cache_is_keyed_on_width_and_channels(ops):
 
 
 @pytest.mark.parametrize("cfg", [(2, 37, 53, 64, 128, 3, 3, 2, 1), (1, 64, 96, 32, 160, 2, 2, 2, 0), (3, 40, 40, 128, 256, 1, 1, 2, 0),
-                                 (8, 128, 256, 128, 128, 3, 3, 2, 1), (2, 128, 256, 256, 512, 1, 1, 2, 0), (4, 256, 512, 64, 256, 3, 3, 2, 1)])
+                                 (8, 128, 256, 128, 128, 3, 3, 2, 1), (2, 128, 256, 256, 512, 1, 1, 2, 0), (4, 256, 512, 64, 256, 3, 3, 2, 1),
+                                 (2, 128, 257, 64, 64, 3, 3, 1, 1)])
 def test_conv_gemm_split_equals_im2col_plus_gemm(ops, cfg):
     """awseg_conv_gemm_split_bias_act (A operand gathered from the NHWC image while the K tiles are staged) against the
     im2col matrix + the same GEMM — bit-identical — and against torch's convolution in float64: stride-2 3x3 with padding,
-    kernel == stride patches, stride-2 1x1 downsample; ragged tile edges, tiles spanning two images, every block-tile shape."""
+    kernel == stride patches, stride-2 1x1 downsample; ragged tile edges, tiles spanning two images, every block-tile shape
+    (the last one: 256-row tiles at 64 columns, K = 576 > 512 on 257 tiles)."""
     B, H, W, C, Nn, kh, kw, st, pd = cfg
     g = torch.Generator(device="cuda").manual_seed(sum(cfg))
     x = torch.randn(B, H, W, C, device="cuda", generator=g)
@@ -1231,6 +1235,37 @@ def test_gemm_split_propagates_inf_nan(ops):
     ok = torch.ones(256, dtype=torch.bool, device="cuda"); ok[3] = ok[77] = False
     ref = x[ok].double() @ w.double().t()
     assert (got[ok].double() - ref).abs().max().item() < 1e-4
+
+
+def test_second_device_runs_the_large_lds_kernels(ops):
+    """The launchers' state is per device: after a two-source split GEMM (gemm_split3, > 64 KB of dynamic LDS) and a batched
+    weather launch (weather_batch_kernel with the fog ring in LDS) on cuda:0, the same calls on cuda:1 succeed — the LDS
+    attribute is set there too, the CU count is that device's — and give the first device's bits."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one-GPU lease: needs a second device in the same process")
+    import numpy as np
+    g = torch.Generator().manual_seed(21)
+    m, k1, k2, n = 33000, 64, 64, 256
+    a, b = torch.randn(m, k1, generator=g), torch.randn(m, k2, generator=g)
+    w, bias = torch.randn(n, k1 + k2, generator=g) * 0.05, torch.randn(n, generator=g)
+    imgs = torch.randint(0, 256, (2, 64, 96, 3), generator=g, dtype=torch.uint8)
+    jobs = np.zeros(2, dtype=ops.N.WEATHER_JOB)                       # one fog frame (the fog ring: > 64 KB of LDS), one clean frame
+    fj = ops.fog_jobs([0], [0.6], [1234])[0]
+    jobs[0]["kind"], jobs[0]["image"], jobs[0]["a"], jobs[0]["b"], jobs[0]["seed"] = ops.N.WEATHER_FOG, 0, fj["beta"], fj["atmos"], fj["seed"]
+    jobs[1]["kind"], jobs[1]["image"] = ops.N.WEATHER_CLEAN, 1
+    got = []
+    for dev in ("cuda:0", "cuda:1"):
+        with torch.cuda.device(dev):
+            y = ops.gemm_split_dual(a.to(dev), b.to(dev), ops.gemm_split_weights(w.to(dev)), bias.to(dev), 1)
+            assert y is not None, f"{dev}: the two-source GEMM was declined"
+            x = imgs.to(dev)
+            out, norm = torch.zeros_like(x), torch.zeros(2, 3, 64, 96, device=dev)
+            assert ops.weather_batch(x, jobs, None, None, norm, out=out), f"{dev}: the batched weather launch was declined"
+            torch.cuda.synchronize()
+            got.append((y.cpu(), out.cpu(), norm.cpu()))
+    for p, q in zip(*got):
+        assert torch.equal(p, q)
+    assert not torch.equal(got[0][1][0], imgs[0])                     # the fog frame was really written
 
 
 @pytest.mark.parametrize("qs,ks,vs", [(1.0, 1.0, 1e5), (1e5, 1e-4, 1.0), (300.0, 300.0, 7e4), (1e5, 1e5, 1e5), (1e-3, 5e4, 1e20)])

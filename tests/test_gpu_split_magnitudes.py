@@ -10,11 +10,6 @@ power-of-two scaled activations.  The guard is per TILE (per block of rows), not
 rows of every tile at 2^-12 next to O(1) rows and hold the kernel to the documented per-tile contract, a per-column normaliser
 max_m D(m, n)."""
 import math
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -83,57 +78,25 @@ def gemm_ref(x, w, b, r, act):
 
 
 # ------------------------------------------------------------------ awseg_gemm_split_bias_act, one shape per kernel configuration
-# The dispatcher (gemm_launch, gemm_split.hip) sends a shape to the LDS-DMA kernel of gemm_split3.hip whenever it is eligible and
-# has at least CUs / 2 tiles (256 CUs: 128); only the rest reach the register-staged kernels of gemm_split.hip.  With the default
-# dispatch (AWSEG_GEMM_SPLIT_V3=1):
+# The dispatcher (gemm_launch, gemm_split.hip) sends a shape to the LDS-DMA kernel of gemm_split3.hip whenever it is eligible
+# (K >= 32 among other things) and has at least CUs / 2 tiles (256 CUs: 128); the rest reach the register-staged two-accumulator
+# kernels of gemm_split.hip: 128 x 256 when N % 256 == 0 and ceil(M/128) N/256 >= 256, else 128 x 128.
 GEMM_CONFIGS = [
     ((300, 256, 128), "128x128 two-accumulator kernel (gemm_split.hip): 6 tiles, too few for gemm_split3"),
+    ((300, 256, 136), "128x128 two-accumulator kernel, K tail (gemm_split.hip)"),
+    ((32768, 256, 16), "128x256 two-accumulator kernel, K tail (gemm_split.hip): K < 32, 256 tiles"),
+    ((32768, 256, 24), "128x256 two-accumulator kernel, K tail (gemm_split.hip): K < 32, 256 tiles"),
     ((38400, 256, 128), "gemm_split3.hip, 256-row tiles (150 tiles)"),
     ((70000, 384, 136), "gemm_split3.hip, K tail (K % 32 = 8)"),
     ((262300, 32, 32), "gemm_split3.hip, masked 64-column tile"),
     ((65536, 256, 256), "gemm_split3.hip, 256x256 tiles"),
 ]
-# With AWSEG_GEMM_SPLIT_V3=0 (the register-staged kernels, still selectable) the dispatcher picks, on 256 CUs: 256 x 256 single
-# accumulator when N % 256 == 0, K >= 128 and ceil(M/256) N/256 >= 256; else 128 x 256 when N % 256 == 0 and ceil(M/128) N/256
-# >= 256; else 256 x 128 single accumulator when N % 128 == 0, K >= 128 and ceil(M/256) N/128 >= 256; else 128 x 128.
-REGISTER_STAGED_CONFIGS = [
-    ((300, 256, 128), "128x128 two-accumulator kernel (gemm_split.hip)"),
-    ((38400, 256, 128), "128x256 two-accumulator kernel (gemm_split.hip)"),
-    ((65600, 512, 136), "256x256 single-accumulator kernel, K tail (gemm_split.hip)"),
-    ((70000, 384, 136), "256x128 single-accumulator kernel, K tail (gemm_split.hip)"),
-]
-ROOT = Path(__file__).resolve().parent.parent
 
 
 @pytest.mark.parametrize("shape,kernel", GEMM_CONFIGS, ids=[f"{m}x{n}x{k}" for (m, n, k), _ in GEMM_CONFIGS])
 def test_gemm_split_magnitude_sweep(ops, shape, kernel):
     failures = _gemm_sweep(ops, shape, kernel)
     assert not failures, "\n".join(failures)
-
-
-def test_gemm_split_register_staged_kernels_magnitude_sweep():
-    """The same sweep on the register-staged kernels of gemm_split.hip (two-accumulator 128x128 / 128x256, single-accumulator
-    256x256 / 256x128), which the default dispatch reaches for small problems only: in a child process with
-    AWSEG_GEMM_SPLIT_V3=0 (the dispatcher reads it once per process)."""
-    env = dict(os.environ, AWSEG_GEMM_SPLIT_V3="0")
-    r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_split_magnitudes import _register_staged_main; _register_staged_main()"],
-                       cwd=str(ROOT), env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
-    out = r.stdout.decode(errors="replace")
-    print(out)
-    assert r.returncode == 0, out[-3000:]
-    assert out.count("ok   gemm") + out.count("FAIL gemm") == len(REGISTER_STAGED_CONFIGS) * (len(WEIGHTS) * len(SCALES) + 1)
-
-
-def _register_staged_main():
-    assert os.environ.get("AWSEG_GEMM_SPLIT_V3") == "0"
-    from adverse_weather_semantic_segmentation_robustness_benchmark_amd import _native, ops
-    _native.lib()
-    failures = []
-    for shape, kernel in REGISTER_STAGED_CONFIGS:
-        failures += _gemm_sweep(ops, shape, kernel)
-    if failures:
-        print("\n".join(failures))
-        sys.exit(1)
 
 
 def _gemm_sweep(ops, shape, kernel):

@@ -1,4 +1,4 @@
-// Cycle stamps of the split-operand Winograd kernel: where do a wave's cycles per 16-channel chunk go?
+// Cycle stamps of the split-operand Winograd kernels (wino8s_kernel / wino8p_kernel): where do a wave's cycles per 16-channel chunk go?
 // Build and run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -DAWSEG_WS_STAMP -Iinclude \
 //         -Iadverse_weather_semantic_segmentation_robustness_benchmark_amd/csrc tools/probe_wino_stamps.hip -o /tmp/probe_ws && /tmp/probe_ws
@@ -22,34 +22,24 @@ static void run(int B, int H, int W, int cin, int cout, int dil, bool head)
     hipMemset(sh, 0, cout * 4); hipMemset(w2, 0, 256); hipMemset(b2, 0, 4);
     for (int rep = 0; rep < 3; ++rep) awseg_conv3x3_winograd_split_nhwc(x, B, H, W, cin, cout, dil, u, sh, nullptr, 1, head ? w2 : nullptr, head ? b2 : nullptr, o, nullptr);
     hipDeviceSynchronize();
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0}, r[8];
-    hipMemcpyToSymbol(HIP_SYMBOL(g_ws_stamp), z, sizeof z);
-    hipMemcpyToSymbol(HIP_SYMBOL(g_ws_stamp2), z, sizeof z);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, nullptr);
     int rc = awseg_conv3x3_winograd_split_nhwc(x, B, H, W, cin, cout, dil, u, sh, nullptr, 1, head ? w2 : nullptr, head ? b2 : nullptr, o, nullptr);
     hipEventRecord(e1, nullptr); hipDeviceSynchronize();
     float ms = 0; hipEventElapsedTime(&ms, e0, e1);
-    hipMemcpyFromSymbol(r, HIP_SYMBOL(g_ws_stamp), sizeof r);
-    unsigned long long r2[8];
-    hipMemcpyFromSymbol(r2, HIP_SYMBOL(g_ws_stamp2), sizeof r2);
-    const double n = (double)r[4];
-    printf("%d x %dx%d  %d->%d d%d head=%d: rc %d, %.3f ms (stamped build); block 0 wave 0: %llu chunks\n", B, H, W, cin, cout, dil, (int)head, rc, ms, r[4]);
-    printf("  per chunk (s_memtime ticks): slot A work %.0f | barrier A %.0f | slot B work %.0f | barrier B %.0f | total %.0f;  prologue %llu, whole block %llu\n",
-           r[0] / n, r[1] / n, r[2] / n, r[3] / n, (r[0] + r[1] + r[2] + r[3]) / n, r[5], r[7]);
-    printf("  slot A in detail: vmcnt wait %.0f | DMA issue %.0f | position group 0 %.0f | group 1 %.0f | group 2 %.0f\n", r2[0] / n, r2[1] / n, r2[2] / n, r2[3] / n, r2[4] / n);
+    printf("%d x %dx%d  %d->%d d%d head=%d: rc %d, %.3f ms (stamped build)\n", B, H, W, cin, cout, dil, (int)head, rc, ms);
     unsigned long long w8[2][8];
     hipMemcpyFromSymbol(w8, HIP_SYMBOL(g_w8_stamp), sizeof w8);
     for (int g = 0; g < 2; ++g) {
         const double m = (double)w8[g][4];
-        if (m > 0) printf("  8-wave kernel, block 0 wave %d (%s rows): per chunk: slot A work %.0f | barrier A %.0f | slot B work %.0f | barrier B %.0f | total %.0f (%.0f chunks)\n",
-                          4 * g, g ? "odd: A = DMA + U + transform, B = MFMA" : "even: A = MFMA, B = U + transform", w8[g][0] / m, w8[g][1] / m, w8[g][2] / m, w8[g][3] / m,
+        if (m > 0) printf("  block 0 wave %d (%s): per chunk: slot A work %.0f | barrier A %.0f | slot B work %.0f | barrier B %.0f | total %.0f (%.0f chunks)\n",
+                          4 * g, g ? "transforms, then multiplies" : "multiplies, then transforms", w8[g][0] / m, w8[g][1] / m, w8[g][2] / m, w8[g][3] / m,
                           (w8[g][0] + w8[g][1] + w8[g][2] + w8[g][3]) / m, m);
-        if (m > 0 && w8[g][5]) printf("      symmetric kernel, slot A in detail: %s %.0f | patch DMA issue %.0f\n", g ? "(waves 4-7) DMA issue" : "(waves 0-3) MFMAs + U fetch", w8[g][5] / m, w8[g][6] / m);
+        if (m > 0 && w8[g][5]) printf("      slot A in detail: %s %.0f | patch DMA issue %.0f\n", g ? "(waves 4-7) DMA issue" : "(waves 0-3) MFMAs + U fetch", w8[g][5] / m, w8[g][6] / m);
     }
     unsigned long long wb[16];
     hipMemcpyFromSymbol(wb, HIP_SYMBOL(g_w8s_block), sizeof wb);
-    if (wb[3]) printf("  symmetric kernel, middle block of the grid: prologue %llu | chunk loop %llu | guard + epilogue %llu cycles\n", wb[0] / wb[3], wb[1] / wb[3], wb[2] / wb[3]);
+    if (wb[3]) printf("  middle block of the grid: prologue %llu | chunk loop %llu | guard + epilogue %llu cycles\n", wb[0] / wb[3], wb[1] / wb[3], wb[2] / wb[3]);
     if (wb[3]) printf("      prologue: index arithmetic %llu | DMA + U requests %llu | accumulators zeroed + patch 0 landed %llu | barrier %llu | first V row %llu | barrier %llu\n", wb[8] / wb[3], wb[9] / wb[3], wb[10] / wb[3], wb[11] / wb[3], wb[12] / wb[3], wb[13] / wb[3]);
     if (wb[3]) printf("      epilogue: range guard %llu | exchange written + barrier %llu | read back + inverse transform %llu | bias / act / stores (head: 1x1 + sigmoid) %llu\n", wb[4] / wb[3], wb[5] / wb[3], wb[6] / wb[3], wb[7] / wb[3]);
     unsigned long long zb[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
