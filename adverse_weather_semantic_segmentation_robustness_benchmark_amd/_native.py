@@ -131,6 +131,8 @@ SIGNATURES = {
     "awseg_depth_eval_stats": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_i, c_p]),
     "awseg_ensemble_failure_stats": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     "awseg_failure_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p]),
+    "awseg_boundary_workspace": (c_i64, [c_i64, c_i, c_i, c_i, c_i]),
+    "awseg_boundary_stats": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
 
 

@@ -16,13 +16,6 @@ constexpr int kThreads = 256;
 constexpr int kPer = 16;                                                  // pixels per lane per step
 constexpr int kRowMax = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES + 4;
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ void unpack16(const uint4 q, int (&v)[kPer])
 {
     const uint32_t w[4] = { q.x, q.y, q.z, q.w };
@@ -98,7 +91,7 @@ void consistency_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restr
     } else if (r >= n_refs && blockIdx.x == 0 && threadIdx.x == 0) {
         atomicAdd((unsigned long long*)oob, (unsigned long long)hw);    // a row index the reference maps do not have: frame not counted
     }
-    t_cc = wave_sum_u32(t_cc); t_cw = wave_sum_u32(t_cw); t_wc = wave_sum_u32(t_wc); t_ww = wave_sum_u32(t_ww); bad = wave_sum_u32(bad);
+    t_cc = awseg_wave_sum_u32(t_cc); t_cw = awseg_wave_sum_u32(t_cw); t_wc = awseg_wave_sum_u32(t_wc); t_ww = awseg_wave_sum_u32(t_ww); bad = awseg_wave_sum_u32(bad);
     if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0) {
         if (t_cc) atomicAdd(&hist[bins + 0], t_cc);
         if (t_cw) atomicAdd(&hist[bins + 1], t_cw);
@@ -109,38 +102,6 @@ void consistency_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restr
     __syncthreads();
     uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * row;
     for (int i = threadIdx.x; i < row; i += kThreads) dst[i] = hist[i];
-}
-
-// Fold the per-block partials of one image into slot 0 and slot 1 + cond[img] (metrics.hip's fold_partials_kernel rule): a block
-// owns 64 counters, its 16 waves each sum a sixteenth of the partials, one LDS step combines them.
-constexpr int kFoldSlices = 16;
-__global__ __launch_bounds__(kFoldSlices * 64)
-void consistency_fold_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row,
-                             const int32_t* __restrict__ cond, int n_slots, int64_t* __restrict__ stats)
-{
-    __shared__ unsigned long long s_sum[kFoldSlices][64];
-    const int img = blockIdx.x;
-    const int kl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int k = blockIdx.y * 64 + kl;
-    const uint32_t* src = partial + (int64_t)img * blocks_per_image * row;
-    unsigned long long s = 0;
-    if (k < row) {
-#pragma unroll 8
-        for (int b = slice; b < blocks_per_image; b += kFoldSlices) s += src[(int64_t)b * row + k];
-    }
-    s_sum[slice][kl] = s;
-    __syncthreads();
-    if (slice == 0 && k < row) {
-        s = 0;
-#pragma unroll
-        for (int j = 0; j < kFoldSlices; ++j) s += s_sum[j][kl];
-        if (s) {
-            int slot = -1;
-            if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-            atomicAdd((unsigned long long*)&stats[k], s);
-            if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * row + k], s);
-        }
-    }
 }
 
 int cons_blocks_per_image(int64_t hw, int64_t batch)
@@ -189,7 +150,7 @@ AWSEG_API int awseg_prediction_consistency(const uint8_t* pred, const uint8_t* r
     else { if (vec) AWSEG_CONS(AWSEG_I64, true); else AWSEG_CONS(AWSEG_I64, false); }
 #undef AWSEG_CONS
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(consistency_fold_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kFoldSlices * 64), 0, s, partial, bpi, row,
+    hipLaunchKernelGGL(awseg_fold_u32_partials_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kAwsegFoldSlices * 64), 0, s, partial, bpi, row,
                        cond, n_slots, stats);
     AWSEG_LAUNCH_CHECK();
     return 0;

@@ -28,8 +28,8 @@ import torch.nn.functional as F
 from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
-from .metrics import (ConfidenceCalibration, RobustnessMetrics, calibration_from_stats, depth_metrics_from_stats,
-                      failure_metrics_from_stats, iou_from_counts, severity_sweep_results)
+from .metrics import (ConfidenceCalibration, RobustnessMetrics, boundary_metrics_from_stats, calibration_from_stats,
+                      depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts, severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -97,6 +97,21 @@ def failure_option(config) -> bool:
     return bool(on)
 
 
+def boundary_option(config):
+    """`evaluation.boundary_widths` (default off): 1 .. 4 strictly increasing integer band widths within [1, 16] for the
+    boundary-band counters (trimap mIoU / Boundary IoU per condition).  -> None when absent, else the list."""
+    spec = _cfg(config, "evaluation.boundary_widths", None)
+    if spec is None:
+        return None
+    try:
+        if isinstance(spec, (bool, str, bytes, dict, int, float, np.number, np.bool_)):
+            raise ValueError("not a list")
+        return [int(d) for d in ops.boundary_widths(list(spec))]
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"evaluation.boundary_widths is a list of 1 .. {ops.BOUNDARY_MAX_WIDTHS} strictly increasing integers within "
+                         f"[1, {ops.BOUNDARY_MAX_RADIUS}], got {spec!r} ({e})") from None
+
+
 def check_depth_budget(pixels: int) -> None:
     """The depth counters are int64 sums of per-pixel terms up to 2^31 (include/awseg.h): raise before they could wrap."""
     if pixels > ops.DEPTH_PIXEL_BUDGET:
@@ -107,7 +122,8 @@ class EvalState:
     """All cross-batch state of one evaluation run (device resident, additive)."""
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
-                 temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False):
+                 temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
+                 boundary=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -140,6 +156,13 @@ class EvalState:
         if failure:
             self.failure = {"stats": ops.new_failure_stats(device, 1 + len(conditions)), "conditions": list(conditions),
                             "single": not ensemble}
+        # boundary-band counters (off unless boundary = boundary_option(config)): int64 [slot, ring, C*C + 2 C]; 'scratch': the uint8
+        # prediction map of the batch where no severity sweep keeps one
+        self.boundary = None
+        if boundary is not None:
+            widths = [int(d) for d in ops.boundary_widths(boundary)]
+            self.boundary = {"widths": widths, "stats": ops.new_boundary_stats(metrics.num_classes, len(widths), device, 1 + len(conditions)),
+                             "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -190,6 +213,15 @@ class EvalState:
         if pd["scratch"] is None or pd["scratch"].numel() < numel:
             pd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
         return pd["scratch"][:numel].view((n,) + tuple(shape))
+
+    def boundary_pred_out(self, shape, device):
+        """The reused uint8 [B, H, W] map the statistics pass writes this batch's prediction into (no severity sweep: nothing else
+        keeps one)."""
+        bd = self.boundary
+        numel = int(np.prod(shape))
+        if bd["scratch"] is None or bd["scratch"].numel() < numel:
+            bd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
+        return bd["scratch"][:numel].view(tuple(shape))
 
     def update_consistency(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
         """Count a variant batch's maps against its sources' clean maps (slot 0 + its condition slot); free the rows of sources whose
@@ -277,6 +309,8 @@ class EvalState:
             ts += [self.depth["stats"], depth_pixels]
         if getattr(self, "failure", None) is not None:
             ts.append(self.failure["stats"])
+        if getattr(self, "boundary", None) is not None:                  # (getattr: all_reduce also serves states built without it)
+            ts += [self.boundary["stats"], self.boundary["oob"]]
         pd = getattr(self, "paired", None)
         if pd is not None:
             if pd["live"]:
@@ -332,6 +366,9 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         if unknown:
             raise ValueError(f"batch conditions {unknown} are not slots of the severity sweep")
         pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
+    bd = getattr(st, "boundary", None)
+    if bd is not None and pred_out is None:
+        pred_out = st.boundary_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     depth_kw = {}
     if st.depth is not None:
@@ -390,7 +427,9 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_calibration(labels, cond, logits=logits)
         if st.failure is not None:
             ops.failure_stats(logits, labels, st.failure["stats"], cond)
-    if pred_out is not None:
+    if bd is not None:
+        ops.boundary_stats(pred_out, labels.reshape(pred_out.shape), bd["widths"], metrics.num_classes, bd["stats"], bd["oob"], cond)
+    if st.sweep is not None:                                          # (pred_out alone no longer says so: the boundary counters ask for one too)
         st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
 
@@ -410,7 +449,8 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
     st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
-                   depth=depth_options(config), failure=failure_option(config))
+                   depth=depth_options(config), failure=failure_option(config),
+                   boundary=boundary_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -474,6 +514,14 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                   kinds=st.sweep.kinds if st.sweep is not None else None,
                                                   levels=st.sweep.levels if st.sweep is not None else 0,
                                                   single=st.failure["single"]))
+    bd = getattr(st, "boundary", None)
+    if bd is not None:
+        if int(bd["oob"].item()):
+            raise IndexError("prediction map value outside [0, num_classes) in the boundary counters")
+        results.update(boundary_metrics_from_stats(bd["stats"].cpu().numpy(), bd["widths"], st.acc.conditions, metrics.num_classes,
+                                                   kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                   levels=st.sweep.levels if st.sweep is not None else 0,
+                                                   degradation=metrics.compute_robustness_degradation_ratio))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -454,6 +454,66 @@ def failure_metrics_from_stats(stats, conditions: List[str], kinds=None, levels:
     return res
 
 
+def boundary_metrics_from_stats(stats, widths, conditions: List[str], num_classes: int, kinds=None, levels: int = 0,
+                                degradation=None) -> Dict[str, float]:
+    """Result keys of the boundary-band counters (int64 [1 + len(conditions), len(widths) + 1, C*C + 2 C], include/awseg.h; slot 0 =
+    every frame, slot 1 + k = conditions[k]).  Host only; every value a float.  Per width d (the band: labelled pixels within
+    Chebyshev distance d of a class boundary, the rings 0 .. k of the counters summed) and suffix ('' | _<condition>):
+      boundary_miou_w<d>       iou_from_counts on the band's confusion matrix (trimap mIoU; band of the label map)
+      boundary_accuracy_w<d>   trace / total of it (trimap accuracy)
+      boundary_iou_w<d>        mean over the classes with a non-empty union of inter / (gt + pr - inter): gt[c] the band's labelled
+                               pixels of class c (label band), pr[c] those predicted c within the prediction's band, inter[c] those
+                               where both hold and the classes agree (Boundary IoU, Cheng et al. 2021, over the labelled pixels)
+      boundary_fraction_w<d>   share of the labelled pixels inside the label band
+    and per suffix interior_miou (iou_from_counts on the last ring: farther than the widest band from any label boundary).  A band
+    without a pixel yields its fraction only; a slot without a labelled pixel yields no keys.
+    Severity sweep (kinds, levels): conditions are its slots ('clean', '<kind>_s<j>'); each kind also gets keys from the summed
+    counters of its slots.  With 'clean' present, for every adverse kind (without a sweep: every other condition)
+      boundary_degradation_w<d>_<kind> = degradation(boundary_iou_w<d>_clean, boundary_iou_w<d>_<kind>)
+      interior_degradation_<kind>      = degradation(interior_miou_clean, interior_miou_<kind>)
+    degradation: RobustnessMetrics.compute_robustness_degradation_ratio unless given."""
+    w = [int(d) for d in ops.boundary_widths(widths)]
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    C = int(num_classes)
+    if raw.ndim != 3 or raw.shape != (1 + len(conditions), len(w) + 1, C * (C + 2)):
+        raise ValueError(f"boundary stats must be int64 [{1 + len(conditions)}, {len(w) + 1}, {C * (C + 2)}], got {raw.shape}")
+    if degradation is None:
+        degradation = RobustnessMetrics(C).compute_robustness_degradation_ratio
+    named = [("", raw[0])] + [("_" + name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        named.append(("_" + kind, raw[idx].sum(0)))
+    res: Dict[str, float] = {}
+    for suffix, slot in named:
+        dec = ops.boundary_stats_to_numpy(slot, C)
+        total = int(dec["conf"].sum())
+        if total <= 0:
+            continue
+        conf, inter, pr = (np.cumsum(dec[k], axis=0) for k in ("conf", "inter", "pr"))
+        for k, d in enumerate(w):
+            band = int(conf[k].sum())
+            res[f"boundary_fraction_w{d}{suffix}"] = float(band / total)
+            if band <= 0:
+                continue
+            res[f"boundary_miou_w{d}{suffix}"] = float(iou_from_counts(torch.from_numpy(conf[k].reshape(-1).copy()), C)["mean_iou"])
+            res[f"boundary_accuracy_w{d}{suffix}"] = float(np.trace(conf[k]) / band)
+            union = conf[k].sum(axis=1) + pr[k] - inter[k]
+            seen = union > 0
+            res[f"boundary_iou_w{d}{suffix}"] = float((inter[k][seen] / union[seen].astype(np.float64)).mean())
+        last = dec["conf"][len(w)]
+        if int(last.sum()) > 0:
+            res[f"interior_miou{suffix}"] = float(iou_from_counts(torch.from_numpy(last.reshape(-1).copy()), C)["mean_iou"])
+    adverse = list(kinds) if kinds else [name for name in conditions if name != "clean"]
+    for kind in adverse:
+        for d in w:
+            a, b = f"boundary_iou_w{d}_clean", f"boundary_iou_w{d}_{kind}"
+            if a in res and b in res:
+                res[f"boundary_degradation_w{d}_{kind}"] = float(degradation(res[a], res[b]))
+        if "interior_miou_clean" in res and f"interior_miou_{kind}" in res:
+            res[f"interior_degradation_{kind}"] = float(degradation(res["interior_miou_clean"], res[f"interior_miou_{kind}"]))
+    return res
+
+
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""
 

@@ -5,6 +5,7 @@ reads this one."""
 from __future__ import annotations
 
 import json
+import re
 from pathlib import Path
 from typing import Any, Dict, Optional
 
@@ -38,7 +39,31 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += depth_section(results)
     if any(k.startswith("failure_auroc_") for k in results):
         lines += failure_section(results)
+    if any(k.startswith("boundary_iou_") for k in results):
+        lines += boundary_section(results)
     return "\n".join(lines)
+
+
+def boundary_section(results: Dict[str, Any]) -> list:
+    """Boundary bands (evaluation.boundary_widths): condition x width Boundary IoU, the interior mIoU, and what each adverse kind
+    loses at the boundary (widest band) against what it loses in the interior."""
+    import re
+    widths = sorted({int(m.group(1)) for k in results for m in [re.match(r"boundary_fraction_w(\d+)$", k)] if m})
+    first = f"boundary_fraction_w{widths[0]}_"
+    names = [""] + [k[len(first):] for k in results if k.startswith(first)]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    lines = ["", "## Boundary Bands", "", "Boundary IoU over the labelled pixels within w pixels (Chebyshev) of a class boundary; "
+             "interior: mIoU beyond the widest band.", "",
+             "| Condition | " + " | ".join(f"w = {d}" for d in widths) + f" | Band share (w = {widths[-1]}) | Interior mIoU | "
+             f"Boundary degradation (w = {widths[-1]}) | Interior degradation |", "|---" * (len(widths) + 5) + "|"]
+    for n in names:
+        sfx = "_" + n if n else ""
+        lines.append(f"| {n or 'all'} | " + " | ".join(cell(f"boundary_iou_w{d}{sfx}") for d in widths) +
+                     f" | {cell(f'boundary_fraction_w{widths[-1]}{sfx}')} | {cell('interior_miou' + sfx)} | "
+                     f"{cell(f'boundary_degradation_w{widths[-1]}{sfx}') if n else '-'} | {cell('interior_degradation' + sfx) if n else '-'} |")
+    return lines
 
 
 FAILURE_SCORES = ("mi", "entropy", "variance", "msp")

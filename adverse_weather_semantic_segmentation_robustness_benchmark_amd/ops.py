@@ -197,6 +197,68 @@ def consistency_stats_to_numpy(stats, num_classes: int) -> dict:
     return {"agreement": raw[..., :c2].reshape(raw.shape[:-1] + (num_classes, num_classes)), "transitions": raw[..., c2:c2 + 4]}
 
 
+# ----------------------------------------------------------------------------- boundary-band counters (include/awseg.h)
+BOUNDARY_MAX_WIDTHS = 4                # AWSEG_BOUNDARY_MAX_WIDTHS
+BOUNDARY_MAX_RADIUS = 16               # AWSEG_BOUNDARY_MAX_RADIUS
+
+
+def boundary_widths(widths) -> np.ndarray:
+    """The band widths as a host int32 array, checked before any launch (the C ABI refuses the same lists with AWSEG_EINVAL)."""
+    w = [widths] if isinstance(widths, (int, np.integer)) and not isinstance(widths, (bool, np.bool_)) else list(widths)
+    if any(isinstance(d, (bool, np.bool_)) or not isinstance(d, (int, np.integer)) for d in w):
+        raise ValueError(f"band widths are integers, got {widths!r}")
+    if not 1 <= len(w) <= BOUNDARY_MAX_WIDTHS:
+        raise ValueError(f"1 .. {BOUNDARY_MAX_WIDTHS} band widths, got {len(w)}")
+    if any(d < 1 or d > BOUNDARY_MAX_RADIUS for d in w) or any(b <= a for a, b in zip(w, w[1:])):
+        raise ValueError(f"band widths must be strictly increasing within [1, {BOUNDARY_MAX_RADIUS}], got {list(w)}")
+    return np.ascontiguousarray(w, dtype=np.int32)
+
+
+def new_boundary_stats(num_classes: int, n_widths: int, device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, n_widths + 1, C*C + 2 C]: per slot and ring (ring k < n: edge distance within width k but not k - 1; ring n:
+    the interior) the row C*C conf | C inter | C pr of include/awseg.h (zeroed: the launches accumulate)."""
+    return torch.zeros(n_slots, n_widths + 1, num_classes * (num_classes + 2), dtype=torch.int64, device=device)
+
+
+def boundary_stats(pred: torch.Tensor, label: torch.Tensor, widths, num_classes: int, stats: torch.Tensor, oob: torch.Tensor,
+                   cond: Optional[torch.Tensor] = None, ignore_index: int = 255) -> None:
+    """Boundary-band counters of the uint8 prediction maps `pred` [B, H, W] against `label` [B, H, W] (uint8 or int64) for the band
+    widths `widths`, accumulated into `stats` (new_boundary_stats; slot 0 + slot 1 + cond[b]); labelled pixels whose prediction
+    value is >= C go to `oob` (int64 [1])."""
+    w = boundary_widths(widths)
+    if pred.dim() != 3 or pred.dtype != torch.uint8:
+        raise ValueError(f"boundary_stats: pred is uint8 [B, H, W], got {pred.dtype} {tuple(pred.shape)}")
+    if label.dtype not in (torch.uint8, torch.int64) or tuple(label.shape) != tuple(pred.shape):
+        raise ValueError(f"boundary_stats: label is uint8 or int64 {tuple(pred.shape)}, got {label.dtype} {tuple(label.shape)}")
+    if pred.numel() < 1:
+        raise ValueError(f"boundary_stats: empty maps {tuple(pred.shape)}")
+    if not 1 <= int(num_classes) <= N.MAX_CLASSES:
+        raise ValueError(f"boundary_stats: 1 .. {N.MAX_CLASSES} classes, got {num_classes}")
+    if stats.dim() != 3 or stats.dtype != torch.int64 or tuple(stats.shape[1:]) != (w.size + 1, num_classes * (num_classes + 2)):
+        raise ValueError(f"stats must be int64 [slots, {w.size + 1}, {num_classes * (num_classes + 2)}] (new_boundary_stats), got "
+                         f"{stats.dtype} {tuple(stats.shape)}")
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    b, H, W = pred.shape
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    pred, label = pred.contiguous(), label.contiguous()
+    ws = N.workspace.get(pred.device, N.lib().awseg_boundary_workspace(b, int(num_classes), H, W, int(w.size)), tag="boundary")
+    N.call("awseg_boundary_stats", N.ptr(pred), N.ptr(label), N.label_dtype(label), int(ignore_index), b, H, W, int(num_classes),
+           N.host(w), int(w.size), N.ptr(cond), N.ptr(stats), stats.shape[0], N.ptr(oob), N.ptr(ws), N.stream())
+
+
+def boundary_stats_to_numpy(stats, num_classes: int) -> dict:
+    """int64 [slots, rings, C*C + 2 C] -> {'conf' [slots, rings, C, C] (rows: label, columns: prediction; ring of the label's edge
+    distance), 'inter' [slots, rings, C] (label == prediction; ring of the larger distance), 'pr' [slots, rings, C] (ring of the
+    prediction's distance)}."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    c, c2 = num_classes, num_classes * num_classes
+    if raw.shape[-1] != c2 + 2 * c:
+        raise ValueError(f"boundary stats rows hold {c}^2 + 2 x {c} counters, got {raw.shape[-1]}")
+    return {"conf": raw[..., :c2].reshape(raw.shape[:-1] + (c, c)), "inter": raw[..., c2:c2 + c], "pr": raw[..., c2 + c:]}
+
+
 ECE_CONF_UNIT = 2.0 ** -30     # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

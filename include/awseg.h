@@ -1072,6 +1072,48 @@ int awseg_ensemble_failure_stats(const float* seg1, const float* seg2, const flo
 int awseg_failure_stats(const float* logits, int64_t batch, int num_classes, int64_t hw, const void* label, int label_dtype,
                         const int32_t* cond, int64_t* stats, int n_slots, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Boundary-band segmentation counters (trimap accuracy / mIoU as in the DeepLab papers; Boundary IoU, Cheng et al. 2021;
+ *  DESIGN.md 10f)
+ * ------------------------------------------------------------------------- *
+ * pred uint8 [B, H, W], label uint8 / int64 [B, H, W] (label_dtype).  A label pixel is valid when its label is neither
+ * ignore_index nor outside [0, C) (the rule of awseg_prediction_consistency; no uint8 wrapping); a prediction pixel is valid
+ * when its value is < C.  C = num_classes <= AWSEG_MAX_CLASSES.
+ *
+ * Edge distance e_M(p) of a valid pixel p of map M: the smallest d >= 1 such that some pixel q of the SAME frame with
+ * max(|dy|, |dx|) <= d (Chebyshev distance: the square structuring element of Boundary IoU's erosion) is valid and has
+ * M(q) != M(p); infinite when there is none.  Equivalently, with the window min and max over the valid values within distance d:
+ * e_M(p) <= d  <=>  min < M(p) or max > M(p).  Invalid pixels and everything outside the frame never form a boundary: a
+ * one-class frame has no band, not even at its border.  (The published Boundary IoU code pads the mask before it erodes, so
+ * there an object that touches the image border has a band along it; here it has none.)  Two classes separated by a stripe of
+ * ignored pixels see each other through it.  The prediction's distances come from the whole prediction map: ignored regions are
+ * ordinary neighbours there.
+ *
+ * widths: HOST int32[n_widths], d_1 < d_2 < ... < d_n, 1 <= n <= AWSEG_BOUNDARY_MAX_WIDTHS, 1 <= d_k <= AWSEG_BOUNDARY_MAX_RADIUS
+ * (they travel in the kernel arguments).  ring(e) = the smallest k (from 0) with e <= d_(k+1), or n when e > d_n (the interior).
+ * Only labelled pixels (valid in the label map) are counted.  With t = label, p = prediction, each adds 1 to
+ *     conf[ring(e_label)][t * C + p]
+ *     pr[ring(e_pred)][p]
+ *     inter[ring(max(e_label, e_pred))][t]          when t == p
+ * except a labelled pixel whose prediction value is >= C, which adds 1 to oob (int64[1]) and nothing else (such a value is
+ * also invalid as a neighbour).  Cumulative sums over rings 0 .. k give the band of width d_(k+1), ring n the interior; conf
+ * summed over all rings is the confusion matrix of the labelled pixels.
+ *
+ * stats int64 [n_slots][n_widths + 1][C * C + 2 * C] (accumulated, never cleared), the row of one (slot, ring) laid out
+ * C * C conf | C inter | C pr.  Slot rule of every other counter: each frame into slot 0 and into slot 1 + cond[b] when
+ * 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0 only).  Integer sums only: the counts do not depend on
+ * grid shape, batch split or rank count and are additive over launches.  Any H, W >= 1 (frames smaller than the widest band
+ * and single rows / columns included) with H * W < 2^31 and batch <= 65535 (AWSEG_ERANGE beyond).  workspace:
+ * awseg_boundary_workspace(batch, num_classes, height, width, n_widths) bytes.  AWSEG_EINVAL for a NULL pointer (cond
+ * excepted), a size < 1, an unknown label dtype, or widths that are empty, too many, not strictly increasing, < 1 or
+ * > AWSEG_BOUNDARY_MAX_RADIUS. */
+#define AWSEG_BOUNDARY_MAX_WIDTHS 4
+#define AWSEG_BOUNDARY_MAX_RADIUS 16
+int64_t awseg_boundary_workspace(int64_t batch, int num_classes, int height, int width, int n_widths);
+int awseg_boundary_stats(const uint8_t* pred, const void* label, int label_dtype, int ignore_index, int64_t batch, int height,
+                         int width, int num_classes, const int32_t* widths, int n_widths, const int32_t* cond, int64_t* stats,
+                         int n_slots, int64_t* oob, void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

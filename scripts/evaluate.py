@@ -61,6 +61,14 @@ def parse_severities(text: str):
         raise ValueError(f"--severities takes 'reference' or comma-separated intensities, got {text!r}") from None
 
 
+def parse_boundary_widths(text: str):
+    """--boundary-widths: comma-separated integers (the harness checks their range and order)."""
+    try:
+        return [int(x) for x in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--boundary-widths takes comma-separated integers such as 1,2,4,8, got {text!r}") from None
+
+
 def main():
     ap = argparse.ArgumentParser(description="Evaluate adverse-weather segmentation model (MI355X-native path)")
     ap.add_argument("checkpoint", type=str)
@@ -74,6 +82,9 @@ def main():
     ap.add_argument("--failure-detection", action="store_true",
                     help="AUROC / AURC of four uncertainty scores against the prediction's errors, per condition "
                          "(sets evaluation.failure_detection)")
+    ap.add_argument("--boundary-widths", type=str, default=None,
+                    help="boundary-band metrics (trimap mIoU, Boundary IoU) per condition: 1-4 comma-separated increasing band widths in "
+                         "pixels, each within [1, 16], e.g. 1,2,4,8 (sets evaluation.boundary_widths)")
     args = ap.parse_args()
     try:
         config = load_config(args.config) if args.config else create_default_config()
@@ -88,6 +99,8 @@ def main():
             config.set("evaluation.depth_metrics", True)
         if args.failure_detection:
             config.set("evaluation.failure_detection", True)
+        if args.boundary_widths is not None:
+            config.set("evaluation.boundary_widths", parse_boundary_widths(args.boundary_widths))
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",

@@ -168,6 +168,14 @@ def main():
         lambda: ops.prediction_consistency(var_c, ref_c, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
     cases["prediction consistency, independent random maps"] = (
         lambda: ops.prediction_consistency(var_r, ref_r, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
+    # boundary-band counters, widths 1, 2, 4, 8, on the maps of the two consistency cases above (label = the clean map, prediction =
+    # the variant): 2 B/px from HBM, so the row's "of peak" says how far from HBM-bound the stencil is, not how well it streams
+    bw = [1, 2, 4, 8]
+    bst, boob = ops.new_boundary_stats(C, len(bw), dev, 6), torch.zeros(1, dtype=torch.int64, device=dev)
+    cases["boundary stats w=1,2,4,8, coherent 16 x 16 blocks, ~5 % flipped"] = (
+        lambda: ops.boundary_stats(var_c, ref_c, bw, C, bst, boob, cond), "hbm", 2 * px * B)
+    cases["boundary stats w=1,2,4,8, independent random maps"] = (
+        lambda: ops.boundary_stats(var_r, ref_r, bw, C, bst, boob, cond), "hbm", 2 * px * B)
     for K in (100, 16):                      # streamed temperature calibration: K x C exponentials per pixel, issue-bound
         grid = ops.DEFAULT_TEMPERATURE_GRID if K == 100 else np.linspace(0.25, 4.0, K).astype(np.float32)
         tst = ops.new_temperature_grid_stats(K, 15, dev, 6)
