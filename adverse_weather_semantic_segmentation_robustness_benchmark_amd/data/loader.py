@@ -197,7 +197,9 @@ class CityscapesKITTIDataset:
         ids = list(range(start, start + n)) if self.weather_transforms.rng == "philox" else None   # numpy mode keeps the reference's global stream
         h, w = self.image_size
         image = torch.empty(n, 3, h, w, dtype=torch.float32, device=self.device)
-        batch = {"image": image, "label": labels, "weather_condition": conds, "dataset": ["synthetic"] * n}
+        # 'source': the global sample indices, as the paired batches carry them (in both rng modes; `ids` above is None in numpy mode)
+        batch = {"image": image, "label": labels, "weather_condition": conds, "dataset": ["synthetic"] * n,
+                 "source": list(range(start, start + n))}
         if self.depth_preprocessor is None:
             self.weather_transforms.apply_batch(imgs, conds, norm_out=image, frame_ids=ids)
         else:

@@ -28,8 +28,9 @@ import torch.nn.functional as F
 from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
-from .metrics import (ConfidenceCalibration, RobustnessMetrics, boundary_metrics_from_stats, calibration_from_stats,
-                      depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts, severity_sweep_results)
+from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
+                      calibration_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
+                      severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -112,6 +113,49 @@ def boundary_option(config):
                          f"[1, {ops.BOUNDARY_MAX_RADIUS}], got {spec!r} ({e})") from None
 
 
+BOOTSTRAP_MAX_REPLICATES = 65536
+
+
+def bootstrap_options(config, num_sources=None):
+    """`evaluation.bootstrap_replicates` (default absent = off: an integer in [1, 65536]), `evaluation.bootstrap_confidence` (a
+    float in (0, 1), default 0.95) and `evaluation.bootstrap_seed` (an integer in [0, 2^63), default 0): the paired frame bootstrap
+    of the per-condition mIoU.  -> None when off, else {'replicates', 'confidence', 'seed', 'sources'} with
+    'sources' = num_sources (the number of source frames of the evaluation set: the resampling unit)."""
+    def integer(key, v, lo, hi):
+        if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"evaluation.{key} is an integer in [{lo}, {hi}], got {v!r}")
+        return int(v)
+    conf = _cfg(config, "evaluation.bootstrap_confidence", 0.95)
+    if isinstance(conf, (bool, np.bool_, str, bytes)) or not isinstance(conf, (int, float, np.floating, np.integer)) \
+            or not 0.0 < float(conf) < 1.0:
+        raise ValueError(f"evaluation.bootstrap_confidence is a number in (0, 1), got {conf!r}")
+    seed = integer("bootstrap_seed", _cfg(config, "evaluation.bootstrap_seed", 0), 0, 2 ** 63 - 1)
+    reps = _cfg(config, "evaluation.bootstrap_replicates", None)
+    if reps is None:
+        return None
+    reps = integer("bootstrap_replicates", reps, 1, BOOTSTRAP_MAX_REPLICATES)
+    if num_sources is not None and (isinstance(num_sources, bool) or not isinstance(num_sources, (int, np.integer)) or num_sources < 1):
+        raise ValueError(f"the frame bootstrap resamples the source frames of a sized dataset, got {num_sources!r} of them")
+    return {"replicates": reps, "confidence": float(conf), "seed": seed, "sources": None if num_sources is None else int(num_sources)}
+
+
+def bootstrap_resampling_set(table: torch.Tensor, seen: torch.Tensor, slot: torch.Tensor, oob: torch.Tensor):
+    """The summed tables of the frame bootstrap (EvalState.bootstrap, after the all-reduce) -> (table [n, V, 3 C], slots int32
+    [n, V], the n kept source indices): the sources of which no frame came (drop_last, a short shard) leave the resampling set, the
+    rest are compacted where they are.  ValueError when a (source, variant) came more than once (its row would hold two frames and
+    its slot entry a sum), IndexError when the per-frame pass met a value outside the classes."""
+    twice = (seen > 1).any(dim=1).nonzero()
+    if twice.numel():
+        raise ValueError(f"source {int(twice[0, 0])}: a frame came more than once; the frame bootstrap needs every "
+                         "(source, variant) at most once")
+    if int(oob.item()):
+        raise IndexError("prediction map or label value outside [0, num_classes) in the per-frame counters")
+    keep = (seen.sum(dim=1) > 0).nonzero().view(-1)
+    if keep.numel() == 0:
+        raise ValueError("the frame bootstrap saw no frame")
+    return table.index_select(0, keep), slot.index_select(0, keep).to(torch.int32), keep
+
+
 def check_depth_budget(pixels: int) -> None:
     """The depth counters are int64 sums of per-pixel terms up to 2^31 (include/awseg.h): raise before they could wrap."""
     if pixels > ops.DEPTH_PIXEL_BUDGET:
@@ -123,7 +167,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None):
+                 boundary=None, bootstrap=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -163,6 +207,21 @@ class EvalState:
             widths = [int(d) for d in ops.boundary_widths(boundary)]
             self.boundary = {"widths": widths, "stats": ops.new_boundary_stats(metrics.num_classes, len(widths), device, 1 + len(conditions)),
                              "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+        # frame bootstrap (off unless bootstrap = bootstrap_options(config, num_sources)): per-frame IoU counters int64
+        # [source, variant, 3 C], how often each (source, variant) came, and 1 + its condition slot; variant 0 is the only one
+        # without a sweep, under a sweep variant = the frame's slot index (0 clean, 1 + k S + j - 1 for kind k at level j).
+        # 'scratch': the uint8 prediction map of the batch where neither the sweep nor the boundary counters keep one
+        self.bootstrap = None
+        if bootstrap is not None:
+            if bootstrap.get("sources") is None:
+                raise ValueError("the frame bootstrap needs the number of source frames (a loader with a sized dataset)")
+            n_src, variants = int(bootstrap["sources"]), len(conditions) if sweep is not None else 1
+            self.bootstrap = {"replicates": int(bootstrap["replicates"]), "confidence": float(bootstrap["confidence"]),
+                              "seed": int(bootstrap["seed"]), "sources": n_src, "variants": variants,
+                              "table": ops.new_frame_counts(n_src * variants, metrics.num_classes, device).view(n_src, variants, -1),
+                              "seen": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
+                              "slot": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
+                              "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -222,6 +281,47 @@ class EvalState:
         if bd["scratch"] is None or bd["scratch"].numel() < numel:
             bd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
         return bd["scratch"][:numel].view(tuple(shape))
+
+    def bootstrap_pred_out(self, shape, device):
+        """boundary_pred_out for the frame bootstrap: the reused uint8 [B, H, W] map of the batch when nothing else keeps one."""
+        bs = self.bootstrap
+        numel = int(np.prod(shape))
+        if bs["scratch"] is None or bs["scratch"].numel() < numel:
+            bs["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
+        return bs["scratch"][:numel].view(tuple(shape))
+
+    def update_bootstrap(self, pred, labels, sources, cond_ids, num_classes: int) -> None:
+        """Per-frame IoU counters of this batch into rows (source, variant); cond_ids: the host list cond was made from."""
+        bs = self.bootstrap
+        if any(c < 0 for c in cond_ids):
+            raise ValueError("the frame bootstrap needs every frame's condition among the counter slots "
+                             f"{self.acc.conditions} (data.weather_conditions)")
+        bad = [s for s in sources if not 0 <= s < bs["sources"]]
+        if bad:
+            raise ValueError(f"source {bad[0]} is outside the evaluation set's {bs['sources']} source frames")
+        if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not bs.get("warned"):
+            bs["warned"] = True
+            logger.warning("frame bootstrap: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
+                           "wrapped index, the per-frame counters never wrap: the intervals describe the unwrapped mIoU and need not "
+                           "contain the pooled point estimates (DESIGN.md 10g)", num_classes)
+        v = bs["variants"]
+        rows = [s * v + (c if v > 1 else 0) for s, c in zip(sources, cond_ids)]
+        # one host-to-device copy: the rows, and 1 + slot of each
+        host = torch.tensor([rows, [1 + c for c in cond_ids]], dtype=torch.int64).to(pred.device, non_blocking=True)
+        ops.frame_iou_counts(pred, labels, num_classes, host[0].to(torch.int32), bs["table"], bs["oob"])
+        bs["seen"].view(-1).index_add_(0, host[0], torch.ones_like(host[0]))
+        bs["slot"].view(-1).index_add_(0, host[0], host[1])           # a frame that comes twice is caught by 'seen' after the reduce
+
+    def bootstrap_replicates(self):
+        """After all_reduce: check the tables, drop the sources no rank saw, resample.  -> (int64 [R, slots, 3 C] on the host,
+        number of sources resampled)."""
+        bs = self.bootstrap
+        table, slots, keep = bootstrap_resampling_set(bs["table"], bs["seen"], bs["slot"], bs["oob"])
+        oob = torch.zeros(1, dtype=torch.int64, device=table.device)
+        rep = ops.bootstrap_counts(table, slots, 1 + len(self.acc.conditions), bs["seed"], bs["replicates"], oob)
+        if int(oob.item()):
+            raise IndexError("slot outside the counter slots in the frame bootstrap's slot table")
+        return rep.cpu().numpy(), int(keep.numel())
 
     def update_consistency(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
         """Count a variant batch's maps against its sources' clean maps (slot 0 + its condition slot); free the rows of sources whose
@@ -311,6 +411,9 @@ class EvalState:
             ts.append(self.failure["stats"])
         if getattr(self, "boundary", None) is not None:                  # (getattr: all_reduce also serves states built without it)
             ts += [self.boundary["stats"], self.boundary["oob"]]
+        bs = getattr(self, "bootstrap", None)
+        if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
+            ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
         pd = getattr(self, "paired", None)
         if pd is not None:
             if pd["live"]:
@@ -369,6 +472,15 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     bd = getattr(st, "boundary", None)
     if bd is not None and pred_out is None:
         pred_out = st.boundary_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
+    bs = getattr(st, "bootstrap", None)
+    if bs is not None:
+        if sources is None:
+            raise ValueError("the frame bootstrap needs the loader's 'source' (global sample indices) for every batch")
+        sources = [int(s) for s in sources]
+        if len(sources) != images.shape[0]:
+            raise ValueError(f"{len(sources)} sources for a batch of {images.shape[0]} frames")
+        if pred_out is None:
+            pred_out = st.bootstrap_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     depth_kw = {}
     if st.depth is not None:
@@ -429,6 +541,9 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             ops.failure_stats(logits, labels, st.failure["stats"], cond)
     if bd is not None:
         ops.boundary_stats(pred_out, labels.reshape(pred_out.shape), bd["widths"], metrics.num_classes, bd["stats"], bd["oob"], cond)
+    if bs is not None:
+        ids = [st.acc.conditions.index(str(c)) if str(c) in st.acc.conditions else -1 for c in conds]      # cond_ids' rule
+        st.update_bootstrap(pred_out, labels, sources, ids, metrics.num_classes)
     if st.sweep is not None:                                          # (pred_out alone no longer says so: the boundary counters ask for one too)
         st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
@@ -446,15 +561,24 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
         ds = getattr(test_loader, "dataset", None)
         rng = getattr(getattr(ds, "weather_transforms", None), "rng", "philox")
         sweep = resolve_severities(spec, conditions, rng)
+    bootstrap = bootstrap_options(config)
+    if bootstrap is not None:
+        try:
+            bootstrap["sources"] = len(test_loader.dataset)
+        except (AttributeError, TypeError):
+            raise ValueError("evaluation.bootstrap_replicates: the frame bootstrap resamples source frames and needs a loader with a "
+                             "sized dataset (len(test_loader.dataset))") from None
     st = EvalState(metrics, conditions, device, num_bins, ensemble=is_ensemble,
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
                    depth=depth_options(config), failure=failure_option(config),
-                   boundary=boundary_option(config))
+                   boundary=boundary_option(config), bootstrap=bootstrap)
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
         extra = {"sources": batch.get("source"), "severity": batch.get("severity")} if sweep is not None else {}
+        if st.bootstrap is not None:
+            extra["sources"] = batch.get("source")
         if st.depth is not None:
             extra["depth"] = None if batch.get("depth") is None else batch["depth"].to(device)
         eval_batch(model, st, images, labels, batch.get("weather_condition", ["clean"] * images.size(0)), metrics, **extra)
@@ -531,4 +655,13 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                 if f"robustness_degradation_{w}" in results]
         if degs:
             results["robustness_degradation_ratio"] = np.mean(degs)
+    bs = getattr(st, "bootstrap", None)
+    if bs is not None:
+        # last: a quantity gets an interval when its point estimate is above.  The point estimates stay the pooled ones.
+        rep, n_sources = st.bootstrap_replicates()
+        results.update(bootstrap_metrics_from_replicates(rep, st.acc.conditions, metrics.num_classes, results, bs["confidence"],
+                                                         bs["seed"], kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                         levels=st.sweep.levels if st.sweep is not None else 0,
+                                                         degradation=metrics.compute_robustness_degradation_ratio))
+        results["bootstrap_sources"] = float(n_sources)
     return results

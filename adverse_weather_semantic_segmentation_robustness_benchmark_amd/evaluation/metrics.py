@@ -514,6 +514,93 @@ def boundary_metrics_from_stats(stats, widths, conditions: List[str], num_classe
     return res
 
 
+ADVERSE_KINDS = ("fog", "rain", "snow", "night")                     # the kinds finalize() reports a degradation for
+
+
+def replicate_miou(counts, num_classes: int):
+    """mIoU of every row of int64 [..., 3 C] counters (C intersection | C label count | C prediction count): iou_from_counts'
+    float32 expressions (int64 / int64 true-divide, mean over the classes with a non-empty union) on the marginals instead of the
+    confusion matrix.  -> (miou float64 [...], NaN where no class has a union; present bool [...]: some labelled pixel)."""
+    t = torch.as_tensor(np.ascontiguousarray(counts), dtype=torch.int64)
+    c = int(num_classes)
+    if t.shape[-1] != 3 * c:
+        raise ValueError(f"frame count rows hold 3 x {c} counters, got {t.shape[-1]}")
+    inter, lab, prd = t[..., :c], t[..., c:2 * c], t[..., 2 * c:]
+    union = lab + prd - inter
+    valid = union > 0
+    per = torch.where(valid, inter / union.clamp(min=1), torch.zeros((), dtype=torch.float32))
+    miou = per.sum(-1) / valid.sum(-1).to(torch.float32)
+    return miou.to(torch.float64).numpy(), (lab.sum(-1) > 0).numpy()
+
+
+def bootstrap_metrics_from_replicates(replicates, conditions: List[str], num_classes: int, point: Dict[str, Any],
+                                      confidence: float = 0.95, seed: int = 0, kinds=None, levels: int = 0,
+                                      degradation=None) -> Dict[str, float]:
+    """Interval keys of the frame bootstrap from the replicate sums int64 [R, 1 + len(conditions), 3 C] (ops.bootstrap_counts: slot 0
+    = every frame, slot 1 + k = conditions[k]) and the pooled point estimates `point` (the results so far: a quantity gets an
+    interval when its point estimate is there).  Host only.  Per quantity Q
+      Q_ci_low, Q_ci_high   percentile interval: np.quantile(method='linear') of the valid replicates at (1 -+ confidence) / 2
+      Q_se                  their standard deviation (ddof = 1; NaN below two)
+    for Q = overall_miou, miou_<slot>, miou_<kind> (sweep: the kind's severity slots summed per replicate),
+    robustness_degradation_<kind>[_s<j>] (`degradation` on the replicate's clean and adverse mIoU: the reference's clamp at 0 stays,
+    so an interval can sit on 0), robustness_degradation_ratio (mean over kinds per replicate) and the unclamped
+    miou_drop_<kind>[_s<j>] = clean - adverse, whose point value is a new key and which also gets miou_drop_*_p_nonpositive: the share
+    of valid replicates with a drop <= 0 (the paired one-sided bootstrap p-value of 'this kind costs nothing').  A replicate in which
+    a slot drew no labelled pixel is left out of every quantity that needs that slot (bootstrap_empty_replicates_<slot> counts them,
+    when there are any)."""
+    degradation = degradation or RobustnessMetrics().compute_robustness_degradation_ratio
+    rep = replicates.cpu().numpy() if isinstance(replicates, torch.Tensor) else np.asarray(replicates, dtype=np.int64)
+    if rep.ndim != 3 or rep.shape[1] != 1 + len(conditions) or rep.shape[2] != 3 * num_classes or rep.shape[0] < 1:
+        raise ValueError(f"replicate sums must be int64 [R, {1 + len(conditions)}, {3 * num_classes}], got {rep.shape}")
+    if not 0.0 < float(confidence) < 1.0:
+        raise ValueError(f"confidence lies in (0, 1), got {confidence!r}")
+    R = rep.shape[0]
+    res: Dict[str, float] = {"bootstrap_replicates": float(R), "bootstrap_confidence": float(confidence), "bootstrap_seed": float(seed)}
+    miou, present = replicate_miou(rep, num_classes)
+    series: Dict[str, Any] = {}                                       # name in the mIoU namespace -> (values [R], valid [R])
+    if "overall_miou" in point:
+        series["overall"] = (miou[:, 0], present[:, 0])
+    for k, name in enumerate(conditions):
+        if f"miou_{name}" in point:
+            series[name] = (miou[:, 1 + k], present[:, 1 + k])
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        if f"miou_{kind}" in point:
+            series[kind] = replicate_miou(rep[:, idx].sum(axis=1), num_classes)
+    lo_q, hi_q = (1.0 - float(confidence)) / 2.0, (1.0 + float(confidence)) / 2.0
+
+    def summarise(key, values, valid):
+        v = np.asarray(values, dtype=np.float64)[valid]
+        low, high = (np.quantile(v, [lo_q, hi_q], method="linear") if v.size else (np.nan, np.nan))
+        res[f"{key}_ci_low"], res[f"{key}_ci_high"] = float(low), float(high)
+        res[f"{key}_se"] = float(np.std(v, ddof=1)) if v.size >= 2 else float("nan")
+        return v
+
+    for name, (values, valid) in series.items():
+        summarise("overall_miou" if name == "overall" else f"miou_{name}", values, valid)
+        empty = int(R - valid.sum())
+        if empty and name not in (kinds or []):
+            res[f"bootstrap_empty_replicates_{name}"] = float(empty)
+    if "clean" in series:
+        clean, clean_ok = series["clean"]
+        degs = {}
+        for name, (values, valid) in series.items():
+            if f"robustness_degradation_{name}" not in point:
+                continue
+            ok = clean_ok & valid
+            deg = np.array([degradation(float(a), float(b)) if o else np.nan for a, b, o in zip(clean, values, ok)], dtype=np.float64)
+            summarise(f"robustness_degradation_{name}", deg, ok)
+            if name in ADVERSE_KINDS:
+                degs[name] = (deg, ok)
+            res[f"miou_drop_{name}"] = float(point["miou_clean"] - point[f"miou_{name}"])
+            drop = summarise(f"miou_drop_{name}", clean - values, ok)
+            res[f"miou_drop_{name}_p_nonpositive"] = float(np.mean(drop <= 0)) if drop.size else float("nan")
+        if degs and "robustness_degradation_ratio" in point:
+            ok = np.logical_and.reduce([o for _, o in degs.values()])
+            summarise("robustness_degradation_ratio", np.mean([d for d, _ in degs.values()], axis=0), ok)
+    return res
+
+
 class EnsembleDisagreementMetrics:
     """PKG/evaluation/metrics.py:324-467 — torch ops on whatever device the logits live on."""
 

@@ -15,6 +15,13 @@ DEFAULT_TARGETS = {"miou_clean": 0.78, "miou_fog": 0.65, "miou_rain": 0.62, "rob
 ADVERSE = ("fog", "rain", "snow", "night")
 
 
+def _ci(results: Dict[str, Any], key: str) -> str:
+    """' [low, high]' of the frame bootstrap's percentile interval of `key`, or '' when the run had none."""
+    if f"{key}_ci_low" not in results:
+        return ""
+    return f" [{results[f'{key}_ci_low']:.3f}, {results[f'{key}_ci_high']:.3f}]"
+
+
 def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, float]] = None) -> str:
     targets = DEFAULT_TARGETS if target_metrics is None else target_metrics
     lines = ["# Adverse Weather Semantic Segmentation Evaluation Report", "", "## Summary Metrics", "",
@@ -23,11 +30,13 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         got = results.get(name, 0.0)
         lines.append(f"| {name} | {want:.3f} | {got:.3f} | {'✓' if got >= want else '✗'} |")    # `>=` for every row, :315
     lines += ["", "## Weather-Specific Performance", ""]
-    lines += [f"- **{c.title()}**: mIoU = {results[f'miou_{c}']:.3f}" for c in ("clean",) + ADVERSE if f"miou_{c}" in results]
+    lines += [f"- **{c.title()}**: mIoU = {results[f'miou_{c}']:.3f}{_ci(results, f'miou_{c}')}" for c in ("clean",) + ADVERSE if f"miou_{c}" in results]
     lines += ["", "## Robustness Analysis", ""]
     if "robustness_degradation_ratio" in results:
-        lines.append(f"- **Overall Degradation Ratio**: {results['robustness_degradation_ratio']:.3f}")
-    lines += [f"- **{c.title()} Degradation**: {results[f'robustness_degradation_{c}']:.3f}" for c in ADVERSE
+        lines.append(f"- **Overall Degradation Ratio**: {results['robustness_degradation_ratio']:.3f}"
+                     f"{_ci(results, 'robustness_degradation_ratio')}")
+    lines += [f"- **{c.title()} Degradation**: {results[f'robustness_degradation_{c}']:.3f}{_ci(results, f'robustness_degradation_{c}')}"
+              for c in ADVERSE
               if f"robustness_degradation_{c}" in results]
     if "expected_calibration_error" in results:
         lines += ["", "## Confidence Calibration", "", f"- **Expected Calibration Error**: {results['expected_calibration_error']:.3f}"]
@@ -41,7 +50,30 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += failure_section(results)
     if any(k.startswith("boundary_iou_") for k in results):
         lines += boundary_section(results)
+    if "bootstrap_replicates" in results:
+        lines += bootstrap_section(results)
     return "\n".join(lines)
+
+
+def bootstrap_section(results: Dict[str, Any]) -> list:
+    """Frame bootstrap (evaluation.bootstrap_replicates): every quantity with an interval, its pooled point estimate, the
+    percentile interval, the standard error and, for the unclamped mIoU drops, the share of replicates with no drop."""
+    names = [k[:-len("_ci_low")] for k in results if k.endswith("_ci_low")]
+    conf = 100.0 * float(results.get("bootstrap_confidence", 0.95))
+    lines = ["", "## Bootstrap Intervals", "",
+             f"{int(results['bootstrap_replicates'])} paired bootstrap replicates over {int(results.get('bootstrap_sources', 0))} source "
+             f"frames (all variants of a source drawn together), seed {int(results.get('bootstrap_seed', 0))}; {conf:g} % percentile "
+             "intervals.  Degradations are clamped at 0 as their point estimates are; the mIoU drops are not.", "",
+             "| Quantity | Point | Low | High | SE | P(drop <= 0) |", "|---|---|---|---|---|---|"]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    for n in names:
+        lines.append(f"| {n} | {cell(n)} | {cell(n + '_ci_low')} | {cell(n + '_ci_high')} | {cell(n + '_se')} | "
+                     f"{cell(n + '_p_nonpositive')} |")
+    empty = [f"- **Replicates without a labelled pixel of {k[len('bootstrap_empty_replicates_'):]}**: {int(results[k])}"
+             for k in results if k.startswith("bootstrap_empty_replicates_")]
+    return lines + ([""] + empty if empty else [])
 
 
 def boundary_section(results: Dict[str, Any]) -> list:
@@ -134,7 +166,8 @@ def severity_section(results: Dict[str, Any]) -> list:
                   "|-------|-----------|------|-------------|-------------|-----------------------|"]
         for j in range(1, levels + 1):
             n = f"{kind}_s{j}"
-            lines.append(f"| {j} | {cell('severity_intensity_' + n)} | {cell('miou_' + n)} | {cell('robustness_degradation_' + n)} | "
+            lines.append(f"| {j} | {cell('severity_intensity_' + n)} | {cell('miou_' + n)}{_ci(results, 'miou_' + n)} | "
+                         f"{cell('robustness_degradation_' + n)}{_ci(results, 'robustness_degradation_' + n)} | "
                          f"{cell('consistency_' + n)} | {cell('corruption_error_rate_' + n)} |")
     return lines
 

@@ -259,6 +259,88 @@ def boundary_stats_to_numpy(stats, num_classes: int) -> dict:
     return {"conf": raw[..., :c2].reshape(raw.shape[:-1] + (c, c)), "inter": raw[..., c2:c2 + c], "pr": raw[..., c2 + c:]}
 
 
+# ----------------------------------------------------------------------------- frame bootstrap (include/awseg.h)
+BOOTSTRAP_STAGED_DRAWS = 4096          # AWSEG_BOOTSTRAP_STAGED_DRAWS
+BOOTSTRAP_CHUNK_BYTES = 64 << 20       # replicate rows asked for per launch: bootstrap_counts splits R so that a chunk stays below this
+
+
+def new_frame_counts(n_rows: int, num_classes: int, device) -> torch.Tensor:
+    """int64 [n_rows, 3 C]: one row C intersection | C label count | C prediction count per frame (zeroed: the launches accumulate).
+    Replaces nothing in the reference, which keeps no per-frame statistics."""
+    if n_rows < 1 or not 1 <= int(num_classes) <= N.MAX_CLASSES:
+        raise ValueError(f"new_frame_counts: n_rows >= 1 and 1 .. {N.MAX_CLASSES} classes, got {n_rows}, {num_classes}")
+    return torch.zeros(int(n_rows), 3 * int(num_classes), dtype=torch.int64, device=device)
+
+
+def frame_iou_counts(pred: torch.Tensor, label: torch.Tensor, num_classes: int, frame_row: torch.Tensor, table: torch.Tensor,
+                     oob: torch.Tensor, ignore_index: int = 255) -> None:
+    """Per-frame IoU counters of the uint8 prediction maps `pred` [B, ...] against `label` [B, ...] (uint8 or int64): frame b adds
+    into row `frame_row[b]` (device int32 [B]; < 0 skips the frame) of `table` (new_frame_counts, viewed as [rows, 3 C]).  Prediction
+    values >= C, labels outside [0, C) other than ignore_index and frames whose row the table lacks go to `oob` (int64 [1])."""
+    if pred.dim() < 2 or pred.dtype != torch.uint8:
+        raise ValueError(f"frame_iou_counts: pred is uint8 [B, ...], got {pred.dtype} {tuple(pred.shape)}")
+    if label.dtype not in (torch.uint8, torch.int64) or label.numel() != pred.numel() or label.shape[0] != pred.shape[0]:
+        raise ValueError(f"frame_iou_counts: label is uint8 or int64 with pred's {tuple(pred.shape)} elements, got {label.dtype} "
+                         f"{tuple(label.shape)}")
+    if pred.numel() < 1:
+        raise ValueError(f"frame_iou_counts: empty maps {tuple(pred.shape)}")
+    if not 1 <= int(num_classes) <= N.MAX_CLASSES:
+        raise ValueError(f"frame_iou_counts: 1 .. {N.MAX_CLASSES} classes, got {num_classes}")
+    b = pred.shape[0]
+    hw = pred[0].numel()
+    if frame_row.dtype != torch.int32 or frame_row.numel() != b:
+        raise ValueError("frame_row must be int32 [B]")
+    if table.dtype != torch.int64 or table.dim() < 2 or table.shape[-1] != 3 * int(num_classes) or table.numel() < 1:
+        raise ValueError(f"table must be int64 [..., {3 * int(num_classes)}] (new_frame_counts), got {table.dtype} {tuple(table.shape)}")
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    pred, label = pred.contiguous(), label.contiguous()
+    ws = N.workspace.get(pred.device, N.lib().awseg_frame_iou_workspace(b, int(num_classes), hw), tag="frame_iou")
+    N.call("awseg_frame_iou_counts", N.ptr(pred), N.ptr(label), N.label_dtype(label), int(ignore_index), b, hw, int(num_classes),
+           N.ptr(frame_row), N.ptr(table), table.numel() // table.shape[-1], N.ptr(oob), N.ptr(ws), N.stream())
+
+
+def bootstrap_counts(table: torch.Tensor, slots: torch.Tensor, n_slots: int, seed: int, replicates: int, oob: torch.Tensor,
+                     r0: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Replicate sums of a paired bootstrap over sources: `table` int64 [n, V, W] (the per-frame rows of n sources x V variants),
+    `slots` int32 [n, V] (0: no such frame, s >= 1: the frame's counter slot) -> int64 [replicates, n_slots, W], row r the sum over
+    the n draws of replicate r0 + r of the drawn sources' frames, into slot 0 and their own slot.  The draw rule is in
+    include/awseg.h; rows depend on (seed, replicate index, table, slots) only, so the launches this splits large requests into give
+    what one would.  Slot values outside [0, n_slots) are skipped and counted into `oob` (int64 [1]) once per launch."""
+    if table.dim() != 3 or table.dtype != torch.int64 or table.numel() < 1:
+        raise ValueError(f"bootstrap_counts: table is int64 [n, V, W], got {table.dtype} {tuple(table.shape)}")
+    n, v, w = (int(d) for d in table.shape)
+    if slots.dtype != torch.int32 or tuple(slots.shape) != (n, v):
+        raise ValueError(f"bootstrap_counts: slots is int32 [{n}, {v}], got {slots.dtype} {tuple(slots.shape)}")
+    for name, val, lo, hi in (("n_slots", n_slots, 1, 2 ** 31 - 1), ("seed", seed, 0, 2 ** 64 - 1), ("replicates", replicates, 1, 2 ** 31 - 1),
+                              ("r0", r0, 0, 2 ** 62)):
+        if isinstance(val, (bool, np.bool_)) or not isinstance(val, (int, np.integer)) or not lo <= int(val) <= hi:
+            raise ValueError(f"bootstrap_counts: {name} is an integer in [{lo}, {hi}], got {val!r}")
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    n_slots, replicates, r0 = int(n_slots), int(replicates), int(r0)
+    if out is None:
+        out = torch.empty(replicates, n_slots, w, dtype=torch.int64, device=table.device)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (replicates, n_slots, w) or not out.is_contiguous():
+        raise ValueError(f"bootstrap_counts: out is contiguous int64 [{replicates}, {n_slots}, {w}]")
+    table, slots = table.contiguous(), slots.contiguous()
+    step = max(1, BOOTSTRAP_CHUNK_BYTES // (n_slots * w * 8))
+    for a in range(0, replicates, step):
+        m = min(step, replicates - a)
+        N.call("awseg_bootstrap_counts", N.ptr(table), N.ptr(slots), n, v, w, n_slots, int(seed), r0 + a, m, N.ptr(out[a:a + m]),
+               N.ptr(oob), N.stream())
+    return out
+
+
+def frame_counts_to_numpy(counts, num_classes: int) -> dict:
+    """int64 [..., 3 C] (a table of per-frame rows or replicate sums) -> {'intersection', 'label', 'prediction'}, each [..., C]."""
+    raw = counts.cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts, dtype=np.int64)
+    c = int(num_classes)
+    if raw.shape[-1] != 3 * c:
+        raise ValueError(f"frame count rows hold 3 x {c} counters, got {raw.shape[-1]}")
+    return {"intersection": raw[..., :c], "label": raw[..., c:2 * c], "prediction": raw[..., 2 * c:]}
+
+
 ECE_CONF_UNIT = 2.0 ** -30     # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

@@ -1114,6 +1114,49 @@ int awseg_boundary_stats(const uint8_t* pred, const void* label, int label_dtype
                          int width, int num_classes, const int32_t* widths, int n_widths, const int32_t* cond, int64_t* stats,
                          int n_slots, int64_t* oob, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Frame bootstrap: per-frame IoU counters and their replicate sums
+ *       replaces nothing: the reference has no per-frame statistics (REF/scripts/evaluate.py:203-218 concatenates every frame
+ *       and divides once), so it cannot put an interval on any of its numbers
+ * ------------------------------------------------------------------------- *
+ * awseg_frame_iou_counts: pred uint8 [B, hw], label uint8 / int64 [B, hw] (label_dtype), ignore_index, C = num_classes <=
+ * AWSEG_MAX_CLASSES.  frame_row device int32[B]: frame b adds into row frame_row[b] of table int64 [n_rows][3 C] (accumulated,
+ * never cleared), a row laid out
+ *     [c]          labelled pixels with label == prediction == c       (intersection)
+ *     [C + c]      labelled pixels with label == c                     (label count)
+ *     [2 C + c]    labelled pixels with prediction == c                (prediction count)
+ * so IoU_c = [c] / ([C + c] + [2 C + c] - [c]).  A labelled pixel is one whose label is neither ignore_index nor outside [0, C)
+ * (the rule of awseg_prediction_consistency; no uint8 wrapping).  A pixel whose prediction value is >= C, labelled or not, adds 1
+ * to oob (int64[1]) and is not counted; a label outside [0, C) that is not ignore_index adds 1 to oob as well (a pixel with both
+ * adds 2).  frame_row[b] < 0: frame b is skipped; frame_row[b] >= n_rows: frame b is not counted and adds hw to oob.  Two frames
+ * of one batch may name the same row: both add to it.  Integer sums only: the table is independent of grid shape, batch split
+ * and rank count and additive over launches.  Any hw < 2^31 (AWSEG_ERANGE beyond; batch <= 65535): 16 pixels per lane from
+ * 16-byte loads when hw % 16 == 0 and pred and label are 16-byte aligned, byte loads otherwise.  workspace:
+ * awseg_frame_iou_workspace(batch, num_classes, hw) bytes.  AWSEG_EINVAL for a NULL pointer, a size < 1 or an unknown label
+ * dtype.
+ *
+ * awseg_bootstrap_counts: table int64 [n][V][W] (n sources, V variants of each, W counters per frame: W = 3 C for the rows
+ * above, but any additive counters do), slots int32 [n][V]: 0 = the source has no such frame, s >= 1 = the frame belongs to
+ * counter slot s.  out int64 [R][n_slots][W] is OVERWRITTEN with R = replicates rows: row r is bootstrap replicate q = r0 + r,
+ * the sum over n draws of the drawn source's present frames, each frame added to slot 0 and to its own slot.  All V variants of
+ * a drawn source are taken together (a paired bootstrap over sources).  Draw j of replicate q is source
+ *     i = mulhi32(u, n) = floor(u * n / 2^32),   u = word (j % 4) of Philox4x32-7(key = seed, counter = q * ceil(n / 4) + j / 4)
+ * with the generator of the weather kernels on a stream constant of its own (0x0B07 in counter word 2, 0x9E3779B9 in word 3).
+ * mulhi32 is not exactly uniform: a source's probability is within n / 2^32 (relative) of 1 / n; there is no rejection step.
+ * Replicate q depends on (seed, q, table, slots) only, so any split of a range of replicates over calls gives the same rows.
+ * The draws of a replicate are staged in on-chip memory AWSEG_BOOTSTRAP_STAGED_DRAWS at a time; larger n is walked in that many
+ * draws per pass, with the same result.  A slots value outside [0, n_slots) is skipped; every call adds the number of such
+ * entries of the slot table to oob (int64[1]).  64-bit sums throughout.  AWSEG_EINVAL for a NULL pointer, n, V, W, n_slots or
+ * replicates < 1, or r0 < 0; AWSEG_ERANGE for n * V, n_slots * W or replicates > INT32_MAX. */
+#define AWSEG_BOOTSTRAP_STAGED_DRAWS 4096
+int64_t awseg_frame_iou_workspace(int64_t batch, int num_classes, int64_t hw);
+int awseg_frame_iou_counts(const uint8_t* pred, const void* label, int label_dtype, int ignore_index, int64_t batch, int64_t hw,
+                           int num_classes, const int32_t* frame_row, int64_t* table, int64_t n_rows, int64_t* oob,
+                           void* workspace, awseg_stream_t stream);
+int awseg_bootstrap_counts(const int64_t* table, const int32_t* slots, int64_t n, int64_t variants, int64_t width,
+                           int64_t n_slots, uint64_t seed, int64_t r0, int64_t replicates, int64_t* out, int64_t* oob,
+                           awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,7 +69,7 @@ def parse_boundary_widths(text: str):
         raise ValueError(f"--boundary-widths takes comma-separated integers such as 1,2,4,8, got {text!r}") from None
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Evaluate adverse-weather segmentation model (MI355X-native path)")
     ap.add_argument("checkpoint", type=str)
     ap.add_argument("--config", type=str, default=None)
@@ -85,7 +85,26 @@ def main():
     ap.add_argument("--boundary-widths", type=str, default=None,
                     help="boundary-band metrics (trimap mIoU, Boundary IoU) per condition: 1-4 comma-separated increasing band widths in "
                          "pixels, each within [1, 16], e.g. 1,2,4,8 (sets evaluation.boundary_widths)")
-    args = ap.parse_args()
+    ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
+                    help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
+                         "mIoU and degradation (sets evaluation.bootstrap_replicates)")
+    ap.add_argument("--bootstrap-confidence", type=float, default=None, metavar="C",
+                    help="confidence level of the intervals, in (0, 1) (sets evaluation.bootstrap_confidence; default 0.95)")
+    ap.add_argument("--bootstrap-seed", type=int, default=None, metavar="S",
+                    help="seed of the resampling draws (sets evaluation.bootstrap_seed; default 0)")
+    return ap
+
+
+def apply_bootstrap_options(args, config) -> None:
+    """--bootstrap / --bootstrap-confidence / --bootstrap-seed into the configuration (the harness checks their ranges)."""
+    for flag, key in (("bootstrap", "evaluation.bootstrap_replicates"), ("bootstrap_confidence", "evaluation.bootstrap_confidence"),
+                      ("bootstrap_seed", "evaluation.bootstrap_seed")):
+        if getattr(args, flag) is not None:
+            config.set(key, getattr(args, flag))
+
+
+def main():
+    args = build_parser().parse_args()
     try:
         config = load_config(args.config) if args.config else create_default_config()
         setup_logging(config)
@@ -101,6 +120,7 @@ def main():
             config.set("evaluation.failure_detection", True)
         if args.boundary_widths is not None:
             config.set("evaluation.boundary_widths", parse_boundary_widths(args.boundary_widths))
+        apply_bootstrap_options(args, config)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",

@@ -19,6 +19,7 @@ from adverse_weather_semantic_segmentation_robustness_benchmark_amd import ops  
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.data import preprocessing as P  # noqa: E402
 
 HBM, MFMA = 8000.0, 157.3
+L2_GATHER = 16800.0     # GB/s, rows gathered from a table resident in every XCD's L2 (MI355X_MICROARCH.md): the replicate sums' yardstick
 # issue-bound rows (the streamed temperature calibration): one multiply + one v_exp_f32 + one add per (pixel, class, temperature)
 # = 4 + 8 + 4 SIMD-cycles per 64 terms (MI355X_MICROARCH.md, vector-instruction issue costs) on 1024 SIMDs at 2.4 GHz, in Tterm/s
 EXP_TERMS = 1024 * 2.4e9 * 64 / 16 / 1e12
@@ -176,6 +177,21 @@ def main():
         lambda: ops.boundary_stats(var_c, ref_c, bw, C, bst, boob, cond), "hbm", 2 * px * B)
     cases["boundary stats w=1,2,4,8, independent random maps"] = (
         lambda: ops.boundary_stats(var_r, ref_r, bw, C, bst, boob, cond), "hbm", 2 * px * B)
+    # frame bootstrap: the per-frame IoU counters on the maps of the two consistency cases (label = the clean map, prediction = the
+    # variant; 2 B/px, the consistency pass without its third map), and the replicate sums of a paired sweep's table (500 sources x
+    # 13 variants x 57 counters = 3 MB, resident in L2; every entry is read once per replicate)
+    ftab, foob = ops.new_frame_counts(B, C, dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    cases["frame iou counts, 95 % agreement in coherent regions"] = (
+        lambda: ops.frame_iou_counts(var_c, ref_c, C, fref, ftab, foob), "hbm", 2 * px * B)
+    cases["frame iou counts, independent random maps"] = (
+        lambda: ops.frame_iou_counts(var_r, ref_r, C, fref, ftab, foob), "hbm", 2 * px * B)
+    bn, bv = 500, 13
+    btab = torch.randint(0, 1 << 20, (bn, bv, 3 * C), device=dev, generator=g)
+    bslots = torch.arange(1, bv + 1, dtype=torch.int32, device=dev).repeat(bn, 1)
+    for R in (1000, 10000):
+        bout = torch.empty(R, 1 + bv, 3 * C, dtype=torch.int64, device=dev)
+        cases[f"bootstrap counts n={bn} V={bv} C={C} R={R}"] = (
+            lambda R=R, bout=bout: ops.bootstrap_counts(btab, bslots, 1 + bv, 7, R, foob, out=bout), "l2_gather", 8.0 * bn * bv * 3 * C * R)
     for K in (100, 16):                      # streamed temperature calibration: K x C exponentials per pixel, issue-bound
         grid = ops.DEFAULT_TEMPERATURE_GRID if K == 100 else np.linspace(0.25, 4.0, K).astype(np.float32)
         tst = ops.new_temperature_grid_stats(K, 15, dev, 6)
@@ -314,6 +330,8 @@ def main():
         med, best = timeit(fn, a.iters)
         if bound == "hbm":
             ach, peak, unit = work / (med * 1e-3) / 1e9, HBM, "GB/s"
+        elif bound == "l2_gather":
+            ach, peak, unit = work / (med * 1e-3) / 1e9, L2_GATHER, "GB/s"
         elif bound == "exp_issue":
             ach, peak, unit = work / (med * 1e-3) / 1e12, EXP_TERMS, "Tterm/s"
         elif bound == "mfma_f16":
