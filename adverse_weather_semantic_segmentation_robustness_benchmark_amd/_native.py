@@ -136,6 +136,9 @@ SIGNATURES = {
     "awseg_frame_iou_workspace": (c_i64, [c_i64, c_i, c_i64]),
     "awseg_frame_iou_counts": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_p]),
     "awseg_bootstrap_counts": (c_i, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_u64, c_i64, c_i64, c_p, c_p, c_p]),
+    "awseg_change_strata": (c_i, [c_p, c_p, c_i, c_i64, c_i, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "awseg_strata_workspace": (c_i64, [c_i64, c_i, c_i64, c_i]),
+    "awseg_stratified_stats": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i64, c_i64, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
 
 

@@ -71,7 +71,7 @@ __device__ __forceinline__ uint32_t awseg_wave_sum_u32(uint32_t v)
 
 // Fold per-block uint32 partials [img][blocks_per_image][row] into int64 stats [n_slots][row]: slot 0 and slot 1 + cond[img]
 // (metrics.hip's fold_partials_kernel rule).  grid = (B, ceil(row / 64)), block = kAwsegFoldSlices * 64: a block owns 64 counters,
-// its 16 waves each sum a sixteenth of the partials, one LDS step combines them.  consistency.hip and boundary.hip launch it.
+// its 16 waves each sum a sixteenth of the partials, one LDS step combines them.  consistency.hip, boundary.hip and strata.hip launch it.
 constexpr int kAwsegFoldSlices = 16;
 static __global__ __launch_bounds__(kAwsegFoldSlices * 64)
 void awseg_fold_u32_partials_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row,

@@ -29,7 +29,7 @@ from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
-                      calibration_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
+                      calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
                       severity_sweep_results)
 
 logger = logging.getLogger(__name__)
@@ -113,6 +113,33 @@ def boundary_option(config):
                          f"[1, {ops.BOUNDARY_MAX_RADIUS}], got {spec!r} ({e})") from None
 
 
+def change_option(config, images=None):
+    """`evaluation.change_strata` (default off): the edges of the change strata, a list of 1 .. 7 strictly increasing finite numbers
+    >= 0 in 8-bit grey levels of the loader's normalisation, or 'default' = [0.5, 4.5, 16.5, 64.5].  The errors of
+    every corrupted frame are then split by how much the corruption changed each input pixel against the clean frame, so the option
+    needs a severity sweep (evaluation.severities).  `images`, when given, is a batch of frames: they must be float32 [B, 3, H, W].
+    -> None when absent, else the list of edges."""
+    spec = _cfg(config, "evaluation.change_strata", None)
+    if spec is None:
+        return None
+    try:
+        edges = [float(v) for v in ops.change_edges(spec)]
+    except (ValueError, TypeError) as e:
+        raise ValueError(f"evaluation.change_strata is 'default' or a list of 1 .. {ops.MAX_STRATA - 1} strictly increasing finite "
+                         f"numbers >= 0, got {spec!r} ({e})") from None
+    if _cfg(config, "evaluation.severities", None) is None:
+        raise ValueError("evaluation.change_strata needs a severity sweep (evaluation.severities): without one a corrupted frame has "
+                         "no clean twin to measure the change against")
+    if images is not None:
+        check_change_frames(images)
+    return edges
+
+
+def check_change_frames(images) -> None:
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"evaluation.change_strata: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+
+
 BOOTSTRAP_MAX_REPLICATES = 65536
 
 
@@ -167,7 +194,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None):
+                 boundary=None, bootstrap=None, change=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -222,6 +249,17 @@ class EvalState:
                               "seen": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
                               "slot": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
                               "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+        # change strata (off unless change = change_option(config)): int64 [slot, stratum, C*C + 6] over the sweep's slots.  'rows':
+        # the clean frames as the model saw them, one float32 row of 3 hw per live source at the row indices of the clean prediction
+        # maps (self.paired['rows']): allocated, reused and freed with them; 'scratch': the uint8 stratum map of a variant batch
+        self.change = None
+        if change is not None:
+            if sweep is None:
+                raise ValueError("change strata need a severity sweep")
+            edges = ops.change_edges(change)
+            self.change = {"edges": [float(v) for v in edges],
+                           "stats": ops.new_strata_stats(metrics.num_classes, len(edges) + 1, device, 1 + len(conditions)),
+                           "oob": torch.zeros(1, dtype=torch.int64, device=device), "rows": None, "scratch": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -323,6 +361,38 @@ class EvalState:
             raise IndexError("slot outside the counter slots in the frame bootstrap's slot table")
         return rep.cpu().numpy(), int(keep.numel())
 
+    def update_change(self, images, pred, labels, sources, severity, cond, num_classes: int) -> None:
+        """A clean batch (after paired_pred_out gave its sources their rows) leaves its frames in those rows; a variant batch is
+        split into change strata against its sources' clean frames and counted against their clean maps.  Runs before
+        update_consistency releases the rows."""
+        ch, pd = self.change, self.paired
+        rows = [pd["live"][s][0] for s in sources]
+        n_rows, width = pd["rows"].shape[0], images[0].numel()
+        if ch["rows"] is None or ch["rows"].shape[0] < n_rows:
+            new = torch.empty(n_rows, width, dtype=torch.float32, device=images.device)
+            if ch["rows"] is not None:
+                new[:ch["rows"].shape[0]].copy_(ch["rows"])
+            ch["rows"] = new
+        if ch["rows"].shape[1] != width:
+            raise ValueError("every frame of a severity sweep must have the same size")
+        if severity == 0:
+            idx = torch.tensor(rows, dtype=torch.int64).to(images.device, non_blocking=True)
+            ch["rows"].index_copy_(0, idx, images.reshape(len(rows), width))
+            return
+        if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not ch.get("warned"):
+            ch["warned"] = True
+            logger.warning("change strata: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
+                           "wrapped index, the stratified counters never wrap: miou_*_chg<k> describes the unwrapped confusion matrix "
+                           "and the strata need not recombine to the pooled mIoU (DESIGN.md 10h)", num_classes)
+        frame_ref = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
+        numel = pred.numel()
+        if ch["scratch"] is None or ch["scratch"].numel() < numel:
+            ch["scratch"] = torch.empty(numel, dtype=torch.uint8, device=images.device)
+        strata = ch["scratch"][:numel].view(pred.shape)
+        ops.change_strata(images, ch["rows"], frame_ref, ch["edges"], out=strata, oob=ch["oob"])
+        ops.stratified_stats(pred, labels, strata, len(ch["edges"]) + 1, num_classes, ch["stats"], ch["oob"], ref_maps=pd["rows"],
+                             frame_ref=frame_ref, cond=cond)
+
     def update_consistency(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
         """Count a variant batch's maps against its sources' clean maps (slot 0 + its condition slot); free the rows of sources whose
         sweep is complete."""
@@ -411,6 +481,8 @@ class EvalState:
             ts.append(self.failure["stats"])
         if getattr(self, "boundary", None) is not None:                  # (getattr: all_reduce also serves states built without it)
             ts += [self.boundary["stats"], self.boundary["oob"]]
+        if getattr(self, "change", None) is not None:
+            ts += [self.change["stats"], self.change["oob"]]
         bs = getattr(self, "bootstrap", None)
         if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
             ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
@@ -469,6 +541,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         if unknown:
             raise ValueError(f"batch conditions {unknown} are not slots of the severity sweep")
         pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
+    if getattr(st, "change", None) is not None:
+        check_change_frames(images)
     bd = getattr(st, "boundary", None)
     if bd is not None and pred_out is None:
         pred_out = st.boundary_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
@@ -544,6 +618,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     if bs is not None:
         ids = [st.acc.conditions.index(str(c)) if str(c) in st.acc.conditions else -1 for c in conds]      # cond_ids' rule
         st.update_bootstrap(pred_out, labels, sources, ids, metrics.num_classes)
+    if getattr(st, "change", None) is not None:
+        st.update_change(images, pred_out, labels, sources, severity, cond, metrics.num_classes)
     if st.sweep is not None:                                          # (pred_out alone no longer says so: the boundary counters ask for one too)
         st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
@@ -572,7 +648,7 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
                    depth=depth_options(config), failure=failure_option(config),
-                   boundary=boundary_option(config), bootstrap=bootstrap)
+                   boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -646,6 +722,13 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                    kinds=st.sweep.kinds if st.sweep is not None else None,
                                                    levels=st.sweep.levels if st.sweep is not None else 0,
                                                    degradation=metrics.compute_robustness_degradation_ratio))
+    ch = getattr(st, "change", None)
+    if ch is not None:
+        if int(ch["oob"].item()):
+            raise IndexError("prediction map value outside [0, num_classes), or a clean-frame row outside the buffer, in the "
+                             "change-strata counters")
+        results.update(change_metrics_from_stats(ch["stats"].cpu().numpy(), ch["edges"], st.acc.conditions, st.sweep.kinds,
+                                                 st.sweep.levels, metrics.num_classes))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -514,7 +514,65 @@ def boundary_metrics_from_stats(stats, widths, conditions: List[str], num_classe
     return res
 
 
-ADVERSE_KINDS = ("fog", "rain", "snow", "night")                     # the kinds finalize() reports a degradation for
+def change_metrics_from_stats(stats, edges, slots: List[str], kinds, levels: int, num_classes: int) -> Dict[str, float]:
+    """Result keys of the change-strata counters (int64 [1 + len(slots), K + 1, C*C + 6], include/awseg.h; slot 0 = every corrupted
+    frame, slot 1 + k = slots[k]; K = len(edges) + 1 strata, row K the unmeasured pixels).  Host only; every value a float.  Stratum
+    k holds the pixels whose input change lies in [edges[k - 1], edges[k]) (stratum 0: below edges[0], stratum K - 1: from the last
+    edge up).  Pooling as severity_sweep_results: per '<kind>_s<j>', per '<kind>' from the summed counters of its levels, and over
+    slot 0 under the prefix 'mean_'.  With <n> the name and k = 0 .. K - 1 (the mean_ keys carry no name: mean_miou_chg0):
+      change_fraction_<n>_chg<k>           pixels[k] / all pixels, the unmeasured row included
+      miou_<n>_chg<k>                      iou_from_counts on conf[k]; absent without a labelled pixel
+      accuracy_<n>_chg<k>                  trace / total of conf[k]; absent without a labelled pixel
+      consistency_<n>_chg<k>               agree[k] / pixels[k]; absent without a pixel
+      corruption_error_rate_<n>_chg<k>     cw / (cc + cw): of the labelled pixels the clean prediction gets right, those the
+                                           corrupted one gets wrong; absent when the clean prediction gets none right
+      corruption_error_share_<n>_chg<k>    cw[k] / sum of cw over every row (the unmeasured one included): the share of the newly
+                                           introduced errors that sit in stratum k; absent when there is no such error
+    and change_edge_<k> (k = 0 .. K - 2) plus change_unmeasured_pixels (slot 0, when non-zero).  A name without a pixel yields no
+    keys.  Known limit: these counters never wrap uint8 labels, the pooled confusion counters do at C = 19 (as the reference does),
+    so there miou_*_chg<k> describes the unwrapped confusion matrix and the strata need not recombine to the pooled miou_<n>."""
+    e = ops.change_edges(list(edges))
+    K, C = int(e.size) + 1, int(num_classes)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.ndim != 3 or raw.shape != (1 + len(slots), K + 1, C * C + 6):
+        raise ValueError(f"change-strata stats must be int64 [{1 + len(slots)}, {K + 1}, {C * C + 6}], got {raw.shape}")
+    named = []
+    for kind in kinds:
+        idx = [1 + slots.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        named += [(f"_{kind}_s{j}", raw[i]) for j, i in zip(range(1, levels + 1), idx)]
+        named.append((f"_{kind}", raw[idx].sum(0)))
+    named.append((None, raw[0]))
+    res: Dict[str, float] = {f"change_edge_{k}": float(e[k]) for k in range(K - 1)}
+    for name, slot in named:
+        dec = ops.strata_stats_to_numpy(slot, C)
+        total = int(dec["pixels"].sum())
+        if total <= 0:
+            continue
+        new_errors = int(dec["transitions"][:, 1].sum())
+
+        def key(metric, k, name=name):
+            return f"mean_{metric}_chg{k}" if name is None else f"{metric}{name}_chg{k}"
+        for k in range(K):
+            px, conf, t = int(dec["pixels"][k]), dec["conf"][k], dec["transitions"][k]
+            res[key("change_fraction", k)] = float(px / total)
+            labelled = int(conf.sum())
+            if labelled > 0:
+                res[key("miou", k)] = float(iou_from_counts(torch.from_numpy(conf.reshape(-1).copy()), C)["mean_iou"])
+                res[key("accuracy", k)] = float(int(np.trace(conf)) / labelled)
+            if px > 0:
+                res[key("consistency", k)] = float(int(dec["agree"][k]) / px)
+            clean_right = int(t[0]) + int(t[1])
+            if clean_right > 0:
+                res[key("corruption_error_rate", k)] = float(int(t[1]) / clean_right)
+            if new_errors > 0:
+                res[key("corruption_error_share", k)] = float(int(t[1]) / new_errors)
+    unmeasured = int(raw[0, K, C * C + 5])
+    if unmeasured:
+        res["change_unmeasured_pixels"] = float(unmeasured)
+    return res
+
+
+ADVERSE_KINDS = ("fog", "rain", "snow", "night")                    # the kinds finalize() reports a degradation for
 
 
 def replicate_miou(counts, num_classes: int):

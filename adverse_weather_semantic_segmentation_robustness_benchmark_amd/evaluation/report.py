@@ -50,9 +50,39 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += failure_section(results)
     if any(k.startswith("boundary_iou_") for k in results):
         lines += boundary_section(results)
+    if any(k.startswith("change_fraction_") for k in results):
+        lines += change_section(results)
     if "bootstrap_replicates" in results:
         lines += bootstrap_section(results)
     return "\n".join(lines)
+
+
+def change_section(results: Dict[str, Any]) -> list:
+    """Change strata (evaluation.change_strata): one line per kind and stratum of the input change against the clean frame."""
+    edges = []
+    while f"change_edge_{len(edges)}" in results:
+        edges.append(results[f"change_edge_{len(edges)}"])
+    K = len(edges) + 1
+    bounds = [f"< {edges[0]:g}"] + [f"[{a:g}, {b:g})" for a, b in zip(edges, edges[1:])] + [f">= {edges[-1]:g}"]
+    names = list(dict.fromkeys(m.group(1) for k in results for m in [re.match(r"change_fraction_(.+)_chg\d+$", k)]
+                               if m and not re.search(r"_s\d+$", m.group(1))))
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    lines = ["", "## Change Strata", "", "Pixels split by how much the corruption changed the input against the clean frame (largest "
+             "channel difference, 8-bit grey levels).  Error share: the part of the errors the corruption introduced (clean right, "
+             "corrupted wrong) that falls into the stratum.", "",
+             "| Kind | Change | Pixel share | mIoU | Accuracy | Consistency | Corruption error rate | Error share |", "|---" * 8 + "|"]
+    for n in names + [None]:
+        for k in range(K):
+            key = (lambda m, n=n, k=k: f"mean_{m}_chg{k}" if n is None else f"{m}_{n}_chg{k}")
+            if key("change_fraction") not in results:
+                continue
+            lines.append(f"| {n or 'all'} | {bounds[k]} | {cell(key('change_fraction'))} | {cell(key('miou'))} | {cell(key('accuracy'))} | "
+                         f"{cell(key('consistency'))} | {cell(key('corruption_error_rate'))} | {cell(key('corruption_error_share'))} |")
+    if "change_unmeasured_pixels" in results:
+        lines += ["", f"- **Pixels without a measured change**: {int(results['change_unmeasured_pixels'])}"]
+    return lines
 
 
 def bootstrap_section(results: Dict[str, Any]) -> list:

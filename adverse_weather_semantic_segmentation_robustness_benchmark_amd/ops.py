@@ -341,7 +341,131 @@ def frame_counts_to_numpy(counts, num_classes: int) -> dict:
     return {"intersection": raw[..., :c], "label": raw[..., c:2 * c], "prediction": raw[..., 2 * c:]}
 
 
-ECE_CONF_UNIT = 2.0 ** -30     # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
+# ----------------------------------------------------------------------------- change strata (include/awseg.h)
+MAX_STRATA = 8                         # AWSEG_MAX_STRATA
+STRATUM_NONE = 255                     # AWSEG_STRATUM_NONE: no measured change (NaN difference, no clean twin)
+STRATA_SMALL = ("both_correct", "clean_correct_variant_wrong", "clean_wrong_variant_correct", "both_wrong", "agree", "pixels")
+DEFAULT_CHANGE_EDGES = (0.5, 4.5, 16.5, 64.5)     # 8-bit grey levels; half integers: see change_edges
+
+
+def change_edges(spec) -> np.ndarray:
+    """The stratum edges as a host float32 array, checked before any launch (the C ABI refuses the same lists with AWSEG_EINVAL):
+    1 .. MAX_STRATA - 1 finite numbers >= 0, strictly increasing (also after rounding to float32), or 'default' =
+    DEFAULT_CHANGE_EDGES.  With the default scale the change of a frame rendered from 8-bit data lies within 3.1e-5 of an integer
+    number of grey levels, so half-integer edges never sit on a rounding seam."""
+    if isinstance(spec, str):
+        if spec != "default":
+            raise ValueError(f"stratum edges are a list of numbers or 'default', got {spec!r}")
+        spec = DEFAULT_CHANGE_EDGES
+    if isinstance(spec, (bool, np.bool_, bytes, dict, int, float, np.number)):
+        raise ValueError(f"stratum edges are a list of numbers, got {spec!r}")
+    e = list(spec)
+    if any(isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)) for v in e):
+        raise ValueError(f"stratum edges are numbers, got {spec!r}")
+    if not 1 <= len(e) <= MAX_STRATA - 1:
+        raise ValueError(f"1 .. {MAX_STRATA - 1} stratum edges, got {len(e)}")
+    with np.errstate(over="ignore"):
+        out = np.ascontiguousarray(e, dtype=np.float32)
+    if not np.isfinite(out).all() or (out < 0).any() or (np.diff(out) <= 0).any():
+        raise ValueError(f"stratum edges must be finite, >= 0 and strictly increasing, got {e}")
+    return out
+
+
+def change_strata(image: torch.Tensor, ref_images: torch.Tensor, frame_ref: torch.Tensor, edges, out: Optional[torch.Tensor] = None,
+                  scale=None, oob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [B, ...] stratum map of the float32 frames `image` [B, Ch, ...] against rows `frame_ref` (device int32 [B]; < 0: no
+    twin, the frame's map is STRATUM_NONE) of the clean frames `ref_images` [R, Ch, ...]: per pixel the number of `edges` at or
+    below max_c |image - ref| * scale[c].  `scale` defaults to 255 * IMAGENET_STD (Ch = 3): the change in 8-bit grey levels of a
+    frame the loader normalised.  A row index outside `ref_images` adds the frame's pixels to `oob` (int64 [1])."""
+    e = change_edges(edges)
+    if image.dim() < 3 or image.dtype != torch.float32 or ref_images.dtype != torch.float32 or ref_images.dim() < 1:
+        raise ValueError(f"change_strata: image is float32 [B, Ch, ...], got {image.dtype} {tuple(image.shape)}")
+    b, ch = image.shape[0], image.shape[1]
+    hw = int(np.prod(image.shape[2:]))
+    if not 1 <= ch <= 4 or hw < 1:
+        raise ValueError(f"change_strata: 1 .. 4 channels and at least one pixel, got {tuple(image.shape)}")
+    r = ref_images.shape[0]
+    if r < 1 or ref_images[0].numel() != ch * hw:
+        raise ValueError(f"change_strata: ref_images holds rows of {ch} x {hw} float32, got {tuple(ref_images.shape)}")
+    if frame_ref.dtype != torch.int32 or frame_ref.numel() != b:
+        raise ValueError("frame_ref must be int32 [B]")
+    if scale is None:
+        if ch != 3:
+            raise ValueError("change_strata: the default scale (255 * IMAGENET_STD) is for three channels")
+        scale = 255.0 * IMAGENET_STD
+    sc = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+    if sc.size != ch or not np.isfinite(sc).all() or (sc <= 0).any():
+        raise ValueError(f"change_strata: scale holds {ch} finite numbers > 0, got {scale!r}")
+    if out is None:
+        out = torch.empty((b,) + tuple(image.shape[2:]), dtype=torch.uint8, device=image.device)
+    if out.dtype != torch.uint8 or out.numel() != b * hw:
+        raise ValueError(f"out must be uint8 with {b} x {hw} elements")
+    if oob is None:
+        oob = torch.zeros(1, dtype=torch.int64, device=image.device)
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    image, ref_images = image.contiguous(), ref_images.contiguous()
+    N.call("awseg_change_strata", N.ptr(image), N.ptr(ref_images), r, b, ch, hw, N.ptr(frame_ref), N.host(sc), N.host(e), int(e.size) + 1,
+           N.ptr(out), N.ptr(oob), N.stream())
+    return out
+
+
+def new_strata_stats(num_classes: int, n_strata: int, device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, n_strata + 1, C*C + 6]: per slot and stratum (row n_strata: unmeasured pixels) the row C*C conf | 4 paired
+    cells | agree | pixels of include/awseg.h (zeroed: the launches accumulate)."""
+    return torch.zeros(n_slots, n_strata + 1, num_classes * num_classes + 6, dtype=torch.int64, device=device)
+
+
+def stratified_stats(pred: torch.Tensor, label: torch.Tensor, stratum: torch.Tensor, n_strata: int, num_classes: int,
+                     stats: torch.Tensor, oob: torch.Tensor, ref_maps: Optional[torch.Tensor] = None,
+                     frame_ref: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, ignore_index: int = 255) -> None:
+    """Count the uint8 prediction maps `pred` [B, ...] against `label` (uint8 or int64) and, when given, rows `frame_ref` (device
+    int32 [B], < 0 skips a frame) of the clean maps `ref_maps` [R, ...], split by the uint8 map `stratum` [B, ...] (values >=
+    n_strata: the unmeasured row), into `stats` (new_strata_stats; slot 0 + slot 1 + cond[b]); map values >= C go to `oob`."""
+    k, c = int(n_strata), int(num_classes)
+    if not 1 <= k <= MAX_STRATA:
+        raise ValueError(f"stratified_stats: 1 .. {MAX_STRATA} strata, got {n_strata}")
+    if not 1 <= c <= N.MAX_CLASSES:
+        raise ValueError(f"stratified_stats: 1 .. {N.MAX_CLASSES} classes, got {num_classes}")
+    if pred.dtype != torch.uint8 or stratum.dtype != torch.uint8 or pred.dim() < 1 or pred.numel() < 1:
+        raise ValueError("stratified_stats: pred and stratum are non-empty uint8 maps [B, ...]")
+    b = pred.shape[0]
+    hw = pred[0].numel()
+    if stratum.numel() != b * hw or label.numel() != b * hw or label.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"stratified_stats: stratum uint8 and label uint8 / int64 with {b} x {hw} elements")
+    if (ref_maps is None) != (frame_ref is None):
+        raise ValueError("stratified_stats: ref_maps and frame_ref come together")
+    r = 0
+    if ref_maps is not None:
+        r = ref_maps.shape[0]
+        if ref_maps.dtype != torch.uint8 or r < 1 or ref_maps[0].numel() != hw or frame_ref.dtype != torch.int32 or frame_ref.numel() != b:
+            raise ValueError("stratified_stats: ref_maps uint8 [R, HW], frame_ref int32 [B]")
+        ref_maps = ref_maps.contiguous()
+    if stats.dim() != 3 or stats.dtype != torch.int64 or tuple(stats.shape[1:]) != (k + 1, c * c + 6):
+        raise ValueError(f"stats must be int64 [slots, {k + 1}, {c * c + 6}] (new_strata_stats), got {stats.dtype} {tuple(stats.shape)}")
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    pred, label, stratum = pred.contiguous(), label.contiguous(), stratum.contiguous()
+    ws = N.workspace.get(pred.device, N.lib().awseg_strata_workspace(b, c, hw, k), tag="strata")
+    N.call("awseg_stratified_stats", N.ptr(pred), N.ptr(label), N.label_dtype(label), int(ignore_index), N.ptr(stratum), k,
+           N.ptr(ref_maps), r, N.ptr(frame_ref), b, hw, c, N.ptr(cond), N.ptr(stats), stats.shape[0], N.ptr(oob), N.ptr(ws), N.stream())
+
+
+def strata_stats_to_numpy(stats, num_classes: int) -> dict:
+    """int64 [..., strata + 1, C*C + 6] -> {'conf' [..., strata + 1, C, C] (rows: label, columns: prediction), 'transitions'
+    [..., strata + 1, 4] (both correct, clean correct + variant wrong, clean wrong + variant correct, both wrong), 'agree' and
+    'pixels' [..., strata + 1]}; the last stratum row holds the unmeasured pixels."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    c, c2 = num_classes, num_classes * num_classes
+    if raw.shape[-1] != c2 + 6:
+        raise ValueError(f"strata stats rows hold {c}^2 + 6 counters, got {raw.shape[-1]}")
+    return {"conf": raw[..., :c2].reshape(raw.shape[:-1] + (c, c)), "transitions": raw[..., c2:c2 + 4], "agree": raw[..., c2 + 4],
+            "pixels": raw[..., c2 + 5]}
+
+
+ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 
 def ece_bins_to_numpy(bins: torch.Tensor) -> np.ndarray:

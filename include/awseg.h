@@ -1157,6 +1157,62 @@ int awseg_bootstrap_counts(const int64_t* table, const int32_t* slots, int64_t n
                            int64_t n_slots, uint64_t seed, int64_t r0, int64_t replicates, int64_t* out, int64_t* oob,
                            awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Change strata: errors attributed to the pixels the corruption changed (paired severity sweep)
+ *       replaces nothing: the reference evaluates each rendered frame on its own (REF/scripts/evaluate.py:166-200) and never
+ *       compares it with its clean frame
+ * ------------------------------------------------------------------------- *
+ * awseg_change_strata: image float32 [B, Ch, hw]: B corrupted frames as the model sees them; ref_images float32 [n_refs, Ch, hw]:
+ * clean frames; frame_ref device int32[B]: the row of ref_images frame b is compared with, with the meaning it has in
+ * awseg_prediction_consistency.  Ch = channels <= 4.  scale: HOST float32[Ch], finite and > 0; edges: HOST float32[K - 1], finite,
+ * >= 0, strictly increasing, K = n_strata, 2 <= K <= AWSEG_MAX_STRATA (both travel in the kernel arguments).  Per pixel p of
+ * frame b with r = frame_ref[b], in float32:
+ *     change  = max over c of fabsf(image[b,c,p] - ref_images[r,c,p]) * scale[c]     (one subtraction, one product, compares:
+ *               nothing an FMA could contract, so numpy float32 gives the same bits)
+ *     out[b,p] = the number of edges with change >= edge                              (a change equal to an edge: the upper stratum)
+ * A pixel of which any channel's difference is NaN gets AWSEG_STRATUM_NONE (tested explicitly: a maximum would drop the NaN); an
+ * infinite difference lands in stratum K - 1.  frame_ref[b] < 0: row b of out is filled with AWSEG_STRATUM_NONE;
+ * frame_ref[b] >= n_refs: the same, and hw is added to oob (int64[1]).  out uint8 [B, hw] is overwritten.  Four pixels per lane
+ * from 16-byte loads and one 4-byte store when hw % 4 == 0, image and ref_images are 16-byte aligned and out is 4-byte aligned;
+ * scalar loads and stores otherwise.  No workspace.  AWSEG_EINVAL for a NULL pointer, a size < 1 (batch < 0), Ch > 4, a bad scale
+ * or bad edges; AWSEG_ERANGE for batch > 65535 or hw >= 2^31; batch == 0 returns 0.
+ *
+ * awseg_stratified_stats: the scan of awseg_prediction_consistency with one more byte per pixel.  pred uint8 [B, hw], label
+ * uint8 / int64 [B, hw] (label_dtype), ignore_index, stratum uint8 [B, hw] (any map: awseg_change_strata's, or another
+ * stratifier's), K = n_strata in [1, AWSEG_MAX_STRATA], C = num_classes <= AWSEG_MAX_CLASSES.  ref_maps uint8 [n_refs, hw] with
+ * frame_ref device int32[B] as in awseg_prediction_consistency (< 0: frame b is skipped entirely; >= n_refs: frame b is not
+ * counted and adds hw to oob); both may be NULL together (one alone is AWSEG_EINVAL): every frame is counted, the paired cells and
+ * `agree` stay 0.  stats int64 [n_slots][K + 1][AWSEG_STRATA_ROW(C)] (accumulated, never cleared), slot rule of every other
+ * counter: each frame into slot 0 and into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0
+ * only).  A pixel goes to row stratum[b,p], a value >= K (AWSEG_STRATUM_NONE included) to row K, the unmeasured row, so the rows
+ * always sum to the totals.  Row of one (slot, stratum):
+ *     [t * C + p]   conf: t = label, p = prediction, over the labelled pixels
+ *     [C * C + 0]   labelled pixels where both maps equal the label           \
+ *     [C * C + 1]   reference correct, variant wrong                           |  the paired cells of
+ *     [C * C + 2]   reference wrong, variant correct                           |  awseg_prediction_consistency, in its order
+ *     [C * C + 3]   both wrong                                                /
+ *     [C * C + 4]   agree: pred == ref, over EVERY pixel
+ *     [C * C + 5]   pixels: every pixel
+ * A labelled pixel is one whose label is neither ignore_index nor outside [0, C) (no uint8 wrapping).  A pixel whose prediction
+ * value is >= C adds 1 to oob (int64[1]) and nothing else; with ref_maps the same holds when its reference value is >= C.  Summed
+ * over the rows, the paired cells equal awseg_prediction_consistency's on the same tensors, agree the trace of its matrix and
+ * pixels its total.  Integer sums only: independent of grid shape, batch split and rank count, additive over launches.  Any
+ * hw < 2^31 (AWSEG_ERANGE beyond; batch <= 65535): 16 pixels per lane from 16-byte loads when hw % 16 == 0 and pred, stratum,
+ * label and ref_maps are 16-byte aligned, byte loads otherwise.  workspace: awseg_strata_workspace(batch, num_classes, hw,
+ * n_strata) bytes.  AWSEG_EINVAL for a NULL pointer (cond and the ref_maps / frame_ref pair excepted), a size < 1, n_strata
+ * outside [1, AWSEG_MAX_STRATA] or an unknown label dtype. */
+#define AWSEG_MAX_STRATA    8
+#define AWSEG_STRATUM_NONE  255
+#define AWSEG_STRATA_ROW(C) ((C) * (C) + 6)
+int awseg_change_strata(const float* image, const float* ref_images, int n_refs, int64_t batch, int channels, int64_t hw,
+                        const int32_t* frame_ref, const float* scale, const float* edges, int n_strata, uint8_t* out,
+                        int64_t* oob, awseg_stream_t stream);
+int64_t awseg_strata_workspace(int64_t batch, int num_classes, int64_t hw, int n_strata);
+int awseg_stratified_stats(const uint8_t* pred, const void* label, int label_dtype, int ignore_index, const uint8_t* stratum,
+                           int n_strata, const uint8_t* ref_maps, int n_refs, const int32_t* frame_ref, int64_t batch, int64_t hw,
+                           int num_classes, const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob, void* workspace,
+                           awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,16 @@ def parse_boundary_widths(text: str):
         raise ValueError(f"--boundary-widths takes comma-separated integers such as 1,2,4,8, got {text!r}") from None
 
 
+def parse_change_strata(text: str):
+    """--change-strata: 'default' or comma-separated numbers (the harness checks their range and order)."""
+    if text.strip() == "default":
+        return "default"
+    try:
+        return [float(x) for x in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--change-strata takes 'default' or comma-separated numbers such as 0.5,4.5,16.5, got {text!r}") from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Evaluate adverse-weather segmentation model (MI355X-native path)")
     ap.add_argument("checkpoint", type=str)
@@ -85,6 +95,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--boundary-widths", type=str, default=None,
                     help="boundary-band metrics (trimap mIoU, Boundary IoU) per condition: 1-4 comma-separated increasing band widths in "
                          "pixels, each within [1, 16], e.g. 1,2,4,8 (sets evaluation.boundary_widths)")
+    ap.add_argument("--change-strata", type=str, default=None, metavar="EDGES",
+                    help="split every corrupted frame's errors by how much the corruption changed each input pixel against the clean "
+                         "frame: 'default' (0.5,4.5,16.5,64.5) or 1-7 comma-separated increasing edges in 8-bit grey levels; needs "
+                         "--severities (sets evaluation.change_strata)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -120,6 +134,8 @@ def main():
             config.set("evaluation.failure_detection", True)
         if args.boundary_widths is not None:
             config.set("evaluation.boundary_widths", parse_boundary_widths(args.boundary_widths))
+        if args.change_strata is not None:
+            config.set("evaluation.change_strata", parse_change_strata(args.change_strata))
         apply_bootstrap_options(args, config)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}

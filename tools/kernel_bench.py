@@ -169,6 +169,26 @@ def main():
         lambda: ops.prediction_consistency(var_c, ref_c, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
     cases["prediction consistency, independent random maps"] = (
         lambda: ops.prediction_consistency(var_r, ref_r, fref, labels, C, cst, coob, cond), "hbm", 3 * px * B)
+    # change strata (evaluation.change_strata): the stratum map of a corrupted float32 frame against its clean twin, 25 B/px (two
+    # three-channel float32 frames in, one byte out): a veil of up to 8 grey levels over the upper half and 16 x 16 flakes elsewhere
+    chg_clean = ops.normalize(imgs)
+    flakes = (torch.rand(B, H // 16, W // 16, 1, device=dev, generator=g) < 0.1).repeat_interleave(16, 1).repeat_interleave(16, 2)
+    chg_u8 = imgs.to(torch.int16) + (torch.randint(0, 120, (B, H, W, 3), device=dev, generator=g) * flakes).to(torch.int16)
+    chg_u8[:, :H // 2] += torch.randint(0, 9, (B, H // 2, W, 3), device=dev, generator=g).to(torch.int16)
+    chg_var = ops.normalize(chg_u8.clamp_(0, 255).to(torch.uint8))
+    del flakes, chg_u8
+    smap_c, soob = torch.empty(B, H, W, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    cases["change strata, default edges (5 strata)"] = (
+        lambda: ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob), "hbm", 25 * px * B)
+    # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
+    # Coherent: the stratum map of the case above; random: an independent stratum per pixel
+    ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
+    smap_r = torch.randint(0, 5, (B, H, W), device=dev, generator=g).to(torch.uint8)
+    sst = ops.new_strata_stats(C, 5, dev, 6)
+    cases["stratified stats K=5, 95 % agreement in coherent regions, coherent strata"] = (
+        lambda: ops.stratified_stats(var_c, labels, smap_c, 5, C, sst, soob, ref_maps=ref_c, frame_ref=fref, cond=cond), "hbm", 4 * px * B)
+    cases["stratified stats K=5, independent random maps and strata"] = (
+        lambda: ops.stratified_stats(var_r, labels, smap_r, 5, C, sst, soob, ref_maps=ref_r, frame_ref=fref, cond=cond), "hbm", 4 * px * B)
     # boundary-band counters, widths 1, 2, 4, 8, on the maps of the two consistency cases above (label = the clean map, prediction =
     # the variant): 2 B/px from HBM, so the row's "of peak" says how far from HBM-bound the stencil is, not how well it streams
     bw = [1, 2, 4, 8]
