@@ -139,6 +139,8 @@ SIGNATURES = {
     "awseg_change_strata": (c_i, [c_p, c_p, c_i, c_i64, c_i, c_i64, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "awseg_strata_workspace": (c_i64, [c_i64, c_i, c_i64, c_i]),
     "awseg_stratified_stats": (c_i, [c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_i64, c_i64, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "awseg_image_quality_workspace": (c_i64, [c_i64, c_i, c_i64, c_i64]),
+    "awseg_image_quality": (c_i, [c_p, c_p, c_i, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
 
 

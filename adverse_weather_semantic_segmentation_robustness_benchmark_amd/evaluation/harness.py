@@ -30,7 +30,7 @@ from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
                       calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
-                      severity_sweep_results)
+                      quality_metrics_from_stats, severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -140,6 +140,51 @@ def check_change_frames(images) -> None:
         raise ValueError(f"evaluation.change_strata: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
 
 
+IQ_DEFAULT_TARGETS = (0.9, 0.75, 0.5)
+IQ_MAX_TARGETS = 8
+
+
+def quality_options(config, images=None):
+    """`evaluation.image_quality` (bool, default off): PSNR and SSIM (with its luminance and contrast-structure factors) of every
+    corrupted frame against its clean frame, and the mIoU of every kind at equal SSIM; needs a severity sweep
+    (evaluation.severities).  `evaluation.image_quality_targets`: the SSIM values the mIoU is interpolated at, a list of 1 .. 8
+    numbers in (0, 1), default [0.9, 0.75, 0.5]; checked also when the option is off.  `images`, when given, is a batch of frames:
+    they must be float32 [B, 3, H, W].  -> None when off, else {'targets': [...]}."""
+    on = _cfg(config, "evaluation.image_quality", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"evaluation.image_quality is true or false, got {on!r}")
+    spec = _cfg(config, "evaluation.image_quality_targets", list(IQ_DEFAULT_TARGETS))
+    bad = isinstance(spec, (bool, str, bytes, dict, int, float, np.number, np.bool_))
+    try:
+        targets = [] if bad else list(spec)
+    except TypeError:
+        bad, targets = True, []
+    if bad or not 1 <= len(targets) <= IQ_MAX_TARGETS or any(
+            isinstance(t, (bool, np.bool_, str, bytes)) or not isinstance(t, (int, float, np.integer, np.floating))
+            or not 0.0 < float(t) < 1.0 for t in targets):
+        raise ValueError(f"evaluation.image_quality_targets is a list of 1 .. {IQ_MAX_TARGETS} numbers in (0, 1), got {spec!r}")
+    if not on:
+        return None
+    if _cfg(config, "evaluation.severities", None) is None:
+        raise ValueError("evaluation.image_quality needs a severity sweep (evaluation.severities): without one a corrupted frame has "
+                         "no clean twin to measure the image quality against")
+    if images is not None:
+        check_quality_frames(images)
+    return {"targets": [float(t) for t in targets]}
+
+
+def check_quality_frames(images) -> None:
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"evaluation.image_quality: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+
+
+def check_quality_budget(terms: int) -> None:
+    """The image-quality counters are int64 sums of per-term values up to 2^26 (include/awseg.h): raise before they could wrap."""
+    if terms > ops.IQ_TERM_BUDGET:
+        raise OverflowError(f"image-quality counters hold {ops.IQ_TERM_BUDGET} pixel-channels (summed over ranks); {terms} would "
+                            "exceed that")
+
+
 BOOTSTRAP_MAX_REPLICATES = 65536
 
 
@@ -194,7 +239,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None, change=None):
+                 boundary=None, bootstrap=None, change=None, quality=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -249,9 +294,12 @@ class EvalState:
                               "seen": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
                               "slot": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
                               "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+        # the clean frames as the model saw them (kept when the change strata or the image-quality counters are on): one float32 row
+        # of 3 hw per live source at the row indices of the clean prediction maps (self.paired['rows']): allocated, reused and freed
+        # with them, filled once per clean batch (keep_clean_frames)
+        self.clean_frames = None
         # change strata (off unless change = change_option(config)): int64 [slot, stratum, C*C + 6] over the sweep's slots.  'rows':
-        # the clean frames as the model saw them, one float32 row of 3 hw per live source at the row indices of the clean prediction
-        # maps (self.paired['rows']): allocated, reused and freed with them; 'scratch': the uint8 stratum map of a variant batch
+        # the buffer of self.clean_frames; 'scratch': the uint8 stratum map of a variant batch
         self.change = None
         if change is not None:
             if sweep is None:
@@ -260,6 +308,17 @@ class EvalState:
             self.change = {"edges": [float(v) for v in edges],
                            "stats": ops.new_strata_stats(metrics.num_classes, len(edges) + 1, device, 1 + len(conditions)),
                            "oob": torch.zeros(1, dtype=torch.int64, device=device), "rows": None, "scratch": None}
+            self.clean_frames = {"rows": None}
+        # image-quality counters (off unless quality = quality_options(config)): int64 [slot, AWSEG_IQ_ROW] over the sweep's slots;
+        # 'terms': the pixel-channels counted so far, against the fixed-point budget of the sums
+        self.quality = None
+        if quality is not None:
+            if sweep is None:
+                raise ValueError("image-quality counters need a severity sweep")
+            self.quality = {"targets": [float(t) for t in quality["targets"]], "terms": 0,
+                            "stats": ops.new_image_quality_stats(device, 1 + len(conditions)),
+                            "oob": torch.zeros(1, dtype=torch.int64, device=device)}
+            self.clean_frames = {"rows": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -361,23 +420,42 @@ class EvalState:
             raise IndexError("slot outside the counter slots in the frame bootstrap's slot table")
         return rep.cpu().numpy(), int(keep.numel())
 
-    def update_change(self, images, pred, labels, sources, severity, cond, num_classes: int) -> None:
-        """A clean batch (after paired_pred_out gave its sources their rows) leaves its frames in those rows; a variant batch is
-        split into change strata against its sources' clean frames and counted against their clean maps.  Runs before
-        update_consistency releases the rows."""
-        ch, pd = self.change, self.paired
+    def keep_clean_frames(self, images, sources, severity) -> list:
+        """The rows of this batch's sources in the clean-frame buffer, grown to the clean-map buffer's rows; a clean batch (after
+        paired_pred_out gave its sources their rows) leaves its frames there.  Once per batch, for the change strata and the
+        image-quality counters alike; runs before update_consistency releases the rows."""
+        cf, pd = self.clean_frames, self.paired
         rows = [pd["live"][s][0] for s in sources]
         n_rows, width = pd["rows"].shape[0], images[0].numel()
-        if ch["rows"] is None or ch["rows"].shape[0] < n_rows:
+        if cf["rows"] is None or cf["rows"].shape[0] < n_rows:
             new = torch.empty(n_rows, width, dtype=torch.float32, device=images.device)
-            if ch["rows"] is not None:
-                new[:ch["rows"].shape[0]].copy_(ch["rows"])
-            ch["rows"] = new
-        if ch["rows"].shape[1] != width:
+            if cf["rows"] is not None:
+                new[:cf["rows"].shape[0]].copy_(cf["rows"])
+            cf["rows"] = new
+            if self.change is not None:
+                self.change["rows"] = new
+        if cf["rows"].shape[1] != width:
             raise ValueError("every frame of a severity sweep must have the same size")
         if severity == 0:
             idx = torch.tensor(rows, dtype=torch.int64).to(images.device, non_blocking=True)
-            ch["rows"].index_copy_(0, idx, images.reshape(len(rows), width))
+            cf["rows"].index_copy_(0, idx, images.reshape(len(rows), width))
+        return rows
+
+    def update_quality(self, images, rows, cond) -> None:
+        """A variant batch's image-quality counters against its sources' clean frames (rows: keep_clean_frames').  Raises before the
+        fixed-point budget of the sums would be exceeded."""
+        q = self.quality
+        check_quality_budget(q["terms"] + images.numel())
+        q["terms"] += images.numel()
+        frame_ref = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
+        twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
+        ops.image_quality(images, twins, frame_ref, q["stats"], cond=cond, oob=q["oob"])
+
+    def update_change(self, images, pred, labels, rows, severity, cond, num_classes: int) -> None:
+        """A variant batch is split into change strata against its sources' clean frames (rows: keep_clean_frames') and counted
+        against their clean maps.  Runs before update_consistency releases the rows."""
+        ch, pd = self.change, self.paired
+        if severity == 0:
             return
         if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not ch.get("warned"):
             ch["warned"] = True
@@ -483,6 +561,10 @@ class EvalState:
             ts += [self.boundary["stats"], self.boundary["oob"]]
         if getattr(self, "change", None) is not None:
             ts += [self.change["stats"], self.change["oob"]]
+        quality_terms = None
+        if getattr(self, "quality", None) is not None:
+            quality_terms = torch.tensor([self.quality["terms"]], dtype=torch.int64, device=self.quality["stats"].device)
+            ts += [self.quality["stats"], self.quality["oob"], quality_terms]
         bs = getattr(self, "bootstrap", None)
         if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
             ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
@@ -498,6 +580,8 @@ class EvalState:
             check_calibration_budget(int(pixels.item()))
         if depth_pixels is not None:
             check_depth_budget(int(depth_pixels.item()))
+        if quality_terms is not None:
+            check_quality_budget(int(quality_terms.item()))
 
     def auroc_value(self) -> float:
         neg, pos = self.auroc[0].double(), self.auroc[1].double()
@@ -543,6 +627,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
     if getattr(st, "change", None) is not None:
         check_change_frames(images)
+    if getattr(st, "quality", None) is not None:
+        check_quality_frames(images)
     bd = getattr(st, "boundary", None)
     if bd is not None and pred_out is None:
         pred_out = st.boundary_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
@@ -618,8 +704,12 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     if bs is not None:
         ids = [st.acc.conditions.index(str(c)) if str(c) in st.acc.conditions else -1 for c in conds]      # cond_ids' rule
         st.update_bootstrap(pred_out, labels, sources, ids, metrics.num_classes)
-    if getattr(st, "change", None) is not None:
-        st.update_change(images, pred_out, labels, sources, severity, cond, metrics.num_classes)
+    if getattr(st, "clean_frames", None) is not None:
+        rows = st.keep_clean_frames(images, sources, severity)
+        if getattr(st, "quality", None) is not None and severity != 0:
+            st.update_quality(images, rows, cond)
+        if getattr(st, "change", None) is not None:
+            st.update_change(images, pred_out, labels, rows, severity, cond, metrics.num_classes)
     if st.sweep is not None:                                          # (pred_out alone no longer says so: the boundary counters ask for one too)
         st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
     st.samples += images.size(0)
@@ -648,7 +738,8 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    temperature_grid=temperature_grid(_cfg(config, "evaluation.temperature_grid", None)),
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
                    depth=depth_options(config), failure=failure_option(config),
-                   boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config))
+                   boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config),
+                   quality=quality_options(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -729,6 +820,13 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                              "change-strata counters")
         results.update(change_metrics_from_stats(ch["stats"].cpu().numpy(), ch["edges"], st.acc.conditions, st.sweep.kinds,
                                                  st.sweep.levels, metrics.num_classes))
+    q = getattr(st, "quality", None)
+    if q is not None:
+        # after the sweep results: the matched-damage keys read miou_clean and miou_<kind>_s<j>
+        if int(q["oob"].item()):
+            raise IndexError("a clean-frame row outside the buffer in the image-quality counters")
+        results.update(quality_metrics_from_stats(q["stats"].cpu().numpy(), st.acc.conditions, st.sweep.kinds, st.sweep.levels, results,
+                                                  q["targets"], metrics.compute_robustness_degradation_ratio))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

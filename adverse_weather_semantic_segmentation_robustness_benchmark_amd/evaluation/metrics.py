@@ -572,6 +572,90 @@ def change_metrics_from_stats(stats, edges, slots: List[str], kinds, levels: int
     return res
 
 
+IQ_SLOPE_MIN_DAMAGE = 1e-6                                          # miou_drop_per_ssim needs 1 - ssim at least this
+
+
+def quality_metrics_from_stats(stats, slots: List[str], kinds, levels: int, results: Dict[str, Any], targets=(0.9, 0.75, 0.5),
+                               degradation=None) -> Dict[str, float]:
+    """Result keys of the image-quality counters (int64 [1 + len(slots), AWSEG_IQ_ROW], include/awseg.h; slot 0 = every corrupted
+    frame, slot 1 + k = slots[k]; the clean slot stays empty: a clean frame has no twin) and, with the sweep's mIoU keys in
+    `results` (miou_clean, miou_<kind>_s<j>), the mIoU at equal SSIM.  Host only, float64 on exact integer sums; every value a float.
+    Pooling as severity_sweep_results: per '<kind>_s<j>', per '<kind>' from the summed counters of its levels, and over slot 0 under
+    the prefix 'mean_' (mean_psnr, mean_ssim).  With <n> the name:
+      mse_<n>                  sum of squared differences / error terms, on the [0, 1] scale; present when terms were measured
+      psnr_<n>                 10 log10(1 / mse) in dB; absent when mse == 0
+      mean_abs_change_<n>      mean absolute difference in 8-bit grey levels (x 255)
+      ssim_<n>, ssim_luminance_<n>, ssim_contrast_<n>   means over the measured windows of s, l and cs; present when windows were
+                               measured.  The accuracy of these numbers is that of the float32 window arithmetic
+    and quality_unmeasured_terms, quality_unmeasured_windows (slot 0, when non-zero).
+    Matched damage, per kind: the points (1, miou_clean), (ssim_<kind>_s<j>, miou_<kind>_s<j>) for j = 1 .. levels must all be
+    there and SSIM must strictly decrease with j, else the kind gets none of the following and ssim_not_monotonic_<kind> = 1.0.
+    For every target t in `targets` within [ssim_<kind>_s<levels>, 1] (no extrapolation), TT = round(100 t):
+      miou_at_ssim<TT>_<kind>                        piecewise linear in SSIM between the points
+      robustness_degradation_at_ssim<TT>_<kind>      degradation(miou_clean, that)
+      mean_miou_at_ssim<TT>                          mean over the kinds, only when every kind has the value
+    and per level miou_drop_per_ssim_<kind>_s<j> = (miou_clean - miou_<kind>_s<j>) / (1 - ssim_<kind>_s<j>), absent when the
+    denominator is below 1e-6.  degradation: RobustnessMetrics.compute_robustness_degradation_ratio unless given."""
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.ndim != 2 or raw.shape != (1 + len(slots), ops.IQ_ROW):
+        raise ValueError(f"image-quality stats must be int64 [{1 + len(slots)}, {ops.IQ_ROW}], got {raw.shape}")
+    degradation = degradation or RobustnessMetrics().compute_robustness_degradation_ratio
+    kinds, levels = list(kinds), int(levels)
+    named = []
+    for kind in kinds:
+        idx = [1 + slots.index(f"{kind}_s{j}") for j in range(1, levels + 1)]
+        named += [(f"{kind}_s{j}", raw[i]) for j, i in zip(range(1, levels + 1), idx)]
+        named.append((kind, raw[idx].sum(0)))
+    named.append((None, raw[0]))
+    res: Dict[str, float] = {}
+    for name, row in named:
+        dec = {f: int(v) for f, v in ops.image_quality_to_numpy(row).items()}
+
+        def key(metric, name=name):
+            return f"mean_{metric}" if name is None else f"{metric}_{name}"
+        if dec["error_terms"] > 0:
+            mse = dec["sum_sq"] * ops.IQ_UNIT / dec["error_terms"]
+            res[key("mse")] = float(mse)
+            if mse > 0:
+                res[key("psnr")] = float(10.0 * np.log10(1.0 / mse))
+            res[key("mean_abs_change")] = float(255.0 * dec["sum_abs"] * ops.IQ_UNIT / dec["error_terms"])
+        if dec["windows"] > 0:
+            res[key("ssim")] = float(dec["sum_ssim"] * ops.IQ_UNIT / dec["windows"])
+            res[key("ssim_luminance")] = float(dec["sum_luminance"] * ops.IQ_UNIT / dec["windows"])
+            res[key("ssim_contrast")] = float(dec["sum_contrast"] * ops.IQ_UNIT / dec["windows"])
+    for k, field in (("quality_unmeasured_terms", "error_terms_unmeasured"), ("quality_unmeasured_windows", "windows_unmeasured")):
+        v = int(ops.image_quality_to_numpy(raw[0])[field])
+        if v:
+            res[k] = float(v)
+    clean = results.get("miou_clean")
+    at = {}                                                                 # TT -> {kind: interpolated mIoU}
+    for kind in kinds:
+        pts = [(1.0, clean)] + [(res.get(f"ssim_{kind}_s{j}"), results.get(f"miou_{kind}_s{j}")) for j in range(1, levels + 1)]
+        if clean is not None:
+            for j in range(1, levels + 1):
+                q, m = pts[j]
+                if q is not None and m is not None and 1.0 - q >= IQ_SLOPE_MIN_DAMAGE:
+                    res[f"miou_drop_per_ssim_{kind}_s{j}"] = float((float(clean) - float(m)) / (1.0 - q))
+        if any(q is None or m is None for q, m in pts) or any(not pts[j + 1][0] < pts[j][0] for j in range(levels)):
+            res[f"ssim_not_monotonic_{kind}"] = 1.0
+            continue
+        qs = np.array([q for q, _ in pts][::-1], dtype=np.float64)          # ascending for np.interp
+        ms = np.array([float(m) for _, m in pts][::-1], dtype=np.float64)
+        for t in targets:
+            t = float(t)
+            if not qs[0] <= t <= 1.0:
+                continue
+            tt = int(round(100.0 * t))
+            v = float(np.interp(t, qs, ms))
+            res[f"miou_at_ssim{tt}_{kind}"] = v
+            res[f"robustness_degradation_at_ssim{tt}_{kind}"] = float(degradation(float(clean), v))
+            at.setdefault(tt, {})[kind] = v
+    for tt, per in at.items():
+        if kinds and all(k in per for k in kinds):
+            res[f"mean_miou_at_ssim{tt}"] = float(np.mean([per[k] for k in kinds]))
+    return res
+
+
 ADVERSE_KINDS = ("fog", "rain", "snow", "night")                    # the kinds finalize() reports a degradation for
 
 

@@ -52,9 +52,44 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += boundary_section(results)
     if any(k.startswith("change_fraction_") for k in results):
         lines += change_section(results)
+    if any(re.match(r"mse_.+_s\d+$", k) for k in results):
+        lines += quality_section(results)
     if "bootstrap_replicates" in results:
         lines += bootstrap_section(results)
     return "\n".join(lines)
+
+
+def quality_section(results: Dict[str, Any]) -> list:
+    """Image quality (evaluation.image_quality): one line per kind and level with what the rendering did to the image (PSNR, SSIM
+    and its luminance and contrast-structure factors) next to the mIoU, then the mIoU of every kind at equal SSIM."""
+    names = list(dict.fromkeys(m.group(1) for k in results for m in [re.match(r"mse_(.+_s\d+)$", k)] if m))
+    kinds = list(dict.fromkeys(n.rsplit("_s", 1)[0] for n in names))
+
+    def cell(key, fmt=".3f"):
+        return format(results[key], fmt) if key in results else "-"
+    lines = ["", "## Image Quality", "", "Every corrupted frame against its clean frame, on the [0, 1] scale: PSNR in dB, SSIM over "
+             "whole 11 x 11 Gaussian windows and its two factors (luminance; contrast and structure).", "",
+             "| Kind | Level | PSNR | SSIM | Luminance | Contrast | mIoU | mIoU drop per SSIM |", "|---" * 8 + "|"]
+    for n in names:
+        kind, level = n.rsplit("_s", 1)
+        lines.append(f"| {kind} | {level} | {cell('psnr_' + n, '.2f')} | {cell('ssim_' + n)} | {cell('ssim_luminance_' + n)} | "
+                     f"{cell('ssim_contrast_' + n)} | {cell('miou_' + n)} | {cell('miou_drop_per_ssim_' + n)} |")
+    if "mean_ssim" in results:
+        lines.append(f"| all | - | {cell('mean_psnr', '.2f')} | {cell('mean_ssim')} | {cell('mean_ssim_luminance')} | "
+                     f"{cell('mean_ssim_contrast')} | - | - |")
+    targets = sorted({int(m.group(1)) for k in results for m in [re.match(r"(?:mean_)?miou_at_ssim(\d+)(?:_|$)", k)] if m}, reverse=True)
+    if targets:
+        lines += ["", "mIoU at equal SSIM (piecewise linear between the levels, never extrapolated) / degradation against clean:", "",
+                  "| Kind | " + " | ".join(f"SSIM {t / 100:g}" for t in targets) + " |", "|---" * (len(targets) + 1) + "|"]
+        for kind in kinds:
+            lines.append(f"| {kind} | " + " | ".join(
+                f"{cell(f'miou_at_ssim{t}_{kind}')} / {cell(f'robustness_degradation_at_ssim{t}_{kind}')}" for t in targets) + " |")
+        lines.append("| mean | " + " | ".join(cell(f"mean_miou_at_ssim{t}") for t in targets) + " |")
+    extra = [f"- **SSIM does not decrease with the level for {k[len('ssim_not_monotonic_'):]}**: no mIoU at equal SSIM"
+             for k in results if k.startswith("ssim_not_monotonic_")]
+    extra += [f"- **{title}**: {int(results[key])}" for key, title in (("quality_unmeasured_terms", "Error terms not measured"),
+                                                                      ("quality_unmeasured_windows", "Windows not measured")) if key in results]
+    return lines + ([""] + extra if extra else [])
 
 
 def change_section(results: Dict[str, Any]) -> list:

@@ -465,6 +465,97 @@ def strata_stats_to_numpy(stats, num_classes: int) -> dict:
             "pixels": raw[..., c2 + 5]}
 
 
+# ----------------------------------------------------------------------------- image quality (include/awseg.h)
+IQ_FIELDS = ("frames", "error_terms", "sum_abs", "sum_sq", "error_terms_unmeasured", "windows", "sum_luminance", "sum_contrast",
+             "sum_ssim", "windows_unmeasured")
+IQ_ROW = len(IQ_FIELDS)                # AWSEG_IQ_ROW
+IQ_UNIT = 2.0 ** -24                   # the sums are int64 in fixed point: exact, order-independent
+IQ_TERM_BUDGET = 1 << 36               # AWSEG_IQ_TERM_BUDGET: pixel-channels one stats tensor holds, summed over ranks (x 2^26 < 2^63)
+IQ_TILE_H, IQ_TILE_W = 32, 64          # AWSEG_IQ_TILE_H, AWSEG_IQ_TILE_W: window centres per block
+IQ_TAPS = 11
+
+
+def ssim_taps() -> np.ndarray:
+    """The 11 float32 weights of the SSIM window of Wang et al. 2004: a Gaussian of sigma 1.5 over 11 pixels, normalised."""
+    return np.ascontiguousarray(gaussian_taps(1.5, 3.5), dtype=np.float32)
+
+
+def new_image_quality_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, IQ_ROW]: per slot the row IQ_FIELDS of include/awseg.h (zeroed: the launches accumulate)."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_image_quality_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), IQ_ROW, dtype=torch.int64, device=device)
+
+
+def _iq_positive(name: str, v) -> float:
+    if isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating)):
+        raise ValueError(f"image_quality: {name} is a finite number > 0, got {v!r}")
+    with np.errstate(over="ignore"):
+        f = float(np.float32(v))
+    if not (np.isfinite(f) and f > 0):
+        raise ValueError(f"image_quality: {name} is a finite number > 0 (also as float32), got {v!r}")
+    return f
+
+
+def image_quality(image: torch.Tensor, ref_images: torch.Tensor, frame_ref: torch.Tensor, stats: torch.Tensor,
+                  cond: Optional[torch.Tensor] = None, oob: Optional[torch.Tensor] = None, mean=None, std=None,
+                  c1: float = 1e-4, c2: float = 9e-4, taps=None) -> None:
+    """Image-quality counters of the float32 frames `image` [B, Ch, H, W] against rows `frame_ref` (device int32 [B]; < 0: no twin,
+    the frame is skipped) of the clean frames `ref_images` [R, Ch, H, W], into `stats` (new_image_quality_stats; slot 0 + slot
+    1 + cond[b]): the error terms of MSE / PSNR at every pixel and the luminance, contrast-structure and SSIM terms of every whole
+    11 x 11 window, as include/awseg.h defines them.  `mean`, `std`: the loader's normalisation (default: ImageNet's, Ch = 3), so
+    that image * std + mean lies in [0, 1]; c1, c2: the SSIM constants for that range ((0.01)^2, (0.03)^2); `taps`: the window
+    (default ssim_taps()).  A row index outside `ref_images` adds the frame's pixels to `oob` (int64 [1])."""
+    if image.dim() != 4 or image.dtype != torch.float32:
+        raise ValueError(f"image_quality: image is float32 [B, Ch, H, W], got {image.dtype} {tuple(image.shape)}")
+    b, ch, h, w = (int(d) for d in image.shape)
+    if not 1 <= ch <= 4 or h < 1 or w < 1:
+        raise ValueError(f"image_quality: 1 .. 4 channels and at least one pixel, got {tuple(image.shape)}")
+    if ref_images.dim() != 4 or ref_images.dtype != torch.float32 or ref_images.shape[0] < 1:
+        raise ValueError(f"image_quality: ref_images is float32 [R, Ch, H, W] with R >= 1, got {ref_images.dtype} {tuple(ref_images.shape)}")
+    if tuple(ref_images.shape[1:]) != (ch, h, w):
+        raise ValueError(f"image_quality: frames {(ch, h, w)} and twins {tuple(ref_images.shape[1:])} differ in size")
+    if b > 65535 or h * w >= 2 ** 31:
+        raise ValueError(f"image_quality: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
+    r = int(ref_images.shape[0])
+    if frame_ref.dtype != torch.int32 or frame_ref.numel() != b:
+        raise ValueError("frame_ref must be int32 [B]")
+    if mean is None and std is None and ch != 3:
+        raise ValueError("image_quality: the default normalisation (ImageNet mean and std) is for three channels")
+    if (mean is None) != (std is None):
+        raise ValueError("image_quality: mean and std come together")
+    m, s = _mean_std(mean, std)
+    m, s = m.reshape(-1), s.reshape(-1)
+    if m.size != ch or s.size != ch or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
+        raise ValueError(f"image_quality: mean holds {ch} finite numbers and std {ch} finite numbers > 0, got {mean!r}, {std!r}")
+    t = np.ascontiguousarray(ssim_taps() if taps is None else taps, dtype=np.float32).reshape(-1)
+    if t.size != IQ_TAPS or not np.isfinite(t).all():
+        raise ValueError(f"image_quality: taps holds {IQ_TAPS} finite numbers, got {taps!r}")
+    c1, c2 = _iq_positive("c1", c1), _iq_positive("c2", c2)
+    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != IQ_ROW:
+        raise ValueError(f"stats must be int64 [slots, {IQ_ROW}] (new_image_quality_stats), got {stats.dtype} {tuple(stats.shape)}")
+    if oob is None:
+        oob = torch.zeros(1, dtype=torch.int64, device=image.device)
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    if b == 0:
+        return
+    image, ref_images = image.contiguous(), ref_images.contiguous()
+    ws = N.workspace.get(image.device, N.lib().awseg_image_quality_workspace(b, ch, h, w), tag="image_quality")
+    N.call("awseg_image_quality", N.ptr(image), N.ptr(ref_images), r, b, ch, h, w, N.ptr(frame_ref), N.host(m), N.host(s), N.host(t),
+           c1, c2, N.ptr(cond), N.ptr(stats), stats.shape[0], N.ptr(oob), N.ptr(ws), N.stream())
+
+
+def image_quality_to_numpy(stats) -> dict:
+    """int64 [..., IQ_ROW] -> {field: int64 [...]} for IQ_FIELDS; the four sums stay in units of IQ_UNIT (exact integers)."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != IQ_ROW:
+        raise ValueError(f"image quality rows hold {IQ_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(IQ_FIELDS)}
+
+
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

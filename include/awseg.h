@@ -1213,6 +1213,51 @@ int awseg_stratified_stats(const uint8_t* pred, const void* label, int label_dty
                            int num_classes, const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob, void* workspace,
                            awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Image quality of a corrupted frame against its clean twin: PSNR error terms and the SSIM factors (paired severity sweep,
+ *  DESIGN.md 10i)
+ *       replaces nothing: the reference reports mIoU per rendered intensity and never measures what the rendering did to the image
+ * ------------------------------------------------------------------------- *
+ * awseg_image_quality: image float32 [B, Ch, H, W]: B corrupted frames as the model sees them; ref_images float32
+ * [n_refs, Ch, H, W]: clean frames; frame_ref device int32[B] with the meaning it has in awseg_change_strata (< 0: frame b is
+ * skipped; >= n_refs: frame b is skipped and H * W is added to oob, int64[1]).  Ch = channels <= 4.  mean, std: HOST float32[Ch],
+ * the loader's normalisation, x = image * std + mean in [0, 1]; taps: HOST float32[11]; c1, c2 > 0 (all travel in the kernel
+ * arguments).  Every step below is one float32 operation with the parenthesisation given (the library is built without FMA
+ * contraction and float32 division is correctly rounded), so numpy float32 gives the same bits.  Per channel c of frame b with
+ * r = frame_ref[b]:
+ *   error terms, at every pixel p:
+ *     d = (image[b,c,p] - ref_images[r,c,p]) * std[c];  measured iff fabsf(d) <= 2.0f (NaN fails);
+ *     abs_q = (int64) rintf(fabsf(d) * 2^24),  sq_q = (int64) rintf((d * d) * 2^24)
+ *   window terms, at every window whose 11 x 11 pixels lie inside the frame ((H - 10) * (W - 10) of them; none when H < 11 or
+ *   W < 11):
+ *     x = image * std[c] + mean[c], y likewise from the twin; the five maps x, y, x*x, y*y, x*y are filtered separably, along
+ *     the row first and then down the column of the row sums, each pass as acc = taps[0] * v0; acc = acc + taps[k] * vk for
+ *     k = 1 .. 10 (left to right, top to bottom), giving mx, my, mxx, myy, mxy;
+ *     vx = mxx - mx*mx;  vy = myy - my*my;  cxy = mxy - mx*my;
+ *     l  = ((2*mx)*my + c1) / ((mx*mx + my*my) + c1);   cs = (2*cxy + c2) / ((vx + vy) + c2);   s = l * cs;
+ *     measured iff fabsf(l), fabsf(cs) and fabsf(s) are all <= 2.0f;  l_q, cs_q, s_q = (int64) rintf(v * 2^24)
+ * stats int64 [n_slots][AWSEG_IQ_ROW] (accumulated, never cleared), slot rule of every other counter: each counted frame into slot
+ * 0 and into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0 only).  Row:
+ *     [0] frames   [1] error terms measured   [2] sum abs_q   [3] sum sq_q   [4] error terms unmeasured
+ *     [5] windows measured   [6] sum l_q   [7] sum cs_q   [8] sum s_q   [9] windows unmeasured
+ * Integer sums only: independent of grid shape, batch split and rank count, additive over launches.  A term is at most 2^26 units
+ * (2.0 * 2^24, squared: 4.0 * 2^24), so one stats tensor holds AWSEG_IQ_TERM_BUDGET = 2^36 pixel-channels (B * Ch * H * W summed
+ * over launches and ranks) before an int64 sum could wrap (2^36 * 2^26 = 2^62); the caller keeps count.  A block owns
+ * AWSEG_IQ_TILE_H x AWSEG_IQ_TILE_W windows and stages them with a 10-pixel apron in LDS; 16-byte loads when W % 4 == 0 and image
+ * and ref_images are 16-byte aligned, scalar loads otherwise.  workspace: awseg_image_quality_workspace(batch, channels, height,
+ * width) bytes.  AWSEG_EINVAL for a NULL pointer (cond excepted), a size < 1 (batch < 0), Ch > 4, a std that is not finite and > 0,
+ * a non-finite mean or tap, c1 or c2 not finite and > 0; AWSEG_ERANGE for batch > 65535 or H * W >= 2^31; batch == 0 returns 0. */
+#define AWSEG_IQ_ROW          10
+#define AWSEG_IQ_TILE_H       32
+#define AWSEG_IQ_TILE_W       64
+#define AWSEG_IQ_TERM_BUDGET  (1LL << 36)
+int64_t awseg_image_quality_workspace(int64_t batch, int channels, int64_t height, int64_t width);
+int awseg_image_quality(const float* image, const float* ref_images, int n_refs, int64_t batch, int channels,
+                        int64_t height, int64_t width, const int32_t* frame_ref,
+                        const float* mean, const float* std, const float* taps, float c1, float c2,
+                        const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob,
+                        void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

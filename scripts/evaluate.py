@@ -79,6 +79,14 @@ def parse_change_strata(text: str):
         raise ValueError(f"--change-strata takes 'default' or comma-separated numbers such as 0.5,4.5,16.5, got {text!r}") from None
 
 
+def parse_image_quality_targets(text: str):
+    """--image-quality-targets: comma-separated SSIM values (the harness checks their number and range)."""
+    try:
+        return [float(x) for x in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--image-quality-targets takes comma-separated numbers such as 0.9,0.75,0.5, got {text!r}") from None
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="Evaluate adverse-weather segmentation model (MI355X-native path)")
     ap.add_argument("checkpoint", type=str)
@@ -99,6 +107,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="split every corrupted frame's errors by how much the corruption changed each input pixel against the clean "
                          "frame: 'default' (0.5,4.5,16.5,64.5) or 1-7 comma-separated increasing edges in 8-bit grey levels; needs "
                          "--severities (sets evaluation.change_strata)")
+    ap.add_argument("--image-quality", action="store_true",
+                    help="PSNR and SSIM (with its luminance and contrast factors) of every corrupted frame against its clean frame, "
+                         "and the mIoU of every kind at equal SSIM; needs --severities (sets evaluation.image_quality)")
+    ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
+                    help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
+                         "(sets evaluation.image_quality_targets)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -136,6 +150,10 @@ def main():
             config.set("evaluation.boundary_widths", parse_boundary_widths(args.boundary_widths))
         if args.change_strata is not None:
             config.set("evaluation.change_strata", parse_change_strata(args.change_strata))
+        if args.image_quality:
+            config.set("evaluation.image_quality", True)
+        if args.image_quality_targets is not None:
+            config.set("evaluation.image_quality_targets", parse_image_quality_targets(args.image_quality_targets))
         apply_bootstrap_options(args, config)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}

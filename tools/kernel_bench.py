@@ -180,6 +180,16 @@ def main():
     smap_c, soob = torch.empty(B, H, W, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
     cases["change strata, default edges (5 strata)"] = (
         lambda: ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob), "hbm", 25 * px * B)
+    # image quality (evaluation.image_quality): PSNR error terms and SSIM window terms of a corrupted float32 frame against its clean
+    # twin, 24 B/px from HBM plus the tiles' aprons (the change-strata pass's inputs); ~220 float32 operations per pixel-channel, so
+    # the row's "of peak" says how far from HBM-bound the stencil is.  Rendered-like: the frames of the change-strata case; random:
+    # independent values (no measured branch differs: the arithmetic is the same)
+    iqst, iqoob = ops.new_image_quality_stats(dev, 6), torch.zeros(1, dtype=torch.int64, device=dev)
+    iq_rand = (torch.rand(2, B, 3, H, W, device=dev, generator=g) - 0.45) / 0.225
+    cases["image quality, rendered-like frames"] = (
+        lambda: ops.image_quality(chg_var, chg_clean, fref, iqst, cond=cond, oob=iqoob), "hbm", 24 * px * B)
+    cases["image quality, independent random frames"] = (
+        lambda: ops.image_quality(iq_rand[0], iq_rand[1], fref, iqst, cond=cond, oob=iqoob), "hbm", 24 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
