@@ -32,6 +32,9 @@ inline int awseg_cu_count()
     return n_cu;
 }
 
+// p is aligned to `bytes` (a power of two): the test every vector-load path makes of its bases
+static inline bool awseg_aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
+
 // Memory-bound grids: cap at 8 resident 256-thread blocks per CU and grid-stride the rest
 // (cdna_hip_programming.md Guideline 11).
 static inline int awseg_grid_1d(int64_t work_items, int per_block, int max_blocks = AWSEG_CUS * 8)
@@ -67,39 +70,6 @@ __device__ __forceinline__ uint32_t awseg_wave_sum_u32(uint32_t v)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
-}
-
-// Fold per-block uint32 partials [img][blocks_per_image][row] into int64 stats [n_slots][row]: slot 0 and slot 1 + cond[img]
-// (metrics.hip's fold_partials_kernel rule).  grid = (B, ceil(row / 64)), block = kAwsegFoldSlices * 64: a block owns 64 counters,
-// its 16 waves each sum a sixteenth of the partials, one LDS step combines them.  consistency.hip, boundary.hip and strata.hip launch it.
-constexpr int kAwsegFoldSlices = 16;
-static __global__ __launch_bounds__(kAwsegFoldSlices * 64)
-void awseg_fold_u32_partials_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row,
-                                    const int32_t* __restrict__ cond, int n_slots, int64_t* __restrict__ stats)
-{
-    __shared__ unsigned long long s_sum[kAwsegFoldSlices][64];
-    const int img = blockIdx.x;
-    const int kl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int k = blockIdx.y * 64 + kl;
-    const uint32_t* src = partial + (int64_t)img * blocks_per_image * row;
-    unsigned long long s = 0;
-    if (k < row) {
-#pragma unroll 8
-        for (int b = slice; b < blocks_per_image; b += kAwsegFoldSlices) s += src[(int64_t)b * row + k];
-    }
-    s_sum[slice][kl] = s;
-    __syncthreads();
-    if (slice == 0 && k < row) {
-        s = 0;
-#pragma unroll
-        for (int j = 0; j < kAwsegFoldSlices; ++j) s += s_sum[j][kl];
-        if (s) {
-            int slot = -1;
-            if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-            atomicAdd((unsigned long long*)&stats[k], s);
-            if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * row + k], s);
-        }
-    }
 }
 
 // label load for the two dtypes the reference produces (uint8 from the loader, int64 in its tests)

@@ -1,31 +1,30 @@
 // bootstrap.hip — the two device passes of the frame bootstrap: per-frame IoU counters, and their replicate sums
 // under a paired resampling of the source frames.
 //
-// awseg_frame_iou_counts is consistency.hip's scan with one map less: each lane owns 16 consecutive pixels (one 16-byte load per
-// map when every row base is 16-byte aligned and hw % 16 == 0, byte loads otherwise), merges its (label, prediction) pairs into
-// runs in registers and touches the per-block LDS row [C intersection | C label | C prediction] once per run.  Blocks write uint32
-// partials; a second launch folds them into the int64 table row frame_row[b] names.  Integer sums only.
+// awseg_frame_iou_counts is a map scan (awseg_mapscan.h) of the prediction and the label map: a lane merges the
+// (label, prediction) pairs of its 16 pixels into runs in registers and touches the per-block LDS row [C intersection | C label |
+// C prediction] once per run.  Blocks write uint32 partials; the shared fold adds them into the int64 table row frame_row[b] names.
 //
 // awseg_bootstrap_counts runs one block per replicate: the replicate's draws (Philox4x32-7, stream kBootStream, index =
 // mulhi32(word, n)) are staged in LDS once, kBootDraws at a time, then every thread owns output cells (slot, column) and walks the
 // draws — no atomics, one fixed order, 64-bit accumulators; slot 0 is folded from the block's own cells at the end.
-#include "awseg_common.h"
+#include "awseg_mapscan.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPer = 16;                                                  // pixels per lane per step
+constexpr int kResident = 4;                                              // blocks per CU the scan's grid is capped at (2 B/px)
+constexpr int kFoldSlices = 4;                                            // a row of 3 C counters: four waves per fold block
+constexpr int kPer = kAwsegScanPer;
 constexpr int kRowMax = 3 * AWSEG_MAX_CLASSES;
 constexpr uint32_t kBootStream = 0x0B07u;                                 // weather.hip owns 0x0F06, 0x0F07, 0x0A17, 0x0DE5
 constexpr int kBootDraws = AWSEG_BOOTSTRAP_STAGED_DRAWS;                  // draws staged in LDS per pass (16 KB); larger n is chunked
 static_assert(kBootDraws % 4 == 0, "a Philox call fills four consecutive draws");
 
-__device__ __forceinline__ void unpack16(const uint4 q, int (&v)[kPer])
-{
-    const uint32_t w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = (int)((w[k >> 2] >> ((k & 3) * 8)) & 0xFF);
-}
+struct iou_key {                                                          // a (label, prediction) pair
+    int t = -1, p = -1;
+    __device__ __forceinline__ bool operator==(const iou_key& o) const { return t == o.t && p == o.p; }
+};
 
 // grid = (blocks_per_image, B); block x of image y writes partial[(y * gridDim.x + x)][3 C].
 // VEC: hw % 16 == 0 and pred and label 16-byte aligned (every row base then is); else byte loads.
@@ -36,41 +35,25 @@ void frame_iou_kernel(const uint8_t* __restrict__ pred, const void* __restrict__
 {
     __shared__ uint32_t hist[kRowMax];
     const int row = 3 * C;
-    for (int i = threadIdx.x; i < row; i += kThreads) hist[i] = 0u;
+    awseg_scan_zero<kThreads>(hist, row);
     __syncthreads();
     const int64_t img = blockIdx.y;
     const int64_t r = frame_row[img];
     uint32_t bad = 0;
     if (r >= 0 && r < n_rows) {
         const uint8_t* pp = pred + img * hw;
-        const int64_t lb = img * hw;
         const int64_t nchunk = (hw + kPer - 1) / kPer;
+        const auto flush = [&](const iou_key& key, uint32_t n) {
+            atomicAdd(&hist[C + key.t], n);
+            atomicAdd(&hist[2 * C + key.p], n);
+            if (key.t == key.p) atomicAdd(&hist[key.t], n);
+        };
         for (int64_t ch = (int64_t)blockIdx.x * kThreads + threadIdx.x; ch < nchunk; ch += (int64_t)gridDim.x * kThreads) {
             const int64_t base = ch * kPer;
             int pv[kPer];
             int64_t lv[kPer];
-            if constexpr (VEC) {
-                unpack16(*reinterpret_cast<const uint4*>(pp + base), pv);
-                if constexpr (LDT == AWSEG_U8) {
-                    int l8[kPer];
-                    unpack16(*reinterpret_cast<const uint4*>((const uint8_t*)label + lb + base), l8);
-#pragma unroll
-                    for (int k = 0; k < kPer; ++k) lv[k] = l8[k];
-                } else {
-                    const longlong2* lp = reinterpret_cast<const longlong2*>((const int64_t*)label + lb + base);
-#pragma unroll
-                    for (int k = 0; k < kPer / 2; ++k) { const longlong2 q = lp[k]; lv[2 * k] = q.x; lv[2 * k + 1] = q.y; }
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < kPer; ++k) {
-                    const bool in = base + k < hw;
-                    pv[k] = in ? (int)pp[base + k] : 0;
-                    lv[k] = in ? awseg_ld_label<LDT>(label, lb + base + k) : (int64_t)ignore_index;
-                }
-            }
-            int run_t = -1, run_p = -1;
-            uint32_t run = 0;
+            awseg_load_chunk16<LDT, VEC>(label, img * hw, base, hw, ignore_index, lv, awseg_map16{ pp, pv });
+            awseg_run<iou_key> run;
 #pragma unroll
             for (int k = 0; k < kPer; ++k) {
                 if (!VEC && base + k >= hw) break;
@@ -80,72 +63,18 @@ void frame_iou_kernel(const uint8_t* __restrict__ pred, const void* __restrict__
                 if (pk >= C) ++bad;                                       // a map value no argmax over C classes produces
                 if (!labelled && t != ignore_index) ++bad;                // a label that is neither a class nor the ignore value
                 if (!labelled || pk >= C) continue;
-                const int tk = (int)t;
-                if (tk == run_t && pk == run_p) { ++run; continue; }
-                if (run) {
-                    atomicAdd(&hist[C + run_t], run);
-                    atomicAdd(&hist[2 * C + run_p], run);
-                    if (run_t == run_p) atomicAdd(&hist[run_t], run);
-                }
-                run_t = tk; run_p = pk; run = 1;
+                run.add(iou_key{ (int)t, pk }, flush);
             }
-            if (run) {
-                atomicAdd(&hist[C + run_t], run);
-                atomicAdd(&hist[2 * C + run_p], run);
-                if (run_t == run_p) atomicAdd(&hist[run_t], run);
-            }
+            run.finish(flush);
         }
-    } else if (r >= n_rows && blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd((unsigned long long*)oob, (unsigned long long)hw);    // a row the table does not have: frame not counted
+    } else if (r >= n_rows) {
+        awseg_scan_row_outside(hw, oob);                                  // a row the table does not have: frame not counted
     }
-    bad = awseg_wave_sum_u32(bad);
-    if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0 && bad) atomicAdd((unsigned long long*)oob, (unsigned long long)bad);
-    __syncthreads();
-    uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * row;
-    for (int i = threadIdx.x; i < row; i += kThreads) dst[i] = hist[i];
+    awseg_scan_count_bad(bad, oob);
+    awseg_scan_store<kThreads>(hist, row, partial);
 }
 
-// awseg_fold_u32_partials_kernel with a row instead of a condition slot as the destination: partials [img][blocks_per_image][row]
-// into table[frame_row[img]][row] (frames whose row is outside [0, n_rows) wrote zero partials and are skipped here as well).
-// grid = (B, ceil(row / 64)), block = kFoldSlices * 64.
-constexpr int kFoldSlices = 4;
-__global__ __launch_bounds__(kFoldSlices * 64)
-void frame_fold_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row, const int32_t* __restrict__ frame_row,
-                       int64_t n_rows, int64_t* __restrict__ table)
-{
-    __shared__ unsigned long long s_sum[kFoldSlices][64];
-    const int img = blockIdx.x;
-    const int kl = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const int k = blockIdx.y * 64 + kl;
-    const uint32_t* src = partial + (int64_t)img * blocks_per_image * row;
-    unsigned long long s = 0;
-    if (k < row) {
-#pragma unroll 8
-        for (int b = slice; b < blocks_per_image; b += kFoldSlices) s += src[(int64_t)b * row + k];
-    }
-    s_sum[slice][kl] = s;
-    __syncthreads();
-    if (slice == 0 && k < row) {
-        s = 0;
-#pragma unroll
-        for (int j = 0; j < kFoldSlices; ++j) s += s_sum[j][kl];
-        const int64_t r = frame_row[img];
-        if (s && r >= 0 && r < n_rows) atomicAdd((unsigned long long*)&table[r * row + k], s);   // two frames may name one row
-    }
-}
-
-int fiou_blocks_per_image(int64_t hw, int64_t batch)
-{
-    // 256 CUs x 4 resident blocks over the whole batch (a 2 B/px scan), grid-stride beyond: consistency.hip's rule
-    int64_t want = ((hw + kPer - 1) / kPer + kThreads - 1) / kThreads;
-    int64_t cap = (AWSEG_CUS * 4 + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int fiou_blocks_per_image(int64_t hw, int64_t batch) { return awseg_blocks_per_image((hw + kPer - 1) / kPer, kThreads, batch, kResident); }
 
 // grid = R, block = kThreads.  Replicate q = r0 + blockIdx.x; out[blockIdx.x][n_slots][W].
 __global__ __launch_bounds__(kThreads)
@@ -220,20 +149,16 @@ AWSEG_API int awseg_frame_iou_counts(const uint8_t* pred, const void* label, int
     hipStream_t s = awseg_s(stream);
     const int bpi = fiou_blocks_per_image(hw, batch);                          // same count the workspace query assumed
     const int row = 3 * num_classes;
-    const bool vec = (hw % kPer == 0) && aligned16(pred) && aligned16(label);
+    const bool vec = (hw % kPer == 0) && awseg_aligned(pred, 16) && awseg_aligned(label, 16);
     uint32_t* partial = (uint32_t*)workspace;
     dim3 grid(bpi, (unsigned)batch), block(kThreads);
-#define AWSEG_FIOU(L, V) \
-    hipLaunchKernelGGL((frame_iou_kernel<L, V>), grid, block, 0, s, pred, label, ignore_index, hw, num_classes, frame_row, n_rows, \
-                       partial, oob)
-    if (label_dtype == AWSEG_U8) { if (vec) AWSEG_FIOU(AWSEG_U8, true); else AWSEG_FIOU(AWSEG_U8, false); }
-    else { if (vec) AWSEG_FIOU(AWSEG_I64, true); else AWSEG_FIOU(AWSEG_I64, false); }
-#undef AWSEG_FIOU
+    awseg_by_label(label_dtype, [&](auto L) { awseg_by_flag(vec, [&](auto V) {
+        hipLaunchKernelGGL((frame_iou_kernel<decltype(L)::value, decltype(V)::value>), grid, block, 0, s, pred, label, ignore_index, hw,
+                           num_classes, frame_row, n_rows, partial, oob);
+    }); });
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(frame_fold_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kFoldSlices * 64), 0, s, partial, bpi, row,
-                       frame_row, n_rows, table);
-    AWSEG_LAUNCH_CHECK();
-    return 0;
+    // frames whose row is outside [0, n_rows) wrote zero partials and are skipped by the fold as well; two frames may name one row
+    return awseg_fold_u32_launch(partial, batch, bpi, row, frame_row, n_rows, false, table, s, kFoldSlices);
 }
 
 AWSEG_API int awseg_bootstrap_counts(const int64_t* table, const int32_t* slots, int64_t n, int64_t variants, int64_t width,

@@ -13,13 +13,14 @@
 // rows (odd row pitch: no bank conflict), the column pass across the columns.  The hit count over the widths is the ring (the
 // windows are nested).  The label map and the prediction map go through the same LDS one after the other; their rings stay in
 // registers.  Then each lane merges its 8 vertically adjacent pixels into runs of equal (rings, classes) before the per-block LDS
-// histogram (consistency.hip's run merging).  Blocks write uint32 partials, a second launch folds them into the int64 slots:
+// histogram; the block's partials and their fold into the int64 slots are the map scan's (awseg_mapscan.h):
 // integer sums only, so the counts do not depend on grid shape, batch split or rank count.
-#include "awseg_common.h"
+#include "awseg_mapscan.h"
 
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kResident = 4;                                              // blocks per CU the grid is capped at
 constexpr int kTH = 32, kTW = 64;                                         // tile; kThreads lanes x 8 rows
 constexpr int kPer = 8;                                                   // outputs per lane per window8
 constexpr int kHP = kTW + 1;                                              // row pitch of the row-pass result (odd)
@@ -69,7 +70,7 @@ void boundary_kernel(const uint8_t* __restrict__ pred, const void* __restrict__ 
     uint32_t* hbuf = staged + SR * SP;
     uint32_t* hist = hbuf + SR * kHP;
     const int row = C * C + 2 * C, nh = (n + 1) * row;
-    for (int i = threadIdx.x; i < nh; i += kThreads) hist[i] = 0u;
+    awseg_scan_zero<kThreads>(hist, nh);
     const int64_t img = blockIdx.y, hw = (int64_t)H * W;
     const uint8_t* pp = pred + img * hw;
     const int x = threadIdx.x & (kTW - 1), y0 = (threadIdx.x / kTW) * kPer;
@@ -118,7 +119,9 @@ void boundary_kernel(const uint8_t* __restrict__ pred, const void* __restrict__ 
                 __syncthreads();                                          // before the next width overwrites hbuf
             }
         }
-        // runs of equal (label ring, prediction ring, label, prediction) down the lane's 8 rows: one set of LDS adds per run
+        // runs of equal (label ring, prediction ring, label, prediction) down the lane's 8 rows: one set of LDS adds per run.  Open-coded:
+        // on awseg_run (awseg_mapscan.h) the same registers and occupancy came out, and 1.2 % more time in every run
+        // (profiles/mapscan_kernel_bench_hip_events.log)
         uint32_t run_key = ~0u, run = 0;
 #pragma unroll
         for (int j = 0; j <= kPer; ++j) {
@@ -138,24 +141,13 @@ void boundary_kernel(const uint8_t* __restrict__ pred, const void* __restrict__ 
             run_key = key; run = 1;
         }
     }
-    bad = awseg_wave_sum_u32(bad);
-    if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0 && bad) atomicAdd((unsigned long long*)oob, (unsigned long long)bad);
-    __syncthreads();
-    uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * nh;
-    for (int i = threadIdx.x; i < nh; i += kThreads) dst[i] = hist[i];
+    awseg_scan_count_bad(bad, oob);
+    awseg_scan_store<kThreads>(hist, nh, partial);
 }
 
 int64_t bnd_tiles(int height, int width) { return (int64_t)((height + kTH - 1) / kTH) * ((width + kTW - 1) / kTW); }
 
-int bnd_blocks_per_image(int64_t tiles, int64_t batch)
-{
-    // 256 CUs x 4 resident blocks over the whole batch, tile-stride beyond
-    int64_t cap = (AWSEG_CUS * 4 + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    int64_t want = tiles < cap ? tiles : cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
+int bnd_blocks_per_image(int64_t tiles, int64_t batch) { return awseg_blocks_per_image(tiles, 1, batch, kResident); }   // a block per tile
 
 int bnd_row(int num_classes, int n_widths) { return (n_widths + 1) * (num_classes * num_classes + 2 * num_classes); }
 
@@ -197,15 +189,10 @@ AWSEG_API int awseg_boundary_stats(const uint8_t* pred, const void* label, int l
     uint32_t* partial = (uint32_t*)workspace;
     dim3 grid(bpi, (unsigned)batch), block(kThreads);
     const int tiles_x = (width + kTW - 1) / kTW;
-    if (label_dtype == AWSEG_U8)
-        hipLaunchKernelGGL((boundary_kernel<AWSEG_U8>), grid, block, lds, s, pred, label, ignore_index, height, width, num_classes,
-                           wd, tiles_x, (int)tiles, partial, oob);
-    else
-        hipLaunchKernelGGL((boundary_kernel<AWSEG_I64>), grid, block, lds, s, pred, label, ignore_index, height, width, num_classes,
-                           wd, tiles_x, (int)tiles, partial, oob);
+    awseg_by_label(label_dtype, [&](auto L) {
+        hipLaunchKernelGGL((boundary_kernel<decltype(L)::value>), grid, block, lds, s, pred, label, ignore_index, height, width,
+                           num_classes, wd, tiles_x, (int)tiles, partial, oob);
+    });
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(awseg_fold_u32_partials_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kAwsegFoldSlices * 64), 0, s, partial, bpi, row,
-                       cond, n_slots, stats);
-    AWSEG_LAUNCH_CHECK();
-    return 0;
+    return awseg_fold_u32_launch(partial, batch, bpi, row, cond, n_slots, true, stats, s);
 }

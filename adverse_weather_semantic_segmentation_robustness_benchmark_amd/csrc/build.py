@@ -60,7 +60,7 @@ def needs_build() -> bool:
     if not STAMP.exists() or STAMP.read_text() != _flag_stamp():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "awseg_common.h", HEADER]
+    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [HEADER]
     return any(d.stat().st_mtime > t for d in deps)
 
 

@@ -308,8 +308,6 @@ int launch_chunks(const float* seg1, const float* seg2, int64_t batch, int C, in
     return 0;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 AWSEG_API int awseg_temperature_grid_stats(const float* logits, int64_t batch, int num_classes, int64_t hw, const void* label,
@@ -319,7 +317,7 @@ AWSEG_API int awseg_temperature_grid_stats(const float* logits, int64_t batch, i
     if (!logits) return AWSEG_EINVAL;
     if (int rc = check_common(batch, num_classes, hw, label, label_dtype, temps, n_temps, edges, n_bins, stats, n_slots)) return rc;
     hipStream_t s = awseg_s(stream);
-    const bool vec19 = (num_classes == 19) && !(hw & 3) && aligned16(logits);   // the ece19_kernel condition
+    const bool vec19 = (num_classes == 19) && !(hw & 3) && awseg_aligned(logits, 16);   // the ece19_kernel condition
     const bool u8 = label_dtype == AWSEG_U8;
 #define AWSEG_TG(L, PX, CT, CM) launch_chunks<3, L, PX, CT, CM>(logits, nullptr, batch, num_classes, hw, nullptr, nullptr, label, cond, \
                                                                   temps, n_temps, edges, n_bins, stats, n_slots, s)
@@ -342,7 +340,7 @@ AWSEG_API int awseg_ensemble_temperature_grid_stats(const float* seg1, const flo
     if (num_classes != 19) return AWSEG_ERANGE;                  // awseg_combine_confusion_stats' eligibility
     if (mode != AWSEG_COMBINE_WEIGHTED && mode != AWSEG_COMBINE_MEAN) return AWSEG_ERANGE;
     if (mode == AWSEG_COMBINE_WEIGHTED && !weights) return AWSEG_EINVAL;
-    if ((hw & 3) || !aligned16(seg1) || !aligned16(seg2)) return AWSEG_EALIGN;
+    if ((hw & 3) || !awseg_aligned(seg1, 16) || !awseg_aligned(seg2, 16)) return AWSEG_EALIGN;
     hipStream_t s = awseg_s(stream);
     const bool u8 = label_dtype == AWSEG_U8;
 #define AWSEG_TGE(M, L) launch_chunks<M, L, 4, 19, 19>(seg1, seg2, batch, 19, hw, weights, temperature, label, cond, temps, n_temps, \

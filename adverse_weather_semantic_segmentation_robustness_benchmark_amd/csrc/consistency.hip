@@ -2,26 +2,18 @@
 // sweep): per condition slot, the C x C agreement matrix A[ref class][variant class] over every pixel and the four
 // correct / wrong transitions over the labelled pixels.
 //
-// A 2-3 B/px scan (two uint8 maps + the label map).  Each lane owns 16 consecutive pixels: one 16-byte load per map when every row
-// base is 16-byte aligned and hw % 16 == 0, byte loads otherwise (ragged frames).  Clean and corrupted predictions agree over large
-// connected regions, so the 16 agreement indices of a lane are merged into runs in registers before they touch the per-block LDS
-// histogram (one ds_add per run: one per 16 pixels in the common case); the four transition counters never touch LDS per pixel:
-// they live in registers, are summed over the wave and added once per wave.  Blocks write uint32 partials, a second launch folds
-// them into the int64 counters: integer sums only, so the counts do not depend on grid shape, batch split or rank count.
-#include "awseg_common.h"
+// A 2-3 B/px map scan (two uint8 maps + the label map; awseg_mapscan.h).  Clean and corrupted predictions agree over
+// large connected regions, so the 16 agreement indices of a lane are merged into runs in registers before they touch the per-block
+// LDS histogram (one ds_add per run: one per 16 pixels in the common case); the four transition counters never touch LDS per pixel:
+// they live in registers, are summed over the wave and added once per wave.
+#include "awseg_mapscan.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kPer = 16;                                                  // pixels per lane per step
+constexpr int kResident = 4;                                              // blocks per CU the grid is capped at (a 2-3 B/px scan)
+constexpr int kPer = kAwsegScanPer;
 constexpr int kRowMax = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES + 4;
-
-__device__ __forceinline__ void unpack16(const uint4 q, int (&v)[kPer])
-{
-    const uint32_t w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = (int)((w[k >> 2] >> ((k & 3) * 8)) & 0xFF);
-}
 
 // grid = (blocks_per_image, B); block x of image y writes partial[(y * gridDim.x + x)][C * C + 4].
 // VEC: hw % 16 == 0 and pred, ref_maps and label 16-byte aligned (every row base then is); else byte loads.
@@ -33,7 +25,7 @@ void consistency_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restr
 {
     __shared__ uint32_t hist[kRowMax];
     const int bins = C * C, row = bins + 4;
-    for (int i = threadIdx.x; i < row; i += kThreads) hist[i] = 0u;
+    awseg_scan_zero<kThreads>(hist, row);
     __syncthreads();
     const int64_t img = blockIdx.y;
     const int r = frame_ref[img];
@@ -42,80 +34,43 @@ void consistency_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restr
     if (r >= 0 && r < n_refs) {
         const uint8_t* pp = pred + img * hw;
         const uint8_t* rp = ref_maps + (int64_t)r * hw;
-        const int64_t lb = img * hw;
         const int64_t nchunk = (hw + kPer - 1) / kPer;
+        const auto flush = [&](int idx, uint32_t n) { atomicAdd(&hist[idx], n); };
         for (int64_t ch = (int64_t)blockIdx.x * kThreads + threadIdx.x; ch < nchunk; ch += (int64_t)gridDim.x * kThreads) {
             const int64_t base = ch * kPer;
             int pv[kPer], rv[kPer];
             int64_t lv[kPer];
-            if constexpr (VEC) {
-                unpack16(*reinterpret_cast<const uint4*>(pp + base), pv);
-                unpack16(*reinterpret_cast<const uint4*>(rp + base), rv);
-                if constexpr (LDT == AWSEG_U8) {
-                    int l8[kPer];
-                    unpack16(*reinterpret_cast<const uint4*>((const uint8_t*)label + lb + base), l8);
-#pragma unroll
-                    for (int k = 0; k < kPer; ++k) lv[k] = l8[k];
-                } else {
-                    const longlong2* lp = reinterpret_cast<const longlong2*>((const int64_t*)label + lb + base);
-#pragma unroll
-                    for (int k = 0; k < kPer / 2; ++k) { const longlong2 q = lp[k]; lv[2 * k] = q.x; lv[2 * k + 1] = q.y; }
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < kPer; ++k) {
-                    const bool in = base + k < hw;
-                    pv[k] = in ? (int)pp[base + k] : 0;
-                    rv[k] = in ? (int)rp[base + k] : 0;
-                    lv[k] = in ? awseg_ld_label<LDT>(label, lb + base + k) : (int64_t)ignore_index;
-                }
-            }
-            int run_idx = -1;
-            uint32_t run = 0;
+            awseg_load_chunk16<LDT, VEC>(label, img * hw, base, hw, ignore_index, lv, awseg_map16{ pp, pv }, awseg_map16{ rp, rv });
+            awseg_run<int> run;
 #pragma unroll
             for (int k = 0; k < kPer; ++k) {
                 if (!VEC && base + k >= hw) break;
                 const int pk = pv[k], rk = rv[k];
                 if (pk >= C || rk >= C) { ++bad; continue; }             // a map value no argmax over C classes produces
-                const int idx = rk * C + pk;
-                if (idx == run_idx) ++run;
-                else { if (run) atomicAdd(&hist[run_idx], run); run_idx = idx; run = 1; }
+                run.add(rk * C + pk, flush);
                 const int64_t t = lv[k];
                 if (t != ignore_index && t >= 0 && t < C) {
                     const uint32_t rc = (int64_t)rk == t, vc = (int64_t)pk == t;
                     t_cc += rc & vc; t_cw += rc & (vc ^ 1u); t_wc += (rc ^ 1u) & vc; t_ww += (rc ^ 1u) & (vc ^ 1u);
                 }
             }
-            if (run) atomicAdd(&hist[run_idx], run);
+            run.finish(flush);
         }
-    } else if (r >= n_refs && blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd((unsigned long long*)oob, (unsigned long long)hw);    // a row index the reference maps do not have: frame not counted
+    } else if (r >= n_refs) {
+        awseg_scan_row_outside(hw, oob);                                  // a row index the reference maps do not have: frame not counted
     }
-    t_cc = awseg_wave_sum_u32(t_cc); t_cw = awseg_wave_sum_u32(t_cw); t_wc = awseg_wave_sum_u32(t_wc); t_ww = awseg_wave_sum_u32(t_ww); bad = awseg_wave_sum_u32(bad);
+    t_cc = awseg_wave_sum_u32(t_cc); t_cw = awseg_wave_sum_u32(t_cw); t_wc = awseg_wave_sum_u32(t_wc); t_ww = awseg_wave_sum_u32(t_ww);
     if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0) {
         if (t_cc) atomicAdd(&hist[bins + 0], t_cc);
         if (t_cw) atomicAdd(&hist[bins + 1], t_cw);
         if (t_wc) atomicAdd(&hist[bins + 2], t_wc);
         if (t_ww) atomicAdd(&hist[bins + 3], t_ww);
-        if (bad) atomicAdd((unsigned long long*)oob, (unsigned long long)bad);
     }
-    __syncthreads();
-    uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * row;
-    for (int i = threadIdx.x; i < row; i += kThreads) dst[i] = hist[i];
+    awseg_scan_count_bad(bad, oob);
+    awseg_scan_store<kThreads>(hist, row, partial);
 }
 
-int cons_blocks_per_image(int64_t hw, int64_t batch)
-{
-    // 256 CUs x 4 resident blocks over the whole batch (a 2-3 B/px scan), grid-stride beyond
-    int64_t want = ((hw + kPer - 1) / kPer + kThreads - 1) / kThreads;
-    int64_t cap = (AWSEG_CUS * 4 + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+int cons_blocks_per_image(int64_t hw, int64_t batch) { return awseg_blocks_per_image((hw + kPer - 1) / kPer, kThreads, batch, kResident); }
 
 }  // namespace
 
@@ -140,18 +95,13 @@ AWSEG_API int awseg_prediction_consistency(const uint8_t* pred, const uint8_t* r
     hipStream_t s = awseg_s(stream);
     const int bpi = cons_blocks_per_image(hw, batch);                          // same count the workspace query assumed
     const int row = num_classes * num_classes + 4;
-    const bool vec = (hw % kPer == 0) && aligned16(pred) && aligned16(ref_maps) && aligned16(label);
+    const bool vec = (hw % kPer == 0) && awseg_aligned(pred, 16) && awseg_aligned(ref_maps, 16) && awseg_aligned(label, 16);
     uint32_t* partial = (uint32_t*)workspace;
     dim3 grid(bpi, (unsigned)batch), block(kThreads);
-#define AWSEG_CONS(L, V) \
-    hipLaunchKernelGGL((consistency_kernel<L, V>), grid, block, 0, s, pred, ref_maps, n_refs, hw, frame_ref, label, ignore_index, \
-                       num_classes, partial, oob)
-    if (label_dtype == AWSEG_U8) { if (vec) AWSEG_CONS(AWSEG_U8, true); else AWSEG_CONS(AWSEG_U8, false); }
-    else { if (vec) AWSEG_CONS(AWSEG_I64, true); else AWSEG_CONS(AWSEG_I64, false); }
-#undef AWSEG_CONS
+    awseg_by_label(label_dtype, [&](auto L) { awseg_by_flag(vec, [&](auto V) {
+        hipLaunchKernelGGL((consistency_kernel<decltype(L)::value, decltype(V)::value>), grid, block, 0, s, pred, ref_maps, n_refs, hw,
+                           frame_ref, label, ignore_index, num_classes, partial, oob);
+    }); });
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(awseg_fold_u32_partials_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kAwsegFoldSlices * 64), 0, s, partial, bpi, row,
-                       cond, n_slots, stats);
-    AWSEG_LAUNCH_CHECK();
-    return 0;
+    return awseg_fold_u32_launch(partial, batch, bpi, row, cond, n_slots, true, stats, s);
 }

@@ -183,8 +183,6 @@ void depth_eval_kernel(const float* __restrict__ d1, const float* __restrict__ d
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 AWSEG_API int awseg_depth_eval_stats(const float* d1, const float* d2_low, int batch, int low_height, int low_width, int height,
@@ -198,7 +196,7 @@ AWSEG_API int awseg_depth_eval_stats(const float* d1, const float* d2_low, int b
     if (batch == 0) return 0;
     const int64_t hw = (int64_t)height * width;
     if (batch > 65535 || hw > INT32_MAX || (d2_low && (int64_t)low_height * low_width > INT32_MAX)) return AWSEG_ERANGE;
-    const bool vec = !(width & 3) && aligned16(d1) && aligned16(target);
+    const bool vec = !(width & 3) && awseg_aligned(d1, 16) && awseg_aligned(target, 16);
     // 256 CUs x 8 resident blocks over the whole batch, grid-stride beyond (a lane then walks 8 steps at 8 x 1024 x 2048)
     const int64_t items = vec ? hw / 4 : hw;
     int64_t bpi = (items + kThreads - 1) / kThreads;

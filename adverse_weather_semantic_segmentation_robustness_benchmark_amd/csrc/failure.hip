@@ -226,8 +226,6 @@ void failure_kernel(const float* __restrict__ seg1, const float* __restrict__ se
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <int MODE, int LDT, int TH, int PX, int CT, int CMAX>
 int launch(const float* seg1, const float* seg2, const float* comb, int64_t batch, int C, int64_t hw, const float* weights,
            const float* temperature, const void* label, const int32_t* cond, int64_t* stats, int n_slots, hipStream_t s)
@@ -301,7 +299,7 @@ AWSEG_API int awseg_failure_stats(const float* logits, int64_t batch, int num_cl
     if (num_classes > AWSEG_CALIB_MAX_CLASSES || hw > INT32_MAX || batch > 65535) return AWSEG_ERANGE;
     if (batch == 0) return 0;
     hipStream_t s = awseg_s(stream);
-    const bool vec = num_classes == 19 && !(hw & 3) && aligned16(logits);
+    const bool vec = num_classes == 19 && !(hw & 3) && awseg_aligned(logits, 16);
     const bool u8 = label_dtype == AWSEG_U8;
 #define AWSEG_FS(TH, PX, CT, CM) (u8 ? launch<3, AWSEG_U8, TH, PX, CT, CM>(logits, nullptr, nullptr, batch, num_classes, hw, nullptr, nullptr, \
                                                                           label, cond, stats, n_slots, s)                                   \

@@ -11,13 +11,14 @@
 // apart, so each lane owns 4 consecutive pixels and walks the channels with 16-byte loads
 // (64 lanes x 16 B = one 1 KiB wave access per channel plane).  Confusion counts go to a
 // per-block LDS histogram (ds_add_u32), are written once per block as uint32 partials and
-// folded into the caller's int64 counters by a tiny second launch — no same-address global
-// atomics on the streaming path, and the result is order-independent (integers).
-#include "awseg_common.h"
+// folded into the caller's int64 counters by a tiny second launch (awseg_mapscan.h) — no same-address
+// global atomics on the streaming path, and the result is order-independent (integers).
+#include "awseg_mapscan.h"
 
 namespace {
 
 constexpr int kThreads = 256;
+constexpr int kResident = 8;                                              // blocks per CU the streaming grids are capped at
 constexpr int kMaxBins = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES;
 
 // torch argmax update rule (awseg_common.h, shared with the prediction maps consistency.hip compares)
@@ -155,36 +156,36 @@ void combine_argmax_confusion_kernel(const float* __restrict__ seg1, const float
     }
 }
 
-// Fold the per-block uint32 partial histograms of one image into slot 0 and slot 1+cond[img].
-// grid = (images, ceil(bins/64)), 1024 threads: a block owns 64 bins and its 16 waves each sum a
-// sixteenth of the partials (independent, unrolled loads), then one LDS step combines them — the
-// dependent-load chain is blocks_per_image/16 long and the bins run in parallel across blocks.
-constexpr int kFoldSlices = 16;
-__global__ __launch_bounds__(kFoldSlices * 64)
-void fold_partials_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int bins,
-                          const int32_t* __restrict__ cond, int n_slots, int64_t* __restrict__ counts)
+// The one fold of the map-scan passes (awseg_mapscan.h), launched by awseg_fold_u32_launch below.
+// grid = (images, ceil(row / 64)), block = SLICES * 64: a block owns 64 counters, its SLICES waves each sum that share of the
+// image's partials (independent, unrolled loads), one LDS step combines them — the dependent-load chain is blocks_per_image /
+// SLICES long and the counters run in parallel across blocks.  first = 1: row 0 takes every image and row 1 + index[img] the
+// image's condition; first = 0: row index[img] alone.  Two images may name one row, so the adds are atomic.
+template <int SLICES>
+__global__ __launch_bounds__(SLICES * 64)
+void fold_u32_kernel(const uint32_t* __restrict__ partial, int blocks_per_image, int row, const int32_t* __restrict__ index,
+                     int64_t n_rows, int first, int64_t* __restrict__ dst)
 {
-    __shared__ unsigned long long s_sum[kFoldSlices][64];
+    __shared__ unsigned long long s_sum[SLICES][64];
     const int img = blockIdx.x;
     const int kl = threadIdx.x & 63, slice = threadIdx.x >> 6;
     const int k = blockIdx.y * 64 + kl;
-    const uint32_t* src = partial + (int64_t)img * blocks_per_image * bins;
+    const uint32_t* src = partial + (int64_t)img * blocks_per_image * row;
     unsigned long long s = 0;
-    if (k < bins) {
+    if (k < row) {
 #pragma unroll 8
-        for (int b = slice; b < blocks_per_image; b += kFoldSlices) s += src[(int64_t)b * bins + k];
+        for (int b = slice; b < blocks_per_image; b += SLICES) s += src[(int64_t)b * row + k];
     }
     s_sum[slice][kl] = s;
     __syncthreads();
-    if (slice == 0 && k < bins) {
+    if (slice == 0 && k < row) {
         s = 0;
 #pragma unroll
-        for (int j = 0; j < kFoldSlices; ++j) s += s_sum[j][kl];
+        for (int j = 0; j < SLICES; ++j) s += s_sum[j][kl];
         if (s) {
-            int slot = -1;
-            if (cond) { int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-            atomicAdd((unsigned long long*)&counts[k], s);
-            if (slot > 0) atomicAdd((unsigned long long*)&counts[(int64_t)slot * bins + k], s);
+            const int64_t r = index ? (int64_t)index[img] + first : -1;
+            if (first) atomicAdd((unsigned long long*)&dst[k], s);
+            if (r >= first && r < n_rows) atomicAdd((unsigned long long*)&dst[r * row + k], s);
         }
     }
 }
@@ -194,6 +195,17 @@ void fold_partials_kernel(const uint32_t* __restrict__ partial, int blocks_per_i
 // merged in registers before touching LDS (segmentation maps are piecewise constant, so the
 // common case is one ds_add per 16 pixels; random maps degrade to one per pixel).
 // ---------------------------------------------------------------------------------------
+// a full chunk of a prediction or label map: one 16-byte load of a uint8 map (the host requires the alignment), element loads of an
+// int64 one (8-byte aligned only)
+template <int DT> __device__ __forceinline__ void conf_load_full16(const void* __restrict__ p, int64_t base, int64_t (&v)[kAwsegScanPer])
+{
+    if constexpr (DT == AWSEG_U8) awseg_load_label16<AWSEG_U8, true>(p, 0, base, 0, 0, v);
+    else {
+#pragma unroll
+        for (int k = 0; k < kAwsegScanPer; ++k) v[k] = ((const int64_t*)p)[base + k];
+    }
+}
+
 template <int PDT, int LDT>
 __global__ __launch_bounds__(kThreads)
 void confusion_kernel(const void* __restrict__ pred, const void* __restrict__ label, int64_t n, int C,
@@ -201,55 +213,33 @@ void confusion_kernel(const void* __restrict__ pred, const void* __restrict__ la
 {
     __shared__ uint32_t hist[kMaxBins];
     const int bins = C * C;
-    for (int i = threadIdx.x; i < bins; i += kThreads) hist[i] = 0u;
+    awseg_scan_zero<kThreads>(hist, bins);
     __syncthreads();
-    constexpr int PER = 16;
+    constexpr int PER = kAwsegScanPer;
     const int64_t nchunk = (n + PER - 1) / PER;
+    const auto flush = [&](int64_t idx, uint32_t run) { atomicAdd(&hist[idx], run); };
     for (int64_t ch = (int64_t)blockIdx.x * kThreads + threadIdx.x; ch < nchunk; ch += (int64_t)gridDim.x * kThreads) {
         const int64_t base = ch * PER;
         int64_t pv[PER], lv[PER];
-        if (base + PER <= n) {
-            if (PDT == AWSEG_U8) {
-                uint4 q = *reinterpret_cast<const uint4*>((const uint8_t*)pred + base);
-                uint32_t w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-                for (int k = 0; k < PER; ++k) pv[k] = (w[k >> 2] >> ((k & 3) * 8)) & 0xFF;
-            } else {
-#pragma unroll
-                for (int k = 0; k < PER; ++k) pv[k] = ((const int64_t*)pred)[base + k];
-            }
-            if (LDT == AWSEG_U8) {
-                uint4 q = *reinterpret_cast<const uint4*>((const uint8_t*)label + base);
-                uint32_t w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-                for (int k = 0; k < PER; ++k) lv[k] = (w[k >> 2] >> ((k & 3) * 8)) & 0xFF;
-            } else {
-#pragma unroll
-                for (int k = 0; k < PER; ++k) lv[k] = ((const int64_t*)label)[base + k];
-            }
+        if (base + PER <= n) {                                            // decided per chunk: only the last one is ragged
+            conf_load_full16<PDT>(pred, base, pv);
+            conf_load_full16<LDT>(label, base, lv);
         } else {
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                bool in = base + k < n;
-                pv[k] = in ? (PDT == AWSEG_U8 ? (int64_t)((const uint8_t*)pred)[base + k] : ((const int64_t*)pred)[base + k]) : 0;
-                lv[k] = in ? awseg_ld_label<LDT>(label, base + k) : (int64_t)ignore_index;
-            }
+            awseg_load_label16<PDT, false>(pred, 0, base, n, 0, pv);
+            awseg_load_label16<LDT, false>(label, 0, base, n, ignore_index, lv);
         }
-        int64_t run_idx = -1; uint32_t run = 0;
+        awseg_run<int64_t> run;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             if (lv[k] == ignore_index) continue;
             int64_t b = wrap ? (int64_t)(uint8_t)(lv[k] * C) : lv[k] * (int64_t)C;
             int64_t idx = b + pv[k];
             if (idx < 0 || idx >= bins || pv[k] < 0 || pv[k] >= C) { atomicAdd((unsigned long long*)oob, 1ull); continue; }
-            if (idx == run_idx) { ++run; }
-            else { if (run) atomicAdd(&hist[run_idx], run); run_idx = idx; run = 1; }
+            run.add(idx, flush);
         }
-        if (run) atomicAdd(&hist[run_idx], run);
+        run.finish(flush);
     }
-    __syncthreads();
-    uint32_t* dst = partial + (int64_t)blockIdx.x * bins;
-    for (int i = threadIdx.x; i < bins; i += kThreads) dst[i] = hist[i];
+    awseg_scan_store<kThreads>(hist, bins, partial);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -391,7 +381,7 @@ __global__ void ece_fold_kernel(const ece_cell* __restrict__ partial, int blocks
 // ---------------------------------------------------------------------------------------
 // CONF = true: the same pass ALSO counts the 19 x 19 confusion matrix of argmax(r) against the labels, with the combine kernel's
 // rules (torch's argmax update, ignore_index, the reference's uint8 index wrap, out-of-range count) into per-block partials that
-// fold_partials_kernel folds — the separate awseg_combine_argmax_confusion pass over the two logit maps (2.55 GB per batch of 8
+// the shared fold (awseg_mapscan.h) adds up — the separate awseg_combine_argmax_confusion pass over the two logit maps (2.55 GB per batch of 8
 // at 1024 x 2048) is not needed when neither the ensemble logits nor the prediction map are asked for.
 // TH threads x PX pixels per lane: the block's 64 KB score histogram allows two blocks per CU, so 256 threads are two waves per SIMD
 // whatever the register count; 512 threads with 2 pixels per lane (2 x 19 x 2 logits: < 128 registers) are four.
@@ -523,16 +513,7 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
 
 constexpr int kHistMax = 8192;
 
-int blocks_per_image(int64_t hw, int64_t batch, int vec)
-{
-    // enough blocks to fill 256 CUs x 8 resident blocks across the whole batch, grid-stride beyond
-    int64_t want = (hw / vec + kThreads - 1) / kThreads;
-    int64_t cap = (AWSEG_CUS * 8 + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
+int blocks_per_image(int64_t hw, int64_t batch, int vec) { return awseg_blocks_per_image(hw / vec, kThreads, batch, kResident); }
 
 template <int MODE, int VEC>
 int launch_fused(const float* seg1, const float* seg2, int64_t batch, int C, int64_t hw,
@@ -559,9 +540,21 @@ int launch_fused(const float* seg1, const float* seg2, int64_t batch, int C, int
     return 0;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
+
+int awseg_fold_u32_launch(const uint32_t* partial, int64_t images, int blocks_per_image, int row, const int32_t* index,
+                          int64_t n_rows, bool total, int64_t* dst, hipStream_t stream, int slices)
+{
+    const dim3 grid((unsigned)images, (row + 63) / 64);
+    if (slices == 4)
+        hipLaunchKernelGGL(fold_u32_kernel<4>, grid, dim3(4 * 64), 0, stream, partial, blocks_per_image, row, index, n_rows, (int)total, dst);
+    else if (slices == 16)
+        hipLaunchKernelGGL(fold_u32_kernel<16>, grid, dim3(16 * 64), 0, stream, partial, blocks_per_image, row, index, n_rows, (int)total, dst);
+    else
+        return AWSEG_EINVAL;                                              // no such instantiation
+    AWSEG_LAUNCH_CHECK();
+    return 0;
+}
 
 AWSEG_API int64_t awseg_metrics_workspace(int64_t batch, int num_classes, int64_t hw)
 {
@@ -583,8 +576,8 @@ static int fused_impl(int mode, const float* seg1, const float* seg2, int64_t ba
     if (batch > 65535) return AWSEG_ERANGE;
     if ((pdt != AWSEG_U8 && pdt != AWSEG_I64) || (ldt != AWSEG_U8 && ldt != AWSEG_I64)) return AWSEG_EINVAL;
     if (label && (!counts || !oob || !workspace || n_slots < 1)) return AWSEG_EINVAL;
-    const bool vec4 = (hw % 4 == 0) && aligned16(seg1) && (mode == 3 || aligned16(seg2)) &&
-                      (!out_logits || aligned16(out_logits)) && (!pred || pdt != AWSEG_U8 || ((uintptr_t)pred & 3) == 0);
+    const bool vec4 = (hw % 4 == 0) && awseg_aligned(seg1, 16) && (mode == 3 || awseg_aligned(seg2, 16)) &&
+                      (!out_logits || awseg_aligned(out_logits, 16)) && (!pred || pdt != AWSEG_U8 || awseg_aligned(pred, 4));
     const int bpi = blocks_per_image(hw, batch, 1);   // same count the workspace query assumed
     uint32_t* partial = (uint32_t*)workspace;
 #define AWSEG_MODE(M)                                                                                           \
@@ -601,12 +594,7 @@ static int fused_impl(int mode, const float* seg1, const float* seg2, int64_t ba
     }
 #undef AWSEG_MODE
     AWSEG_LAUNCH_CHECK();
-    if (label) {
-        hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)batch, (C * C + 63) / 64), dim3(kFoldSlices * 64), 0, s, partial, bpi,
-                           C * C, cond, n_slots, counts);
-        AWSEG_LAUNCH_CHECK();
-    }
-    return 0;
+    return label ? awseg_fold_u32_launch(partial, batch, bpi, C * C, cond, n_slots, true, counts, s) : 0;
 }
 
 AWSEG_API int awseg_combine_argmax_confusion(const float* seg1, const float* seg2, int64_t batch, int num_classes,
@@ -652,23 +640,16 @@ AWSEG_API int awseg_confusion_accumulate(const void* pred, int pred_dtype, const
     int nblk = blocks_per_image((n + 15) / 16, 1, 1);
     if (nblk > 1024) nblk = 1024;
     uint32_t* partial = (uint32_t*)workspace;
-    const bool al = aligned16(pred) && aligned16(label);
-    (void)al;  // unaligned byte maps still work: the uint4 path requires 16-B alignment
-    if ((pred_dtype == AWSEG_U8 && !aligned16(pred)) || (label_dtype == AWSEG_U8 && !aligned16(label))) return AWSEG_EALIGN;
+    // the 16-byte loads of a uint8 map need its base aligned
+    if ((pred_dtype == AWSEG_U8 && !awseg_aligned(pred, 16)) || (label_dtype == AWSEG_U8 && !awseg_aligned(label, 16))) return AWSEG_EALIGN;
+    if ((pred_dtype != AWSEG_U8 && pred_dtype != AWSEG_I64) || (label_dtype != AWSEG_U8 && label_dtype != AWSEG_I64)) return AWSEG_EINVAL;
     dim3 grid(nblk), block(kThreads);
-#define AWSEG_CONF(P, L) \
-    hipLaunchKernelGGL((confusion_kernel<P, L>), grid, block, 0, s, pred, label, n, num_classes, ignore_index, label_wrap_u8, partial, oob)
-    if (pred_dtype == AWSEG_U8 && label_dtype == AWSEG_U8) AWSEG_CONF(AWSEG_U8, AWSEG_U8);
-    else if (pred_dtype == AWSEG_U8 && label_dtype == AWSEG_I64) AWSEG_CONF(AWSEG_U8, AWSEG_I64);
-    else if (pred_dtype == AWSEG_I64 && label_dtype == AWSEG_U8) AWSEG_CONF(AWSEG_I64, AWSEG_U8);
-    else if (pred_dtype == AWSEG_I64 && label_dtype == AWSEG_I64) AWSEG_CONF(AWSEG_I64, AWSEG_I64);
-    else return AWSEG_EINVAL;
-#undef AWSEG_CONF
+    awseg_by_label(pred_dtype, [&](auto P) { awseg_by_label(label_dtype, [&](auto L) {
+        hipLaunchKernelGGL((confusion_kernel<decltype(P)::value, decltype(L)::value>), grid, block, 0, s, pred, label, n, num_classes,
+                           ignore_index, label_wrap_u8, partial, oob);
+    }); });
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fold_partials_kernel, dim3(1, (num_classes * num_classes + 63) / 64), dim3(kFoldSlices * 64), 0, s, partial, nblk,
-                       num_classes * num_classes, (const int32_t*)nullptr, 1, counts);
-    AWSEG_LAUNCH_CHECK();
-    return 0;
+    return awseg_fold_u32_launch(partial, 1, nblk, num_classes * num_classes, nullptr, 1, true, counts, s);   // one image, slot 0 alone
 }
 
 AWSEG_API int awseg_ece_accumulate(const float* logits, int64_t batch, int num_classes, int64_t hw, const void* label,
@@ -679,7 +660,7 @@ AWSEG_API int awseg_ece_accumulate(const float* logits, int64_t batch, int num_c
     if (n_bins < 1 || n_bins > 64 || n_slots < 1 || batch < 1 || batch > 65535 || hw < 1) return AWSEG_EINVAL;
     if (num_classes < 1 || num_classes > AWSEG_MAX_CLASSES) return AWSEG_EINVAL;
     hipStream_t s = awseg_s(stream);
-    const bool vec19 = (num_classes == 19) && !(hw & 3) && !((uintptr_t)logits & 15);
+    const bool vec19 = (num_classes == 19) && !(hw & 3) && awseg_aligned(logits, 16);
     const int bpi = blocks_per_image(hw, batch, vec19 ? 4 : 1);
     dim3 grid(bpi, (unsigned)batch), block(kThreads);
     if (label_dtype != AWSEG_U8 && label_dtype != AWSEG_I64) return AWSEG_EINVAL;
@@ -713,12 +694,10 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
     if (mode != AWSEG_COMBINE_WEIGHTED && mode != AWSEG_COMBINE_MEAN) return AWSEG_ERANGE;
     if (mode == AWSEG_COMBINE_WEIGHTED && !weights) return AWSEG_EINVAL;
     if (n_bins < 1 || n_bins > 64 || n_slots < 1 || n_hist < 2 || n_hist > kHistMax || batch < 1 || batch > 65535 || hw < 4 || !(hist_hi > hist_lo)) return AWSEG_EINVAL;
-    if ((hw & 3) || ((uintptr_t)seg1 & 15) || ((uintptr_t)seg2 & 15)) return AWSEG_EALIGN;
-    if (pred && (!conf || ((uintptr_t)pred & 3))) return pred && !conf ? AWSEG_EINVAL : AWSEG_EALIGN;
+    if ((hw & 3) || !awseg_aligned(seg1, 16) || !awseg_aligned(seg2, 16)) return AWSEG_EALIGN;
+    if (pred && (!conf || !awseg_aligned(pred, 4))) return pred && !conf ? AWSEG_EINVAL : AWSEG_EALIGN;
     hipStream_t s = awseg_s(stream);
-    int bpi = blocks_per_image(hw, batch, 1);
-    const int cap = (int)((AWSEG_CUS * 2 + batch - 1) / batch);   // 64 KB of LDS per block: two blocks per CU
-    if (bpi > cap) bpi = cap < 1 ? 1 : cap;
+    const int bpi = awseg_blocks_per_image(hw, kThreads, batch, 2);   // 64 KB of LDS per block: two blocks per CU
     dim3 grid(bpi, (unsigned)batch);
     static int wide = -1;                                           // AWSEG_STATS_WIDE=0: 256 threads x 4 pixels per lane (A/B measurements)
     if (wide < 0) { const char* e = getenv("AWSEG_STATS_WIDE"); wide = e ? atoi(e) : 1; }
@@ -742,12 +721,7 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
     hipLaunchKernelGGL(ece_fold_kernel, dim3((unsigned)batch), dim3(64), 0, s, (const ece_cell*)workspace, bpi, n_bins, cond,
                        n_slots, (ece_out*)ece_bins);
     AWSEG_LAUNCH_CHECK();
-    if (conf) {
-        hipLaunchKernelGGL(fold_partials_kernel, dim3((unsigned)batch, (19 * 19 + 63) / 64), dim3(kFoldSlices * 64), 0, s, conf_partial, bpi,
-                           19 * 19, cond, count_slots, counts);
-        AWSEG_LAUNCH_CHECK();
-    }
-    return 0;
+    return conf ? awseg_fold_u32_launch(conf_partial, batch, bpi, 19 * 19, cond, count_slots, true, counts, s) : 0;
 }
 
 AWSEG_API int awseg_ensemble_eval_stats(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,

@@ -252,7 +252,6 @@ int64_t tiles_of(int64_t n, int tile)                                      // ti
     return centres < 1 ? 1 : (centres + tile - 1) / tile;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool is_finite(float v) { return v >= -FLT_MAX && v <= FLT_MAX; }
 
 }  // namespace
@@ -291,7 +290,7 @@ AWSEG_API int awseg_image_quality(const float* image, const float* ref_images, i
     hipStream_t s = awseg_s(stream);
     const int tiles_x = (int)tiles_of(width, kTW);
     const int tiles = (int)(tiles_of(height, kTH) * tiles_x);                  // the count the workspace query assumed
-    const bool vec = (width % 4 == 0) && aligned16(image) && aligned16(ref_images);
+    const bool vec = (width % 4 == 0) && awseg_aligned(image, 16) && awseg_aligned(ref_images, 16);
     long long* partial = (long long*)workspace;
     dim3 grid((unsigned)tiles, (unsigned)batch), block(kThreads);
     auto kern = vec ? image_quality_kernel<true> : image_quality_kernel<false>;

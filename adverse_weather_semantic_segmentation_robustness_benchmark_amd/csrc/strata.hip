@@ -4,22 +4,22 @@
 // |image - ref| * scale, stratum = the number of edges <= change.  25 B/px of traffic at three channels (2 x 3 x 4 in, 1 out) and a
 // handful of compares: four pixels per lane from 16-byte loads and one packed 4-byte store when the rows allow, scalar otherwise.
 //
-// awseg_stratified_stats: the consistency scan (consistency.hip: 16 pixels per lane, 16-byte loads or byte loads) with one more
-// byte per pixel, the stratum, which selects the counter row: per (slot, stratum) the C x C confusion matrix of the labelled pixels,
+// awseg_stratified_stats: a map scan (awseg_mapscan.h, DESIGN.md §10j: 16 pixels per lane, 16-byte loads or byte loads) of three or
+// four maps; the stratum byte selects the counter row: per (slot, stratum) the C x C confusion matrix of the labelled pixels,
 // the four clean / corrupted transitions, the agreeing pixels and the pixel count.  Strata are connected regions (a flake, a
 // streak, the whole frame under fog), so a lane keeps the six small counters of its current stratum in registers and touches the
 // per-block LDS histogram only when the stratum changes; confusion cells are merged into runs in the same way (measured against one
 // LDS atomic per counter and pixel at 8 x 1024 x 2048: 0.045 against 0.146 ms on coherent maps, 0.048 against 0.047 ms on independent
-// random ones; profiles/strata_kernel_bench_hip_events.log).  Blocks write uint32 partials, awseg_fold_u32_partials_kernel folds
-// them into the int64 counters: integer sums only.
-#include "awseg_common.h"
+// random ones; profiles/strata_kernel_bench_hip_events.log).  Blocks write uint32 partials, the shared fold adds them into the
+// int64 counters: integer sums only.
+#include "awseg_mapscan.h"
 #include <float.h>
 
 namespace {
 
 constexpr int kChangeThreads = 256;
-constexpr int kStatThreads = 512;                                          // two resident blocks per CU: the partials stay small
-constexpr int kPer = 16;                                                   // pixels per lane per step (stratified_stats)
+constexpr int kStatThreads = 512, kStatResident = 2;                       // two resident blocks per CU: the partials stay small
+constexpr int kPer = kAwsegScanPer;                                        // pixels per lane per step (stratified_stats)
 constexpr int kSmall = 6;                                                  // cc, cw, wc, ww, agree, pixels
 
 struct change_args {
@@ -102,13 +102,6 @@ void change_strata_kernel(const float* __restrict__ image, const float* __restri
     }
 }
 
-__device__ __forceinline__ void unpack16(const uint4 q, int (&v)[kPer])
-{
-    const uint32_t w[4] = { q.x, q.y, q.z, q.w };
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) v[k] = (int)((w[k >> 2] >> ((k & 3) * 8)) & 0xFF);
-}
-
 // The six small counters of one stratum, kept in registers while a lane stays inside it.
 struct small_run {
     int s = -1;
@@ -133,7 +126,7 @@ void stratified_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restri
 {
     extern __shared__ uint32_t hist[];
     const int bins = C * C, row = bins + kSmall, total = (K + 1) * row;
-    for (int i = threadIdx.x; i < total; i += kStatThreads) hist[i] = 0u;
+    awseg_scan_zero<kStatThreads>(hist, total);
     __syncthreads();
     const int64_t img = blockIdx.y;
     const int r = PAIRED ? frame_ref[img] : 0;
@@ -142,39 +135,17 @@ void stratified_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restri
         const uint8_t* pp = pred + img * hw;
         const uint8_t* sp = stratum + img * hw;
         const uint8_t* rp = PAIRED ? ref_maps + (int64_t)r * hw : nullptr;
-        const int64_t lb = img * hw;
         const int64_t nchunk = (hw + kPer - 1) / kPer;
         small_run sm;
-        int run_idx = -1;                                                  // run of equal confusion cells (stratum included)
-        uint32_t run = 0;
+        awseg_run<int> run;                                                // run of equal confusion cells (stratum included)
+        const auto flush = [&](int idx, uint32_t n) { atomicAdd(&hist[idx], n); };
         for (int64_t ch = (int64_t)blockIdx.x * kStatThreads + threadIdx.x; ch < nchunk; ch += (int64_t)gridDim.x * kStatThreads) {
             const int64_t base = ch * kPer;
             int pv[kPer], sv[kPer], rv[kPer];
             int64_t lv[kPer];
-            if constexpr (VEC) {
-                unpack16(*reinterpret_cast<const uint4*>(pp + base), pv);
-                unpack16(*reinterpret_cast<const uint4*>(sp + base), sv);
-                if constexpr (PAIRED) unpack16(*reinterpret_cast<const uint4*>(rp + base), rv);
-                if constexpr (LDT == AWSEG_U8) {
-                    int l8[kPer];
-                    unpack16(*reinterpret_cast<const uint4*>((const uint8_t*)label + lb + base), l8);
-#pragma unroll
-                    for (int k = 0; k < kPer; ++k) lv[k] = l8[k];
-                } else {
-                    const longlong2* lp = reinterpret_cast<const longlong2*>((const int64_t*)label + lb + base);
-#pragma unroll
-                    for (int k = 0; k < kPer / 2; ++k) { const longlong2 q = lp[k]; lv[2 * k] = q.x; lv[2 * k + 1] = q.y; }
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < kPer; ++k) {
-                    const bool in = base + k < hw;
-                    pv[k] = in ? (int)pp[base + k] : 0;
-                    sv[k] = in ? (int)sp[base + k] : 0;
-                    if constexpr (PAIRED) rv[k] = in ? (int)rp[base + k] : 0;
-                    lv[k] = in ? awseg_ld_label<LDT>(label, lb + base + k) : (int64_t)ignore_index;
-                }
-            }
+            const awseg_map16 pm{ pp, pv }, smap{ sp, sv }, rm{ rp, rv };
+            if constexpr (PAIRED) awseg_load_chunk16<LDT, VEC>(label, img * hw, base, hw, ignore_index, lv, pm, smap, rm);
+            else awseg_load_chunk16<LDT, VEC>(label, img * hw, base, hw, ignore_index, lv, pm, smap);
 #pragma unroll
             for (int k = 0; k < kPer; ++k) {
                 if (!VEC && base + k >= hw) break;
@@ -186,9 +157,7 @@ void stratified_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restri
                 if constexpr (PAIRED) sm.n[4] += pk == rk;
                 const int64_t t = lv[k];
                 if (t != ignore_index && t >= 0 && t < C) {
-                    const int idx = s * row + (int)t * C + pk;
-                    if (idx == run_idx) ++run;
-                    else { if (run) atomicAdd(&hist[run_idx], run); run_idx = idx; run = 1; }
+                    run.add(s * row + (int)t * C + pk, flush);
                     if constexpr (PAIRED) {
                         const uint32_t rc = (int64_t)rk == t, vc = (int64_t)pk == t;
                         sm.n[0] += rc & vc; sm.n[1] += rc & (vc ^ 1u); sm.n[2] += (rc ^ 1u) & vc; sm.n[3] += (rc ^ 1u) & (vc ^ 1u);
@@ -196,30 +165,16 @@ void stratified_kernel(const uint8_t* __restrict__ pred, const uint8_t* __restri
                 }
             }
         }
-        if (run) atomicAdd(&hist[run_idx], run);
+        run.finish(flush);
         sm.flush(hist, row, bins);
-    } else if (r >= n_refs && blockIdx.x == 0 && threadIdx.x == 0) {
-        atomicAdd((unsigned long long*)oob, (unsigned long long)hw);      // a row index the reference maps do not have: frame not counted
+    } else if (r >= n_refs) {
+        awseg_scan_row_outside(hw, oob);                                   // a row index the reference maps do not have: frame not counted
     }
-    bad = awseg_wave_sum_u32(bad);
-    if ((threadIdx.x & (AWSEG_WAVE - 1)) == 0 && bad) atomicAdd((unsigned long long*)oob, (unsigned long long)bad);
-    __syncthreads();
-    uint32_t* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * total;
-    for (int i = threadIdx.x; i < total; i += kStatThreads) dst[i] = hist[i];
+    awseg_scan_count_bad(bad, oob);
+    awseg_scan_store<kStatThreads>(hist, total, partial);
 }
 
-int strata_blocks_per_image(int64_t hw, int64_t batch)
-{
-    // 256 CUs x 2 resident 512-thread blocks over the whole batch, grid-stride beyond
-    int64_t want = ((hw + kPer - 1) / kPer + kStatThreads - 1) / kStatThreads;
-    int64_t cap = (AWSEG_CUS * 2 + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
-bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+int strata_blocks_per_image(int64_t hw, int64_t batch) { return awseg_blocks_per_image((hw + kPer - 1) / kPer, kStatThreads, batch, kStatResident); }
 
 }  // namespace
 
@@ -243,7 +198,7 @@ AWSEG_API int awseg_change_strata(const float* image, const float* ref_images, i
     if (batch > 65535 || hw > INT32_MAX) return AWSEG_ERANGE;                  // grid.y
     if (batch == 0) return 0;
     hipStream_t s = awseg_s(stream);
-    const bool vec = (hw % 4 == 0) && aligned(image, 16) && aligned(ref_images, 16) && aligned(out, 4);
+    const bool vec = (hw % 4 == 0) && awseg_aligned(image, 16) && awseg_aligned(ref_images, 16) && awseg_aligned(out, 4);
     const int64_t items = vec ? hw / 4 : hw;
     int64_t cap = (AWSEG_CUS * 8 + batch - 1) / batch;
     const int bpi = awseg_grid_1d(items, kChangeThreads, (int)(cap < 1 ? 1 : cap));
@@ -290,21 +245,15 @@ AWSEG_API int awseg_stratified_stats(const uint8_t* pred, const void* label, int
     const int row = (n_strata + 1) * (num_classes * num_classes + kSmall);
     const bool paired = ref_maps != nullptr;
     if (!paired) n_refs = 1;                                                   // every frame is counted
-    const bool vec = (hw % kPer == 0) && aligned(pred, 16) && aligned(stratum, 16) && aligned(label, 16) && (!paired || aligned(ref_maps, 16));
+    const bool vec = (hw % kPer == 0) && awseg_aligned(pred, 16) && awseg_aligned(stratum, 16) && awseg_aligned(label, 16) &&
+                     (!paired || awseg_aligned(ref_maps, 16));
     uint32_t* partial = (uint32_t*)workspace;
     dim3 grid(bpi, (unsigned)batch), block(kStatThreads);
     const size_t lds = (size_t)row * sizeof(uint32_t);
-#define AWSEG_STRAT(L, V, P) \
-    hipLaunchKernelGGL((stratified_kernel<L, V, P>), grid, block, lds, s, pred, stratum, n_strata, ref_maps, n_refs, hw, frame_ref, \
-                       label, ignore_index, num_classes, partial, oob)
-#define AWSEG_STRAT_P(L, V) do { if (paired) AWSEG_STRAT(L, V, true); else AWSEG_STRAT(L, V, false); } while (0)
-    if (label_dtype == AWSEG_U8) { if (vec) AWSEG_STRAT_P(AWSEG_U8, true); else AWSEG_STRAT_P(AWSEG_U8, false); }
-    else { if (vec) AWSEG_STRAT_P(AWSEG_I64, true); else AWSEG_STRAT_P(AWSEG_I64, false); }
-#undef AWSEG_STRAT_P
-#undef AWSEG_STRAT
+    awseg_by_label(label_dtype, [&](auto L) { awseg_by_flag(vec, [&](auto V) { awseg_by_flag(paired, [&](auto P) {
+        hipLaunchKernelGGL((stratified_kernel<decltype(L)::value, decltype(V)::value, decltype(P)::value>), grid, block, lds, s, pred,
+                           stratum, n_strata, ref_maps, n_refs, hw, frame_ref, label, ignore_index, num_classes, partial, oob);
+    }); }); });
     AWSEG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(awseg_fold_u32_partials_kernel, dim3((unsigned)batch, (row + 63) / 64), dim3(kAwsegFoldSlices * 64), 0, s, partial, bpi, row,
-                       cond, n_slots, stats);
-    AWSEG_LAUNCH_CHECK();
-    return 0;
+    return awseg_fold_u32_launch(partial, batch, bpi, row, cond, n_slots, true, stats, s);
 }

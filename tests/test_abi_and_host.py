@@ -46,6 +46,37 @@ def test_python_binding_covers_header():
     _native.lib()                                          # binds every symbol; raises on drift
 
 
+def test_workspace_queries_equal_their_closed_forms():
+    """Each counter pass sizes its partials as blocks_per_image x batch x row x 4 bytes, and the launch takes the same block count
+    from the same rule (csrc/awseg_mapscan.h): enough 256- or 512-thread blocks for one item per lane, at most `resident` blocks on
+    each of 256 CUs over the whole batch, at least one."""
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd import _native
+    lib = _native.lib()
+
+    def ceil(a, b):
+        return -(-a // b)
+
+    def blocks(items, threads, batch, resident):
+        return max(1, min(ceil(items, threads), ceil(256 * resident, batch)))
+
+    assert lib.awseg_consistency_workspace(8, 19, 2097152) == 1495040
+    assert lib.awseg_strata_workspace(8, 19, 2097152, 5) == 4509696
+    frames = [(1, hw) for hw in (1, 15, 16, 17, 4095, 4096, 4097)] + [(1024, 2048)]
+    for batch in (1, 8, 9, 1024, 1025, 65535):
+        for h, w in frames:
+            hw, chunks = h * w, ceil(h * w, 16)
+            for c in (1, 7, 19, 32):
+                at = (batch, h, w, c)
+                assert lib.awseg_metrics_workspace(batch, c, hw) == blocks(hw, 256, batch, 8) * batch * (c * c * 4 + 64 * 24), at
+                assert lib.awseg_consistency_workspace(batch, c, hw) == blocks(chunks, 256, batch, 4) * batch * (c * c + 4) * 4, at
+                assert lib.awseg_frame_iou_workspace(batch, c, hw) == blocks(chunks, 256, batch, 4) * batch * 3 * c * 4, at
+                for k in (1, 5, 8):
+                    assert lib.awseg_strata_workspace(batch, c, hw, k) == blocks(chunks, 512, batch, 2) * batch * (k + 1) * (c * c + 6) * 4, at
+                tiles = ceil(h, 32) * ceil(w, 64)                      # a block per 32 x 64 tile
+                for n in (1, 4):
+                    assert lib.awseg_boundary_workspace(batch, c, h, w, n) == blocks(tiles, 1, batch, 4) * batch * (n + 1) * (c * c + 2 * c) * 4, at
+
+
 def test_library_built_from_another_header_is_refused(monkeypatch):
     """The library carries 60 bits of sha256(include/awseg.h) from its build; the binding refuses a library whose hash is not the
     hash of the header beside it (a stale .so next to newer sources would be called with the wrong arguments otherwise)."""
