@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <type_traits>
 #include "../../include/awseg.h"
 
 #define AWSEG_API extern "C" __attribute__((visibility("default")))
@@ -103,6 +104,38 @@ __device__ __forceinline__ int awseg_ece_find_bin(float conf, const float* s_edg
     for (int k = 0; k < n_bins; ++k)
         if (conf > s_edges[k] && conf <= s_edges[k + 1]) return k;
     return -1;
+}
+
+// Blocks per image of a grid (blocks_per_image, batch): enough for `lane_items` items at one per thread, at most
+// resident_per_cu resident blocks on each of 256 CUs over the whole batch (the kernels stride beyond), at least one.
+// A launch and its workspace query call this with the same arguments.
+inline int awseg_blocks_per_image(int64_t lane_items, int threads, int64_t batch, int resident_per_cu)
+{
+    int64_t want = (lane_items + threads - 1) / threads;
+    int64_t cap = (AWSEG_CUS * resident_per_cu + batch - 1) / batch;
+    if (cap < 1) cap = 1;
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    return (int)want;
+}
+
+// Template arguments from run-time values: f(std::integral_constant<int, AWSEG_U8 or AWSEG_I64>), f(std::bool_constant<flag>),
+// f(std::integral_constant<int, 0 or 2>) for AWSEG_COMBINE_WEIGHTED / AWSEG_COMBINE_MEAN (the kernels' MODE; the callers have
+// refused every other mode); the callee reads decltype(arg)::value.  Each returns what f returns.
+template <typename F> inline auto awseg_by_label(int label_dtype, F&& f)
+{
+    if (label_dtype == AWSEG_U8) return f(std::integral_constant<int, AWSEG_U8>());
+    return f(std::integral_constant<int, AWSEG_I64>());
+}
+template <typename F> inline auto awseg_by_flag(bool flag, F&& f)
+{
+    if (flag) return f(std::true_type());
+    return f(std::false_type());
+}
+template <typename F> inline auto awseg_by_combine_mode(int mode, F&& f)
+{
+    if (mode == AWSEG_COMBINE_WEIGHTED) return f(std::integral_constant<int, 0>());
+    return f(std::integral_constant<int, 2>());
 }
 
 // Philox4x32-7 counter-based generator (Salmon et al., Random123: 7 rounds pass BigCrush) for the

@@ -7,7 +7,6 @@
 // int64 counters: integer sums only, so the counts do not depend on grid shape, batch split or rank count.
 #pragma once
 #include "awseg_common.h"
-#include <type_traits>
 
 constexpr int kAwsegScanPer = 16;                                         // pixels per lane per step
 
@@ -103,33 +102,9 @@ template <int THREADS> __device__ __forceinline__ void awseg_scan_store(const ui
     for (int i = threadIdx.x; i < cells; i += THREADS) dst[i] = hist[i];
 }
 
-// Blocks per image of a grid (blocks_per_image, batch): enough for `lane_items` items at one per thread, at most
-// resident_per_cu resident blocks on each of 256 CUs over the whole batch (the kernels stride beyond), at least one.
-// A launch and its workspace query call this with the same arguments.
-inline int awseg_blocks_per_image(int64_t lane_items, int threads, int64_t batch, int resident_per_cu)
-{
-    int64_t want = (lane_items + threads - 1) / threads;
-    int64_t cap = (AWSEG_CUS * resident_per_cu + batch - 1) / batch;
-    if (cap < 1) cap = 1;
-    if (want > cap) want = cap;
-    if (want < 1) want = 1;
-    return (int)want;
-}
-
 // Fold uint32 partials [images][blocks_per_image][row] into int64 rows dst[n_rows][row] (metrics.hip; returns the launch error).
 // total = true, the condition slots: every image goes to row 0 and, where 0 <= index[img] < n_rows - 1, to row 1 + index[img]
 // (index may be null).  total = false, a table: image img goes to row index[img] where that is in [0, n_rows), nowhere otherwise.
 // slices: the waves of a fold block, each sums that share of an image's partials; 16 or 4, anything else is AWSEG_EINVAL.
 int awseg_fold_u32_launch(const uint32_t* partial, int64_t images, int blocks_per_image, int row, const int32_t* index,
                           int64_t n_rows, bool total, int64_t* dst, hipStream_t stream, int slices = 16);
-
-// Template arguments from run-time values: f(std::integral_constant<int, AWSEG_U8 or AWSEG_I64>) and f(std::bool_constant<flag>);
-// the callee reads decltype(arg)::value.
-template <typename F> inline void awseg_by_label(int label_dtype, F&& f)
-{
-    if (label_dtype == AWSEG_U8) f(std::integral_constant<int, AWSEG_U8>()); else f(std::integral_constant<int, AWSEG_I64>());
-}
-template <typename F> inline void awseg_by_flag(bool flag, F&& f)
-{
-    if (flag) f(std::true_type()); else f(std::false_type());
-}

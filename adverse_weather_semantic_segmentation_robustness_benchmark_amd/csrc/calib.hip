@@ -37,7 +37,7 @@ struct tgrid_consts { float t[kMaxTemps], s[kMaxTemps], inv[kMaxTemps]; };
 
 __device__ __forceinline__ bool is_nan(float v) { return v != v; }
 
-// torch argmax update rule (metrics.hip amax_step, used by the ensemble statistics with the confusion counts)
+// torch argmax update rule (awseg_amax_step, used by the ensemble statistics with the confusion counts)
 __device__ __forceinline__ void amax_step(float v, int c, float& best, int& bi)
 {
     if (!(v <= best) && !is_nan(best)) { best = v; bi = c; }
@@ -134,7 +134,7 @@ void tgrid_kernel(const float* __restrict__ seg1, const float* __restrict__ seg2
                 if (has_t) rv = rv / T;
                 d[c][j] = rv;
                 if (c == 0) { m[j] = rv; bi[j] = 0; }
-                else if (MODE == 3) { if (rv > m[j]) { m[j] = rv; bi[j] = c; } }   // ece19_kernel / ece_kernel
+                else if (MODE == 3) { if (rv > m[j]) { m[j] = rv; bi[j] = c; } }   // ece_kernel (metrics.hip)
                 else amax_step(rv, c, m[j], bi[j]);                              // ensemble_stats_kernel (with confusion)
             }
         }
@@ -149,7 +149,7 @@ void tgrid_kernel(const float* __restrict__ seg1, const float* __restrict__ seg2
                 d[c][j] = d[c][j] - m[j];
                 if ((int64_t)c == y[j]) dy[j] = d[c][j];
             }
-            // the correctness test of the kernel reproduced: ece19 / ensemble compare with (int)label, ece_kernel in int64
+            // the correctness test of the kernel reproduced: ece_kernel on registers / ensemble compare with (int)label, its strided form in int64
             correct[j] = (PX == 4 || MODE != 3) ? (bi[j] == (int)y[j]) : ((int64_t)bi[j] == y[j]);
         }
         {   // temperature-independent block counters: pixels entering the NLL, out-of-range labels (ECE only)
@@ -281,28 +281,27 @@ int check_common(int64_t batch, int num_classes, int64_t hw, const void* label, 
     return 0;
 }
 
+struct tgrid_launch {                                     // the arguments of one entry point, as the kernel takes them
+    const float *seg1, *seg2; int64_t batch; int C; int64_t hw; const float *weights, *temperature; const void* label;
+    const int32_t* cond; const float* temps; int n_temps; const float* edges; int n_bins; int64_t* stats; int n_slots; hipStream_t s;
+};
+
 template <int MODE, int LDT, int PX, int CT, int CMAX>
-int launch_chunks(const float* seg1, const float* seg2, int64_t batch, int C, int64_t hw, const float* weights,
-                  const float* temperature, const void* label, const int32_t* cond, const float* temps, int n_temps,
-                  const float* edges, int n_bins, int64_t* stats, int n_slots, hipStream_t s)
+int launch_chunks(const tgrid_launch& g)
 {
     auto kern = tgrid_kernel<MODE, LDT, PX, CT, CMAX>;
-    int kc_max = n_temps;
-    while (kc_max > 1 && lds_bytes(kc_max, n_bins) > kLdsBudget) --kc_max;
-    int64_t bpi = (hw / PX + kThreads - 1) / kThreads;
-    const int64_t cap = (AWSEG_CUS * kBlocksPerCU + batch - 1) / batch;
-    if (bpi > cap) bpi = cap;
-    if (bpi < 1) bpi = 1;
-    dim3 grid((unsigned)bpi, (unsigned)batch), block(kThreads);
-    for (int k0 = 0; k0 < n_temps; k0 += kc_max) {          // more temperatures x bins than the LDS budget holds: re-read the logits
-        const int kc = n_temps - k0 < kc_max ? n_temps - k0 : kc_max;
+    int kc_max = g.n_temps;
+    while (kc_max > 1 && lds_bytes(kc_max, g.n_bins) > kLdsBudget) --kc_max;
+    dim3 grid((unsigned)awseg_blocks_per_image(g.hw / PX, kThreads, g.batch, kBlocksPerCU), (unsigned)g.batch), block(kThreads);
+    for (int k0 = 0; k0 < g.n_temps; k0 += kc_max) {        // more temperatures x bins than the LDS budget holds: re-read the logits
+        const int kc = g.n_temps - k0 < kc_max ? g.n_temps - k0 : kc_max;
         tgrid_consts tc;
         for (int k = 0; k < kMaxTemps; ++k) {
-            const float t = k < kc ? temps[k0 + k] : 1.0f;
+            const float t = k < kc ? g.temps[k0 + k] : 1.0f;
             tc.t[k] = t; tc.s[k] = kLog2e / t; tc.inv[k] = 1.0f / t;
         }
-        hipLaunchKernelGGL(kern, grid, block, lds_bytes(kc, n_bins), s, seg1, seg2, C, hw, weights, temperature, label, tc, k0, kc,
-                           n_temps, edges, n_bins, cond, n_slots, (long long*)stats);
+        hipLaunchKernelGGL(kern, grid, block, lds_bytes(kc, g.n_bins), g.s, g.seg1, g.seg2, g.C, g.hw, g.weights, g.temperature, g.label, tc,
+                           k0, kc, g.n_temps, g.edges, g.n_bins, g.cond, g.n_slots, (long long*)g.stats);
         AWSEG_LAUNCH_CHECK();
     }
     return 0;
@@ -316,17 +315,17 @@ AWSEG_API int awseg_temperature_grid_stats(const float* logits, int64_t batch, i
 {
     if (!logits) return AWSEG_EINVAL;
     if (int rc = check_common(batch, num_classes, hw, label, label_dtype, temps, n_temps, edges, n_bins, stats, n_slots)) return rc;
-    hipStream_t s = awseg_s(stream);
-    const bool vec19 = (num_classes == 19) && !(hw & 3) && awseg_aligned(logits, 16);   // the ece19_kernel condition
-    const bool u8 = label_dtype == AWSEG_U8;
-#define AWSEG_TG(L, PX, CT, CM) launch_chunks<3, L, PX, CT, CM>(logits, nullptr, batch, num_classes, hw, nullptr, nullptr, label, cond, \
-                                                                  temps, n_temps, edges, n_bins, stats, n_slots, s)
-    if (vec19) return u8 ? AWSEG_TG(AWSEG_U8, 4, 19, 19) : AWSEG_TG(AWSEG_I64, 4, 19, 19);
-    if (num_classes <= 8) return u8 ? AWSEG_TG(AWSEG_U8, 1, 0, 8) : AWSEG_TG(AWSEG_I64, 1, 0, 8);
-    if (num_classes <= 16) return u8 ? AWSEG_TG(AWSEG_U8, 1, 0, 16) : AWSEG_TG(AWSEG_I64, 1, 0, 16);
-    if (num_classes <= 32) return u8 ? AWSEG_TG(AWSEG_U8, 1, 0, 32) : AWSEG_TG(AWSEG_I64, 1, 0, 32);
-    return u8 ? AWSEG_TG(AWSEG_U8, 1, 0, 64) : AWSEG_TG(AWSEG_I64, 1, 0, 64);
-#undef AWSEG_TG
+    const tgrid_launch g = { logits, nullptr, batch, num_classes, hw, nullptr, nullptr, label, cond, temps, n_temps, edges, n_bins, stats,
+                             n_slots, awseg_s(stream) };
+    const bool vec19 = (num_classes == 19) && !(hw & 3) && awseg_aligned(logits, 16);   // the ECE's condition for its vector kernel
+    return awseg_by_label(label_dtype, [&](auto L) {
+        constexpr int l = decltype(L)::value;
+        if (vec19) return launch_chunks<3, l, 4, 19, 19>(g);
+        if (num_classes <= 8) return launch_chunks<3, l, 1, 0, 8>(g);
+        if (num_classes <= 16) return launch_chunks<3, l, 1, 0, 16>(g);
+        if (num_classes <= 32) return launch_chunks<3, l, 1, 0, 32>(g);
+        return launch_chunks<3, l, 1, 0, 64>(g);
+    });
 }
 
 AWSEG_API int awseg_ensemble_temperature_grid_stats(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,
@@ -341,11 +340,9 @@ AWSEG_API int awseg_ensemble_temperature_grid_stats(const float* seg1, const flo
     if (mode != AWSEG_COMBINE_WEIGHTED && mode != AWSEG_COMBINE_MEAN) return AWSEG_ERANGE;
     if (mode == AWSEG_COMBINE_WEIGHTED && !weights) return AWSEG_EINVAL;
     if ((hw & 3) || !awseg_aligned(seg1, 16) || !awseg_aligned(seg2, 16)) return AWSEG_EALIGN;
-    hipStream_t s = awseg_s(stream);
-    const bool u8 = label_dtype == AWSEG_U8;
-#define AWSEG_TGE(M, L) launch_chunks<M, L, 4, 19, 19>(seg1, seg2, batch, 19, hw, weights, temperature, label, cond, temps, n_temps, \
-                                                       edges, n_bins, stats, n_slots, s)
-    if (mode == AWSEG_COMBINE_WEIGHTED) return u8 ? AWSEG_TGE(0, AWSEG_U8) : AWSEG_TGE(0, AWSEG_I64);
-    return u8 ? AWSEG_TGE(2, AWSEG_U8) : AWSEG_TGE(2, AWSEG_I64);
-#undef AWSEG_TGE
+    const tgrid_launch g = { seg1, seg2, batch, 19, hw, weights, temperature, label, cond, temps, n_temps, edges, n_bins, stats, n_slots,
+                             awseg_s(stream) };
+    return awseg_by_combine_mode(mode, [&](auto M) { return awseg_by_label(label_dtype, [&](auto L) {
+        return launch_chunks<decltype(M)::value, decltype(L)::value, 4, 19, 19>(g);
+    }); });
 }

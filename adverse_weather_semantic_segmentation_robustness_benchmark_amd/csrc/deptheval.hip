@@ -198,20 +198,14 @@ AWSEG_API int awseg_depth_eval_stats(const float* d1, const float* d2_low, int b
     if (batch > 65535 || hw > INT32_MAX || (d2_low && (int64_t)low_height * low_width > INT32_MAX)) return AWSEG_ERANGE;
     const bool vec = !(width & 3) && awseg_aligned(d1, 16) && awseg_aligned(target, 16);
     // 256 CUs x 8 resident blocks over the whole batch, grid-stride beyond (a lane then walks 8 steps at 8 x 1024 x 2048)
-    const int64_t items = vec ? hw / 4 : hw;
-    int64_t bpi = (items + kThreads - 1) / kThreads;
-    const int64_t cap = (AWSEG_CUS * 8 + batch - 1) / batch;
-    if (bpi > cap) bpi = cap;
-    dim3 grid((unsigned)bpi, (unsigned)batch), block(kThreads);
+    dim3 grid((unsigned)awseg_blocks_per_image(vec ? hw / 4 : hw, kThreads, batch, 8), (unsigned)batch), block(kThreads);
     // torch area_pixel_compute_scale(in, out, align_corners=false, scale=None) = (float)in / out, as awseg_depth_upsample_combine
     const float sy = d2_low ? (float)low_height / (float)height : 1.f, sx = d2_low ? (float)low_width / (float)width : 1.f;
     hipStream_t s = awseg_s(stream);
-#define AWSEG_DE(NS, PX) \
-    hipLaunchKernelGGL((depth_eval_kernel<NS, PX>), grid, block, 0, s, d1, d2_low, low_height, low_width, height, width, sy, sx, weights, \
-                       target, min_depth, cond, n_slots, (long long*)stats)
-    if (d2_low) { if (vec) AWSEG_DE(3, 4); else AWSEG_DE(3, 1); }
-    else { if (vec) AWSEG_DE(1, 4); else AWSEG_DE(1, 1); }
-#undef AWSEG_DE
+    awseg_by_flag(d2_low != nullptr, [&](auto THREE) { awseg_by_flag(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((depth_eval_kernel<decltype(THREE)::value ? 3 : 1, decltype(VEC)::value ? 4 : 1>), grid, block, 0, s, d1, d2_low,
+                           low_height, low_width, height, width, sy, sx, weights, target, min_depth, cond, n_slots, (long long*)stats);
+    }); });
     AWSEG_LAUNCH_CHECK();
     return 0;
 }

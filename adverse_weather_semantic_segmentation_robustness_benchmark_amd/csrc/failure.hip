@@ -107,7 +107,7 @@ void failure_kernel(const float* __restrict__ seg1, const float* __restrict__ se
             int b_ent, b_msp, f_mean, f_r;                  // bins and error flags
             int b_mi = 0, b_var = 0;
             if constexpr (MODE == 3) {
-                // softmax(logits): the maximum, exponentials and their sum in class order as ece_kernel / ece19_kernel form them
+                // softmax(logits): the maximum, exponentials and their sum in class order as ece_kernel (metrics.hip) forms them
                 float m = x[0][k]; int bi = 0;
 #pragma unroll
                 for (int c = 0; c < CMAX; ++c) {
@@ -226,35 +226,36 @@ void failure_kernel(const float* __restrict__ seg1, const float* __restrict__ se
     }
 }
 
+struct fail_launch {                                      // the arguments of one entry point, as the kernel takes them
+    const float *seg1, *seg2, *comb; int64_t batch; int C; int64_t hw; const float *weights, *temperature; const void* label;
+    const int32_t* cond; int64_t* stats; int n_slots; hipStream_t s;
+};
+
 template <int MODE, int LDT, int TH, int PX, int CT, int CMAX>
-int launch(const float* seg1, const float* seg2, const float* comb, int64_t batch, int C, int64_t hw, const float* weights,
-           const float* temperature, const void* label, const int32_t* cond, int64_t* stats, int n_slots, hipStream_t s)
+int launch(const fail_launch& g)
 {
     auto kern = failure_kernel<MODE, LDT, TH, PX, CT, CMAX>;
     constexpr int NR = MODE == 3 ? 2 : AWSEG_FAIL_SCORES;
     const size_t lds = ((size_t)NR * kCells + 3) * sizeof(uint32_t);
     // resident blocks per CU: one 96 KB histogram (ensemble); two 512-thread blocks of the single kernel (48 KB each; its
     // 102 registers at C = 19 allow four waves per SIMD)
-    const int per_cu = MODE == 3 ? 2 : 1;
-    int64_t bpi = (hw / PX + TH - 1) / TH;
-    const int64_t cap = (AWSEG_CUS * per_cu + batch - 1) / batch;
-    if (bpi > cap) bpi = cap;
-    if (bpi < 1) bpi = 1;
+    const int bpi = awseg_blocks_per_image(g.hw / PX, TH, g.batch, MODE == 3 ? 2 : 1);
     // (per launch, not once: the attribute belongs to the current device's copy of the kernel)
     if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds))
         return (int)e;
-    hipLaunchKernelGGL(kern, dim3((unsigned)bpi, (unsigned)batch), dim3(TH), lds, s, seg1, seg2, comb, C, hw, weights, temperature,
-                       label, cond, n_slots, (long long*)stats);
+    hipLaunchKernelGGL(kern, dim3((unsigned)bpi, (unsigned)g.batch), dim3(TH), lds, g.s, g.seg1, g.seg2, g.comb, g.C, g.hw, g.weights,
+                       g.temperature, g.label, g.cond, g.n_slots, (long long*)g.stats);
     AWSEG_LAUNCH_CHECK();
     return 0;
 }
 
-template <int MODE, int LDT>
-int launch_ensemble(int C, const float* seg1, const float* seg2, const float* comb, int64_t batch, int64_t hw, const float* weights,
-                    const float* temperature, const void* label, const int32_t* cond, int64_t* stats, int n_slots, hipStream_t s)
+template <int MODE>
+int launch_ensemble(const fail_launch& g, int label_dtype)
 {
-    if (C == 19) return launch<MODE, LDT, 1024, 1, 19, 19>(seg1, seg2, comb, batch, C, hw, weights, temperature, label, cond, stats, n_slots, s);
-    return launch<MODE, LDT, 512, 1, 0, AWSEG_MAX_CLASSES>(seg1, seg2, comb, batch, C, hw, weights, temperature, label, cond, stats, n_slots, s);
+    return awseg_by_label(label_dtype, [&](auto L) {
+        if (g.C == 19) return launch<MODE, decltype(L)::value, 1024, 1, 19, 19>(g);
+        return launch<MODE, decltype(L)::value, 512, 1, 0, AWSEG_MAX_CLASSES>(g);
+    });
 }
 
 int check_common(int64_t batch, int num_classes, int64_t hw, const void* label, int label_dtype, const int64_t* stats, int n_slots)
@@ -279,16 +280,9 @@ AWSEG_API int awseg_ensemble_failure_stats(const float* seg1, const float* seg2,
     }
     if (num_classes > AWSEG_MAX_CLASSES || hw > INT32_MAX || batch > 65535) return AWSEG_ERANGE;
     if (batch == 0) return 0;
-    hipStream_t s = awseg_s(stream);
-    const bool u8 = label_dtype == AWSEG_U8;
-#define AWSEG_FE(M) (u8 ? launch_ensemble<M, AWSEG_U8>(num_classes, seg1, seg2, combined, batch, hw, weights, temperature, label, cond, \
-                                                       stats, n_slots, s)                                                             \
-                        : launch_ensemble<M, AWSEG_I64>(num_classes, seg1, seg2, combined, batch, hw, weights, temperature, label, cond, \
-                                                        stats, n_slots, s))
-    if (combined) return AWSEG_FE(4);
-    if (mode == AWSEG_COMBINE_WEIGHTED) return AWSEG_FE(0);
-    return AWSEG_FE(2);
-#undef AWSEG_FE
+    const fail_launch g = { seg1, seg2, combined, batch, num_classes, hw, weights, temperature, label, cond, stats, n_slots, awseg_s(stream) };
+    if (combined) return launch_ensemble<4>(g, label_dtype);
+    return awseg_by_combine_mode(mode, [&](auto M) { return launch_ensemble<decltype(M)::value>(g, label_dtype); });
 }
 
 AWSEG_API int awseg_failure_stats(const float* logits, int64_t batch, int num_classes, int64_t hw, const void* label, int label_dtype,
@@ -298,15 +292,12 @@ AWSEG_API int awseg_failure_stats(const float* logits, int64_t batch, int num_cl
     if (int rc = check_common(batch, num_classes, hw, label, label_dtype, stats, n_slots)) return rc;
     if (num_classes > AWSEG_CALIB_MAX_CLASSES || hw > INT32_MAX || batch > 65535) return AWSEG_ERANGE;
     if (batch == 0) return 0;
-    hipStream_t s = awseg_s(stream);
+    const fail_launch g = { logits, nullptr, nullptr, batch, num_classes, hw, nullptr, nullptr, label, cond, stats, n_slots, awseg_s(stream) };
     const bool vec = num_classes == 19 && !(hw & 3) && awseg_aligned(logits, 16);
-    const bool u8 = label_dtype == AWSEG_U8;
-#define AWSEG_FS(TH, PX, CT, CM) (u8 ? launch<3, AWSEG_U8, TH, PX, CT, CM>(logits, nullptr, nullptr, batch, num_classes, hw, nullptr, nullptr, \
-                                                                          label, cond, stats, n_slots, s)                                   \
-                                     : launch<3, AWSEG_I64, TH, PX, CT, CM>(logits, nullptr, nullptr, batch, num_classes, hw, nullptr, nullptr, \
-                                                                           label, cond, stats, n_slots, s))
-    if (vec) return AWSEG_FS(512, 4, 19, 19);
-    if (num_classes <= 32) return AWSEG_FS(512, 1, 0, 32);
-    return AWSEG_FS(512, 1, 0, 64);
-#undef AWSEG_FS
+    return awseg_by_label(label_dtype, [&](auto L) {
+        constexpr int l = decltype(L)::value;
+        if (vec) return launch<3, l, 512, 4, 19, 19>(g);
+        if (num_classes <= 32) return launch<3, l, 512, 1, 0, 32>(g);
+        return launch<3, l, 512, 1, 0, 64>(g);
+    });
 }

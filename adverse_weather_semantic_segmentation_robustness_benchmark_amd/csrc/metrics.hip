@@ -14,15 +14,13 @@
 // folded into the caller's int64 counters by a tiny second launch (awseg_mapscan.h) — no same-address
 // global atomics on the streaming path, and the result is order-independent (integers).
 #include "awseg_mapscan.h"
+#include "awseg_logitscan.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kResident = 8;                                              // blocks per CU the streaming grids are capped at
 constexpr int kMaxBins = AWSEG_MAX_CLASSES * AWSEG_MAX_CLASSES;
-
-// torch argmax update rule (awseg_common.h, shared with the prediction maps consistency.hip compares)
-__device__ __forceinline__ void amax_step(float v, int c, float& best, int& bi) { awseg_amax_step(v, c, best, bi); }
 
 template <int LDT>
 __device__ __forceinline__ void hist_add(uint32_t* hist, const void* label, int64_t li, int pred,
@@ -107,7 +105,7 @@ void combine_argmax_confusion_kernel(const float* __restrict__ seg1, const float
 #pragma unroll kUnroll
         for (int c = 0; c < C; ++c) {
             float x[VEC], y[VEC], r[VEC];
-            if constexpr (VEC == 4) {
+            if constexpr (VEC == 4) {                        // (its own loads: through awseg_load_px the kernel schedules differently)
                 float4 xv = *reinterpret_cast<const float4*>(a + (int64_t)c * hw + p);
                 x[0] = xv.x; x[1] = xv.y; x[2] = xv.z; x[3] = xv.w;
                 if (MODE != 3) {
@@ -120,14 +118,13 @@ void combine_argmax_confusion_kernel(const float* __restrict__ seg1, const float
             }
 #pragma unroll
             for (int k = 0; k < VEC; ++k) {
-                // four separately rounded float32 operations (built with -ffp-contract=off)
-                if (MODE == 0) { float u = w0 * x[k]; float t = w1 * y[k]; r[k] = u + t; }
-                else if (MODE == 1) { float u = use[k] * x[k]; float t = (1.f - use[k]) * y[k]; r[k] = u + t; }
-                else if (MODE == 2) { float u = x[k] + y[k]; r[k] = u / 2.f; }
-                else r[k] = x[k];
-                if (MODE != 3 && has_t) r[k] = r[k] / T;
+                if constexpr (MODE == 0 || MODE == 2) r[k] = awseg_combine<MODE>(x[k], y[k], w0, w1, has_t, T);
+                else if constexpr (MODE == 1) {              // separately rounded, as awseg_combine
+                    float u = use[k] * x[k]; float t = (1.f - use[k]) * y[k]; r[k] = u + t;
+                    if (has_t) r[k] = r[k] / T;
+                } else r[k] = x[k];
                 if (c == 0) { best[k] = r[k]; bi[k] = 0; }
-                else amax_step(r[k], c, best[k], bi[k]);
+                else awseg_amax_step(r[k], c, best[k], bi[k]);
             }
             if (o) {
                 if constexpr (VEC == 4) *reinterpret_cast<float4*>(o + (int64_t)c * hw + p) = make_float4(r[0], r[1], r[2], r[3]);
@@ -248,63 +245,16 @@ void confusion_kernel(const void* __restrict__ pred, const void* __restrict__ la
 // multiple of 2^-30, so conf * 2^30 is an exact integer and integer sums do not depend on the order of the atomics, the
 // block schedule or the number of ranks the counters are later all-reduced over (results identical at any
 // GPU count).  2^33 pixels fit.  Block partials: [nblk][n_bins] x {uint32 cnt, uint32 correct, uint64 sum_conf_q30}.
+// The fixed point and the (lo, hi] bin rule (awseg_conf_q30, awseg_ece_find_bin) are shared with calib.hip, whose temperature
+// grid reproduces these bins bit for bit at t = 1.
 // ---------------------------------------------------------------------------------------
 struct ece_cell { uint32_t cnt; uint32_t correct; unsigned long long sum_conf; };
-// the 2^-30 fixed point and the (lo, hi] bin rule are shared with calib.hip (awseg_common.h), whose temperature grid
-// reproduces these bins bit for bit at t = 1
-__device__ __forceinline__ unsigned long long conf_q30(float conf) { return awseg_conf_q30(conf); }
-__device__ __forceinline__ int ece_find_bin(float conf, const float* s_edges, int n_bins) { return awseg_ece_find_bin(conf, s_edges, n_bins); }
 
-// C = 19, hw % 4 == 0: four pixels per lane, the 19 x 4 logits of a lane live in registers (one 16-byte load per class
-// plane instead of two 4-byte passes), fast exponentials.
-template <int LDT>
-__global__ __launch_bounds__(kThreads)
-void ece19_kernel(const float* __restrict__ logits, int64_t hw, const void* __restrict__ label,
-                  const float* __restrict__ edges, int n_bins, ece_cell* __restrict__ partial)
-{
-    constexpr int C = 19;
-    __shared__ uint32_t s_cnt[64], s_cor[64];
-    __shared__ unsigned long long s_sum[64];
-    __shared__ float s_edges[65];
-    for (int i = threadIdx.x; i < n_bins; i += kThreads) { s_cnt[i] = 0; s_cor[i] = 0; s_sum[i] = 0ull; }
-    for (int i = threadIdx.x; i <= n_bins; i += kThreads) s_edges[i] = edges[i];
-    __syncthreads();
-    const int64_t img = blockIdx.y;
-    const float* x = logits + img * C * hw;
-    const int64_t nvec = hw / 4;
-    for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kThreads) {
-        const int64_t p = v * 4;
-        float4 xv[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) xv[c] = *reinterpret_cast<const float4*>(x + (int64_t)c * hw + p);
-        int64_t t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] = awseg_ld_label<LDT>(label, img * hw + p + k);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (t[k] == 255) continue;                    // metrics.py:170 hard-codes 255
-            auto at = [&](int c) { return k == 0 ? xv[c].x : (k == 1 ? xv[c].y : (k == 2 ? xv[c].z : xv[c].w)); };
-            float m = at(0); int bi = 0;
-#pragma unroll
-            for (int c = 1; c < C; ++c) { const float q = at(c); if (q > m) { m = q; bi = c; } }
-            float sum = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) sum += __expf(at(c) - m);
-            const float conf = 1.0f / sum;
-            const int b = ece_find_bin(conf, s_edges, n_bins);
-            if (b >= 0) {
-                atomicAdd(&s_cnt[b], 1u);
-                if (bi == (int)t[k]) atomicAdd(&s_cor[b], 1u);
-                atomicAdd(&s_sum[b], conf_q30(conf));
-            }
-        }
-    }
-    __syncthreads();
-    ece_cell* dst = partial + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * n_bins;
-    for (int i = threadIdx.x; i < n_bins; i += kThreads) { dst[i].cnt = s_cnt[i]; dst[i].correct = s_cor[i]; dst[i].sum_conf = s_sum[i]; }
-}
-
-template <int LDT>
+// PX = 4, CT = 19 (C = 19, hw % 4 == 0, a 16-byte aligned base): four pixels per lane, the 19 x 4 logits of a lane live in
+// registers (one 16-byte load per class plane instead of two 4-byte passes).  PX = 1, CT = 0: any C and hw, the logits read twice.
+// Both form the softmax head with the SAME exponential and summation order (one text below): which of the two runs depends
+// on hw % 4 and on the pointer's alignment, and a view of the same logits must land in the same bins.
+template <int LDT, int PX, int CT>
 __global__ __launch_bounds__(kThreads)
 void ece_kernel(const float* __restrict__ logits, int C, int64_t hw, const void* __restrict__ label,
                 const float* __restrict__ edges, int n_bins, ece_cell* __restrict__ partial)
@@ -315,25 +265,38 @@ void ece_kernel(const float* __restrict__ logits, int C, int64_t hw, const void*
     for (int i = threadIdx.x; i < n_bins; i += kThreads) { s_cnt[i] = 0; s_cor[i] = 0; s_sum[i] = 0ull; }
     for (int i = threadIdx.x; i <= n_bins; i += kThreads) s_edges[i] = edges[i];
     __syncthreads();
+    if (CT > 0) C = CT;
+    const auto add = [&](float conf, bool correct) {     // bins (lo, hi] on the reference's float32 linspace (metrics.py:179-188)
+        const int b = awseg_ece_find_bin(conf, s_edges, n_bins);
+        if (b >= 0) {
+            atomicAdd(&s_cnt[b], 1u);
+            if (correct) atomicAdd(&s_cor[b], 1u);
+            atomicAdd(&s_sum[b], awseg_conf_q30(conf));
+        }
+    };
     const int64_t img = blockIdx.y;
     const float* x = logits + img * C * hw;
-    for (int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x; p < hw; p += (int64_t)gridDim.x * kThreads) {
-        int64_t t = awseg_ld_label<LDT>(label, img * hw + p);
-        if (t == 255) continue;                       // metrics.py:170 hard-codes 255
-        float m = x[p]; int bi = 0;
-        for (int c = 1; c < C; ++c) { float v = x[(int64_t)c * hw + p]; if (v > m) { m = v; bi = c; } }
-        float s = 0.f;
-        // the SAME exponential and summation order as ece19_kernel: which of the two kernels runs depends on hw % 4 and on the
-        // pointer's alignment, and a view of the same logits must land in the same bins
-        for (int c = 0; c < C; ++c) s += __expf(x[(int64_t)c * hw + p] - m);
-        float conf = 1.0f / s;
-        // bins are (lo, hi] on a float32 linspace (metrics.py:179-188); linear scan keeps the
-        // reference's comparison semantics exactly.
-        const int k = ece_find_bin(conf, s_edges, n_bins);
-        if (k >= 0) {
-            atomicAdd(&s_cnt[k], 1u);
-            if (bi == t) atomicAdd(&s_cor[k], 1u);
-            atomicAdd(&s_sum[k], conf_q30(conf));
+    const int64_t nvec = hw / PX;
+    for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kThreads) {
+        const int64_t p = v * PX;
+        float xv[CT > 0 ? CT : 1][PX];
+        if constexpr (CT > 0) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) awseg_load_px(x + (int64_t)c * hw + p, true, xv[c]);
+        }
+        int64_t t[PX];
+#pragma unroll
+        for (int k = 0; k < PX; ++k) t[k] = awseg_ld_label<LDT>(label, img * hw + p + k);
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+            if (t[k] == 255) continue;                    // metrics.py:170 hard-codes 255
+            const auto at = [&](int c) { if constexpr (CT > 0) return xv[c][k]; else return x[(int64_t)c * hw + p + k]; };
+            // softmax head: first maximum, exponentials summed in class order, conf = 1.0f / sum (C is a constant when CT > 0: unrolled)
+            float m = at(0), sum = 0.f; int bi = 0;
+            for (int c = 1; c < C; ++c) awseg_first_max_step(at(c), c, m, bi);
+            for (int c = 0; c < C; ++c) sum += __expf(at(c) - m);
+            // the register form compares the label as (int), the strided one in int64: kept as the two kernels had it
+            add(1.0f / sum, CT > 0 ? bi == (int)t[k] : (int64_t)bi == t[k]);
         }
     }
     __syncthreads();
@@ -419,16 +382,13 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
     if (MODE == 0) { w0 = weights[0]; w1 = weights[1]; }
     if (has_t) T = temperature[0];
     const int64_t nvec = hw / PX;
-    typedef float lvec __attribute__((ext_vector_type(PX)));
     for (int64_t v = (int64_t)blockIdx.x * TH + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * TH) {
         const int64_t p = v * PX;
         float x[C][PX], y[C][PX];
 #pragma unroll
         for (int c = 0; c < C; ++c) {
-            const lvec xv = *reinterpret_cast<const lvec*>(a + (int64_t)c * hw + p);
-            const lvec yv = *reinterpret_cast<const lvec*>(d + (int64_t)c * hw + p);
-#pragma unroll
-            for (int k = 0; k < PX; ++k) { x[c][k] = xv[k]; y[c][k] = yv[k]; }
+            awseg_load_px(a + (int64_t)c * hw + p, true, x[c]);
+            awseg_load_px(d + (int64_t)c * hw + p, true, y[c]);
         }
         uint32_t pk = 0;                                          // PRED: the PX argmax bytes, packed as they are found (one register)
 #pragma unroll
@@ -441,13 +401,11 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
             float m1 = x[0][k], m2 = y[0][k];
 #pragma unroll
             for (int c = 0; c < C; ++c) {
-                float rv;
-                if (MODE == 0) { float u = w0 * x[c][k]; float q = w1 * y[c][k]; rv = u + q; }
-                else { float u = x[c][k] + y[c][k]; rv = u / 2.f; }
-                if (has_t) rv = rv / T;
+                const float rv = awseg_combine<MODE>(x[c][k], y[c][k], w0, w1, has_t, T);
                 r[c] = rv;
-                if (CONF) { if (c == 0) { rmax = rv; rarg = 0; } else amax_step(rv, c, rmax, rarg); }   // torch's argmax rule, as the combine kernel
-                else if (c == 0 || rv > rmax) { rmax = rv; rarg = c; }
+                if (c == 0) { rmax = rv; rarg = 0; }
+                else if (CONF) awseg_amax_step(rv, c, rmax, rarg);                 // torch's argmax rule, as the combine kernel
+                else awseg_first_max_step(rv, c, rmax, rarg);
                 m1 = fmaxf(m1, x[c][k]); m2 = fmaxf(m2, y[c][k]);
             }
             if (PRED) pk |= (uint32_t)rarg << (8 * k);
@@ -458,11 +416,11 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
 #pragma unroll
             for (int c = 0; c < C; ++c) rsum += __expf(r[c] - rmax);
             const float conf = 1.0f / rsum;
-            const int eb = ece_find_bin(conf, s_edges, n_bins);
+            const int eb = awseg_ece_find_bin(conf, s_edges, n_bins);
             if (eb >= 0) {
                 atomicAdd(&s_cnt[eb], 1u);
                 if (rarg == (int)t) atomicAdd(&s_cor[eb], 1u);
-                atomicAdd(&s_sum[eb], conf_q30(conf));
+                atomicAdd(&s_sum[eb], awseg_conf_q30(conf));
             }
             // member softmaxes: the raw logits are dead from here on, their registers take the exponentials.
             // Member entropies without logarithms: p = e / z with e = exp(x - m), so log p = (x - m) - log z and
@@ -479,7 +437,6 @@ void ensemble_stats_kernel(const float* __restrict__ seg1, const float* __restri
             }
             const float i1 = 1.0f / z1, i2 = 1.0f / z2;
             const float h1 = __logf(z1) - t1 * i1, h2 = __logf(z2) - t2 * i2;
-            // disagreement (mutual information) and the error flag of the mean-probability prediction
             float hm = 0.f, mbest = -1.f; int marg = 0;
 #pragma unroll
             for (int c = 0; c < C; ++c) {
@@ -664,15 +621,11 @@ AWSEG_API int awseg_ece_accumulate(const float* logits, int64_t batch, int num_c
     const int bpi = blocks_per_image(hw, batch, vec19 ? 4 : 1);
     dim3 grid(bpi, (unsigned)batch), block(kThreads);
     if (label_dtype != AWSEG_U8 && label_dtype != AWSEG_I64) return AWSEG_EINVAL;
-    if (vec19 && label_dtype == AWSEG_U8)
-        hipLaunchKernelGGL((ece19_kernel<AWSEG_U8>), grid, block, 0, s, logits, hw, label, edges, n_bins, (ece_cell*)workspace);
-    else if (vec19)
-        hipLaunchKernelGGL((ece19_kernel<AWSEG_I64>), grid, block, 0, s, logits, hw, label, edges, n_bins, (ece_cell*)workspace);
-    else if (label_dtype == AWSEG_U8)
-        hipLaunchKernelGGL((ece_kernel<AWSEG_U8>), grid, block, 0, s, logits, num_classes, hw, label, edges, n_bins, (ece_cell*)workspace);
-    else if (label_dtype == AWSEG_I64)
-        hipLaunchKernelGGL((ece_kernel<AWSEG_I64>), grid, block, 0, s, logits, num_classes, hw, label, edges, n_bins, (ece_cell*)workspace);
-    else return AWSEG_EINVAL;
+    awseg_by_label(label_dtype, [&](auto L) { awseg_by_flag(vec19, [&](auto V) {
+        constexpr bool vec = decltype(V)::value;
+        hipLaunchKernelGGL((ece_kernel<decltype(L)::value, vec ? 4 : 1, vec ? 19 : 0>), grid, block, 0, s, logits, num_classes, hw, label,
+                           edges, n_bins, (ece_cell*)workspace);
+    }); });
     AWSEG_LAUNCH_CHECK();
     hipLaunchKernelGGL(ece_fold_kernel, dim3((unsigned)batch), dim3(64), 0, s, (const ece_cell*)workspace, bpi, n_bins, cond,
                        n_slots, (ece_out*)bins);
@@ -706,17 +659,24 @@ static int stats_impl(const float* seg1, const float* seg2, int64_t batch, int n
     unsigned long long* hist = (unsigned long long*)auroc_hist;
     // workspace: [batch][bpi][n_bins] ECE cells, then (conf) [batch][bpi][19 x 19] uint32 histogram partials
     uint32_t* conf_partial = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(workspace) + (size_t)batch * bpi * 64 * sizeof(ece_cell));
-#define AWSEG_ES_K(M, L, CF, TH, PX, PR) { \
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ensemble_stats_kernel<M, L, CF, TH, PX, PR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL; \
-        hipLaunchKernelGGL((ensemble_stats_kernel<M, L, CF, TH, PX, PR>), grid, dim3(TH), lds, s, seg1, seg2, hw, weights, temperature, label, \
-                           edges, n_bins, (ece_cell*)workspace, hist, n_hist, hist_lo, scale, ignore_index, wrap, conf_partial, oob, pred); }
-#define AWSEG_ES(M, L, CF, PR) { if (wide == 1) AWSEG_ES_K(M, L, CF, 512, 2, PR) else if (wide == 2) AWSEG_ES_K(M, L, CF, 384, 2, PR) else AWSEG_ES_K(M, L, CF, kThreads, 4, PR) }
-#define AWSEG_ES2(M, L) { if (pred) AWSEG_ES(M, L, true, true) else if (conf) AWSEG_ES(M, L, true, false) else AWSEG_ES(M, L, false, false) }
-    if (mode == AWSEG_COMBINE_WEIGHTED) { if (label_dtype == AWSEG_U8) AWSEG_ES2(0, AWSEG_U8) else if (label_dtype == AWSEG_I64) AWSEG_ES2(0, AWSEG_I64) else return AWSEG_EINVAL; }
-    else { if (label_dtype == AWSEG_U8) AWSEG_ES2(2, AWSEG_U8) else if (label_dtype == AWSEG_I64) AWSEG_ES2(2, AWSEG_I64) else return AWSEG_EINVAL; }
-#undef AWSEG_ES2
-#undef AWSEG_ES
-#undef AWSEG_ES_K
+    if (label_dtype != AWSEG_U8 && label_dtype != AWSEG_I64) return AWSEG_EINVAL;
+    const auto launch = [&](auto kern, int threads) -> int {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL;
+        hipLaunchKernelGGL(kern, grid, dim3(threads), lds, s, seg1, seg2, hw, weights, temperature, label, edges, n_bins, (ece_cell*)workspace,
+                           hist, n_hist, hist_lo, scale, ignore_index, wrap, conf_partial, oob, pred);
+        return 0;
+    };
+    const int rc = awseg_by_combine_mode(mode, [&](auto M) { return awseg_by_label(label_dtype, [&](auto L) {
+        return awseg_by_flag(conf, [&](auto CF) { return awseg_by_flag(pred != nullptr, [&](auto PR) -> int {
+            constexpr int m = decltype(M)::value, l = decltype(L)::value;
+            constexpr bool cf = decltype(CF)::value, pr = decltype(PR)::value;
+            if constexpr (pr && !cf) return AWSEG_EINVAL;                   // refused above: the prediction map comes out of the confusion pass
+            else if (wide == 1) return launch(ensemble_stats_kernel<m, l, cf, 512, 2, pr>, 512);
+            else if (wide == 2) return launch(ensemble_stats_kernel<m, l, cf, 384, 2, pr>, 384);
+            else return launch(ensemble_stats_kernel<m, l, cf, kThreads, 4, pr>, kThreads);
+        }); });
+    }); });
+    if (rc) return rc;
     AWSEG_LAUNCH_CHECK();
     hipLaunchKernelGGL(ece_fold_kernel, dim3((unsigned)batch), dim3(64), 0, s, (const ece_cell*)workspace, bpi, n_bins, cond,
                        n_slots, (ece_out*)ece_bins);
