@@ -133,6 +133,8 @@ SIGNATURES = {
     "awseg_failure_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p]),
     "awseg_boundary_workspace": (c_i64, [c_i64, c_i, c_i, c_i, c_i]),
     "awseg_boundary_stats": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p]),
+    "awseg_segment_workspace": (c_i64, [c_i64, c_i, c_i]),
+    "awseg_segment_stats": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
     "awseg_frame_iou_workspace": (c_i64, [c_i64, c_i, c_i64]),
     "awseg_frame_iou_counts": (c_i, [c_p, c_p, c_i, c_i, c_i64, c_i64, c_i, c_p, c_p, c_i64, c_p, c_p, c_p]),
     "awseg_bootstrap_counts": (c_i, [c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_u64, c_i64, c_i64, c_p, c_p, c_p]),

@@ -30,7 +30,7 @@ from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
                       calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
-                      quality_metrics_from_stats, severity_sweep_results)
+                      quality_metrics_from_stats, segment_metrics_from_stats, segment_options, severity_sweep_results)
 
 logger = logging.getLogger(__name__)
 
@@ -111,6 +111,25 @@ def boundary_option(config):
     except (ValueError, TypeError) as e:
         raise ValueError(f"evaluation.boundary_widths is a list of 1 .. {ops.BOUNDARY_MAX_WIDTHS} strictly increasing integers within "
                          f"[1, {ops.BOUNDARY_MAX_RADIUS}], got {spec!r} ({e})") from None
+
+
+def segment_option(config):
+    """`evaluation.segment_metrics` (bool, default off): segment-level counters (which label segments the prediction finds, loses and
+    invents per condition).  `evaluation.segment_threshold`: the share of a segment that must be covered, one of
+    0.25 / 0.5 / 0.75 / 1.0 (default 0.5); `evaluation.segment_min_area`: the smallest segment counted, a power of 4 in [1, 4^10]
+    (default 16); both checked also when the option is off.  -> None when off, else {'threshold': float, 'min_area': int}."""
+    on = _cfg(config, "evaluation.segment_metrics", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"evaluation.segment_metrics is true or false, got {on!r}")
+    threshold = _cfg(config, "evaluation.segment_threshold", 0.5)
+    min_area = _cfg(config, "evaluation.segment_min_area", 16)
+    try:
+        segment_options(threshold, min_area)
+    except ValueError as e:
+        raise ValueError(f"evaluation.segment_threshold / evaluation.segment_min_area: {e}") from None
+    if not on:
+        return None
+    return {"threshold": float(threshold), "min_area": int(min_area)}
 
 
 def change_option(config, images=None):
@@ -239,7 +258,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None, change=None, quality=None):
+                 boundary=None, bootstrap=None, change=None, quality=None, segments=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -319,6 +338,14 @@ class EvalState:
                             "stats": ops.new_image_quality_stats(device, 1 + len(conditions)),
                             "oob": torch.zeros(1, dtype=torch.int64, device=device)}
             self.clean_frames = {"rows": None}
+        # segment-level counters (off unless segments = segment_option(config)): int64 [slot, C, 11, 48]; 'scratch': the uint8
+        # prediction map of the batch where nothing else keeps one.  Under a sweep the clean maps of self.paired are the references
+        self.segments = None
+        if segments is not None:
+            segment_options(segments["threshold"], segments["min_area"])
+            self.segments = {"threshold": float(segments["threshold"]), "min_area": int(segments["min_area"]),
+                             "stats": ops.new_segment_stats(metrics.num_classes, device, 1 + len(conditions)),
+                             "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -386,6 +413,26 @@ class EvalState:
         if bs["scratch"] is None or bs["scratch"].numel() < numel:
             bs["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
         return bs["scratch"][:numel].view(tuple(shape))
+
+    def segment_pred_out(self, shape, device):
+        """boundary_pred_out for the segment counters: the reused uint8 [B, H, W] map of the batch when nothing else keeps one."""
+        sg = self.segments
+        numel = int(np.prod(shape))
+        if sg["scratch"] is None or sg["scratch"].numel() < numel:
+            sg["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
+        return sg["scratch"][:numel].view(tuple(shape))
+
+    def update_segments(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
+        """Segment counters of this batch; a variant batch of a sweep is also counted against its sources' clean maps (the rows the
+        paired pass keeps: no map of its own).  Runs before update_consistency releases the rows."""
+        sg, pd = self.segments, self.paired
+        ref_maps = frame_ref = None
+        if pd is not None and severity != 0:
+            rows = [pd["live"][s][0] for s in sources]
+            frame_ref = torch.tensor(rows, dtype=torch.int32).to(pred.device, non_blocking=True)
+            ref_maps = pd["rows"].view((-1,) + tuple(pred.shape[1:]))
+        ops.segment_stats(pred, labels.reshape(pred.shape), num_classes, sg["stats"], sg["oob"], cond, ref_maps=ref_maps,
+                          frame_ref=frame_ref)
 
     def update_bootstrap(self, pred, labels, sources, cond_ids, num_classes: int) -> None:
         """Per-frame IoU counters of this batch into rows (source, variant); cond_ids: the host list cond was made from."""
@@ -565,6 +612,8 @@ class EvalState:
         if getattr(self, "quality", None) is not None:
             quality_terms = torch.tensor([self.quality["terms"]], dtype=torch.int64, device=self.quality["stats"].device)
             ts += [self.quality["stats"], self.quality["oob"], quality_terms]
+        if getattr(self, "segments", None) is not None:
+            ts += [self.segments["stats"], self.segments["oob"]]
         bs = getattr(self, "bootstrap", None)
         if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
             ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
@@ -641,6 +690,9 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             raise ValueError(f"{len(sources)} sources for a batch of {images.shape[0]} frames")
         if pred_out is None:
             pred_out = st.bootstrap_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
+    sg = getattr(st, "segments", None)
+    if sg is not None and pred_out is None:
+        pred_out = st.segment_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     depth_kw = {}
     if st.depth is not None:
@@ -701,6 +753,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             ops.failure_stats(logits, labels, st.failure["stats"], cond)
     if bd is not None:
         ops.boundary_stats(pred_out, labels.reshape(pred_out.shape), bd["widths"], metrics.num_classes, bd["stats"], bd["oob"], cond)
+    if sg is not None:
+        st.update_segments(pred_out, labels, sources, severity, cond, metrics.num_classes)
     if bs is not None:
         ids = [st.acc.conditions.index(str(c)) if str(c) in st.acc.conditions else -1 for c in conds]      # cond_ids' rule
         st.update_bootstrap(pred_out, labels, sources, ids, metrics.num_classes)
@@ -739,7 +793,7 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
                    depth=depth_options(config), failure=failure_option(config),
                    boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config),
-                   quality=quality_options(config))
+                   quality=quality_options(config), segments=segment_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -813,6 +867,14 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                    kinds=st.sweep.kinds if st.sweep is not None else None,
                                                    levels=st.sweep.levels if st.sweep is not None else 0,
                                                    degradation=metrics.compute_robustness_degradation_ratio))
+    sg = getattr(st, "segments", None)
+    if sg is not None:
+        if int(sg["oob"].item()):
+            raise IndexError("prediction map value outside [0, num_classes) in the segment counters")
+        results.update(segment_metrics_from_stats(sg["stats"].cpu().numpy(), st.acc.conditions, metrics.num_classes,
+                                                  threshold=sg["threshold"], min_area=sg["min_area"],
+                                                  kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                  levels=st.sweep.levels if st.sweep is not None else 0))
     ch = getattr(st, "change", None)
     if ch is not None:
         if int(ch["oob"].item()):

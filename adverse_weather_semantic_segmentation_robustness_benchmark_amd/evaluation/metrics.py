@@ -514,6 +514,105 @@ def boundary_metrics_from_stats(stats, widths, conditions: List[str], num_classe
     return res
 
 
+SEGMENT_THRESHOLDS = {0.25: 1, 0.5: 2, 0.75: 3, 1.0: 4}              # h / A >= j / 4  <=>  cov >= j + 1 (include/awseg.h)
+SEGMENT_SIZE_GROUPS = (("small", 0, 5), ("medium", 5, 7), ("large", 7, 11))     # buckets [lo, hi): area < 1024, < 16384, the rest
+
+
+def segment_options(threshold=0.5, min_area=16):
+    """(j, first bucket) of a coverage threshold in {0.25, 0.5, 0.75, 1.0} and a smallest counted area that is a power of 4 in
+    [1, 4^10]; ValueError for anything else."""
+    ok = isinstance(threshold, (int, float, np.integer, np.floating)) and not isinstance(threshold, (bool, np.bool_))
+    if not ok or float(threshold) not in SEGMENT_THRESHOLDS:
+        raise ValueError(f"the segment coverage threshold is one of {sorted(SEGMENT_THRESHOLDS)}, got {threshold!r}")
+    ok = isinstance(min_area, (int, np.integer)) and not isinstance(min_area, (bool, np.bool_))
+    areas = [4 ** k for k in range(11)]
+    if not ok or int(min_area) not in areas:
+        raise ValueError(f"the smallest counted segment area is a power of 4 in [1, 4^10], got {min_area!r}")
+    return SEGMENT_THRESHOLDS[float(threshold)], areas.index(int(min_area))
+
+
+def segment_metrics_from_stats(stats, conditions: List[str], num_classes: int, threshold=0.5, min_area=16, kinds=None,
+                               levels: int = 0) -> Dict[str, float]:
+    """Result keys of the segment-level counters (int64 [1 + len(conditions), C, 11, 48], include/awseg.h; slot 0 = every frame, slot
+    1 + k = conditions[k]).  Host only; every value a float.  A label segment is DETECTED when at least `threshold` of its pixels are
+    predicted as its class (cov >= j + 1), a prediction segment is TRUE when at least `threshold` of its pixels carry its class as
+    label; segments below `min_area` pixels are not counted.  Per suffix ('' | _<condition>), with per class N label segments, TP
+    detected ones, FN = N - TP, M prediction segments, FP the ones that are not true:
+      segment_recall           mean over the classes with N > 0 of TP / N
+      segment_precision        mean over the classes with M > 0 of (M - FP) / M
+      segment_f1               mean over the classes with 2 TP + FN + FP > 0 of 2 TP / (2 TP + FN + FP)
+      segment_miss_rate        share of the label segments of which not one pixel is found (cov == 0)
+      segment_false_rate       share of the prediction segments without one pixel of their class in the label
+      segment_count, segment_pred_count
+      segment_recall_<g>, segment_miss_rate_<g>, segment_f1_<g>    for the size groups g = small (area < 1024), medium (< 16384), large
+      segment_recall_class<c>  TP / N of class c
+    With 'clean' present, for every adverse kind (without a sweep: every other condition)
+      segment_recall_drop_<kind> = segment_recall_clean - segment_recall_<kind>, segment_miss_rate_rise_<kind> the reverse difference.
+    Severity sweep (kinds, levels): conditions are its slots ('clean', '<kind>_s<j>'); each kind also gets keys from the summed
+    counters of its slots, and per '<kind>_s<j>' and '<kind>'
+      segment_lost_<n>         of the label segments the clean twin's map detects, the share this frame's map does not
+      segment_recovered_<n>    of those the clean twin's map does not detect, the share this frame's map does
+    A key whose denominator is 0 is absent."""
+    j, k0 = segment_options(threshold, min_area)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    C = int(num_classes)
+    if raw.shape != (1 + len(conditions), C, ops.SEGMENT_BUCKETS, ops.SEGMENT_CELLS):
+        raise ValueError(f"segment stats must be int64 [{1 + len(conditions)}, {C}, {ops.SEGMENT_BUCKETS}, {ops.SEGMENT_CELLS}], "
+                         f"got {raw.shape}")
+    named = [("", raw[0])] + [("_" + name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{lv}") for lv in range(1, levels + 1)]
+        named.append(("_" + kind, raw[idx].sum(0)))
+    res: Dict[str, float] = {}
+
+    def rates(slot, lo, hi):
+        """slot [C, 11, 48], buckets [max(lo, k0), hi) -> per class N, TP, M, FP and the two cov == 0 counts."""
+        part = slot[:, max(lo, k0):hi].sum(axis=1)
+        lab, prd = part[:, :42].reshape(C, 6, 7), part[:, 42:]
+        return (lab.sum(axis=(1, 2)), lab[:, j + 1:].sum(axis=(1, 2)), prd.sum(axis=1), prd[:, :j + 1].sum(axis=1),
+                int(lab[:, 0].sum()), int(prd[:, 0].sum()), lab)
+
+    def put(key, num, den):
+        if den > 0:
+            res[key] = float(num / den)
+
+    def class_mean(key, num, den):
+        seen = den > 0
+        if seen.any():
+            res[key] = float((num[seen] / den[seen].astype(np.float64)).mean())
+
+    for suffix, slot in named:
+        n, tp, m, fp, miss, false, lab = rates(slot, 0, ops.SEGMENT_BUCKETS)
+        if int(n.sum()) + int(m.sum()) <= 0:
+            continue
+        class_mean("segment_recall" + suffix, tp, n)
+        class_mean("segment_precision" + suffix, m - fp, m)
+        class_mean("segment_f1" + suffix, 2 * tp, 2 * tp + (n - tp) + fp)
+        put("segment_miss_rate" + suffix, miss, int(n.sum()))
+        put("segment_false_rate" + suffix, false, int(m.sum()))
+        res["segment_count" + suffix] = float(n.sum())
+        res["segment_pred_count" + suffix] = float(m.sum())
+        for c in range(C):
+            put(f"segment_recall_class{c}{suffix}", int(tp[c]), int(n[c]))
+        for group, lo, hi in SEGMENT_SIZE_GROUPS:
+            gn, gtp, gm, gfp, gmiss, _, _ = rates(slot, lo, hi)
+            class_mean(f"segment_recall_{group}{suffix}", gtp, gn)
+            put(f"segment_miss_rate_{group}{suffix}", gmiss, int(gn.sum()))
+            class_mean(f"segment_f1_{group}{suffix}", 2 * gtp, 2 * gtp + (gn - gtp) + gfp)
+        if suffix and suffix != "_clean":
+            # rc < 6: the frame had a reference; rows cov, columns rc
+            ref_hit, ref_miss = lab[:, :, j + 1:6], lab[:, :, :j + 1]
+            put("segment_lost" + suffix, int(ref_hit[:, :j + 1].sum()), int(ref_hit.sum()))
+            put("segment_recovered" + suffix, int(ref_miss[:, j + 1:].sum()), int(ref_miss.sum()))
+    adverse = list(kinds) if kinds else [name for name in conditions if name != "clean"]
+    for kind in adverse:
+        for key, out, sign in (("segment_recall", "segment_recall_drop", 1.0), ("segment_miss_rate", "segment_miss_rate_rise", -1.0)):
+            a, b = f"{key}_clean", f"{key}_{kind}"
+            if a in res and b in res:
+                res[f"{out}_{kind}"] = float(sign * (res[a] - res[b]))
+    return res
+
+
 def change_metrics_from_stats(stats, edges, slots: List[str], kinds, levels: int, num_classes: int) -> Dict[str, float]:
     """Result keys of the change-strata counters (int64 [1 + len(slots), K + 1, C*C + 6], include/awseg.h; slot 0 = every corrupted
     frame, slot 1 + k = slots[k]; K = len(edges) + 1 strata, row K the unmeasured pixels).  Host only; every value a float.  Stratum

@@ -50,6 +50,8 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += failure_section(results)
     if any(k.startswith("boundary_iou_") for k in results):
         lines += boundary_section(results)
+    if any(k.startswith("segment_count") for k in results):
+        lines += segment_section(results)
     if any(k.startswith("change_fraction_") for k in results):
         lines += change_section(results)
     if any(re.match(r"mse_.+_s\d+$", k) for k in results):
@@ -90,6 +92,33 @@ def quality_section(results: Dict[str, Any]) -> list:
     extra += [f"- **{title}**: {int(results[key])}" for key, title in (("quality_unmeasured_terms", "Error terms not measured"),
                                                                       ("quality_unmeasured_windows", "Windows not measured")) if key in results]
     return lines + ([""] + extra if extra else [])
+
+
+def segment_section(results: Dict[str, Any]) -> list:
+    """Segments (evaluation.segment_metrics): one line per condition with how many label segments the prediction finds, misses
+    entirely and invents, overall and by size group; under a severity sweep the share of the clean twin's detections each kind and
+    level loses."""
+    names = [""] + [k[len("segment_count_"):] for k in results if k.startswith("segment_count_")]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    lines = ["", "## Segments", "", "8-connected segments of one class: recall, precision and F1 over segments (class means), the share "
+             "of label segments of which no pixel is found (miss rate) and of prediction segments without a pixel of their class "
+             "(false rate); small: below 1024 pixels, medium: below 16384.", "",
+             "| Condition | Segments | Recall | Precision | F1 | Miss rate | False rate | Recall small / medium / large | "
+             "Miss rate small / medium / large |", "|---" * 9 + "|"]
+    for n in names:
+        sfx = "_" + n if n else ""
+        groups = lambda key: " / ".join(cell(f"{key}_{g}{sfx}") for g in ("small", "medium", "large"))      # noqa: E731
+        lines.append(f"| {n or 'all'} | {int(results.get('segment_count' + sfx, 0))} | {cell('segment_recall' + sfx)} | "
+                     f"{cell('segment_precision' + sfx)} | {cell('segment_f1' + sfx)} | {cell('segment_miss_rate' + sfx)} | "
+                     f"{cell('segment_false_rate' + sfx)} | {groups('segment_recall')} | {groups('segment_miss_rate')} |")
+    lost = [k[len("segment_lost_"):] for k in results if k.startswith("segment_lost_")]
+    if lost:
+        lines += ["", "Of the label segments the clean frame's prediction detects, the share the corrupted frame's loses; of those it "
+                  "does not detect, the share the corrupted frame's recovers:", "", "| Kind | Lost | Recovered |", "|---|---|---|"]
+        lines += [f"| {n} | {cell('segment_lost_' + n)} | {cell('segment_recovered_' + n)} |" for n in lost]
+    return lines
 
 
 def change_section(results: Dict[str, Any]) -> list:

@@ -259,6 +259,66 @@ def boundary_stats_to_numpy(stats, num_classes: int) -> dict:
     return {"conf": raw[..., :c2].reshape(raw.shape[:-1] + (c, c)), "inter": raw[..., c2:c2 + c], "pr": raw[..., c2 + c:]}
 
 
+# ----------------------------------------------------------------------------- segment-level counters (include/awseg.h)
+SEGMENT_BUCKETS = 11                   # AWSEG_SEGMENT_BUCKETS
+SEGMENT_CELLS = 48                     # AWSEG_SEGMENT_CELLS
+
+
+def new_segment_stats(num_classes: int, device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, C, 11, 48]: per slot, class and size bucket (bucket k: area in [4^k, 4^(k+1)), the last from 2^20) the cells
+    cov * 7 + rc of the label segments (42) and 42 + cov of the prediction segments (6) of include/awseg.h (zeroed: the launches
+    accumulate).  Replaces nothing in the reference, which counts pixels only."""
+    if n_slots < 1 or not 1 <= int(num_classes) <= N.MAX_CLASSES:
+        raise ValueError(f"new_segment_stats: n_slots >= 1 and 1 .. {N.MAX_CLASSES} classes, got {n_slots}, {num_classes}")
+    return torch.zeros(n_slots, int(num_classes), SEGMENT_BUCKETS, SEGMENT_CELLS, dtype=torch.int64, device=device)
+
+
+def segment_stats(pred: torch.Tensor, label: torch.Tensor, num_classes: int, stats: torch.Tensor, oob: torch.Tensor,
+                  cond: Optional[torch.Tensor] = None, ref_maps: Optional[torch.Tensor] = None,
+                  frame_ref: Optional[torch.Tensor] = None, label_ids: Optional[torch.Tensor] = None,
+                  pred_ids: Optional[torch.Tensor] = None, ignore_index: int = 255) -> None:
+    """Segment-level counters of the uint8 prediction maps `pred` [B, H, W] against `label` [B, H, W] (uint8 or int64): every
+    8-connected label segment and prediction segment adds 1 to its (class, size bucket, coverage cell) of `stats`
+    (new_segment_stats; slot 0 + slot 1 + cond[b]).  ref_maps uint8 [R, H, W] with frame_ref int32 [B] (< 0: no reference): the
+    clean twins' maps, for the rc half of the label cells.  label_ids / pred_ids int32 [B, H, W]: receive the canonical segment id
+    of every pixel (-1: in no segment).  Live pixels whose prediction or reference value is >= C go to `oob` (int64 [1])."""
+    if pred.dim() != 3 or pred.dtype != torch.uint8:
+        raise ValueError(f"segment_stats: pred is uint8 [B, H, W], got {pred.dtype} {tuple(pred.shape)}")
+    if label.dtype not in (torch.uint8, torch.int64) or tuple(label.shape) != tuple(pred.shape):
+        raise ValueError(f"segment_stats: label is uint8 or int64 {tuple(pred.shape)}, got {label.dtype} {tuple(label.shape)}")
+    if pred.numel() < 1:
+        raise ValueError(f"segment_stats: empty maps {tuple(pred.shape)}")
+    if not 1 <= int(num_classes) <= N.MAX_CLASSES:
+        raise ValueError(f"segment_stats: 1 .. {N.MAX_CLASSES} classes, got {num_classes}")
+    if stats.dim() != 4 or stats.dtype != torch.int64 or tuple(stats.shape[1:]) != (int(num_classes), SEGMENT_BUCKETS, SEGMENT_CELLS):
+        raise ValueError(f"stats must be int64 [slots, {num_classes}, {SEGMENT_BUCKETS}, {SEGMENT_CELLS}] (new_segment_stats), got "
+                         f"{stats.dtype} {tuple(stats.shape)}")
+    if oob.dtype != torch.int64 or oob.numel() != 1:
+        raise ValueError("oob must be int64 [1]")
+    b, H, W = pred.shape
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    if (ref_maps is None) != (frame_ref is None):
+        raise ValueError("segment_stats: ref_maps and frame_ref come together")
+    n_refs = 0
+    if ref_maps is not None:
+        if ref_maps.dim() != 3 or ref_maps.dtype != torch.uint8 or tuple(ref_maps.shape[1:]) != (H, W) or ref_maps.shape[0] < 1:
+            raise ValueError(f"segment_stats: ref_maps is uint8 [R, {H}, {W}], got {ref_maps.dtype} {tuple(ref_maps.shape)}")
+        if frame_ref.dtype != torch.int32 or frame_ref.numel() != b:
+            raise ValueError("frame_ref must be int32 [B]")
+        n_refs = int(ref_maps.shape[0])
+    for name, ids in (("label_ids", label_ids), ("pred_ids", pred_ids)):
+        if ids is not None and (ids.dtype != torch.int32 or tuple(ids.shape) != tuple(pred.shape) or not ids.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous int32 {tuple(pred.shape)}")
+    pred, label = pred.contiguous(), label.contiguous()
+    if ref_maps is not None:
+        ref_maps = ref_maps.contiguous()
+    ws = N.workspace.get(pred.device, N.lib().awseg_segment_workspace(b, H, W), tag="segments")
+    N.call("awseg_segment_stats", N.ptr(pred), N.ptr(label), N.label_dtype(label), int(ignore_index), b, H, W, int(num_classes),
+           N.ptr(ref_maps), n_refs, N.ptr(frame_ref), N.ptr(cond), N.ptr(stats), stats.shape[0], N.ptr(oob), N.ptr(label_ids),
+           N.ptr(pred_ids), N.ptr(ws), N.stream())
+
+
 # ----------------------------------------------------------------------------- frame bootstrap (include/awseg.h, DESIGN 10g)
 BOOTSTRAP_STAGED_DRAWS = 4096          # AWSEG_BOOTSTRAP_STAGED_DRAWS
 BOOTSTRAP_CHUNK_BYTES = 64 << 20       # replicate rows asked for per launch: bootstrap_counts splits R so that a chunk stays below this

@@ -1115,6 +1115,52 @@ int awseg_boundary_stats(const uint8_t* pred, const void* label, int label_dtype
                          int n_slots, int64_t* oob, void* workspace, awseg_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ *  Segment-level counters: which objects are found, lost and invented (segment-wise recall / precision / F1 as in MetaSeg,
+ *  Rottmann et al. 2020, and Chan et al. 2021)
+ *       replaces nothing: every number of the reference is a pixel count
+ * ------------------------------------------------------------------------- *
+ * pred uint8 [B, H, W], label uint8 / int64 [B, H, W] (label_dtype), ignore_index, C = num_classes <= AWSEG_MAX_CLASSES.
+ * Optionally ref_maps uint8 [n_refs, H, W] with frame_ref device int32[B], the convention of awseg_prediction_consistency:
+ * frame_ref[b] < 0, a NULL ref_maps or a NULL frame_ref mean that frame b has no reference.
+ *
+ * A pixel is LIVE when its label is neither ignore_index nor outside [0, C) (the rule of awseg_prediction_consistency; no uint8
+ * wrapping).  A LABEL SEGMENT is an 8-connected component, within one frame, of live pixels with equal label t.  Pixels that are
+ * not live belong to no segment and break connectivity; nothing connects across frames or across the frame border.  A PREDICTION
+ * SEGMENT is an 8-connected component of live pixels with pred < C and equal pred value p.  A live pixel with pred >= C adds 1 to
+ * oob (int64[1]), stays in its label segment as a non-hit and belongs to no prediction segment.  A live pixel whose reference
+ * value is >= C also adds 1 to oob and is a non-hit.  A frame_ref[b] >= n_refs adds H * W to oob, and frame b is treated as
+ * having no reference.
+ *
+ * Per label segment: its area A, h = its pixels with pred == t, g = its pixels with reference == t.  Per prediction segment: its
+ * area A, h = its pixels with label == p.  Coverage cell cov(h, A) = 0 when h == 0, else 1 + floor(4 h / A) (in 64 bits): 0 .. 5,
+ * 5 exactly when h == A, and h / A >= j / 4  <=>  cov >= j + 1 for j = 1 .. 4, so the thresholds 0.25 / 0.5 / 0.75 / 1.0 are
+ * host choices over exact integer cells.  Size bucket s = min(10, floor(log2 A) / 2): bucket k holds [4^k, 4^(k+1)), the last one
+ * everything from 2^20.
+ *
+ * stats int64 [n_slots][C][AWSEG_SEGMENT_BUCKETS][AWSEG_SEGMENT_CELLS] (accumulated, never cleared).  Every segment adds 1 to one
+ * cell of (its class, its bucket):
+ *     a label segment       cov(h, A) * 7 + rc,  rc = cov(g, A) when its frame has a reference, else 6        (cells 0 .. 41)
+ *     a prediction segment  42 + cov(h, A)                                                                     (cells 42 .. 47)
+ * Slot rule of every other counter: each frame's segments into slot 0 and into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1
+ * (cond device int32[B] or NULL: slot 0 only).  A segment belongs to exactly one frame: the counts do not depend on grid shape,
+ * batch split or rank count and are additive over launches.
+ *
+ * label_ids, pred_ids: device int32 [B, H, W], either may be NULL.  Each receives, per pixel, the canonical id of its segment: y *
+ * W + x of the segment's first pixel in raster order, or -1 for a pixel in no segment.
+ *
+ * Any H, W >= 1 with H * W < 2^31 and batch <= 65535 (AWSEG_ERANGE beyond).  workspace: awseg_segment_workspace(batch, height,
+ * width) bytes = AWSEG_SEGMENT_WORKSPACE_PER_PIXEL per pixel.  AWSEG_EINVAL for a NULL pointer (cond, ref_maps, frame_ref and the
+ * two id maps excepted), a size < 1 (n_refs only where ref_maps and frame_ref are given) or an unknown label dtype. */
+#define AWSEG_SEGMENT_BUCKETS 11
+#define AWSEG_SEGMENT_CELLS 48
+#define AWSEG_SEGMENT_WORKSPACE_PER_PIXEL 30
+int64_t awseg_segment_workspace(int64_t batch, int height, int width);
+int awseg_segment_stats(const uint8_t* pred, const void* label, int label_dtype, int ignore_index, int64_t batch, int height,
+                        int width, int num_classes, const uint8_t* ref_maps, int n_refs, const int32_t* frame_ref,
+                        const int32_t* cond, int64_t* stats, int n_slots, int64_t* oob, int32_t* label_ids, int32_t* pred_ids,
+                        void* workspace, awseg_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  *  Frame bootstrap: per-frame IoU counters and their replicate sums
  *       replaces nothing: the reference has no per-frame statistics (REF/scripts/evaluate.py:203-218 concatenates every frame
  *       and divides once), so it cannot put an interval on any of its numbers

@@ -103,6 +103,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--boundary-widths", type=str, default=None,
                     help="boundary-band metrics (trimap mIoU, Boundary IoU) per condition: 1-4 comma-separated increasing band widths in "
                          "pixels, each within [1, 16], e.g. 1,2,4,8 (sets evaluation.boundary_widths)")
+    ap.add_argument("--segment-metrics", action="store_true",
+                    help="segment-level metrics per condition: which 8-connected label segments the prediction finds, loses "
+                         "entirely and invents (sets evaluation.segment_metrics)")
+    ap.add_argument("--segment-threshold", type=float, default=None, metavar="T",
+                    help="share of a segment that must be covered for it to count as found: 0.25, 0.5, 0.75 or 1.0 (default 0.5; "
+                         "sets evaluation.segment_threshold)")
+    ap.add_argument("--segment-min-area", type=int, default=None, metavar="A",
+                    help="smallest segment counted, in pixels: a power of 4 (default 16; sets evaluation.segment_min_area)")
     ap.add_argument("--change-strata", type=str, default=None, metavar="EDGES",
                     help="split every corrupted frame's errors by how much the corruption changed each input pixel against the clean "
                          "frame: 'default' (0.5,4.5,16.5,64.5) or 1-7 comma-separated increasing edges in 8-bit grey levels; needs "
@@ -148,6 +156,12 @@ def main():
             config.set("evaluation.failure_detection", True)
         if args.boundary_widths is not None:
             config.set("evaluation.boundary_widths", parse_boundary_widths(args.boundary_widths))
+        if args.segment_metrics:
+            config.set("evaluation.segment_metrics", True)
+        if args.segment_threshold is not None:
+            config.set("evaluation.segment_threshold", args.segment_threshold)
+        if args.segment_min_area is not None:
+            config.set("evaluation.segment_min_area", args.segment_min_area)
         if args.change_strata is not None:
             config.set("evaluation.change_strata", parse_change_strata(args.change_strata))
         if args.image_quality:

@@ -207,6 +207,14 @@ def main():
         lambda: ops.boundary_stats(var_c, ref_c, bw, C, bst, boob, cond), "hbm", 2 * px * B)
     cases["boundary stats w=1,2,4,8, independent random maps"] = (
         lambda: ops.boundary_stats(var_r, ref_r, bw, C, bst, boob, cond), "hbm", 2 * px * B)
+    # segment-level counters on the same maps (label = the clean map, prediction = the variant): 2 B/px in, but the four passes move
+    # ~60 B/px through the workspace, so "of peak" again says how far from a 2 B/px scan the labelling is.  The random maps are the
+    # worst case: millions of one-pixel segments
+    sgst, sgoob = ops.new_segment_stats(C, dev, 6), torch.zeros(1, dtype=torch.int64, device=dev)
+    cases["segment stats, coherent 16 x 16 blocks, ~5 % flipped"] = (
+        lambda: ops.segment_stats(var_c, ref_c, C, sgst, sgoob, cond), "hbm", 2 * px * B)
+    cases["segment stats, independent random maps"] = (
+        lambda: ops.segment_stats(var_r, ref_r, C, sgst, sgoob, cond), "hbm", 2 * px * B)
     # frame bootstrap: the per-frame IoU counters on the maps of the two consistency cases (label = the clean map, prediction = the
     # variant; 2 B/px, the consistency pass without its third map), and the replicate sums of a paired sweep's table (500 sources x
     # 13 variants x 57 counters = 3 MB, resident in L2; every entry is read once per replicate)
