@@ -128,6 +128,7 @@ SIGNATURES = {
     "awseg_temperature_grid_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p]),
     "awseg_ensemble_temperature_grid_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i,
                                                    c_p, c_i, c_p]),
+    "awseg_ensemble_weight_grid_stats": (c_i, [c_p, c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_i, c_i, c_p, c_p, c_i, c_p]),
     "awseg_depth_eval_stats": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_i, c_p]),
     "awseg_ensemble_failure_stats": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_i64, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p]),
     "awseg_failure_stats": (c_i, [c_p, c_i64, c_i, c_i64, c_p, c_i, c_p, c_p, c_i, c_p]),

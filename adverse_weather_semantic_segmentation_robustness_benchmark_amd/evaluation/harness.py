@@ -30,7 +30,8 @@ from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
                       calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
-                      quality_metrics_from_stats, segment_metrics_from_stats, segment_options, severity_sweep_results)
+                      quality_metrics_from_stats, segment_metrics_from_stats, segment_options, severity_sweep_results,
+                      weight_grid_metrics_from_stats)
 
 logger = logging.getLogger(__name__)
 
@@ -130,6 +131,78 @@ def segment_option(config):
     if not on:
         return None
     return {"threshold": float(threshold), "min_area": int(min_area)}
+
+
+WEIGHT_GRID_MAX_SHARES = ops.WGRID_MAX_POINTS - 1        # the model's own pair is always the last point
+
+
+def weight_grid_shares(spec):
+    """The SegFormer shares of `evaluation.ensemble_weight_grid`: an integer n in [2, 63] = n equally spaced shares k / (n - 1), or
+    a list of 1 .. 63 strictly increasing numbers in [0, 1]; 0 and 1 are added when missing (within the 63).  -> list of floats."""
+    what = (f"evaluation.ensemble_weight_grid is an integer in [2, {WEIGHT_GRID_MAX_SHARES}] (equally spaced SegFormer shares) or a "
+            f"list of 1 .. {WEIGHT_GRID_MAX_SHARES} strictly increasing shares in [0, 1] (0 and 1 are added when missing, within "
+            f"the {WEIGHT_GRID_MAX_SHARES}), got {spec!r}")
+    if isinstance(spec, (bool, np.bool_, str, bytes, dict, float, np.floating)):
+        raise ValueError(what)
+    if isinstance(spec, (int, np.integer)):
+        n = int(spec)
+        if not 2 <= n <= WEIGHT_GRID_MAX_SHARES:
+            raise ValueError(what)
+        return [k / (n - 1) for k in range(n)]
+    try:
+        shares = list(spec)
+    except TypeError:
+        raise ValueError(what) from None
+    if not shares or any(isinstance(a, (bool, np.bool_, str, bytes)) or not isinstance(a, (int, float, np.integer, np.floating))
+                         or not 0.0 <= float(a) <= 1.0 for a in shares):                  # (a NaN fails the comparison)
+        raise ValueError(what)
+    shares = [float(a) for a in shares]
+    if any(b <= a for a, b in zip(shares, shares[1:])):
+        raise ValueError(what)
+    shares = ([0.0] if shares[0] != 0.0 else []) + shares + ([1.0] if shares[-1] != 1.0 else [])
+    if len(shares) > WEIGHT_GRID_MAX_SHARES:
+        raise ValueError(what)
+    return shares
+
+
+def weight_grid_pairs(shares, configured) -> np.ndarray:
+    """float32 [len(shares) + 1, 2]: (float32(a), float32(1) - float32(a)) per share, then the model's own pair `configured`."""
+    a = np.asarray(shares, dtype=np.float32)
+    own = np.asarray(configured, dtype=np.float32).reshape(1, 2)
+    return np.ascontiguousarray(np.concatenate([np.stack([a, np.float32(1) - a], axis=1), own], axis=0))
+
+
+def weight_grid_option(config, model=None):
+    """`evaluation.ensemble_weight_grid` (default off): the ensemble weight sweep -- the mIoU of every condition at
+    every member weighting of a grid (weight_grid_shares) plus the model's own softmax(ensemble_weights) as the last point, and how
+    the members' own predictions split the labelled pixels.  `evaluation.weight_grid_condition` (default 'clean'): the evaluated
+    condition the fitted weighting is chosen on.  `model`, when given, must be the two-member ensemble combining by
+    weighted_average; its pair closes the grid.  -> None when off, else {'shares', 'condition'} and, with a model, 'pairs' (float32
+    [G, 2]) and 'configured_index' (G - 1)."""
+    spec = _cfg(config, "evaluation.ensemble_weight_grid", None)
+    condition = _cfg(config, "evaluation.weight_grid_condition", "clean")
+    if not isinstance(condition, str) or not condition:
+        raise ValueError(f"evaluation.weight_grid_condition is the name of an evaluated condition, got {condition!r}")
+    if spec is None:
+        return None
+    opt = {"shares": weight_grid_shares(spec), "condition": condition}
+    sweep = _cfg(config, "evaluation.severities", None) is not None
+    evaluated = list(_cfg(config, "data.weather_conditions", []))
+    if not sweep and condition not in evaluated:
+        raise ValueError(f"evaluation.weight_grid_condition {condition!r} is not among the evaluated conditions {evaluated} "
+                         "(data.weather_conditions)")
+    if model is not None:
+        if not (hasattr(model, "segformer") and hasattr(model, "deeplabv3plus") and hasattr(model, "ensemble_weights")):
+            raise ValueError("evaluation.ensemble_weight_grid sweeps the weights of the SegFormer + DeepLabV3+ ensemble: the model is "
+                             f"a {type(model).__name__}, which has no two members to weigh")
+        strategy = getattr(model, "ensemble_strategy", "weighted_average")
+        if strategy != "weighted_average":
+            raise ValueError("evaluation.ensemble_weight_grid sweeps the weights of model.ensemble_strategy weighted_average; the "
+                             f"model combines by {strategy!r}")
+        own = F.softmax(model.ensemble_weights.detach().float(), dim=0).cpu().numpy()     # the pair the forward pass combines with
+        opt["pairs"] = weight_grid_pairs(opt["shares"], own)
+        opt["configured_index"] = len(opt["shares"])
+    return opt
 
 
 def change_option(config, images=None):
@@ -258,7 +331,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None, change=None, quality=None, segments=None):
+                 boundary=None, bootstrap=None, change=None, quality=None, segments=None, weight_grid=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -346,6 +419,18 @@ class EvalState:
             self.segments = {"threshold": float(segments["threshold"]), "min_area": int(segments["min_area"]),
                              "stats": ops.new_segment_stats(metrics.num_classes, device, 1 + len(conditions)),
                              "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+        # ensemble weight sweep (off unless weight_grid = weight_grid_option(config, model)): int64 [slot, G + 3, 2 C]
+        self.weight_grid = None
+        if weight_grid is not None:
+            if not ensemble or weight_grid.get("pairs") is None:
+                raise ValueError("the ensemble weight sweep needs the two-member ensemble (weight_grid_option(config, model))")
+            if weight_grid["condition"] not in conditions:              # (under a sweep: its slots, known only here)
+                raise ValueError(f"evaluation.weight_grid_condition {weight_grid['condition']!r} is not among the evaluated conditions "
+                                 f"{list(conditions)}")
+            pairs = ops.check_weight_grid(weight_grid["pairs"])
+            self.weight_grid = {"pairs": pairs, "configured_index": int(weight_grid["configured_index"]),
+                                "condition": weight_grid["condition"],
+                                "stats": ops.new_weight_grid_stats(1 + len(conditions), pairs.shape[0], metrics.num_classes, device)}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -571,6 +656,12 @@ class EvalState:
         else:
             ops.temperature_grid_stats(logits, labels, c["stats"], c["temps"], self.edges, cond)
 
+    def update_weight_grid(self, labels: torch.Tensor, cond, members) -> None:
+        """The weight sweep's counters of this batch from the two member maps (members = (seg1, seg2, ...) as update_calibration
+        receives them): every grid point's mIoU counters and the members' own predictions in one pass."""
+        wg = self.weight_grid
+        ops.ensemble_weight_grid_stats(members[0], members[1], wg["pairs"], labels, cond, wg["stats"])
+
     def update_auroc(self, seg1, seg2, labels):
         """Disagreement = mutual information (metrics.py:353-367); error = argmax of the MEAN
         PROBABILITY != label (metrics.py:414-419); pixels with label 255 dropped (:426)."""
@@ -614,6 +705,8 @@ class EvalState:
             ts += [self.quality["stats"], self.quality["oob"], quality_terms]
         if getattr(self, "segments", None) is not None:
             ts += [self.segments["stats"], self.segments["oob"]]
+        if getattr(self, "weight_grid", None) is not None:
+            ts.append(self.weight_grid["stats"])
         bs = getattr(self, "bootstrap", None)
         if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
             ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
@@ -720,6 +813,10 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
                 st.update_calibration(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T))
             else:
                 st.update_calibration(labels, cond, logits=res["segmentation"])
+        if getattr(st, "weight_grid", None) is not None:
+            if strategy != "weighted_average":
+                raise ValueError(f"the ensemble weight sweep needs model.ensemble_strategy weighted_average, got {strategy!r}")
+            st.update_weight_grid(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"]))
         if st.failure is not None:
             # max_confidence hands over its combined logits: the kernel does not know that rule
             mode, w, T = _combine_args(model, strategy)
@@ -737,6 +834,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_auroc(res["segformer_seg"], res["deeplabv3plus_seg"], labels)
             ops.ece_accumulate(res["segmentation"], labels, st.ece, st.edges, cond)
     else:
+        if getattr(st, "weight_grid", None) is not None:
+            raise ValueError("the ensemble weight sweep needs the two-member ensemble")
         out = model(images)
         logits = out["segmentation"].float().contiguous()
         if st.depth is not None:
@@ -793,7 +892,8 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    calibration_condition=str(_cfg(config, "evaluation.calibration_condition", "clean")), sweep=sweep,
                    depth=depth_options(config), failure=failure_option(config),
                    boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config),
-                   quality=quality_options(config), segments=segment_option(config))
+                   quality=quality_options(config), segments=segment_option(config),
+                   weight_grid=weight_grid_option(config, model))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -875,6 +975,12 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                   threshold=sg["threshold"], min_area=sg["min_area"],
                                                   kinds=st.sweep.kinds if st.sweep is not None else None,
                                                   levels=st.sweep.levels if st.sweep is not None else 0))
+    wg = getattr(st, "weight_grid", None)
+    if wg is not None:
+        results.update(weight_grid_metrics_from_stats(wg["stats"].cpu().numpy(), st.acc.conditions, metrics.num_classes, wg["pairs"],
+                                                      wg["configured_index"], calibration_condition=wg["condition"],
+                                                      kinds=st.sweep.kinds if st.sweep is not None else None,
+                                                      levels=st.sweep.levels if st.sweep is not None else 0))
     ch = getattr(st, "change", None)
     if ch is not None:
         if int(ch["oob"].item()):

@@ -755,6 +755,113 @@ def quality_metrics_from_stats(stats, slots: List[str], kinds, levels: int, resu
     return res
 
 
+def weight_grid_row_miou(inter, lab, prd) -> Optional[float]:
+    """mIoU from the marginals of one grid point (int64 [C] each: hits, labelled, predicted): iou_from_counts' expressions (int64 /
+    int64 true-divide to float32, mean over the classes with a non-empty union), so the configured point reproduces the pooled
+    mIoU of the confusion matrix bit for bit.  None when no class has a union."""
+    i, l, p = (torch.as_tensor(np.ascontiguousarray(v), dtype=torch.int64) for v in (inter, lab, prd))
+    union = l + p - i
+    valid = union > 0
+    if not bool(valid.any()):
+        return None
+    return float((i[valid] / union[valid]).mean().item())
+
+
+def weight_grid_metrics_from_stats(stats, conditions: List[str], num_classes: int, grid, configured_index: int,
+                                   calibration_condition: str = "clean", kinds=None, levels=None) -> Dict[str, Any]:
+    """Result keys of the ensemble weight sweep (int64 [1 + len(conditions), G + 3, 2 C], include/awseg.h; slot 0 = every frame, slot
+    1 + k = conditions[k]).  grid: the G float32 pairs the counters were filled with; the SegFormer share of a point is its first
+    weight.  configured_index: the point that holds the model's own softmax(ensemble_weights).  Host only.  Per suffix
+    ('' | _<condition>), for every slot with a labelled pixel:
+      ensemble_weight_best      the share of the point with the highest mIoU of the slot; ties go to the point nearest the configured
+                                share, then to the lower index           miou_best_weight        the mIoU there
+      miou_configured_weight    the mIoU at the configured point
+      miou_fitted_weight        the mIoU at the fitted point: the best point of slot `calibration_condition` (ensemble_weight_fitted)
+      miou_weight_gain          fitted minus configured
+      miou_weight_regret_<s>    named slots only: the slot's own best minus its fitted value (what a clean-fitted weighting loses there)
+      segformer_miou, deeplabv3plus_miou      the grid's ends (1, 0) and (0, 1), when the grid has them
+      member_both_right, member_only_segformer, member_only_deeplabv3plus, member_neither_right, member_oracle_accuracy (1 - neither),
+      member_disagreement       shares of the labelled pixels, from the members' own argmax
+      ensemble_weight_miou_curve               the list of mIoUs, one per point
+    and ensemble_weight_grid (the list of shares), weight_grid_out_of_range_labels / weight_grid_nan_pixels (slot 0, when non-zero).
+    Severity sweep (kinds, levels): conditions are its slots ('clean', '<kind>_s<j>'); each kind gets ensemble_weight_best_<kind> and
+    miou_weight_regret_<kind> from the summed counters of its slots.  All-zero stats give {}."""
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    C = int(num_classes)
+    pairs = np.asarray(grid, dtype=np.float32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.shape[0] < 1:
+        raise ValueError(f"the weight grid is float32 [G, 2], got {pairs.shape}")
+    G = pairs.shape[0]
+    if raw.ndim != 3 or raw.shape != (1 + len(conditions), G + 3, 2 * C):
+        raise ValueError(f"weight grid stats must be int64 [{1 + len(conditions)}, {G + 3}, {2 * C}], got {raw.shape}")
+    if isinstance(configured_index, (bool, np.bool_)) or not 0 <= int(configured_index) < G:
+        raise ValueError(f"configured_index is a grid point in [0, {G}), got {configured_index!r}")
+    cfg = int(configured_index)
+    if not raw.any():
+        return {}
+    shares = [float(v) for v in pairs[:, 0]]
+
+    def curve(slot):
+        return [weight_grid_row_miou(slot[g, :C], slot[G, :C], slot[g, C:]) for g in range(G)]
+
+    def best(miou):
+        top = max(miou)
+        return min((g for g in range(G) if miou[g] == top), key=lambda g: (abs(shares[g] - shares[cfg]), g))
+
+    def present(slot):
+        return int(slot[G, :C].sum()) > 0
+
+    fitted = None
+    if calibration_condition in conditions and present(raw[1 + conditions.index(calibration_condition)]):
+        fitted = best(curve(raw[1 + conditions.index(calibration_condition)]))
+    ends = {"segformer": [g for g in range(G) if pairs[g, 0] == 1.0 and pairs[g, 1] == 0.0],
+            "deeplabv3plus": [g for g in range(G) if pairs[g, 0] == 0.0 and pairs[g, 1] == 1.0]}
+    res: Dict[str, Any] = {"ensemble_weight_grid": shares}
+    if fitted is not None:
+        res["ensemble_weight_fitted"] = shares[fitted]
+    named = [("", raw[0])] + [("_" + name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for suffix, slot in named:
+        if not present(slot):
+            continue
+        miou = curve(slot)
+        b = best(miou)
+        res[f"ensemble_weight_best{suffix}"] = shares[b]
+        res[f"miou_best_weight{suffix}"] = miou[b]
+        res[f"miou_configured_weight{suffix}"] = miou[cfg]
+        if fitted is not None:
+            res[f"miou_fitted_weight{suffix}"] = miou[fitted]
+            res[f"miou_weight_gain{suffix}"] = miou[fitted] - miou[cfg]
+            if suffix:
+                res[f"miou_weight_regret{suffix}"] = miou[b] - miou[fitted]
+        for member, at in ends.items():
+            if at:
+                res[f"{member}_miou{suffix}"] = miou[at[0]]
+        labelled = int(slot[G, :C].sum())
+        both, only1, only2 = int(slot[G, C:].sum()), int(slot[G + 1, :C].sum()), int(slot[G + 1, C:].sum())
+        neither = labelled - both - only1 - only2
+        res[f"member_both_right{suffix}"] = both / labelled
+        res[f"member_only_segformer{suffix}"] = only1 / labelled
+        res[f"member_only_deeplabv3plus{suffix}"] = only2 / labelled
+        res[f"member_neither_right{suffix}"] = neither / labelled
+        res[f"member_oracle_accuracy{suffix}"] = 1.0 - neither / labelled
+        res[f"member_disagreement{suffix}"] = int(slot[G + 2, 2]) / labelled
+        res[f"ensemble_weight_miou_curve{suffix}"] = miou
+    for kind in (kinds or []):
+        idx = [1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels or 0) + 1)]
+        slot = raw[idx].sum(0) if idx else None
+        if slot is None or not present(slot):
+            continue
+        miou = curve(slot)
+        b = best(miou)
+        res[f"ensemble_weight_best_{kind}"] = shares[b]
+        if fitted is not None:
+            res[f"miou_weight_regret_{kind}"] = miou[b] - miou[fitted]
+    for key, v in (("weight_grid_out_of_range_labels", int(raw[0, G + 2, 0])), ("weight_grid_nan_pixels", int(raw[0, G + 2, 1]))):
+        if v:
+            res[key] = float(v)
+    return res
+
+
 ADVERSE_KINDS = ("fog", "rain", "snow", "night")                    # the kinds finalize() reports a degradation for
 
 

@@ -52,6 +52,8 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += boundary_section(results)
     if any(k.startswith("segment_count") for k in results):
         lines += segment_section(results)
+    if "ensemble_weight_grid" in results:
+        lines += weight_grid_section(results)
     if any(k.startswith("change_fraction_") for k in results):
         lines += change_section(results)
     if any(re.match(r"mse_.+_s\d+$", k) for k in results):
@@ -119,6 +121,30 @@ def segment_section(results: Dict[str, Any]) -> list:
                   "does not detect, the share the corrupted frame's recovers:", "", "| Kind | Lost | Recovered |", "|---|---|---|"]
         lines += [f"| {n} | {cell('segment_lost_' + n)} | {cell('segment_recovered_' + n)} |" for n in lost]
     return lines
+
+
+def weight_grid_section(results: Dict[str, Any]) -> list:
+    """Ensemble weights (evaluation.ensemble_weight_grid): one line per condition with the mIoU at the configured, the fitted and the
+    condition's own best weighting, that best SegFormer share, both members' mIoU and the oracle accuracy."""
+    names = [""] + [k[len("miou_best_weight_"):] for k in results if k.startswith("miou_best_weight_")]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    head = "Ensemble mIoU at every SegFormer share of a grid"
+    if "ensemble_weight_fitted" in results:
+        head += f"; the fitted share {results['ensemble_weight_fitted']:.3f} is the best one on the calibration condition"
+    lines = ["", "## Ensemble Weights", "", head + ".  Oracle accuracy: the share of labelled pixels at least one member gets right.", "",
+             "| Condition | Configured mIoU | Fitted mIoU | Best mIoU | Best share | SegFormer mIoU | DeepLabV3+ mIoU | Oracle accuracy |",
+             "|---" * 8 + "|"]
+    for n in names:
+        sfx = "_" + n if n else ""
+        lines.append(f"| {n or 'all'} | {cell('miou_configured_weight' + sfx)} | {cell('miou_fitted_weight' + sfx)} | {cell('miou_best_weight' + sfx)} | "
+                     f"{cell('ensemble_weight_best' + sfx)} | {cell('segformer_miou' + sfx)} | {cell('deeplabv3plus_miou' + sfx)} | "
+                     f"{cell('member_oracle_accuracy' + sfx)} |")
+    extra = [f"- **{title}**: {int(results[key])}" for key, title in (("weight_grid_out_of_range_labels", "Labels out of range"),
+                                                                      ("weight_grid_nan_pixels", "Labelled pixels with a NaN logit"))
+             if key in results]
+    return lines + ([""] + extra if extra else [])
 
 
 def change_section(results: Dict[str, Any]) -> list:

@@ -702,6 +702,57 @@ def temperature_grid_stats_to_numpy(stats) -> dict:
             "nonfinite": rows[..., 3].copy(), "bins": bins, "out_of_range": raw[:, k, 0].copy()}
 
 
+# ----------------------------------------------------------------------------- ensemble weight sweep (include/awseg.h)
+WGRID_MAX_POINTS = 64                  # include/awseg.h AWSEG_WGRID_MAX_POINTS
+
+
+def check_weight_grid(weights) -> np.ndarray:
+    """The grid as a host float32 array [G, 2], checked before any launch (the C ABI refuses the same grids with AWSEG_EINVAL)."""
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.asarray(weights)
+    if w.dtype != np.float32:
+        raise ValueError(f"a weight grid is float32 [G, 2] (the pairs enter the kernel as they are), got {w.dtype}")
+    if w.ndim != 2 or w.shape[1] != 2 or not 1 <= w.shape[0] <= WGRID_MAX_POINTS:
+        raise ValueError(f"a weight grid is float32 [G, 2] with 1 .. {WGRID_MAX_POINTS} points, got {tuple(w.shape)}")
+    if not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError(f"every grid weight must be finite and >= 0, got {w.tolist()}")
+    return np.ascontiguousarray(w)
+
+
+def new_weight_grid_stats(n_slots: int, n_points: int, num_classes: int, device) -> torch.Tensor:
+    """int64 [n_slots, n_points + 3, 2 C], the layout include/awseg.h documents (zeroed: the launches accumulate)."""
+    if n_slots < 1 or not 1 <= n_points <= WGRID_MAX_POINTS or num_classes < 1:
+        raise ValueError(f"new_weight_grid_stats: n_slots >= 1, 1 .. {WGRID_MAX_POINTS} points and >= 1 class, got {n_slots}, "
+                         f"{n_points}, {num_classes}")
+    return torch.zeros(n_slots, n_points + 3, 2 * num_classes, dtype=torch.int64, device=device)
+
+
+def ensemble_weight_grid_stats(seg1: torch.Tensor, seg2: torch.Tensor, weights, labels: torch.Tensor, cond: Optional[torch.Tensor],
+                               stats: torch.Tensor, ignore_index: int = 255) -> None:
+    """The mIoU counters of argmax(w0 * seg1 + w1 * seg2) at every pair of `weights` (float32 CPU tensor or array [G, 2]) and the
+    split of the labelled pixels by the members' own predictions, accumulated into `stats` (new_weight_grid_stats; slot 0 + slot
+    1 + cond[b]) in one pass over the member maps.  C = 19, H*W % 4 == 0."""
+    w = check_weight_grid(weights)
+    if seg1.dtype != torch.float32 or seg2.dtype != torch.float32 or seg1.dim() < 3 or seg1.shape != seg2.shape:
+        raise ValueError(f"ensemble_weight_grid_stats: the members are float32 [B, C, ...] of one shape, got {seg1.dtype} "
+                         f"{tuple(seg1.shape)} and {seg2.dtype} {tuple(seg2.shape)}")
+    b, c = seg1.shape[0], seg1.shape[1]
+    if stats.dim() != 3 or stats.dtype != torch.int64 or stats.shape[1:] != (w.shape[0] + 3, 2 * c):
+        raise ValueError(f"stats must be int64 [slots, {w.shape[0] + 3}, {2 * c}] (new_weight_grid_stats), got {stats.dtype} "
+                         f"{tuple(stats.shape)}")
+    if labels.numel() != seg1[:, 0].numel():
+        raise ValueError(f"ensemble_weight_grid_stats: one label per pixel, got {tuple(labels.shape)} for {tuple(seg1.shape)}")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    if b == 0:
+        return
+    seg1, seg2, labels = seg1.contiguous(), seg2.contiguous(), labels.contiguous()
+    hw = seg1[0, 0].numel()
+    N.call("awseg_ensemble_weight_grid_stats", N.ptr(seg1), N.ptr(seg2), b, c, hw, N.host(w), w.shape[0], N.ptr(labels),
+           N.label_dtype(labels), int(ignore_index), N.ptr(cond), N.ptr(stats), stats.shape[0], N.stream())
+
+
 # ----------------------------------------------------------------------------- depth error sums (include/awseg.h, DESIGN 10d)
 DEPTH_UNIT = 2.0 ** -20                # fixed point of every real-valued term (AWSEG_DEPTH_FRAC_BITS)
 DEPTH_CAP = 2048.0                     # per-term clamp, counted as saturated (AWSEG_DEPTH_CAP)

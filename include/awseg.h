@@ -954,6 +954,42 @@ int awseg_ensemble_temperature_grid_stats(const float* seg1, const float* seg2, 
                                           int64_t* stats, int n_slots, awseg_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
+ *  Ensemble weight sweep: the mIoU counters at every member weighting of a grid
+ *       the second axis beside the temperature grid: the temperature never moves an argmax, the member weights do
+ * ------------------------------------------------------------------------- *
+ * seg1, seg2 float32 [B, 19, hw]: the member logit maps.  weights: HOST float32 [n_points][2] (they travel in the kernel
+ * arguments, as the temperatures do).  For every grid point g, r_g[c] = weights[g][0] * seg1[c] + weights[g][1] * seg2[c] with
+ * the expressions and roundings of the WEIGHTED combine (two products and one sum, each rounded on its own) and pred_g = argmax
+ * r_g under torch's rule (the first maximum, a NaN wins): the rule of the pooled confusion counters.  m1 / m2 = argmax of seg1 /
+ * seg2 alone under the same rule, from the raw logits -- not the grid at (1, 0) / (0, 1), where 0 * inf is NaN.  A labelled pixel
+ * is one whose label (uint8 / int64 [B, hw], label_dtype) is neither ignore_index nor outside [0, C); no uint8 wrap.
+ *
+ * Output (accumulated, never cleared): stats int64 [n_slots][AWSEG_WGRID_ROWS(n_points)][2 C], slot rule of the confusion
+ * counters: every frame into slot 0 and into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond NULL: slot 0 only).
+ *     row g < n_points   [c] labelled c and pred_g == c            [C + c] labelled pixels with pred_g == c
+ *     row n_points       [c] labelled c                            [C + c] labelled c, m1 == c and m2 == c
+ *     row n_points + 1   [c] labelled c, only m1 == c              [C + c] labelled c, only m2 == c
+ *     row n_points + 2   [0] labels neither ignore_index nor in [0, C)   [1] labelled pixels with a NaN in either member (still
+ *                        counted in every row)   [2] labelled pixels with m1 != m2   everything else 0
+ * Integer sums only: independent of launch geometry and batch split, additive over launches and ranks.
+ *
+ * Identity: at a grid point whose two floats are the device weights of awseg_combine_confusion_stats (WEIGHTED, temperature NULL
+ * or 1.0f) the row's first half is the diagonal of that slot's confusion matrix, its second half the matrix's column sums, and
+ * row n_points' first half its row sums, on labels in [0, C) or 255 (label_wrap_u8 = 0 there: these counters never wrap).  There is
+ * no temperature argument: a positive T changes an argmax only through the ties its rounding creates, so the identity is promised
+ * for T absent or equal to 1 only.
+ *
+ * C = 19, hw % 4 == 0 and < 2^31, batch <= 65535, members 16-byte aligned (AWSEG_ERANGE / AWSEG_EALIGN otherwise).  No workspace.
+ * AWSEG_EINVAL for a NULL pointer (cond excepted), a size < 1, n_points outside [1, AWSEG_WGRID_MAX_POINTS], an unknown label
+ * dtype, or a weight that is not finite or is negative. */
+#define AWSEG_WGRID_MAX_POINTS 64
+#define AWSEG_WGRID_ROWS(g)    ((g) + 3)
+int awseg_ensemble_weight_grid_stats(const float* seg1, const float* seg2, int64_t batch, int num_classes, int64_t hw,
+                                     const float* weights /* HOST float32 [n_points][2] */, int n_points,
+                                     const void* label, int label_dtype, int ignore_index, const int32_t* cond,
+                                     int64_t* stats, int n_slots, awseg_stream_t stream);
+
+/* ------------------------------------------------------------------------- *
  *  Depth error sums of the evaluated depth maps against the depth target
  *       scores what PKG/models/model.py:368-371, :471-478 predicts against the loader's batch["depth"]; the reference
  *       evaluation (REF/scripts/evaluate.py) computes no depth metric, so the sums are the standard monocular set

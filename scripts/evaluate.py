@@ -79,6 +79,16 @@ def parse_change_strata(text: str):
         raise ValueError(f"--change-strata takes 'default' or comma-separated numbers such as 0.5,4.5,16.5, got {text!r}") from None
 
 
+def parse_weight_grid(text: str):
+    """--ensemble-weight-grid: an integer n (n equally spaced SegFormer shares) or comma-separated shares (the harness checks their
+    number, range and order)."""
+    try:
+        return [float(x) for x in text.split(",")] if "," in text or "." in text else int(text)
+    except ValueError:
+        raise ValueError(f"--ensemble-weight-grid takes an integer such as 11 or comma-separated shares such as 0.25,0.5,0.75, got "
+                         f"{text!r}") from None
+
+
 def parse_image_quality_targets(text: str):
     """--image-quality-targets: comma-separated SSIM values (the harness checks their number and range)."""
     try:
@@ -111,6 +121,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "sets evaluation.segment_threshold)")
     ap.add_argument("--segment-min-area", type=int, default=None, metavar="A",
                     help="smallest segment counted, in pixels: a power of 4 (default 16; sets evaluation.segment_min_area)")
+    ap.add_argument("--ensemble-weight-grid", type=str, default=None, metavar="N|A,B,C",
+                    help="ensemble weight sweep: the mIoU of every condition at every member weighting of a grid, and which member is "
+                         "right where: an integer n in [2, 63] (n equally spaced SegFormer shares) or 1-63 comma-separated increasing "
+                         "shares in [0, 1] (sets evaluation.ensemble_weight_grid)")
     ap.add_argument("--change-strata", type=str, default=None, metavar="EDGES",
                     help="split every corrupted frame's errors by how much the corruption changed each input pixel against the clean "
                          "frame: 'default' (0.5,4.5,16.5,64.5) or 1-7 comma-separated increasing edges in 8-bit grey levels; needs "
@@ -162,6 +176,8 @@ def main():
             config.set("evaluation.segment_threshold", args.segment_threshold)
         if args.segment_min_area is not None:
             config.set("evaluation.segment_min_area", args.segment_min_area)
+        if args.ensemble_weight_grid is not None:
+            config.set("evaluation.ensemble_weight_grid", parse_weight_grid(args.ensemble_weight_grid))
         if args.change_strata is not None:
             config.set("evaluation.change_strata", parse_change_strata(args.change_strata))
         if args.image_quality:
@@ -179,9 +195,14 @@ def main():
         metrics = RobustnessMetrics(num_classes=config.get("model.num_classes", 19), weather_conditions=config.get("data.weather_conditions"))
         results = evaluate_model(model, loader, metrics, device, config)
         if rank == 0:
-            generate_evaluation_report({k: float(v) for k, v in results.items()}, Path(args.output_dir))   # json + markdown, :277-392
-            for k, v in results.items():
-                logger.info("%s: %.4f", k, v)
+            # (the weight sweep's grid and curves are lists of floats; every other value is a scalar)
+            plain = {k: [float(x) for x in v] if isinstance(v, (list, tuple)) else float(v) for k, v in results.items()}
+            generate_evaluation_report(plain, Path(args.output_dir))   # json + markdown, :277-392
+            for k, v in plain.items():
+                if isinstance(v, list):
+                    logger.info("%s: %s", k, " ".join(f"{x:.4f}" for x in v))
+                else:
+                    logger.info("%s: %.4f", k, v)
     except Exception as e:  # noqa: BLE001 - the reference converts failures to exit code 1 (evaluate.py:506-508)
         logger.error("Evaluation failed: %s", e)
         raise SystemExit(1)

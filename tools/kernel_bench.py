@@ -273,6 +273,21 @@ def main():
         cases[f"ensemble eval stats (the yardstick of failure stats), {tag} logits"] = (
             lambda m1=m1, m2=m2: ops.ensemble_eval_stats(m1, m2, 0, wts, T, labels, cond, edges, bins, hist, -1e-3, 0.70), "hbm", (2 * C * 4 + 1) * px * B)
         cases[f"failure stats single model, {tag} logits"] = (lambda m1=m1: ops.failure_stats(m1, labels, fst, cond), "hbm", (C * 4 + 1) * px * B)
+    # ensemble weight sweep (evaluation.ensemble_weight_grid): G x C combines and argmax steps per pixel in one pass over the member
+    # logits, issue-bound, so "of peak" says how far from a plain scan of the same bytes the sweep is.  Yardsticks on the same
+    # tensors: the failure statistics above and the one-pass confusion + statistics kernel
+    ccnt, coob = ops.new_counts(C, dev, 6), torch.zeros(1, dtype=torch.int64, device=dev)
+    for tag, (m1, m2) in (("random", (s1, s2)), ("trained-like", (t1, t2))):
+        for G in (6, 18, 64):
+            shares = np.linspace(0.0, 1.0, G).astype(np.float32)
+            wpairs = np.stack([shares, np.float32(1) - shares], axis=1)
+            wst = ops.new_weight_grid_stats(6, G, C, dev)
+            cases[f"weight grid G={G}, {tag} logits"] = (
+                lambda m1=m1, m2=m2, wpairs=wpairs, wst=wst: ops.ensemble_weight_grid_stats(m1, m2, wpairs, labels, cond, wst), "hbm",
+                (2 * C * 4 + 1) * px * B)
+        cases[f"combine confusion stats (a yardstick of weight grid), {tag} logits"] = (
+            lambda m1=m1, m2=m2: ops.combine_confusion_stats(m1, m2, 0, wts, T, labels, cond, ccnt, coob, edges, bins, hist, -1e-3, 0.70),
+            "hbm", (2 * C * 4 + 1) * px * B)
     xmp = torch.randn(B, H // 2, W // 2, 64, device=dev)
     cases["maxpool3x3s2 nhwc 64ch (resnet stem)"] = (lambda: ops.maxpool3x3s2_nhwc(xmp), "hbm", 64 * 4 * (H // 2) * (W // 2) * B * (1 + 1 / 4))
     lowl = torch.randn(B, C, H // 4, W // 4, device=dev)
