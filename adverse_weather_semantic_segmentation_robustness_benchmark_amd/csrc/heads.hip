@@ -773,6 +773,25 @@ static int mfma_tile_rows(int h, int w, int H, int W)
     return 0;
 }
 
+// Largest power-of-two tile T <= 32 of one axis for which every tile's pixels plus one halo pixel either side touch at most
+// 3 source cells (the adjoint kernel's register window), 0 when not even one pixel does.
+static int adjoint_tile(int n_in, int n_out)
+{
+    const float sc = (float)n_in / (float)n_out;
+    for (int T = 32; T >= 1; T >>= 1) {
+        bool good = true;
+        for (int p0 = 0; p0 < n_out && good; p0 += T) {
+            int a, b, c, d;
+            host_src(p0 > 0 ? p0 - 1 : 0, sc, n_in, &a, &b);
+            const int pe = p0 + T < n_out ? p0 + T : n_out - 1;
+            host_src(pe, sc, n_in, &c, &d);
+            if (d - a > 2) good = false;
+        }
+        if (good) return T;
+    }
+    return 0;
+}
+
 static int head_waves()
 {
     const char* e = getenv("AWSEG_HEAD_WAVES");
@@ -1062,16 +1081,19 @@ namespace {
 // Adjoint of awseg_upconv3x3_linear with respect to g9 (the backward pass of conv3x3(interpolate(f)) in training):
 //   dG[b, ci, cj, tap, c] = sum over pixels (y, x) whose tap (ky, kx) lands on (y + ky - 1, x + kx - 1) inside the image
 //                           and whose bilinear stencil there touches cell (ci, cj):  l_i * l_j * dz[b, y, x, c]
-// Block = one 32 x 32 pixel tile of one image, thread = one channel (blockDim = Cmid): the shifted rows / columns of the
-// tile touch at most 3 cell rows / columns when H/h >= 32 (checked by the launcher), so a thread keeps 3 x 3 x 9
-// accumulators in registers; per-row and per-column stencil weights of the 34 shifted coordinates come from LDS tables
-// (zero outside the image).  dz is read exactly once, coalesced over channels; the 81 sums per channel are added to dG
-// with float atomics (<= 9 tiles meet in a cell).
+// Block = one TY x TX pixel tile of one image (32 x 32 where that fits), thread = one channel (blockDim = Cmid): the launcher
+// picks TY, TX <= 32 such that the shifted rows / columns of EVERY tile touch at most 3 cell rows / columns (adjoint_tile
+// below walks the tiles with the float expressions of bilinear_src; H/h >= 32 alone does not give that at 32 pixels: at a
+// non-integer factor the phase of a tile's first pixel drifts towards 1 and the last halo pixel's second cell is a fourth
+// one), so a thread keeps 3 x 3 x 9 accumulators in registers; per-row and per-column stencil weights of the <= 34 shifted
+// coordinates come from LDS tables (zero outside the image).  dz is read exactly once, coalesced over channels; the 81 sums
+// per channel are added to dG with float atomics (<= 9 tiles meet in a cell at 32 x 32).
 __global__ __launch_bounds__(256)
-void upconv3x3_adjoint_kernel(const float* __restrict__ dz, int h, int w, int H, int W, int C, float* __restrict__ dg)
+void upconv3x3_adjoint_kernel(const float* __restrict__ dz, int h, int w, int H, int W, int C, int TY, int TX,
+                              float* __restrict__ dg)
 {
     __shared__ float s_wy[34][3], s_wx[34][3];
-    const int b = blockIdx.z, y0 = blockIdx.y * 32, x0 = blockIdx.x * 32;
+    const int b = blockIdx.z, y0 = blockIdx.y * TY, x0 = blockIdx.x * TX;
     const float sh = (float)h / (float)H, sw = (float)w / (float)W;
     const int ibase = bilinear_src(y0 > 0 ? y0 - 1 : 0, sh, h).i0;
     const int jbase = bilinear_src(x0 > 0 ? x0 - 1 : 0, sw, w).i0;
@@ -1099,7 +1121,7 @@ void upconv3x3_adjoint_kernel(const float* __restrict__ dz, int h, int w, int H,
 #pragma unroll
             for (int t = 0; t < 9; ++t) acc[a][bb][t] = 0.f;
     const float* src = dz + (int64_t)b * H * W * C + c;
-    const int ny = (H - y0) < 32 ? (H - y0) : 32, nx = (W - x0) < 32 ? (W - x0) : 32;
+    const int ny = (H - y0) < TY ? (H - y0) : TY, nx = (W - x0) < TX ? (W - x0) : TX;
     for (int r = 0; r < ny; ++r) {
         for (int q = 0; q < nx; ++q) {
             const float v = src[((int64_t)(y0 + r) * W + x0 + q) * C];
@@ -1306,12 +1328,18 @@ AWSEG_API int awseg_upconv3x3_adjoint(const float* dz, int64_t batch, int cmid, 
 {
     if (!dz || !dg9 || batch < 1 || cmid < 1 || h < 1 || w < 1 || height < 1 || width < 1) return AWSEG_EINVAL;
     if (cmid > 256 || batch > 65535) return AWSEG_ERANGE;
-    // a 32-pixel tile (+1 halo) may touch at most 3 cells per axis: true when the upsampling factor is >= 32
     if ((int64_t)h * 32 > height || (int64_t)w * 32 > width) return AWSEG_ERANGE;
+    // a tile (+1 halo) may touch at most 3 cells per axis.  A factor >= 32 does not give that for 32 pixels (34 shifted
+    // coordinates span 33 / 32 of a cell or less, which crosses two cell borders — four cells — once the first one's phase is
+    // close enough to 1: 25 -> 819, 29 -> 945, 33 -> 1074, ...), so the tile is the largest that fits on every tile start;
+    // 16 pixels always do at these factors (17 / 32 of a cell crosses one border).  Host arithmetic only, no device round trip.
+    const int ty = adjoint_tile(h, height), tx = adjoint_tile(w, width);
+    if (ty < 1 || tx < 1) return AWSEG_ERANGE;
+    if ((height + ty - 1) / ty > 65535) return AWSEG_ERANGE;
     hipError_t e = hipMemsetAsync(dg9, 0, (size_t)batch * h * w * 9 * cmid * sizeof(float), awseg_s(stream));
     if (e != hipSuccess) return (int)e;
-    dim3 grid((width + 31) / 32, (height + 31) / 32, (unsigned)batch);
-    hipLaunchKernelGGL(upconv3x3_adjoint_kernel, grid, dim3(cmid), 0, awseg_s(stream), dz, h, w, height, width, cmid, dg9);
+    dim3 grid((width + tx - 1) / tx, (height + ty - 1) / ty, (unsigned)batch);
+    hipLaunchKernelGGL(upconv3x3_adjoint_kernel, grid, dim3(cmid), 0, awseg_s(stream), dz, h, w, height, width, cmid, ty, tx, dg9);
     AWSEG_LAUNCH_CHECK();
     return 0;
 }

@@ -319,6 +319,11 @@ class DeepLabV3PlusDecoder(nn.Module):
         # up x4 (align_corners=True) -> cat -> depthwise 3x3 in one HIP pass (no upsampled map, no concat), then the
         # pointwise half of block2's SeparableConv2d with BN + ReLU in the GEMM epilogue
         dwc, pwc = self.block2[0][0], self.block2[0][1]
+        f = int(self.up.scale_factor)
+        if (hi.shape[2], hi.shape[3]) != (f * a.shape[2], f * a.shape[3]):
+            # the kernel resamples to whatever size the skip has; the as-written graph cannot concatenate these (frame not divisible by 16)
+            raise N.AwsegError(f"DeepLabV3+ decoder: x{f} of the {a.shape[2]}x{a.shape[3]} ASPP map is not the {hi.shape[2]}x{hi.shape[3]} skip map "
+                               "(the frame's sides must be multiples of 16)")
         d = ops.dwconv3x3_upcat(fused.nhwc_view(a), fused.nhwc_view(hi), fused.dw_taps(dwc))
         B, H4, W4, Cc = d.shape
         w, shift = fused.folded_conv_bn(pwc, self.block2[1])

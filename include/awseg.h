@@ -664,7 +664,9 @@ int awseg_attention_d32_packed_kv(const float* q, const float* kv, float* out, i
  *                           BatchNorm in training mode needs the batch statistics of z itself; bias float32 [Cmid];
  *                           Cmid % 32 == 0, <= 256;
  *   awseg_upconv3x3_adjoint dg9 = (d z / d g9)^T dz — dz float32 [B,H,W,Cmid] read once, dg9 zeroed and accumulated with
- *                           float atomics; needs H >= 32 h and W >= 32 w (SegFormer: stride 32).
+ *                           float atomics; needs H >= 32 h and W >= 32 w (SegFormer: stride 32), else AWSEG_ERANGE.  The
+ *                           launcher picks the tile (32 x 32 pixels, or 16 per axis where a non-integer factor makes a
+ *                           32-pixel tile plus halo reach a fourth cell, e.g. 25 -> 819) on the host: exact at every such size.
  * The two small GEMMs either side (g9 = f W; df = dg9 W^T, dW = f^T dg9) are the caller's (torch.matmul). */
 int awseg_upconv3x3_linear(const float* g9, int64_t batch, int cmid, int h, int w, int height, int width,
                            const float* bias, float* out, int channels_last, awseg_stream_t stream);

@@ -141,11 +141,16 @@ def test_aspp_fused_vs_module(P):
 
 @pytest.mark.parametrize("strategy", ["weighted_average", "max_confidence", "mean"])
 def test_ensemble_forward_eval_contract(P, oracle, strategy):
+    ensemble_forward_eval_contract(P, oracle, strategy, (64, 128))
+
+
+def ensemble_forward_eval_contract(P, oracle, strategy, size):
+    Hs, Ws = size
     torch.manual_seed(3)
     m = calibrate_bn(P.EnsembleModel(num_classes=19, include_depth=False, ensemble_strategy=strategy, pretrained=False)).cuda().eval()
     with torch.no_grad():
         m.ensemble_weights.copy_(torch.tensor([0.3, -0.2])); m.temperature.fill_(1.5)
-    x = torch.randn(2, 3, 64, 128, device="cuda")
+    x = torch.randn(2, 3, Hs, Ws, device="cuda")
     out = m(x)
     assert set(out) == {"segmentation", "segformer_seg", "deeplabv3plus_seg"}          # model.py:464-468
     s1, s2 = out["segformer_seg"].cpu().numpy(), out["deeplabv3plus_seg"].cpu().numpy()
@@ -157,7 +162,7 @@ def test_ensemble_forward_eval_contract(P, oracle, strategy):
         maxconf_flips_are_rounding_ties(got, ref, s1, s2)          # exact except float32 rounding ties of the two confidences
     else:
         assert np.array_equal(got, ref)                                                # bit-exact given the member logits
-    labels = torch.randint(0, 19, (2, 64, 128), dtype=torch.uint8, device="cuda")
+    labels = torch.randint(0, 19, (2, Hs, Ws), dtype=torch.uint8, device="cuda")
     counts = torch.zeros(6, 361, dtype=torch.int64, device="cuda")
     oob = torch.zeros(1, dtype=torch.int64, device="cuda")
     res = m.forward_eval(x, labels, counts, oob, torch.tensor([0, 2], dtype=torch.int32, device="cuda"))
@@ -462,8 +467,16 @@ def test_eval_forward_is_a_pure_function_of_the_frame(P):
     del junk
 
 
-@pytest.mark.parametrize("size", [(128, 192), (160, 256)])
-def test_segformer_training_heads_on_hip_match_the_as_written_graph(P, size):
+def mit_last_map(n):
+    """Side of the MiT encoder's last map for an n-pixel side: 7x7 stride 4 pad 3, then three 3x3 stride 2 pad 1 (n // 32 when 32 | n)."""
+    n = (n - 1) // 4 + 1
+    for _ in range(3):
+        n = (n - 1) // 2 + 1
+    return n
+
+
+@pytest.mark.parametrize("size", [(128, 192), (160, 256), (100, 140), (97, 131)])
+def test_segformer_training_heads_on_hip_match_the_as_written_graph(P, size, monkeypatch):
     """BASELINE config 4 / VERDICT r1 #6: in training SegFormerModel runs conv3x3(interpolate(f)) — the first layer of both
     heads (PKG/models/model.py:209-214, :219-221) — as ops._UpConv3x3 (HIP forward + HIP adjoint backward) in front of the
     reference's BatchNorm (batch statistics) / ReLU / Dropout2d / convolution modules.  On well-conditioned encoder features:
@@ -472,9 +485,18 @@ def test_segformer_training_heads_on_hip_match_the_as_written_graph(P, size):
     BatchNorm's backward cancels leading terms and ANY float32 evaluation is further than that from the truth — no further
     from the as-written graph in FLOAT64 (CPU) than 4x what the as-written float32 graph is.  Dropout off (one function for
     all three runs).  (A random-init ENCODER in front would not do: its output is nearly constant over the image, BatchNorm
-    then divides by a variance at rounding level and any two float32 evaluations differ by per cent.)"""
+    then divides by a variance at rounding level and any two float32 evaluations differ by per cent.)
+    Frames off the 32-pixel grid — (100, 140): the encoder's 4 x 5 map is finer than stride 32, ops.upconv3x3_train_supported
+    declines and both heads take the torch graph in front of the fused BatchNorm; (97, 131): H W % 4 != 0, the fused BatchNorm
+    declines as well — must give the same gradients at the same tolerance, without raising and without entering ops._UpConv3x3."""
     import copy
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd import ops as O
     H, W = size
+    hh, ww = mit_last_map(H), mit_last_map(W)
+    assert (hh, ww) == (H // 32, W // 32) or (H % 32 or W % 32)
+    entered = []
+    real_apply = O._UpConv3x3.apply
+    monkeypatch.setattr(O._UpConv3x3, "apply", staticmethod(lambda *a: (entered.append(1), real_apply(*a))[1]))
     torch.manual_seed(31)
     m = P.SegFormerModel(num_classes=19, include_depth=True, pretrained=False)
     for mod in m.modules():
@@ -488,7 +510,7 @@ def test_segformer_training_heads_on_hip_match_the_as_written_graph(P, size):
             torch.nn.init.constant_(mod.bias, 8.0)
     m64 = copy.deepcopy(m).double().train()
     m = m.cuda().train()
-    f0 = torch.randn(2, 256, H // 32, W // 32)
+    f0 = torch.randn(2, 256, hh, ww)
     gseg, gdep = torch.randn(2, 19, H, W), torch.randn(2, 1, H, W)
 
     def run(model, fused, dev, dtype):
@@ -502,7 +524,11 @@ def test_segformer_training_heads_on_hip_match_the_as_written_graph(P, size):
         res.update({"grad " + n: p.grad.double().cpu() for n, p in model.named_parameters() if p.grad is not None})
         return res
 
-    r_h, r_t, r_64 = run(m, True, "cuda", torch.float32), run(m, False, "cuda", torch.float32), run(m64, False, "cpu", torch.float64)
+    r_h = run(m, True, "cuda", torch.float32)
+    # entered for exactly the geometries upconv3x3_train_supported accepts (both heads), never for one it declines
+    assert len(entered) == (2 if O.upconv3x3_train_supported(256, 256, hh, ww, H, W) else 0), (size, entered)
+    assert O.upconv3x3_train_supported(256, 256, hh, ww, H, W) == (H % 32 == 0 and W % 32 == 0)
+    r_t, r_64 = run(m, False, "cuda", torch.float32), run(m64, False, "cpu", torch.float64)
     assert set(r_h) == set(r_64) and "grad segmentation_head.0.weight" in r_h and "grad depth_head.depth_head.0.bias" in r_h
     gmax = max(v.abs().max().item() for k, v in r_64.items() if k.startswith("grad "))
     worst = worst_t = 0.0
@@ -540,3 +566,71 @@ def test_segformer_training_step_through_the_whole_model_runs_on_hip(P):
         opt.step()
         losses.append(loss.item())
     assert losses[-1] < losses[0], losses
+
+
+# ------------------------------------------------------------------ frames off the 32-pixel grid
+def as_written_cpu64(model, x):
+    """Same weights, reference op graph, CPU float64."""
+    m = copy.deepcopy(model).cpu().double().eval()
+    for mod in m.modules():
+        mod.fused_eval = False
+    with torch.no_grad():
+        return m(x.cpu().double())
+
+
+def gate_vs_as_written(model, x, out, what):
+    """north_star's 1e-4 ABSOLUTE on logits and depth against the as-written CPU graph.  Where a case misses it against the float32
+    CPU graph, both float32 evaluations are priced against the as-written graph in FLOAT64 and the gate stays on HIP-vs-float64."""
+    ref = as_written_cpu(model, x)
+    assert set(out) == set(ref)
+    for k in sorted(ref):
+        assert out[k].shape == ref[k].shape, (k, out[k].shape, ref[k].shape)
+        e = abs_err(out[k].cpu(), ref[k], f"{what} {k} vs as-written CPU graph (gate 1e-04)")
+        if not e < 1e-4:
+            r64 = as_written_cpu64(model, x)[k]
+            e_cpu = abs_err(ref[k].double(), r64, f"{what} {k}: as-written float32 CPU graph vs float64")
+            e = abs_err(out[k].cpu().double(), r64, f"{what} {k}: HIP vs as-written float64 graph (gate 1e-04)")
+            assert e < 1e-4, (k, e, e_cpu)
+
+
+@pytest.mark.parametrize("size", [(100, 140), (97, 131), (33, 65)])
+def test_segformer_model_hip_vs_as_written_at_ragged_frames(P, size):
+    """Frames that are no multiple of 32 (nor of 4): the encoder's last map is finer than stride 32 (4 x 5, 4 x 5, 2 x 3), the
+    heads' upsampling factors are 25 / 28, 24.25 / 26.2 and 16.5 / 21.7, and every patch embedding sees an odd map."""
+    torch.manual_seed(40)
+    m = calibrate_bn(P.SegFormerModel(num_classes=19, include_depth=True, pretrained=False)).cuda().eval()
+    x = torch.randn(1, 3, *size, device="cuda")
+    out = m(x)
+    assert out["segmentation"].shape == (1, 19) + size and out["depth"].shape == (1, 1) + size
+    gate_vs_as_written(m, x, out, f"segformer {size[0]}x{size[1]}")
+
+
+@pytest.mark.parametrize("size", [(112, 176), (144, 80)])
+def test_deeplab_model_hip_vs_as_written_at_frames_divisible_by_16_only(P, size):
+    """Divisible by 16, not by 32: the stride-16 maps are odd (7 x 11, 9 x 5), all three ASPP dilations (12, 24, 36) exceed
+    them, the stem's max-pool and the stride-2 convolutions see odd inputs, and the depth map goes up by a factor of 16."""
+    torch.manual_seed(41)
+    m = calibrate_bn(P.DeepLabV3PlusModel(num_classes=19, include_depth=True, pretrained=False)).cuda().eval()
+    x = torch.randn(1, 3, *size, device="cuda")
+    out = m(x)
+    assert out["segmentation"].shape == (1, 19) + size and out["depth"].shape == (1, 1) + size
+    gate_vs_as_written(m, x, out, f"deeplab {size[0]}x{size[1]}")
+
+
+def test_deeplab_frame_not_divisible_by_16_raises_in_both_graphs(P):
+    """(100, 140): the stride-16 map is 7 x 9, the stride-4 skip 25 x 35; the decoder's x4 upsampling gives 28 x 36 and the
+    as-written graph cannot concatenate the two.  The fused decoder resamples to whatever size the skip has, so it must check
+    the sizes itself: an answer here would be a map the reference cannot produce."""
+    torch.manual_seed(42)
+    m = calibrate_bn(P.DeepLabV3PlusModel(num_classes=19, include_depth=True, pretrained=False)).cuda().eval()
+    x = torch.randn(1, 3, 100, 140, device="cuda")
+    with pytest.raises(RuntimeError):
+        as_written_cpu(m, x)
+    with pytest.raises(RuntimeError, match="skip"):
+        m(x)
+    torch.cuda.synchronize()
+    assert m(torch.randn(1, 3, 112, 176, device="cuda"))["segmentation"].shape == (1, 19, 112, 176)      # and the model still serves
+
+
+def test_ensemble_forward_eval_contract_at_a_ragged_frame(P, oracle):
+    ensemble_forward_eval_contract(P, oracle, "weighted_average", (112, 176))
