@@ -51,6 +51,37 @@ def _cfg(config, key, default):
     return default if v is None else v
 
 
+def _flag(config, key) -> bool:
+    on = _cfg(config, key, False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError(f"{key} is true or false, got {on!r}")
+    return bool(on)
+
+
+def _needs_sweep(config, key, why) -> None:
+    if _cfg(config, "evaluation.severities", None) is None:
+        raise ValueError(f"{key} needs a severity sweep (evaluation.severities): without one {why}")
+
+
+def check_frames(option, images) -> None:
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"evaluation.{option}: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
+
+
+def _check_budget(count: int, budget: int, what: str) -> None:
+    """The fixed-point counters are int64 sums of per-term values (include/awseg.h): raise before they could wrap.  `what`: the
+    counters and the unit `budget` is in."""
+    if count > budget:
+        raise OverflowError(f"{what.format(budget)} (summed over ranks); {count} would exceed that")
+
+
+def _warn_wrapped_index(opt, labels, num_classes: int, text: str) -> None:
+    """Once per run: uint8 labels make the pooled confusion counters reproduce the reference's wrapped index, `opt`'s never wrap."""
+    if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not opt.get("warned"):
+        opt["warned"] = True
+        logger.warning(text, num_classes)
+
+
 def temperature_grid(spec):
     """`evaluation.temperature_grid`: a list of temperatures, or {min, max, steps} = torch.linspace(min, max, steps) in float32
     (the reference's grid is {min: 0.1, max: 10.0, steps: 100}).  None / absent: calibration off."""
@@ -62,10 +93,8 @@ def temperature_grid(spec):
 
 
 def check_calibration_budget(pixels: int) -> None:
-    """The NLL counters are int64 sums of per-pixel values up to 2^31 (include/awseg.h): raise before they could wrap."""
-    if pixels > ops.CALIB_PIXEL_BUDGET:
-        raise OverflowError(f"temperature calibration counters hold {ops.CALIB_PIXEL_BUDGET} pixels (summed over ranks); "
-                            f"{pixels} would exceed that")
+    """The NLL counters are int64 sums of per-pixel values up to 2^31."""
+    _check_budget(pixels, ops.CALIB_PIXEL_BUDGET, "temperature calibration counters hold {} pixels")
 
 
 def depth_options(config):
@@ -73,9 +102,7 @@ def depth_options(config):
     that can touch 0, so the relative errors need a floor) and `evaluation.depth_target` ('frame': the loader's target, estimated
     from the frame as rendered; 'clean': under a severity sweep every variant is scored against its clean frame's target).
     -> None when off, else {'min': float, 'target': str}."""
-    on = _cfg(config, "evaluation.depth_metrics", False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError(f"evaluation.depth_metrics is true or false, got {on!r}")
+    on = _flag(config, "evaluation.depth_metrics")
     target = _cfg(config, "evaluation.depth_target", "frame")
     if target not in ("frame", "clean"):
         raise ValueError(f"evaluation.depth_target is 'frame' or 'clean', got {target!r}")
@@ -84,19 +111,15 @@ def depth_options(config):
         raise ValueError(f"evaluation.depth_min must be a finite number > 0, got {md!r}")
     if not on:
         return None
-    if target == "clean" and _cfg(config, "evaluation.severities", None) is None:
-        raise ValueError("evaluation.depth_target: clean needs a severity sweep (evaluation.severities): without one a frame has no "
-                         "clean counterpart")
+    if target == "clean":
+        _needs_sweep(config, "evaluation.depth_target: clean", "a frame has no clean counterpart")
     return {"min": float(md), "target": str(target)}
 
 
 def failure_option(config) -> bool:
     """`evaluation.failure_detection` (bool, default off): per-condition failure-detection counters (AUROC / AURC of four
     uncertainty scores against the prediction's errors)."""
-    on = _cfg(config, "evaluation.failure_detection", False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError(f"evaluation.failure_detection is true or false, got {on!r}")
-    return bool(on)
+    return _flag(config, "evaluation.failure_detection")
 
 
 def boundary_option(config):
@@ -119,9 +142,7 @@ def segment_option(config):
     invents per condition).  `evaluation.segment_threshold`: the share of a segment that must be covered, one of
     0.25 / 0.5 / 0.75 / 1.0 (default 0.5); `evaluation.segment_min_area`: the smallest segment counted, a power of 4 in [1, 4^10]
     (default 16); both checked also when the option is off.  -> None when off, else {'threshold': float, 'min_area': int}."""
-    on = _cfg(config, "evaluation.segment_metrics", False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError(f"evaluation.segment_metrics is true or false, got {on!r}")
+    on = _flag(config, "evaluation.segment_metrics")
     threshold = _cfg(config, "evaluation.segment_threshold", 0.5)
     min_area = _cfg(config, "evaluation.segment_min_area", 16)
     try:
@@ -219,17 +240,10 @@ def change_option(config, images=None):
     except (ValueError, TypeError) as e:
         raise ValueError(f"evaluation.change_strata is 'default' or a list of 1 .. {ops.MAX_STRATA - 1} strictly increasing finite "
                          f"numbers >= 0, got {spec!r} ({e})") from None
-    if _cfg(config, "evaluation.severities", None) is None:
-        raise ValueError("evaluation.change_strata needs a severity sweep (evaluation.severities): without one a corrupted frame has "
-                         "no clean twin to measure the change against")
+    _needs_sweep(config, "evaluation.change_strata", "a corrupted frame has no clean twin to measure the change against")
     if images is not None:
-        check_change_frames(images)
+        check_frames("change_strata", images)
     return edges
-
-
-def check_change_frames(images) -> None:
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
-        raise ValueError(f"evaluation.change_strata: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
 
 
 IQ_DEFAULT_TARGETS = (0.9, 0.75, 0.5)
@@ -242,9 +256,7 @@ def quality_options(config, images=None):
     (evaluation.severities).  `evaluation.image_quality_targets`: the SSIM values the mIoU is interpolated at, a list of 1 .. 8
     numbers in (0, 1), default [0.9, 0.75, 0.5]; checked also when the option is off.  `images`, when given, is a batch of frames:
     they must be float32 [B, 3, H, W].  -> None when off, else {'targets': [...]}."""
-    on = _cfg(config, "evaluation.image_quality", False)
-    if not isinstance(on, (bool, np.bool_)):
-        raise ValueError(f"evaluation.image_quality is true or false, got {on!r}")
+    on = _flag(config, "evaluation.image_quality")
     spec = _cfg(config, "evaluation.image_quality_targets", list(IQ_DEFAULT_TARGETS))
     bad = isinstance(spec, (bool, str, bytes, dict, int, float, np.number, np.bool_))
     try:
@@ -257,24 +269,15 @@ def quality_options(config, images=None):
         raise ValueError(f"evaluation.image_quality_targets is a list of 1 .. {IQ_MAX_TARGETS} numbers in (0, 1), got {spec!r}")
     if not on:
         return None
-    if _cfg(config, "evaluation.severities", None) is None:
-        raise ValueError("evaluation.image_quality needs a severity sweep (evaluation.severities): without one a corrupted frame has "
-                         "no clean twin to measure the image quality against")
+    _needs_sweep(config, "evaluation.image_quality", "a corrupted frame has no clean twin to measure the image quality against")
     if images is not None:
-        check_quality_frames(images)
+        check_frames("image_quality", images)
     return {"targets": [float(t) for t in targets]}
 
 
-def check_quality_frames(images) -> None:
-    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
-        raise ValueError(f"evaluation.image_quality: the frames are float32 [B, 3, H, W], got {images.dtype} {tuple(images.shape)}")
-
-
 def check_quality_budget(terms: int) -> None:
-    """The image-quality counters are int64 sums of per-term values up to 2^26 (include/awseg.h): raise before they could wrap."""
-    if terms > ops.IQ_TERM_BUDGET:
-        raise OverflowError(f"image-quality counters hold {ops.IQ_TERM_BUDGET} pixel-channels (summed over ranks); {terms} would "
-                            "exceed that")
+    """The image-quality counters are int64 sums of per-term values up to 2^26."""
+    _check_budget(terms, ops.IQ_TERM_BUDGET, "image-quality counters hold {} pixel-channels")
 
 
 BOOTSTRAP_MAX_REPLICATES = 65536
@@ -321,9 +324,49 @@ def bootstrap_resampling_set(table: torch.Tensor, seen: torch.Tensor, slot: torc
 
 
 def check_depth_budget(pixels: int) -> None:
-    """The depth counters are int64 sums of per-pixel terms up to 2^31 (include/awseg.h): raise before they could wrap."""
-    if pixels > ops.DEPTH_PIXEL_BUDGET:
-        raise OverflowError(f"depth error counters hold {ops.DEPTH_PIXEL_BUDGET} pixels (summed over ranks); {pixels} would exceed that")
+    """The depth counters are int64 sums of per-pixel terms up to 2^31."""
+    _check_budget(pixels, ops.DEPTH_PIXEL_BUDGET, "depth error counters hold {} pixels")
+
+
+# The optional counters of EvalState in the order they join the all-reduce (the same on every rank).  Per option: the attribute that
+# holds its dict (None when off), the keys whose tensors are summed, the host count that travels behind them with the check of its
+# budget on the SUMMED count, and what finalize raises when the summed 'oob' word is not zero (the bootstrap's is checked where its
+# tables are read: bootstrap_resampling_set).
+COUNTERS = (
+    ("calib", ("stats",), "pixels", check_calibration_budget, None),
+    ("depth", ("stats",), "pixels", check_depth_budget, None),
+    ("failure", ("stats",), None, None, None),
+    ("boundary", ("stats", "oob"), None, None, "prediction map value outside [0, num_classes) in the boundary counters"),
+    ("change", ("stats", "oob"), None, None, "prediction map value outside [0, num_classes), or a clean-frame row outside the buffer, "
+                                             "in the change-strata counters"),
+    ("quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality counters"),
+    ("segments", ("stats", "oob"), None, None, "prediction map value outside [0, num_classes) in the segment counters"),
+    ("weight_grid", ("stats",), None, None, None),
+    ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
+    ("paired", ("stats", "oob", "sources"), None, None, "prediction map value outside [0, num_classes) in the consistency counters"),
+)
+
+
+def _grown(buf, numel: int, device):
+    """A flat uint8 buffer of at least numel elements: `buf` when it is large enough (grow-only, contents not kept)."""
+    return buf if buf is not None and buf.numel() >= numel else torch.empty(numel, dtype=torch.uint8, device=device)
+
+
+def _keep_rows(store, n_rows: int, data, idx, fill: bool):
+    """store['rows']: float32 [rows, width] of per-source clean data at the row indices of the clean prediction maps, grown to their
+    n_rows with the old rows kept.  `data` [B, ...] is this batch's, `idx` (EvalState.frame_ref) its sources' rows: a clean batch
+    (fill) leaves its data there.  -> the buffer."""
+    rows, width = store["rows"], data[0].numel()
+    if rows is not None and rows.shape[1] != width:
+        raise ValueError("every frame of a severity sweep must have the same size")
+    if rows is None or rows.shape[0] < n_rows:
+        store["rows"] = torch.empty(n_rows, width, dtype=torch.float32, device=data.device)
+        if rows is not None:
+            store["rows"][:rows.shape[0]].copy_(rows)
+        rows = store["rows"]
+    if fill:
+        rows.index_copy_(0, idx.long(), data.reshape(data.shape[0], width))
+    return rows
 
 
 class EvalState:
@@ -344,6 +387,9 @@ class EvalState:
         self.edges = torch.linspace(0, 1, num_bins + 1).to(device)
         self.auroc = torch.zeros(2, AUROC_BINS, dtype=torch.int64, device=device) if ensemble else None
         self.samples = 0
+        # the uint8 prediction map of the batch in flight, for whichever counters read one (pred_map); clean maps of a sweep are kept
+        # in self.paired instead
+        self.pred_scratch = None
         # streamed temperature calibration (off unless a grid is given): NLL + ECE bins per (slot, grid temperature)
         self.calib = None
         if temperature_grid is not None:
@@ -355,8 +401,7 @@ class EvalState:
         if depth is not None:
             if depth["target"] == "clean" and sweep is None:
                 raise ValueError("depth_target 'clean' needs a severity sweep")
-            # 'rows': under depth_target 'clean', the clean frames' targets, one float32 row per live source, at the row indices of
-            # the clean prediction maps (self.paired['rows']): allocated, reused and freed with them
+            # 'rows': under depth_target 'clean', the clean frames' targets (_keep_rows)
             self.depth = {"stats": ops.new_depth_eval_stats(device, 1 + len(conditions)), "min": float(depth["min"]),
                           "target": depth["target"], "pixels": 0, "rows": None}
         # failure-detection counters (off unless failure = failure_option(config)): int64 [slot, AWSEG_FAIL_ROW] over this run's slots
@@ -364,17 +409,15 @@ class EvalState:
         if failure:
             self.failure = {"stats": ops.new_failure_stats(device, 1 + len(conditions)), "conditions": list(conditions),
                             "single": not ensemble}
-        # boundary-band counters (off unless boundary = boundary_option(config)): int64 [slot, ring, C*C + 2 C]; 'scratch': the uint8
-        # prediction map of the batch where no severity sweep keeps one
+        # boundary-band counters (off unless boundary = boundary_option(config)): int64 [slot, ring, C*C + 2 C]
         self.boundary = None
         if boundary is not None:
             widths = [int(d) for d in ops.boundary_widths(boundary)]
             self.boundary = {"widths": widths, "stats": ops.new_boundary_stats(metrics.num_classes, len(widths), device, 1 + len(conditions)),
-                             "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+                             "oob": torch.zeros(1, dtype=torch.int64, device=device)}
         # frame bootstrap (off unless bootstrap = bootstrap_options(config, num_sources)): per-frame IoU counters int64
         # [source, variant, 3 C], how often each (source, variant) came, and 1 + its condition slot; variant 0 is the only one
-        # without a sweep, under a sweep variant = the frame's slot index (0 clean, 1 + k S + j - 1 for kind k at level j).
-        # 'scratch': the uint8 prediction map of the batch where neither the sweep nor the boundary counters keep one
+        # without a sweep, under a sweep variant = the frame's slot index (0 clean, 1 + k S + j - 1 for kind k at level j)
         self.bootstrap = None
         if bootstrap is not None:
             if bootstrap.get("sources") is None:
@@ -385,13 +428,12 @@ class EvalState:
                               "table": ops.new_frame_counts(n_src * variants, metrics.num_classes, device).view(n_src, variants, -1),
                               "seen": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
                               "slot": torch.zeros(n_src, variants, dtype=torch.int64, device=device),
-                              "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
-        # the clean frames as the model saw them (kept when the change strata or the image-quality counters are on): one float32 row
-        # of 3 hw per live source at the row indices of the clean prediction maps (self.paired['rows']): allocated, reused and freed
-        # with them, filled once per clean batch (keep_clean_frames)
+                              "oob": torch.zeros(1, dtype=torch.int64, device=device)}
+        # the clean frames as the model saw them (kept when the change strata or the image-quality counters are on): 'rows' of 3 hw,
+        # filled once per clean batch (keep_clean_frames, _keep_rows)
         self.clean_frames = None
         # change strata (off unless change = change_option(config)): int64 [slot, stratum, C*C + 6] over the sweep's slots.  'rows':
-        # the buffer of self.clean_frames; 'scratch': the uint8 stratum map of a variant batch
+        # the buffer of self.clean_frames; 'scratch': the uint8 stratum map of a variant batch (live next to its prediction map)
         self.change = None
         if change is not None:
             if sweep is None:
@@ -411,14 +453,14 @@ class EvalState:
                             "stats": ops.new_image_quality_stats(device, 1 + len(conditions)),
                             "oob": torch.zeros(1, dtype=torch.int64, device=device)}
             self.clean_frames = {"rows": None}
-        # segment-level counters (off unless segments = segment_option(config)): int64 [slot, C, 11, 48]; 'scratch': the uint8
-        # prediction map of the batch where nothing else keeps one.  Under a sweep the clean maps of self.paired are the references
+        # segment-level counters (off unless segments = segment_option(config)): int64 [slot, C, 11, 48].  Under a sweep the clean
+        # maps of self.paired are the references
         self.segments = None
         if segments is not None:
             segment_options(segments["threshold"], segments["min_area"])
             self.segments = {"threshold": float(segments["threshold"]), "min_area": int(segments["min_area"]),
                              "stats": ops.new_segment_stats(metrics.num_classes, device, 1 + len(conditions)),
-                             "oob": torch.zeros(1, dtype=torch.int64, device=device), "scratch": None}
+                             "oob": torch.zeros(1, dtype=torch.int64, device=device)}
         # ensemble weight sweep (off unless weight_grid = weight_grid_option(config, model)): int64 [slot, G + 3, 2 C]
         self.weight_grid = None
         if weight_grid is not None:
@@ -437,7 +479,7 @@ class EvalState:
             # been counted yet; rows are reused once a source is done
             self.paired = {"stats": ops.new_consistency_stats(metrics.num_classes, device, 1 + len(conditions)),
                            "oob": torch.zeros(1, dtype=torch.int64, device=device), "rows": None, "free": [], "live": {},
-                           "done": set(), "variants": len(sweep.kinds) * sweep.levels, "scratch": None,
+                           "done": set(), "variants": len(sweep.kinds) * sweep.levels,
                            "sources": torch.zeros(1, dtype=torch.int64, device=device)}
 
     def _ref_rows(self, n: int, shape, device):
@@ -477,45 +519,28 @@ class EvalState:
             if s not in pd["live"]:
                 raise ValueError(f"source {s}: a corrupted frame came before its clean frame" if s not in pd["done"] else
                                  f"source {s}: more corrupted frames than the sweep's {pd['variants']}")
-        numel = n * int(np.prod(shape))
-        if pd["scratch"] is None or pd["scratch"].numel() < numel:
-            pd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
-        return pd["scratch"][:numel].view((n,) + tuple(shape))
+        return self.pred_map((n,) + tuple(shape), device)
 
-    def boundary_pred_out(self, shape, device):
-        """The reused uint8 [B, H, W] map the statistics pass writes this batch's prediction into (no severity sweep: nothing else
-        keeps one)."""
-        bd = self.boundary
+    def pred_map(self, shape, device):
+        """The reused uint8 [B, H, W] map the statistics pass writes this batch's prediction into, for every counter that reads it."""
         numel = int(np.prod(shape))
-        if bd["scratch"] is None or bd["scratch"].numel() < numel:
-            bd["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
-        return bd["scratch"][:numel].view(tuple(shape))
+        self.pred_scratch = _grown(self.pred_scratch, numel, device)
+        return self.pred_scratch[:numel].view(tuple(shape))
 
-    def bootstrap_pred_out(self, shape, device):
-        """boundary_pred_out for the frame bootstrap: the reused uint8 [B, H, W] map of the batch when nothing else keeps one."""
-        bs = self.bootstrap
-        numel = int(np.prod(shape))
-        if bs["scratch"] is None or bs["scratch"].numel() < numel:
-            bs["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
-        return bs["scratch"][:numel].view(tuple(shape))
+    def frame_ref(self, sources, severity, device):
+        """The rows of this batch's sources in the clean-map buffer (and in every row store kept in step with it) as an int32
+        device tensor: made once per batch, after paired_pred_out, for every update that reads those rows.  None on a clean batch
+        with no row store to fill: nothing reads them."""
+        if severity == 0 and self.clean_frames is None and (self.depth is None or self.depth["target"] != "clean"):
+            return None
+        rows = [self.paired["live"][s][0] for s in sources]
+        return torch.tensor(rows, dtype=torch.int32).to(device, non_blocking=True)
 
-    def segment_pred_out(self, shape, device):
-        """boundary_pred_out for the segment counters: the reused uint8 [B, H, W] map of the batch when nothing else keeps one."""
+    def update_segments(self, pred, labels, frame_ref, cond, num_classes: int) -> None:
+        """Segment counters of this batch; a variant batch of a sweep (frame_ref: its sources' rows) is also counted against their
+        clean maps (the rows the paired pass keeps: no map of its own).  Runs before update_consistency releases the rows."""
         sg = self.segments
-        numel = int(np.prod(shape))
-        if sg["scratch"] is None or sg["scratch"].numel() < numel:
-            sg["scratch"] = torch.empty(numel, dtype=torch.uint8, device=device)
-        return sg["scratch"][:numel].view(tuple(shape))
-
-    def update_segments(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
-        """Segment counters of this batch; a variant batch of a sweep is also counted against its sources' clean maps (the rows the
-        paired pass keeps: no map of its own).  Runs before update_consistency releases the rows."""
-        sg, pd = self.segments, self.paired
-        ref_maps = frame_ref = None
-        if pd is not None and severity != 0:
-            rows = [pd["live"][s][0] for s in sources]
-            frame_ref = torch.tensor(rows, dtype=torch.int32).to(pred.device, non_blocking=True)
-            ref_maps = pd["rows"].view((-1,) + tuple(pred.shape[1:]))
+        ref_maps = None if frame_ref is None else self.paired["rows"].view((-1,) + tuple(pred.shape[1:]))
         ops.segment_stats(pred, labels.reshape(pred.shape), num_classes, sg["stats"], sg["oob"], cond, ref_maps=ref_maps,
                           frame_ref=frame_ref)
 
@@ -528,11 +553,10 @@ class EvalState:
         bad = [s for s in sources if not 0 <= s < bs["sources"]]
         if bad:
             raise ValueError(f"source {bad[0]} is outside the evaluation set's {bs['sources']} source frames")
-        if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not bs.get("warned"):
-            bs["warned"] = True
-            logger.warning("frame bootstrap: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
-                           "wrapped index, the per-frame counters never wrap: the intervals describe the unwrapped mIoU and need not "
-                           "contain the pooled point estimates (DESIGN.md 10g)", num_classes)
+        _warn_wrapped_index(bs, labels, num_classes,
+                            "frame bootstrap: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
+                            "wrapped index, the per-frame counters never wrap: the intervals describe the unwrapped mIoU and need not "
+                            "contain the pooled point estimates (DESIGN.md 10g)")
         v = bs["variants"]
         rows = [s * v + (c if v > 1 else 0) for s, c in zip(sources, cond_ids)]
         # one host-to-device copy: the rows, and 1 + slot of each
@@ -552,65 +576,42 @@ class EvalState:
             raise IndexError("slot outside the counter slots in the frame bootstrap's slot table")
         return rep.cpu().numpy(), int(keep.numel())
 
-    def keep_clean_frames(self, images, sources, severity) -> list:
-        """The rows of this batch's sources in the clean-frame buffer, grown to the clean-map buffer's rows; a clean batch (after
-        paired_pred_out gave its sources their rows) leaves its frames there.  Once per batch, for the change strata and the
-        image-quality counters alike; runs before update_consistency releases the rows."""
-        cf, pd = self.clean_frames, self.paired
-        rows = [pd["live"][s][0] for s in sources]
-        n_rows, width = pd["rows"].shape[0], images[0].numel()
-        if cf["rows"] is None or cf["rows"].shape[0] < n_rows:
-            new = torch.empty(n_rows, width, dtype=torch.float32, device=images.device)
-            if cf["rows"] is not None:
-                new[:cf["rows"].shape[0]].copy_(cf["rows"])
-            cf["rows"] = new
-            if self.change is not None:
-                self.change["rows"] = new
-        if cf["rows"].shape[1] != width:
-            raise ValueError("every frame of a severity sweep must have the same size")
-        if severity == 0:
-            idx = torch.tensor(rows, dtype=torch.int64).to(images.device, non_blocking=True)
-            cf["rows"].index_copy_(0, idx, images.reshape(len(rows), width))
-        return rows
+    def keep_clean_frames(self, images, frame_ref, severity) -> None:
+        """The clean-frame buffer in step with the clean-map buffer; a clean batch (after paired_pred_out gave its sources their
+        rows) leaves its frames there.  Once per batch, for the change strata and the image-quality counters alike."""
+        rows = _keep_rows(self.clean_frames, self.paired["rows"].shape[0], images, frame_ref, severity == 0)
+        if self.change is not None:
+            self.change["rows"] = rows
 
     def update_quality(self, images, rows, cond) -> None:
-        """A variant batch's image-quality counters against its sources' clean frames (rows: keep_clean_frames').  Raises before the
-        fixed-point budget of the sums would be exceeded."""
+        """A variant batch's image-quality counters against its sources' clean frames (rows: frame_ref's tensor, or the list it is
+        made from).  Raises before the fixed-point budget of the sums would be exceeded."""
         q = self.quality
         check_quality_budget(q["terms"] + images.numel())
         q["terms"] += images.numel()
-        frame_ref = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
+        if not torch.is_tensor(rows):
+            rows = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
         twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
-        ops.image_quality(images, twins, frame_ref, q["stats"], cond=cond, oob=q["oob"])
+        ops.image_quality(images, twins, rows, q["stats"], cond=cond, oob=q["oob"])
 
-    def update_change(self, images, pred, labels, rows, severity, cond, num_classes: int) -> None:
-        """A variant batch is split into change strata against its sources' clean frames (rows: keep_clean_frames') and counted
-        against their clean maps.  Runs before update_consistency releases the rows."""
-        ch, pd = self.change, self.paired
-        if severity == 0:
-            return
-        if labels.dtype == torch.uint8 and num_classes * (num_classes - 1) > 255 and not ch.get("warned"):
-            ch["warned"] = True
-            logger.warning("change strata: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
-                           "wrapped index, the stratified counters never wrap: miou_*_chg<k> describes the unwrapped confusion matrix "
-                           "and the strata need not recombine to the pooled mIoU (DESIGN.md 10h)", num_classes)
-        frame_ref = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
-        numel = pred.numel()
-        if ch["scratch"] is None or ch["scratch"].numel() < numel:
-            ch["scratch"] = torch.empty(numel, dtype=torch.uint8, device=images.device)
-        strata = ch["scratch"][:numel].view(pred.shape)
+    def update_change(self, images, pred, labels, frame_ref, cond, num_classes: int) -> None:
+        """A variant batch is split into change strata against its sources' clean frames and counted against their clean maps.
+        Runs before update_consistency releases the rows."""
+        ch = self.change
+        _warn_wrapped_index(ch, labels, num_classes,
+                            "change strata: with uint8 labels and %d classes the pooled confusion counters reproduce the reference's "
+                            "wrapped index, the stratified counters never wrap: miou_*_chg<k> describes the unwrapped confusion matrix "
+                            "and the strata need not recombine to the pooled mIoU (DESIGN.md 10h)")
+        ch["scratch"] = _grown(ch["scratch"], pred.numel(), images.device)
+        strata = ch["scratch"][:pred.numel()].view(pred.shape)
         ops.change_strata(images, ch["rows"], frame_ref, ch["edges"], out=strata, oob=ch["oob"])
-        ops.stratified_stats(pred, labels, strata, len(ch["edges"]) + 1, num_classes, ch["stats"], ch["oob"], ref_maps=pd["rows"],
-                             frame_ref=frame_ref, cond=cond)
+        ops.stratified_stats(pred, labels, strata, len(ch["edges"]) + 1, num_classes, ch["stats"], ch["oob"],
+                             ref_maps=self.paired["rows"], frame_ref=frame_ref, cond=cond)
 
-    def update_consistency(self, pred, labels, sources, severity, cond, num_classes: int) -> None:
+    def update_consistency(self, pred, labels, sources, frame_ref, cond, num_classes: int) -> None:
         """Count a variant batch's maps against its sources' clean maps (slot 0 + its condition slot); free the rows of sources whose
         sweep is complete."""
         pd = self.paired
-        if severity == 0:
-            return
-        rows = [pd["live"][s][0] for s in sources]
-        frame_ref = torch.tensor(rows, dtype=torch.int32).to(pred.device, non_blocking=True)
         ops.prediction_consistency(pred, pd["rows"], frame_ref, labels, num_classes, pd["stats"], pd["oob"], cond)
         for s in sources:
             ent = pd["live"][s]
@@ -620,9 +621,10 @@ class EvalState:
                 pd["free"].append(ent[0])
                 pd["done"].add(s)
 
-    def depth_target(self, target: torch.Tensor, sources, severity) -> torch.Tensor:
+    def depth_target(self, target: torch.Tensor, frame_ref, severity) -> torch.Tensor:
         """The target this batch's depth maps are scored against, and the pixel budget check.  depth_target 'clean': a clean batch
-        (after paired_pred_out gave its sources their rows) leaves its targets in those rows, a variant batch gathers its sources'."""
+        (after paired_pred_out gave its sources their rows: frame_ref) leaves its targets in those rows, a variant batch gathers its
+        sources'."""
         d = self.depth
         if target.dim() != 3 or target.dtype != torch.float32:
             raise ValueError(f"the depth target is float32 [B, H, W], got {target.dtype} {tuple(target.shape)}")
@@ -630,19 +632,8 @@ class EvalState:
         d["pixels"] += target.numel()
         if d["target"] != "clean":
             return target
-        pd = self.paired
-        rows = [pd["live"][s][0] for s in sources]
-        n_rows, hw = pd["rows"].shape[0], target[0].numel()
-        if d["rows"] is None or d["rows"].shape[0] < n_rows:
-            new = torch.empty(n_rows, hw, dtype=torch.float32, device=target.device)
-            if d["rows"] is not None:
-                new[:d["rows"].shape[0]].copy_(d["rows"])
-            d["rows"] = new
-        idx = torch.tensor(rows, dtype=torch.int64).to(target.device, non_blocking=True)
-        if severity == 0:
-            d["rows"].index_copy_(0, idx, target.reshape(len(rows), hw))
-            return target
-        return d["rows"].index_select(0, idx).view(target.shape)
+        rows = _keep_rows(d, self.paired["rows"].shape[0], target, frame_ref, severity == 0)
+        return target if severity == 0 else rows.index_select(0, frame_ref.long()).view(target.shape)
 
     def update_calibration(self, labels: torch.Tensor, cond, logits=None, members=None) -> None:
         """Grid NLL / ECE of this batch: from the two member maps (members = (seg1, seg2, mode, weights, T)) or materialised
@@ -684,46 +675,32 @@ class EvalState:
         ts = [self.acc.counts, self.acc.oob, self.ece]
         if self.auroc is not None:
             ts.append(self.auroc)
-        pixels = None
-        if self.calib is not None:
-            # the ranks' pixel counts travel in the same message: the budget is that of the SUMMED counters
-            pixels = torch.tensor([self.calib["pixels"]], dtype=torch.int64, device=self.calib["stats"].device)
-            ts += [self.calib["stats"], pixels]
-        depth_pixels = None
-        if getattr(self, "depth", None) is not None:
-            depth_pixels = torch.tensor([self.depth["pixels"]], dtype=torch.int64, device=self.depth["stats"].device)
-            ts += [self.depth["stats"], depth_pixels]
-        if getattr(self, "failure", None) is not None:
-            ts.append(self.failure["stats"])
-        if getattr(self, "boundary", None) is not None:                  # (getattr: all_reduce also serves states built without it)
-            ts += [self.boundary["stats"], self.boundary["oob"]]
-        if getattr(self, "change", None) is not None:
-            ts += [self.change["stats"], self.change["oob"]]
-        quality_terms = None
-        if getattr(self, "quality", None) is not None:
-            quality_terms = torch.tensor([self.quality["terms"]], dtype=torch.int64, device=self.quality["stats"].device)
-            ts += [self.quality["stats"], self.quality["oob"], quality_terms]
-        if getattr(self, "segments", None) is not None:
-            ts += [self.segments["stats"], self.segments["oob"]]
-        if getattr(self, "weight_grid", None) is not None:
-            ts.append(self.weight_grid["stats"])
-        bs = getattr(self, "bootstrap", None)
-        if bs is not None:                                               # ranks fill disjoint rows: the sum is the union
-            ts += [bs["table"], bs["seen"], bs["slot"], bs["oob"]]
-        pd = getattr(self, "paired", None)
+        pd = self.paired
         if pd is not None:
             if pd["live"]:
                 raise ValueError(f"severity sweep incomplete: {len(pd['live'])} source(s) lack corrupted frames, "
                                  f"e.g. source {min(pd['live'])}")
             pd["sources"].fill_(len(pd["done"]))
-            ts += [pd["stats"], pd["oob"], pd["sources"]]
+        summed = []
+        for name, keys, count, check, _ in COUNTERS:
+            opt = getattr(self, name)
+            if opt is None:
+                continue
+            ts += [opt[k] for k in keys]
+            if count is not None:
+                # the ranks' counts travel in the same message: the budget is that of the SUMMED counters
+                ts.append(torch.tensor([opt[count]], dtype=torch.int64, device=opt["stats"].device))
+                summed.append((check, ts[-1]))
         parallel.all_reduce_sum_(ts)
-        if pixels is not None:
-            check_calibration_budget(int(pixels.item()))
-        if depth_pixels is not None:
-            check_depth_budget(int(depth_pixels.item()))
-        if quality_terms is not None:
-            check_quality_budget(int(quality_terms.item()))
+        for check, total in summed:
+            check(int(total.item()))
+
+    def check_oob(self) -> None:
+        """After all_reduce: raise when a counter pass met a value outside its range on any rank."""
+        for name, _, _, _, message in COUNTERS:
+            opt = getattr(self, name)
+            if opt is not None and message is not None and int(opt["oob"].item()):
+                raise IndexError(message)
 
     def auroc_value(self) -> float:
         neg, pos = self.auroc[0].double(), self.auroc[1].double()
@@ -756,7 +733,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     Severity sweep (st.sweep): `sources` (global indices) and `severity` (0 clean, 1..S) of the batch; conds are its kinds.  The
     batch's prediction map is kept (clean) or compared with its sources' clean maps (variants).
     Depth metrics (st.depth): `depth` is the batch's target float32 [B, H, W]; the depth maps are scored in one pass and not kept."""
-    pred_out = None
+    pred_out = rows = None                                            # rows: st.frame_ref of a sweep's batch
     if st.sweep is not None:
         if sources is None or severity is None:
             raise ValueError("a severity sweep needs the paired loader's 'source' and 'severity' for every batch")
@@ -767,25 +744,21 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         if unknown:
             raise ValueError(f"batch conditions {unknown} are not slots of the severity sweep")
         pred_out = st.paired_pred_out(sources, severity, tuple(images.shape[2:]), images.device)
-    if getattr(st, "change", None) is not None:
-        check_change_frames(images)
-    if getattr(st, "quality", None) is not None:
-        check_quality_frames(images)
-    bd = getattr(st, "boundary", None)
-    if bd is not None and pred_out is None:
-        pred_out = st.boundary_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
-    bs = getattr(st, "bootstrap", None)
+        rows = st.frame_ref(sources, severity, images.device)
+    variant = st.sweep is not None and severity != 0
+    if st.change is not None:
+        check_frames("change_strata", images)
+    if st.quality is not None:
+        check_frames("image_quality", images)
+    bd, bs, sg = st.boundary, st.bootstrap, st.segments
     if bs is not None:
         if sources is None:
             raise ValueError("the frame bootstrap needs the loader's 'source' (global sample indices) for every batch")
         sources = [int(s) for s in sources]
         if len(sources) != images.shape[0]:
             raise ValueError(f"{len(sources)} sources for a batch of {images.shape[0]} frames")
-        if pred_out is None:
-            pred_out = st.bootstrap_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
-    sg = getattr(st, "segments", None)
-    if sg is not None and pred_out is None:
-        pred_out = st.segment_pred_out((images.shape[0],) + tuple(images.shape[2:]), images.device)
+    if pred_out is None and (bd is not None or bs is not None or sg is not None):
+        pred_out = st.pred_map((images.shape[0],) + tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     depth_kw = {}
     if st.depth is not None:
@@ -793,7 +766,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             raise ValueError("evaluation.depth_metrics: the loader gives no depth target (batch['depth']; data.include_depth)")
         if not getattr(model, "include_depth", True):
             raise ValueError("evaluation.depth_metrics: the model has no depth head (model.include_depth)")
-        depth = st.depth_target(depth, sources, severity)
+        depth = st.depth_target(depth, rows, severity)
         # the ensemble scores its three series in one pass and writes neither the upsampled nor the combined map
         depth_kw = {"depth_stats": (depth, cond, st.depth["stats"], st.depth["min"]), "want_depth": False}
     if labels.dtype not in (torch.uint8, torch.int64):
@@ -813,7 +786,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
                 st.update_calibration(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T))
             else:
                 st.update_calibration(labels, cond, logits=res["segmentation"])
-        if getattr(st, "weight_grid", None) is not None:
+        if st.weight_grid is not None:
             if strategy != "weighted_average":
                 raise ValueError(f"the ensemble weight sweep needs model.ensemble_strategy weighted_average, got {strategy!r}")
             st.update_weight_grid(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"]))
@@ -834,7 +807,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_auroc(res["segformer_seg"], res["deeplabv3plus_seg"], labels)
             ops.ece_accumulate(res["segmentation"], labels, st.ece, st.edges, cond)
     else:
-        if getattr(st, "weight_grid", None) is not None:
+        if st.weight_grid is not None:
             raise ValueError("the ensemble weight sweep needs the two-member ensemble")
         out = model(images)
         logits = out["segmentation"].float().contiguous()
@@ -853,18 +826,18 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     if bd is not None:
         ops.boundary_stats(pred_out, labels.reshape(pred_out.shape), bd["widths"], metrics.num_classes, bd["stats"], bd["oob"], cond)
     if sg is not None:
-        st.update_segments(pred_out, labels, sources, severity, cond, metrics.num_classes)
+        st.update_segments(pred_out, labels, rows if variant else None, cond, metrics.num_classes)
     if bs is not None:
         ids = [st.acc.conditions.index(str(c)) if str(c) in st.acc.conditions else -1 for c in conds]      # cond_ids' rule
         st.update_bootstrap(pred_out, labels, sources, ids, metrics.num_classes)
-    if getattr(st, "clean_frames", None) is not None:
-        rows = st.keep_clean_frames(images, sources, severity)
-        if getattr(st, "quality", None) is not None and severity != 0:
+    if st.clean_frames is not None:
+        st.keep_clean_frames(images, rows, severity)
+    if variant:                                                       # against the clean frames and maps; the last one releases the rows
+        if st.quality is not None:
             st.update_quality(images, rows, cond)
-        if getattr(st, "change", None) is not None:
-            st.update_change(images, pred_out, labels, rows, severity, cond, metrics.num_classes)
-    if st.sweep is not None:                                          # (pred_out alone no longer says so: the boundary counters ask for one too)
-        st.update_consistency(pred_out, labels, sources, severity, cond, metrics.num_classes)
+        if st.change is not None:
+            st.update_change(images, pred_out, labels, rows, cond, metrics.num_classes)
+        st.update_consistency(pred_out, labels, sources, rows, cond, metrics.num_classes)
     st.samples += images.size(0)
 
 
@@ -910,6 +883,8 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
     """All-reduce the counters, then the scalar host math of evaluate.py:214-271."""
     st.all_reduce()
     st.acc.check()
+    st.check_oob()
+    sweep_kw = {"kinds": st.sweep.kinds if st.sweep is not None else None, "levels": st.sweep.levels if st.sweep is not None else 0}
     results: Dict[str, Any] = {"overall_miou": st.acc.miou(0)}
     weather_mious = {}
     for k, name in enumerate(st.acc.conditions):
@@ -932,8 +907,6 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         # per kind: its severity slots summed (the counters are additive), so miou_<kind> / ece_<kind> / robustness_degradation_<kind>
         # keep their meaning over the kind's frames
         pd = st.paired
-        if int(pd["oob"].item()):
-            raise IndexError("prediction map value outside [0, num_classes) in the consistency counters")
         slots = st.acc.conditions
         for kind in st.sweep.kinds:
             idx = [1 + slots.index(slot_name(kind, j)) for j in range(1, st.sweep.levels + 1)]
@@ -951,48 +924,25 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                               st.sweep.kinds, st.sweep.levels, st.sweep.intensities, int(pd["sources"].item()),
                                               weather_mious, metrics.compute_robustness_degradation_ratio))
     if st.depth is not None:
-        results.update(depth_metrics_from_stats(st.depth["stats"].cpu().numpy(), st.acc.conditions,
-                                                kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                levels=st.sweep.levels if st.sweep is not None else 0))
-    if getattr(st, "failure", None) is not None:
-        results.update(failure_metrics_from_stats(st.failure["stats"].cpu().numpy(), st.failure["conditions"],
-                                                  kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                  levels=st.sweep.levels if st.sweep is not None else 0,
+        results.update(depth_metrics_from_stats(st.depth["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
+    if st.failure is not None:
+        results.update(failure_metrics_from_stats(st.failure["stats"].cpu().numpy(), st.failure["conditions"], **sweep_kw,
                                                   single=st.failure["single"]))
-    bd = getattr(st, "boundary", None)
+    bd, sg, wg, ch, q, bs = st.boundary, st.segments, st.weight_grid, st.change, st.quality, st.bootstrap
     if bd is not None:
-        if int(bd["oob"].item()):
-            raise IndexError("prediction map value outside [0, num_classes) in the boundary counters")
         results.update(boundary_metrics_from_stats(bd["stats"].cpu().numpy(), bd["widths"], st.acc.conditions, metrics.num_classes,
-                                                   kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                   levels=st.sweep.levels if st.sweep is not None else 0,
-                                                   degradation=metrics.compute_robustness_degradation_ratio))
-    sg = getattr(st, "segments", None)
+                                                   **sweep_kw, degradation=metrics.compute_robustness_degradation_ratio))
     if sg is not None:
-        if int(sg["oob"].item()):
-            raise IndexError("prediction map value outside [0, num_classes) in the segment counters")
         results.update(segment_metrics_from_stats(sg["stats"].cpu().numpy(), st.acc.conditions, metrics.num_classes,
-                                                  threshold=sg["threshold"], min_area=sg["min_area"],
-                                                  kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                  levels=st.sweep.levels if st.sweep is not None else 0))
-    wg = getattr(st, "weight_grid", None)
+                                                  threshold=sg["threshold"], min_area=sg["min_area"], **sweep_kw))
     if wg is not None:
         results.update(weight_grid_metrics_from_stats(wg["stats"].cpu().numpy(), st.acc.conditions, metrics.num_classes, wg["pairs"],
-                                                      wg["configured_index"], calibration_condition=wg["condition"],
-                                                      kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                      levels=st.sweep.levels if st.sweep is not None else 0))
-    ch = getattr(st, "change", None)
+                                                      wg["configured_index"], calibration_condition=wg["condition"], **sweep_kw))
     if ch is not None:
-        if int(ch["oob"].item()):
-            raise IndexError("prediction map value outside [0, num_classes), or a clean-frame row outside the buffer, in the "
-                             "change-strata counters")
         results.update(change_metrics_from_stats(ch["stats"].cpu().numpy(), ch["edges"], st.acc.conditions, st.sweep.kinds,
                                                  st.sweep.levels, metrics.num_classes))
-    q = getattr(st, "quality", None)
     if q is not None:
         # after the sweep results: the matched-damage keys read miou_clean and miou_<kind>_s<j>
-        if int(q["oob"].item()):
-            raise IndexError("a clean-frame row outside the buffer in the image-quality counters")
         results.update(quality_metrics_from_stats(q["stats"].cpu().numpy(), st.acc.conditions, st.sweep.kinds, st.sweep.levels, results,
                                                   q["targets"], metrics.compute_robustness_degradation_ratio))
     if "clean" in weather_mious:
@@ -1004,13 +954,10 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                 if f"robustness_degradation_{w}" in results]
         if degs:
             results["robustness_degradation_ratio"] = np.mean(degs)
-    bs = getattr(st, "bootstrap", None)
     if bs is not None:
         # last: a quantity gets an interval when its point estimate is above.  The point estimates stay the pooled ones.
         rep, n_sources = st.bootstrap_replicates()
         results.update(bootstrap_metrics_from_replicates(rep, st.acc.conditions, metrics.num_classes, results, bs["confidence"],
-                                                         bs["seed"], kinds=st.sweep.kinds if st.sweep is not None else None,
-                                                         levels=st.sweep.levels if st.sweep is not None else 0,
-                                                         degradation=metrics.compute_robustness_degradation_ratio))
+                                                         bs["seed"], **sweep_kw, degradation=metrics.compute_robustness_degradation_ratio))
         results["bootstrap_sources"] = float(n_sources)
     return results

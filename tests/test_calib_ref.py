@@ -173,20 +173,17 @@ def test_decoder_layout():
 def test_calibration_budget_is_checked_on_the_summed_counters(monkeypatch):
     from adverse_weather_semantic_segmentation_robustness_benchmark_amd import ops
     from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation import harness
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.metrics import RobustnessMetrics
     harness.check_calibration_budget(ops.CALIB_PIXEL_BUDGET)
     with pytest.raises(OverflowError):
         harness.check_calibration_budget(ops.CALIB_PIXEL_BUDGET + 1)
-
-    class _St:                                                   # a rank whose own count fits, summed with another that does too
-        calib = {"pixels": ops.CALIB_PIXEL_BUDGET // 2 + 1, "stats": torch.zeros(1, 2, 7, dtype=torch.int64)}
-        acc = type("A", (), {"counts": torch.zeros(1, 4, dtype=torch.int64), "oob": torch.zeros(1, dtype=torch.int64)})()
-        ece = torch.zeros(1, 1, 3, dtype=torch.int64)
-        auroc = None
+    st = harness.EvalState(RobustnessMetrics(4, ["clean"]), ["clean"], "cpu", 3, temperature_grid=[0.5, 1.0])
+    st.calib["pixels"] = ops.CALIB_PIXEL_BUDGET // 2 + 1          # a rank whose own count fits, summed with another that does too
 
     def two_ranks(ts):                                           # stands in for the SUM all-reduce over two equal ranks
         for t in ts:
             t.mul_(2)
     monkeypatch.setattr(harness.parallel, "all_reduce_sum_", two_ranks)
     with pytest.raises(OverflowError):
-        harness.EvalState.all_reduce(_St())
+        st.all_reduce()
 

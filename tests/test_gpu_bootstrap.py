@@ -441,7 +441,7 @@ def test_harness_single_model_branch_and_the_scratch_map(P, monkeypatch):
     with torch.no_grad():                                            # the map is the model's argmax
         batch = list(ds.batches(2))[-1]
         ref = model(batch["image"])["segmentation"].float().argmax(1)
-    assert torch.equal(st.bootstrap["scratch"].view(ref.shape).long(), ref)
+    assert torch.equal(st.pred_scratch.view(ref.shape).long(), ref)
 
 
 def test_harness_refuses_duplicates_bad_values_and_missing_sources(P):

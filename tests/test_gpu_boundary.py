@@ -368,7 +368,7 @@ def test_harness_single_model_branch(P, monkeypatch):
         ref = model(batch["image"])["segmentation"].float().argmax(1)
     st = P.harness.EvalState(P.RobustnessMetrics(19, conds), conds, "cuda", 15, False, boundary=widths)
     P.harness.eval_batch(model, st, batch["image"], batch["label"], batch["weather_condition"], P.RobustnessMetrics(19, conds))
-    assert torch.equal(st.boundary["scratch"].view(ref.shape).long(), ref)
+    assert torch.equal(st.pred_scratch.view(ref.shape).long(), ref)
 
 
 def test_harness_raises_on_an_out_of_range_prediction(P):

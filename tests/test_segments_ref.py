@@ -216,7 +216,7 @@ def test_option_off_leaves_the_results_unchanged():
     assert st0.segments is None and st1.segments is None
     assert list(base) == list(off) and repr(list(base.values())) == repr(list(off.values()))
     st2, on = results(harness.segment_option(Cfg({"evaluation.segment_metrics": True})))
-    assert tuple(st2.segments["stats"].shape) == (3, 5, 11, 48) and st2.segments["scratch"] is None
+    assert tuple(st2.segments["stats"].shape) == (3, 5, 11, 48) and st2.pred_scratch is None
     assert {k: on[k] for k in base} == base and not any(k.startswith("segment_") for k in on)            # no segment was counted
     one = SR.segment_counters(*_case(3), 5, cond=[0, 1], n_slots=3)[0]
     st2.segments["stats"].copy_(torch.from_numpy(one))
