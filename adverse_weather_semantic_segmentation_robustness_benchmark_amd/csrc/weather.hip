@@ -56,6 +56,43 @@ __device__ __forceinline__ void lut_fill(weather_lut& L, const norm_consts& nc, 
     }
 }
 
+// The store epilogue of the 4-pixels-per-lane kernels that normalise through the LDS table: the 12 result bytes `res` (HWC) of the pixels p .. p + 3 of one frame go to
+// `dst` as three dwords and, through the table, to the planes of `ndst` as three float4s.  vec_u8 / vec_f32 say that the vector
+// form is allowed (all four pixels inside the row, the address aligned); otherwise the nvalid pixels are stored value by value.
+// A caller that knows its alignment at compile time passes literal true and the scalar path folds away.  The scalar loops run to
+// their constant bounds under a predicate: every index into `res` is then a compile-time one and the bytes stay in registers
+// (behind this pointer the compiler no longer sees a private array, and a runtime-indexed one would go to LDS or scratch).
+__device__ __forceinline__ void store_quad(const uint8_t (&res)[12], uint8_t* dst, float* ndst, int64_t p, int64_t hw,
+                                           int nvalid, bool vec_u8, bool vec_f32, const weather_lut& L)
+{
+    if (dst) {
+        if (vec_u8) {
+            uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
+#pragma unroll
+            for (int w = 0; w < 3; ++w)
+                d4[w] = (uint32_t)res[4 * w] | ((uint32_t)res[4 * w + 1] << 8) | ((uint32_t)res[4 * w + 2] << 16) | ((uint32_t)res[4 * w + 3] << 24);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 12; ++k)
+                if (k < nvalid * 3) dst[p * 3 + k] = res[k];
+        }
+    }
+    if (ndst) {
+        if (vec_f32) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                *reinterpret_cast<float4*>(ndst + (int64_t)c * hw + p) =
+                    make_float4(L.nrm[c][res[c]], L.nrm[c][res[3 + c]], L.nrm[c][res[6 + c]], L.nrm[c][res[9 + c]]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (k < nvalid) ndst[(int64_t)c * hw + p + k] = L.nrm[c][res[k * 3 + c]];
+        }
+    }
+}
+
 // scipy 'reflect' (d c b a | a b c d | d c b a)
 __device__ __forceinline__ int reflect_sym(int i, int n)
 {
@@ -252,6 +289,8 @@ void fog_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awseg_f
                 res[k * 3 + c] = quant_f64(a + hazeterm);          // :120-123
             }
         }
+        // (not store_quad: this kernel has no table in LDS and normalises in place; with the 12 divisions of the unrolled form it
+        // needs 95 registers against 79; with the helper's byte stores alone, 83 and 3 KB more LDS)
         if (dst) {
             if (nvalid == 4 && (((uintptr_t)(dst + p * 3)) & 3) == 0) {
                 uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
@@ -412,27 +451,7 @@ void fog_fast_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<aw
             for (int c = 0; c < 3; ++c)
                 res[k * 3 + c] = (uint8_t)(int)__builtin_amdgcn_fmed3f(fmaf((float)px[k * 3 + c], t, hz), 0.f, 255.f);
         }
-        if (dst) {
-            if (vec) {
-                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
-#pragma unroll
-                for (int w = 0; w < 3; ++w)
-                    d4[w] = (uint32_t)res[4 * w] | ((uint32_t)res[4 * w + 1] << 8) | ((uint32_t)res[4 * w + 2] << 16) | ((uint32_t)res[4 * w + 3] << 24);
-            } else {
-                for (int k = 0; k < nvalid * 3; ++k) dst[p * 3 + k] = res[k];
-            }
-        }
-        if (ndst) {
-            if (nvalid == 4 && (p & 3) == 0 && (hw & 3) == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    *reinterpret_cast<float4*>(ndst + (int64_t)c * hw + p) =
-                        make_float4(L.nrm[c][res[c]], L.nrm[c][res[3 + c]], L.nrm[c][res[6 + c]], L.nrm[c][res[9 + c]]);
-            } else {
-                for (int c = 0; c < 3; ++c)
-                    for (int k = 0; k < nvalid; ++k) ndst[(int64_t)c * hw + p + k] = L.nrm[c][res[k * 3 + c]];
-            }
-        }
+        store_quad(res, dst, ndst, p, hw, nvalid, vec, nvalid == 4 && (p & 3) == 0 && (hw & 3) == 0, L);
     }
 }
 
@@ -560,18 +579,7 @@ __device__ __forceinline__ void fog_strip_body(const uint8_t* __restrict__ imgs,
                 res[e] = (uint8_t)(int)__builtin_amdgcn_fmed3f(fmaf((float)((word >> (8 * (e & 3))) & 0xFFu), t, hz), 0.f, 255.f);
             }
         }
-        if (dst) {
-            uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
-#pragma unroll
-            for (int wq = 0; wq < 3; ++wq)
-                d4[wq] = (uint32_t)res[4 * wq] | ((uint32_t)res[4 * wq + 1] << 8) | ((uint32_t)res[4 * wq + 2] << 16) | ((uint32_t)res[4 * wq + 3] << 24);
-        }
-        if (ndst) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                *reinterpret_cast<float4*>(ndst + (int64_t)c * hw + p) =
-                    make_float4(L.nrm[c][res[c]], L.nrm[c][res[3 + c]], L.nrm[c][res[6 + c]], L.nrm[c][res[9 + c]]);
-        }
+        store_quad(res, dst, ndst, p, hw, 4, true, true, L);
     }
 }
 
@@ -679,27 +687,7 @@ __device__ __forceinline__ void night_body(const uint8_t* __restrict__ imgs, int
                 res[k] = quant_f64((double)v + n);
             }
         }
-        if (dst) {
-            if (v4) {
-                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
-#pragma unroll
-                for (int w = 0; w < 3; ++w)
-                    d4[w] = (uint32_t)res[4 * w] | ((uint32_t)res[4 * w + 1] << 8) | ((uint32_t)res[4 * w + 2] << 16) | ((uint32_t)res[4 * w + 3] << 24);
-            } else {
-                for (int k = 0; k < nvalid * 3; ++k) dst[p * 3 + k] = res[k];
-            }
-        }
-        if (ndst) {
-            if (v4 && (hw & 3) == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    *reinterpret_cast<float4*>(ndst + (int64_t)c * hw + p) =
-                        make_float4(L.nrm[c][res[c]], L.nrm[c][res[3 + c]], L.nrm[c][res[6 + c]], L.nrm[c][res[9 + c]]);
-            } else {
-                for (int c = 0; c < 3; ++c)
-                    for (int k = 0; k < nvalid; ++k) ndst[(int64_t)c * hw + p + k] = L.nrm[c][res[k * 3 + c]];
-            }
-        }
+        store_quad(res, dst, ndst, p, hw, nvalid, v4, v4 && (hw & 3) == 0, L);
     }
 }
 
@@ -716,40 +704,31 @@ void night_kernel(const uint8_t* __restrict__ imgs, int64_t hw, job_pack<awseg_n
 // ---------------------------------------------------------------- rasteriser (A4 / A5)
 // Integer restatement of OpenCV's drawing primitives (PARITY UNPINNED, see the oracle header),
 // producing the same pixel sets as the scanline code in oracle/awseg_oracle.c.  A primitive is
-// rasterised by ONE WAVE into an LDS coverage mask (tile + blur halo, clipped to the image): the
-// inherently serial parts (midpoint-circle recurrence, polygon edge walk) run wave-uniformly, the
-// span fills and the fixed-point line steps are spread over the 64 lanes.
-struct tile_mask {
-    uint8_t* m; int x0, y0, w, h;   // rect origin / size in image coordinates
-    int W, H;                       // image size (OpenCV clips to the image first)
-    uint32_t* bits; int wd;         // frame-wide 1-bit coverage map (wd dwords per row) instead of the byte rect, or NULL
+// rasterised by ONE WAVE into the frame's 1-bit coverage map (atomicOr, clipped to the image as
+// OpenCV clips): the inherently serial parts (midpoint-circle recurrence, polygon edge events) run
+// wave-uniformly, the span fills, the scanlines and the fixed-point line steps are spread over the 64 lanes.
+struct cover_map {
+    uint32_t* bits; int wd;         // frame-wide 1-bit coverage map, wd dwords per row
+    int W, H;                       // image size
 };
-__device__ __forceinline__ void m_set(const tile_mask& k, int rx, int ry)
+__device__ __forceinline__ void m_set(const cover_map& k, int x, int y)
 {
-    if (k.bits) atomicOr(&k.bits[(int64_t)ry * k.wd + (rx >> 5)], 1u << (rx & 31));
-    else k.m[ry * k.w + rx] = 1;
+    atomicOr(&k.bits[(int64_t)y * k.wd + (x >> 5)], 1u << (x & 31));
 }
-__device__ __forceinline__ void m_hline(const tile_mask& k, int y, int xa, int xb, int lane)
+__device__ __forceinline__ void m_hline(const cover_map& k, int y, int xa, int xb, int lane)
 {
     if (y < 0 || y >= k.H) return;
     if (xa < 0) xa = 0;
     if (xb >= k.W) xb = k.W - 1;
-    const int ry = y - k.y0;
-    if (ry < 0 || ry >= k.h) return;
-    int a = xa - k.x0, b = xb - k.x0;
-    if (a < 0) a = 0;
-    if (b >= k.w) b = k.w - 1;
-    for (int x = a + lane; x <= b; x += 64) m_set(k, x, ry);
+    for (int x = xa + lane; x <= xb; x += 64) m_set(k, x, y);
 }
-__device__ __forceinline__ void m_point(const tile_mask& k, int x, int y)
+__device__ __forceinline__ void m_point(const cover_map& k, int x, int y)
 {
     if (x < 0 || x >= k.W || y < 0 || y >= k.H) return;
-    const int rx = x - k.x0, ry = y - k.y0;
-    if (rx < 0 || rx >= k.w || ry < 0 || ry >= k.h) return;
-    m_set(k, rx, ry);
+    m_set(k, x, y);
 }
 // cv::Line (LineIterator, 8-connected, left to right): closed form per step -> one step per lane.
-__device__ void m_line_thin(const tile_mask& k, int x0, int y0, int x1, int y1, int lane)
+__device__ void m_line_thin(const cover_map& k, int x0, int y0, int x1, int y1, int lane)
 {
     if (x1 < x0) { int t = x0; x0 = x1; x1 = t; t = y0; y0 = y1; y1 = t; }
     int dx = x1 - x0, dy = y1 - y0;
@@ -763,7 +742,7 @@ __device__ void m_line_thin(const tile_mask& k, int x0, int y0, int x1, int y1, 
     }
 }
 // cv::Circle(fill): the midpoint recurrence is wave-uniform, each of its spans is filled by the lanes.
-__device__ void m_disc(const tile_mask& k, int cx, int cy, int r, int lane)
+__device__ void m_disc(const cover_map& k, int cx, int cy, int r, int lane)
 {
     int err = 0, dx = r, dy = 0, plus = 1, minus = (r << 1) - 1;
     while (dx >= dy) {
@@ -786,7 +765,7 @@ constexpr int XY_ONE = 1 << XY_SHIFT;
 // ulp), and costs a fraction of the 64-bit integer division sequence.
 __device__ __forceinline__ int64_t div_trunc(int64_t a, int64_t b) { return (int64_t)((double)a / (double)b); }
 // cv::Line2 (16.16 fixed-point DDA): position after j steps is start + j*step -> one step per lane.
-__device__ void m_line2(const tile_mask& k, int64_t x1, int64_t y1, int64_t x2, int64_t y2, int lane)
+__device__ void m_line2(const cover_map& k, int64_t x1, int64_t y1, int64_t x2, int64_t y2, int lane)
 {
     int64_t dx = x2 - x1, dy = y2 - y1;
     const int64_t ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
@@ -807,99 +786,30 @@ __device__ void m_line2(const tile_mask& k, int64_t x1, int64_t y1, int64_t x2, 
         for (int j = lane; j <= ecount; j += 64) m_point(k, (int)((x1 + j * x_step) >> XY_SHIFT), (int)(yb + j));
     }
 }
-// cv::FillConvexPoly for the 4-point thick-line body: wave-uniform edge walk, lane-parallel spans.
-// Vertices are picked with select chains and the two edge states are plain scalars: a runtime-indexed
-// private array would live in scratch memory (hundreds of cycles per access).
+// cv::FillConvexPoly for the 4-point thick-line body, with the SCANLINES spread over the lanes (one wave owns the whole primitive).
+// OpenCV's edge walk (edge A goes +1 through the vertices, edge B -1) changes state only at the scanlines where an edge ends;
+// between two such events an edge's abscissa is x_start + (y - y_start) * dx in exact integer arithmetic — what the serial walk
+// reaches by adding dx once per scanline.  Every lane runs the (wave-uniform, at most npts + 1 iterations) event loop with the
+// serial code's own transition statements, and draws its scanline when the loop passes over it.  A lane writes its whole span
+// itself.  Vertices are picked with select chains and the two edge states are plain scalars: a runtime-indexed private array would
+// live in scratch memory (hundreds of cycles per access).
 __device__ __forceinline__ int64_t sel4(const int64_t* v, int i)
 {
     return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3]));
 }
-__device__ void m_fill_convex4(const tile_mask& k, const int64_t* vx, const int64_t* vy, int lane)
-{
-    const int npts = 4;
-    const int64_t delta = XY_ONE >> 1;
-    int imin = 0, edges = npts;
-    int64_t xmin = vx[0], xmax = vx[0], ymin = vy[0], ymax = vy[0];
-    int64_t px = vx[3], py = vy[3];
-#pragma unroll
-    for (int i = 0; i < npts; ++i) {
-        if (vy[i] < ymin) { ymin = vy[i]; imin = i; }
-        if (vy[i] > ymax) ymax = vy[i];
-        if (vx[i] > xmax) xmax = vx[i];
-        if (vx[i] < xmin) xmin = vx[i];
-        m_line2(k, px, py, vx[i], vy[i], lane);
-        px = vx[i]; py = vy[i];
-    }
-    xmin = (xmin + delta) >> XY_SHIFT; xmax = (xmax + delta) >> XY_SHIFT;
-    ymin = (ymin + delta) >> XY_SHIFT; ymax = (ymax + delta) >> XY_SHIFT;
-    if ((int)xmax < 0 || (int)ymax < 0 || (int)xmin >= k.W || (int)ymin >= k.H) return;
-    if (ymax > k.H - 1) ymax = k.H - 1;
-    int y = (int)ymin;
-    int idxA = imin, idxB = imin, yeA = y, yeB = y;          // edge A walks +1 through the vertices, edge B -1
-    int64_t xA = -XY_ONE, xB = -XY_ONE, dxA = 0, dxB = 0;
-    do {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int& e_idx = i == 0 ? idxA : idxB;
-            int& e_ye = i == 0 ? yeA : yeB;
-            int64_t& e_x = i == 0 ? xA : xB;
-            int64_t& e_dx = i == 0 ? dxA : dxB;
-            const int di = i == 0 ? 1 : npts - 1;
-            if (y >= e_ye) {
-                int idx0 = e_idx;
-                int idx = idx0 + di; if (idx >= npts) idx -= npts;
-                for (; edges-- > 0;) {
-                    const int ty = (int)((sel4(vy, idx) + delta) >> XY_SHIFT);
-                    if (ty > y) {
-                        const int64_t xs = sel4(vx, idx0), xe = sel4(vx, idx);
-                        e_ye = ty;
-                        e_dx = div_trunc((xe - xs) * 2 + (ty - y), 2 * (ty - y));
-                        e_x = xs;
-                        e_idx = idx;
-                        break;
-                    }
-                    idx0 = idx; idx += di; if (idx >= npts) idx -= npts;
-                }
-            }
-        }
-        if (edges < 0) break;
-        if (y >= 0) {
-            const int64_t xl = xA > xB ? xB : xA, xr = xA > xB ? xA : xB;
-            const int xx1 = (int)((xl + (XY_ONE >> 1)) >> XY_SHIFT);
-            const int xx2 = (int)((xr + (XY_ONE >> 1)) >> XY_SHIFT);
-            if (xx2 >= 0 && xx1 < k.W) m_hline(k, y, xx1, xx2, lane);
-        }
-        xA += dxA;
-        xB += dxB;
-    } while (++y <= (int)ymax);
-}
-// The same polygon fill with the SCANLINES spread over the lanes (coverage pre-pass: one wave owns the whole primitive).
-// The edge walk above changes state only at the scanlines where an edge ends; between two such events an edge's abscissa
-// is x_start + (y - y_start) * dx in exact integer arithmetic — what the serial walk reaches by adding dx once per scanline.
-// Every lane runs the (wave-uniform, at most npts + 1 iterations) event loop with the serial code's own transition
-// statements, and draws its scanline when the loop passes over it.  A lane writes its whole span itself.
-__device__ __forceinline__ void m_hline_lane(const tile_mask& k, int y, int xa, int xb)
+__device__ __forceinline__ void m_hline_lane(const cover_map& k, int y, int xa, int xb)
 {
     if (y < 0 || y >= k.H) return;
     if (xa < 0) xa = 0;
     if (xb >= k.W) xb = k.W - 1;
-    const int ry = y - k.y0;
-    if (ry < 0 || ry >= k.h) return;
-    int a = xa - k.x0, b = xb - k.x0;
-    if (a < 0) a = 0;
-    if (b >= k.w) b = k.w - 1;
-    if (k.bits) {
-        for (int dw = a >> 5; dw <= (b >> 5); ++dw) {
-            const int lo = a > dw * 32 ? a - dw * 32 : 0, hi = b < dw * 32 + 31 ? b - dw * 32 : 31;
-            if (hi < lo) continue;
-            const uint32_t m = (hi - lo == 31) ? 0xFFFFFFFFu : (((1u << (hi - lo + 1)) - 1u) << lo);
-            atomicOr(&k.bits[(int64_t)ry * k.wd + dw], m);
-        }
-    } else {
-        for (int x = a; x <= b; ++x) k.m[ry * k.w + x] = 1;
+    for (int dw = xa >> 5; dw <= (xb >> 5); ++dw) {
+        const int lo = xa > dw * 32 ? xa - dw * 32 : 0, hi = xb < dw * 32 + 31 ? xb - dw * 32 : 31;
+        if (hi < lo) continue;
+        const uint32_t m = (hi - lo == 31) ? 0xFFFFFFFFu : (((1u << (hi - lo + 1)) - 1u) << lo);
+        atomicOr(&k.bits[(int64_t)y * k.wd + dw], m);
     }
 }
-__device__ void m_fill_convex4_lanes(const tile_mask& k, const int64_t* vx, const int64_t* vy, int lane)
+__device__ void m_fill_convex4_lanes(const cover_map& k, const int64_t* vx, const int64_t* vy, int lane)
 {
     const int npts = 4;
     const int64_t delta = XY_ONE >> 1;
@@ -965,8 +875,8 @@ __device__ void m_fill_convex4_lanes(const tile_mask& k, const int64_t* vx, cons
         y = ynext;
     }
 }
-template <bool LANES>
-__device__ void m_line_thick_t(const tile_mask& k, int x0, int y0, int x1, int y1, int thickness, int lane)
+// cv::ThickLine: the convex body between the two offset edges, then a disc at either end.
+__device__ void m_line_thick(const cover_map& k, int x0, int y0, int x1, int y1, int thickness, int lane)
 {
     int64_t p0x = (int64_t)x0 << XY_SHIFT, p0y = (int64_t)y0 << XY_SHIFT;
     int64_t p1x = (int64_t)x1 << XY_SHIFT, p1y = (int64_t)y1 << XY_SHIFT;
@@ -980,64 +890,70 @@ __device__ void m_line_thick_t(const tile_mask& k, int x0, int y0, int x1, int y
         int64_t dpx = (int64_t)rint(dy * r), dpy = (int64_t)rint(dx * r);
         int64_t vx[4] = { p0x + dpx, p0x - dpx, p1x - dpx, p1x + dpx };
         int64_t vy[4] = { p0y + dpy, p0y - dpy, p1y - dpy, p1y + dpy };
-        if (LANES) m_fill_convex4_lanes(k, vx, vy, lane); else m_fill_convex4(k, vx, vy, lane);
+        m_fill_convex4_lanes(k, vx, vy, lane);
     }
     int rad = (int)((th + (XY_ONE >> 1)) >> XY_SHIFT);
     m_disc(k, x0, y0, rad, lane);
     m_disc(k, x1, y1, rad, lane);
 }
-__device__ void m_line_thick(const tile_mask& k, int x0, int y0, int x1, int y1, int thickness, int lane)
-{
-    m_line_thick_t<false>(k, x0, y0, x1, y1, thickness, lane);
-}
 
 // ---------------------------------------------------------------------- A4 rain / A5 snow
-// Tile 64 x 32, halo R (1 for 3x3, 3 for 7x7).  The float32 pre-blur image (haze / brightness
-// applied through the LUT, primitives painted) is staged in LDS as [row][72 px][3] — the float
-// image of the frame's byte rows, so interior tiles stage with aligned dword loads; then OpenCV's
-// separable blur: row pass over every staged row, column pass over the tile, 4 pixels (12 values)
-// per lane with 16-byte LDS accesses, 12 B / 3 x 16 B global stores.
+// Both transforms are a per-byte pre-blur map (haze, or brightness boost + clip), the streak colour painted where the frame's
+// 1-bit coverage map (raster_kernel below; bits[job][H][wd] dwords, rasterised once per frame) is set, and OpenCV's separable
+// Gaussian blur: 3 x 3 (rain; snow) or 7 x 7 (snow).  The blur kernels are pure stencils.
 constexpr int BTW = 64, BTH = 32, BRMAX = 3;
 constexpr int kSThreads = 512;                 // one lane per (tile row, 4 px) in the column pass
 constexpr int BSW = 72;                         // staged pixels per row (>= 64 + 2*3, multiple of 4)
-constexpr int MAXHIT = 64;
 
 struct blur_taps { float k[2 * BRMAX + 1]; int r; };
 
-// RR = blur radius (1: 3x3, 3: 7x7).  RR == 1 fuses the row and the column pass in registers
-// (no s_row, 4 blocks per CU); RR == 3 keeps the two LDS passes.
-// BITS = true: the primitives were rasterised beforehand, once per frame, into a 1-bit coverage map (raster_kernel below;
-// bits[job][H][wd] dwords) and this kernel is a pure stencil — no bounding-box scan, no per-tile rasterisation, two barriers
-// fewer.  (With the rasteriser inside, a tile a thick drop touches keeps 7 of its 8 waves waiting on the wave that walks the
-// drop's scanlines, and 44 % of the tiles of a rain frame are touched: 197 us per 8 frames against 128 us without drops.)
-// BITS = false (no workspace given) keeps the self-contained form; both give the same bytes.
-template <bool SNOW, int RR, bool BITS>
-__global__ __launch_bounds__(kSThreads)
-void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awseg_prim_job> jobs,
-                   const int32_t* __restrict__ prims, blur_taps bt,
-                   uint8_t* __restrict__ out, float* __restrict__ norm_out, norm_consts nc,
-                   const uint32_t* __restrict__ bits_all, int wd)
+// Pre-blur value of an input byte, in[0..255]: haze (:134-135) or brightness boost + clip (:179-180); and the normalise table.
+// The strip body's fill; snow7_tile_kernel has the snow half written out (see there).
+template <bool SNOW>
+__device__ __forceinline__ void streak_lut_fill(float* in, weather_lut& L, const awseg_prim_job& job, const norm_consts& nc, bool want_norm,
+                                                int threads)
 {
-    constexpr int R = RR;
+    float pm, pa;
+    if (SNOW) { pm = 1.f; pa = (float)(job.intensity * 0.2); }
+    else { double haze = job.intensity * 0.3; pm = (float)(1.0 - haze); pa = (float)(haze * 0.7); }
+    for (int i = threadIdx.x; i < 256; i += threads) {
+        float v = (float)i / 255.0f;
+        if (SNOW) { v = v + pa; v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
+        else { v = v * pm; v = v + pa; }
+        in[i] = v;
+        if (want_norm) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) L.nrm[c][i] = norm1((uint8_t)i, nc.mean[c], nc.std[c]);
+        }
+    }
+}
+
+// The 7 x 7 snow blur as a TILE kernel (the 3 x 3 blurs are the strip kernel below; 7 x 7 as a strip needs 222 registers, two
+// waves per SIMD: 303 us against 161).  Tile 64 x 32, halo 3.  The float32 pre-blur image is staged in LDS as [row][72 px][3]
+// — the float image of the frame's byte rows, so interior tiles stage with aligned dword loads; then the row pass over every
+// staged row and the column pass over the tile, 4 pixels (12 values) per lane with 16-byte LDS accesses, 12 B / 3 x 16 B
+// global stores.
+__global__ __launch_bounds__(kSThreads)
+void snow7_tile_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awseg_prim_job> jobs, blur_taps bt,
+                       uint8_t* __restrict__ out, float* __restrict__ norm_out, norm_consts nc,
+                       const uint32_t* __restrict__ bits_all, int wd)
+{
+    constexpr int R = 3;
     constexpr int sw = BTW + 2 * R, sh = BTH + 2 * R;
     constexpr int NQ = (sw + 3) / 4;                                        // staged pixel quads per row
     constexpr int RAWD = 56;                                                // dwords per raw staged row
     __shared__ __attribute__((aligned(16))) float s_src[sh * BSW * 3];
-    __shared__ __attribute__((aligned(16))) float s_row[RR == 1 ? 4 : sh * BTW * 3];
+    __shared__ __attribute__((aligned(16))) float s_row[sh * BTW * 3];
     __shared__ uint32_t s_raw[sh * RAWD];
-    __shared__ uint8_t s_mask[BITS ? 4 : sh * BSW];
-    __shared__ uint32_t s_mbits[BITS ? sh * 4 : 1];                          // BITS: the <= 4 coverage dwords a staged row touches
-    __shared__ int s_hits[BITS ? 1 : MAXHIT];
-    __shared__ int s_nhit;
+    __shared__ uint32_t s_mbits[sh * 4];                                    // the <= 4 coverage dwords a staged row touches
     __shared__ weather_lut L;
     const awseg_prim_job job = jobs.j[blockIdx.z];
     const int64_t hw = (int64_t)H * W;
     const uint8_t* src = imgs + (int64_t)job.image * hw * 3;
     const int x0 = blockIdx.x * BTW, y0 = blockIdx.y * BTH;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 
     // Interior tiles: issue the staging loads (aligned dwords of the byte rows) right away; their
-    // latency hides behind the LUT fill, the primitive scan and the rasterisation.
+    // latency hides behind the table fill.
     const bool interior = (x0 - R >= 0) && (x0 + BTW + R <= W) && (y0 - R >= 0) && (y0 + BTH + R <= H) && ((W * 3) % 4 == 0);
     const int b0 = (x0 - R) * 3;
     constexpr int nbytes = sw * 3;
@@ -1054,31 +970,21 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
             else pre[u] = 0u;
         }
     }
-    // BITS: coverage dwords of the staged rows (columns x0-R .. x0+BTW+R-1 span at most 4 dwords)
-    const uint32_t* bits = BITS ? bits_all + (int64_t)blockIdx.z * H * wd : nullptr;
+    // coverage dwords of the staged rows (columns x0-R .. x0+BTW+R-1 span at most 4 dwords)
+    const uint32_t* bits = bits_all + (int64_t)blockIdx.z * H * wd;
     const int mb0 = (x0 - R) >> 5;                                          // first coverage dword of an interior tile's staged rows
     uint32_t mpre = 0u;
-    if (BITS && interior && (int)threadIdx.x < sh * 4) {
+    if (interior && (int)threadIdx.x < sh * 4) {
         const int ty = threadIdx.x >> 2, di = threadIdx.x & 3;
         const int dw = mb0 + di;
         mpre = dw < wd ? bits[(int64_t)(y0 - R + ty) * wd + dw] : 0u;
     }
-    // this lane's primitive for the bounding-box scan
-    const int32_t* pl = prims + (int64_t)job.prim_offset * (SNOW ? 3 : 5);
-    constexpr int PW = SNOW ? 3 : 5;
-    int pv[5] = { 0, 0, 0, 0, 0 };
-    if (!BITS && (int)threadIdx.x < job.prim_count) {
-#pragma unroll
-        for (int f = 0; f < PW; ++f) pv[f] = pl[threadIdx.x * PW + f];
-    }
-    // pre-blur value of an input byte: haze (:134-135) or brightness boost + clip (:179-180)
-    float pm, pa;
-    if (SNOW) { pm = 1.f; pa = (float)(job.intensity * 0.2); }
-    else { double haze = job.intensity * 0.3; pm = (float)(1.0 - haze); pa = (float)(haze * 0.7); }
+    // pre-blur value of an input byte: brightness boost + clip (:179-180).  Written out here, not through streak_lut_fill: with
+    // the helper the compiler schedules this kernel differently (9 more instructions) and it measures 1 % slower.
+    const float pa = (float)(job.intensity * 0.2);
     for (int i = threadIdx.x; i < 256; i += kSThreads) {
         float v = (float)i / 255.0f;
-        if (SNOW) { v = v + pa; v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-        else { v = v * pm; v = v + pa; }
+        v = v + pa; v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
         L.in[i] = v;
         if (norm_out) {
 #pragma unroll
@@ -1091,56 +997,11 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
             const int i = threadIdx.x + u * kSThreads;
             if (i < sh * RAWD) s_raw[i] = pre[u];
         }
-        if (BITS && (int)threadIdx.x < sh * 4) s_mbits[threadIdx.x] = mpre;
-    }
-    // coverage mask over the part of tile+halo that lies inside the image
-    tile_mask mk;
-    mk.m = s_mask; mk.W = W; mk.H = H; mk.bits = nullptr; mk.wd = 0;
-    mk.x0 = x0 - R < 0 ? 0 : x0 - R;
-    mk.y0 = y0 - R < 0 ? 0 : y0 - R;
-    const int xe = x0 + BTW + R > W ? W : x0 + BTW + R, ye = y0 + BTH + R > H ? H : y0 + BTH + R;
-    mk.w = xe - mk.x0; mk.h = ye - mk.y0;
-    if (!BITS) {
-    for (int i = threadIdx.x; i < mk.w * mk.h; i += kSThreads) s_mask[i] = 0;
-    if (threadIdx.x == 0) s_nhit = 0;
-    __syncthreads();
-    // 1. which primitives touch this tile (bounding boxes, all lanes)
-    for (int i = threadIdx.x, u = 0; i < job.prim_count; i += kSThreads, ++u) {
-        int lx, hx, ly, hy;
-        int f0, f1, f2, f3 = 0, f4 = 0;
-        if (u == 0) { f0 = pv[0]; f1 = pv[1]; f2 = pv[2]; f3 = pv[3]; f4 = pv[4]; }
-        else { f0 = pl[i * PW]; f1 = pl[i * PW + 1]; f2 = pl[i * PW + 2]; if (!SNOW) { f3 = pl[i * PW + 3]; f4 = pl[i * PW + 4]; } }
-        if (SNOW) {
-            const int cx = f0, cy = f1, r = f2;
-            lx = cx - r; hx = cx + r; ly = cy - r; hy = cy + r;
-        } else {
-            const int ax = f0, ay = f1, bx = f2, by = f3, th = f4;
-            const int mg = th <= 1 ? 0 : th + 2;
-            lx = (ax < bx ? ax : bx) - mg; hx = (ax > bx ? ax : bx) + mg;
-            ly = (ay < by ? ay : by) - mg; hy = (ay > by ? ay : by) + mg;
-        }
-        if (!(hx < mk.x0 || lx >= xe || hy < mk.y0 || ly >= ye)) {
-            const int slot = atomicAdd(&s_nhit, 1);
-            if (slot < MAXHIT) s_hits[slot] = i;
-        }
+        if ((int)threadIdx.x < sh * 4) s_mbits[threadIdx.x] = mpre;
     }
     __syncthreads();
-    // 2. rasterise: one wave per hit (a tile sees a handful at most; more than MAXHIT -> every primitive)
-    const int nhit = s_nhit;
-    const int nwork = nhit <= MAXHIT ? nhit : job.prim_count;
-    for (int hidx = wv; hidx < nwork; hidx += kSThreads / 64) {
-        const int i = nhit <= MAXHIT ? s_hits[hidx] : hidx;
-        if (SNOW) m_disc(mk, pl[i * 3], pl[i * 3 + 1], pl[i * 3 + 2], lane);
-        else {
-            const int ax = pl[i * 5], ay = pl[i * 5 + 1], bx = pl[i * 5 + 2], by = pl[i * 5 + 3], th = pl[i * 5 + 4];
-            if (th <= 1) m_line_thin(mk, ax, ay, bx, by, lane);
-            else m_line_thick(mk, ax, ay, bx, by, th, lane);
-        }
-    }
-    }   // !BITS
-    __syncthreads();
-    // 3. stage the pre-blur float image of tile + halo: one lane per (row, pixel quad)
-    const float col[3] = { SNOW ? 1.0f : 0.8f, SNOW ? 1.0f : 0.9f, 1.0f };
+    // 1. stage the pre-blur float image of tile + halo: one lane per (row, pixel quad)
+    const float col[3] = { 1.0f, 1.0f, 1.0f };                              // a flake's colour
     if (interior) {
         for (int i = threadIdx.x; i < sh * NQ; i += kSThreads) {
             const int ty = i / NQ, tq = i - ty * NQ;
@@ -1153,19 +1014,15 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
             d[0] = sft ? (w0 >> sft) | (w1 << (32 - sft)) : w0;
             d[1] = sft ? (w1 >> sft) | (w2 << (32 - sft)) : w1;
             d[2] = sft ? (w2 >> sft) | (w3 << (32 - sft)) : w2;
-            const uint8_t* mrow = s_mask + (BITS ? 0 : (y0 - R + ty - mk.y0) * mk.w + (x0 - R + tq * 4 - mk.x0));
-            uint32_t cbits = 0u;                                            // BITS: coverage of the quad's four pixels in bits 0..3
-            if (BITS) {
-                const int bo2 = (x0 - R + tq * 4) - (mb0 << 5);             // bit offset inside the row's staged dwords (0 .. 127)
-                const uint32_t* mr = s_mbits + ty * 4 + (bo2 >> 5);
-                const uint32_t lo = mr[0], hi = (bo2 >> 5) < 3 ? mr[1] : 0u;
-                cbits = (uint32_t)((((uint64_t)hi << 32) | lo) >> (bo2 & 31));
-            }
+            const int bo2 = (x0 - R + tq * 4) - (mb0 << 5);                 // bit offset inside the row's staged dwords (0 .. 127)
+            const uint32_t* mr = s_mbits + ty * 4 + (bo2 >> 5);
+            const uint32_t lo = mr[0], hi = (bo2 >> 5) < 3 ? mr[1] : 0u;
+            const uint32_t cbits = (uint32_t)((((uint64_t)hi << 32) | lo) >> (bo2 & 31));   // coverage of the quad's four pixels in bits 0..3
             float v[12];
 #pragma unroll
             for (int e = 0; e < 12; ++e) {
                 const int k = e / 3, c = e - k * 3;
-                const bool cov = (tq * 4 + k < sw) && (BITS ? ((cbits >> k) & 1u) != 0u : mrow[k] != 0);
+                const bool cov = (tq * 4 + k < sw) && ((cbits >> k) & 1u) != 0u;
                 v[e] = cov ? col[c] : L.in[(d[e >> 2] >> ((e & 3) * 8)) & 0xFF];
             }
             float4* o4 = reinterpret_cast<float4*>(s_src + (ty * BSW + tq * 4) * 3);
@@ -1175,9 +1032,7 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
         for (int i = threadIdx.x; i < sh * sw; i += kSThreads) {
             const int ty = i / sw, tx = i - ty * sw;
             const int gy = reflect_101(y0 - R + ty, H), gx = reflect_101(x0 - R + tx, W);
-            const bool inrect = (gy >= mk.y0 && gy < ye && gx >= mk.x0 && gx < xe);
-            const bool cov = BITS ? ((bits[(int64_t)gy * wd + (gx >> 5)] >> (gx & 31)) & 1u) != 0u
-                                  : (inrect && s_mask[(gy - mk.y0) * mk.w + (gx - mk.x0)]);
+            const bool cov = ((bits[(int64_t)gy * wd + (gx >> 5)] >> (gx & 31)) & 1u) != 0u;
             const uint8_t* px = src + ((int64_t)gy * W + gx) * 3;
 #pragma unroll
             for (int c = 0; c < 3; ++c) s_src[(ty * BSW + tx) * 3 + c] = cov ? col[c] : L.in[px[c]];
@@ -1206,40 +1061,32 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
     float* ndst = norm_out ? norm_out + (int64_t)job.image * hw * 3 : nullptr;
     const int ty = threadIdx.x / (BTW / 4), tq = threadIdx.x - ty * (BTW / 4);   // one (tile row, 4 px) per lane
     const int gy = y0 + ty, gx = x0 + tq * 4;
-    float acc[12];
-    if (RR == 1) {
-        // 4. + 5. fused: the three row-pass results this lane's column pass needs are recomputed in
-        // registers (same operations, same order as the two-pass form)
-        float up[12], ctr[12], dn[12];
-        row_pass(ty, tq, up); row_pass(ty + 1, tq, ctr); row_pass(ty + 2, tq, dn);
+    // 2. row pass over every staged row
+    for (int i = threadIdx.x; i < sh * (BTW / 4); i += kSThreads) {
+        const int ry = i / (BTW / 4), rq = i - ry * (BTW / 4);
+        float o[12];
+        row_pass(ry, rq, o);
+        float4* d = reinterpret_cast<float4*>(s_row + (ry * BTW + rq * 4) * 3);
+        d[0] = make_float4(o[0], o[1], o[2], o[3]); d[1] = make_float4(o[4], o[5], o[6], o[7]); d[2] = make_float4(o[8], o[9], o[10], o[11]);
+    }
+    __syncthreads();
+    // 3. column pass over the tile
+    auto ldrow = [&](int rr, float* v) {
+        const float4* p4 = reinterpret_cast<const float4*>(s_row + (rr * BTW + tq * 4) * 3);
+        float4 a = p4[0], b = p4[1], c = p4[2];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
+    };
+    float acc[12], ctr[12];
+    ldrow(ty + R, ctr);
 #pragma unroll
-        for (int e = 0; e < 12; ++e) { float a0 = bt.k[1] * ctr[e]; float ab = up[e] + dn[e]; float m = bt.k[2] * ab; acc[e] = a0 + m; }
-    } else {
-        for (int i = threadIdx.x; i < sh * (BTW / 4); i += kSThreads) {
-            const int ry = i / (BTW / 4), rq = i - ry * (BTW / 4);
-            float o[12];
-            row_pass(ry, rq, o);
-            float4* d = reinterpret_cast<float4*>(s_row + (ry * BTW + rq * 4) * 3);
-            d[0] = make_float4(o[0], o[1], o[2], o[3]); d[1] = make_float4(o[4], o[5], o[6], o[7]); d[2] = make_float4(o[8], o[9], o[10], o[11]);
-        }
-        __syncthreads();
-        auto ldrow = [&](int rr, float* v) {
-            const float4* p4 = reinterpret_cast<const float4*>(s_row + (rr * BTW + tq * 4) * 3);
-            float4 a = p4[0], b = p4[1], c = p4[2];
-            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-            v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-        };
-        float ctr[12];
-        ldrow(ty + R, ctr);
+    for (int e = 0; e < 12; ++e) acc[e] = bt.k[R] * ctr[e];
 #pragma unroll
-        for (int e = 0; e < 12; ++e) acc[e] = bt.k[R] * ctr[e];
+    for (int j = 1; j <= R; ++j) {
+        float up[12], dn[12];
+        ldrow(ty + R - j, up); ldrow(ty + R + j, dn);
 #pragma unroll
-        for (int j = 1; j <= R; ++j) {
-            float up[12], dn[12];
-            ldrow(ty + R - j, up); ldrow(ty + R + j, dn);
-#pragma unroll
-            for (int e = 0; e < 12; ++e) { float ab = up[e] + dn[e]; float m = bt.k[R + j] * ab; acc[e] = acc[e] + m; }
-        }
+        for (int e = 0; e < 12; ++e) { float ab = up[e] + dn[e]; float m = bt.k[R + j] * ab; acc[e] = acc[e] + m; }
     }
     if (gy < H && gx < W) {
         uint8_t res[12];
@@ -1247,6 +1094,7 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
         for (int e = 0; e < 12; ++e) res[e] = quant_f32(acc[e]);
         const int nvalid = (W - gx) < 4 ? (W - gx) : 4;
         const int64_t p = (int64_t)gy * W + gx;
+        // (its own stores, not store_quad: with the helper's predicated scalar stores this kernel measured 1.5 % slower)
         if (dst) {
             if (nvalid == 4 && (((uintptr_t)(dst + p * 3)) & 3) == 0) {
                 uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
@@ -1271,7 +1119,7 @@ void streak_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awse
     }
 }
 
-// The same transform with the coverage map, as a STRIP kernel: a lane owns 4 adjacent pixels and walks NR rows of them; no
+// The 3 x 3 blurs (rain, snow) as a STRIP kernel: a lane owns 4 adjacent pixels and walks NR rows of them; no
 // float image in LDS, no barrier after the table fill.  Per input row a lane loads the (4 + 2R) pixels of its window as
 // aligned dwords (bytes picked with compile-time shifts), maps them through the LDS table (or the streak colour where the
 // coverage bit is set), runs OpenCV's row pass for its 12 values and keeps the last 2R + 1 row-pass results in registers;
@@ -1294,20 +1142,8 @@ __device__ __forceinline__ void streak_strip_body(const uint8_t* __restrict__ im
     constexpr int R = RR, NR = strip_rows<RR>::value, NW = 4 + 2 * R, NBYTE = NW * 3, RING = 2 * R + 1;
     constexpr int OFF = (4 - ((3 * R) & 3)) & 3;                 // (gx - R) * 3 mod 4 for gx % 4 == 0: 1 (R = 1), 3 (R = 3)
     constexpr int ND = (OFF + NBYTE + 3) / 4;                    // dwords that hold the window's bytes: 5 / 9
-    float pm, pa;
-    if (SNOW) { pm = 1.f; pa = (float)(job.intensity * 0.2); }
-    else { double haze = job.intensity * 0.3; pm = (float)(1.0 - haze); pa = (float)(haze * 0.7); }
-    for (int i = threadIdx.x; i < 256; i += 256) {
-        float v = (float)i / 255.0f;
-        if (SNOW) { v = v + pa; v = v < 0.f ? 0.f : (v > 1.f ? 1.f : v); }
-        else { v = v * pm; v = v + pa; }
-        s_in[i] = v;
-        if (i < 3) s_in[256 + i] = i == 2 ? 1.0f : (SNOW ? 1.0f : (i == 0 ? 0.8f : 0.9f));
-        if (norm_out) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) L.nrm[c][i] = norm1((uint8_t)i, nc.mean[c], nc.std[c]);
-        }
-    }
+    streak_lut_fill<SNOW>(s_in, L, job, nc, norm_out != nullptr, 256);
+    if (threadIdx.x < 3) s_in[256 + threadIdx.x] = threadIdx.x == 2 ? 1.0f : (SNOW ? 1.0f : (threadIdx.x == 0 ? 0.8f : 0.9f));
     __syncthreads();
     const int64_t hw = (int64_t)H * W;
     const int gx = (bx * 64 + (threadIdx.x & 63)) * 4;
@@ -1396,27 +1232,8 @@ __device__ __forceinline__ void streak_strip_body(const uint8_t* __restrict__ im
 #pragma unroll
         for (int e = 0; e < 12; ++e) res[e] = (uint8_t)(int)(__builtin_amdgcn_fmed3f(acc[e], 0.f, 1.f) * 255.0f);   // quant_f32 with one v_med3
         const int64_t p = (int64_t)gy * W + gx;
-        if (dst) {
-            if (FAST || (nvalid == 4 && (((uintptr_t)(dst + p * 3)) & 3) == 0)) {
-                uint32_t* d4 = reinterpret_cast<uint32_t*>(dst + p * 3);
-#pragma unroll
-                for (int q = 0; q < 3; ++q)
-                    d4[q] = (uint32_t)res[4 * q] | ((uint32_t)res[4 * q + 1] << 8) | ((uint32_t)res[4 * q + 2] << 16) | ((uint32_t)res[4 * q + 3] << 24);
-            } else {
-                for (int k = 0; k < nvalid * 3; ++k) dst[p * 3 + k] = res[k];
-            }
-        }
-        if (ndst) {
-            if (FAST || (nvalid == 4 && (p & 3) == 0 && (hw & 3) == 0)) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-                    *reinterpret_cast<float4*>(ndst + (int64_t)c * hw + p) =
-                        make_float4(L.nrm[c][res[c]], L.nrm[c][res[3 + c]], L.nrm[c][res[6 + c]], L.nrm[c][res[9 + c]]);
-            } else {
-                for (int c = 0; c < 3; ++c)
-                    for (int k = 0; k < nvalid; ++k) ndst[(int64_t)c * hw + p + k] = L.nrm[c][res[k * 3 + c]];
-            }
-        }
+        store_quad(res, dst, ndst, p, hw, nvalid, FAST || (nvalid == 4 && (((uintptr_t)(dst + p * 3)) & 3) == 0),
+                   FAST || (nvalid == 4 && (p & 3) == 0 && (hw & 3) == 0), L);
     };
     const int rows_out = (H - y0) < NR ? (H - y0) : NR;           // output rows of this strip (wave-uniform)
     issue(0);
@@ -1455,15 +1272,13 @@ void raster_kernel(int H, int W, job_pack<awseg_prim_job> jobs, const int32_t* _
     const awseg_prim_job job = jobs.j[blockIdx.y];
     const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= job.prim_count) return;                                        // wave-uniform
-    tile_mask mk;
-    mk.m = nullptr; mk.W = W; mk.H = H; mk.x0 = 0; mk.y0 = 0; mk.w = W; mk.h = H;
-    mk.bits = bits_all + (int64_t)blockIdx.y * H * wd; mk.wd = wd;
+    const cover_map mk = { bits_all + (int64_t)blockIdx.y * H * wd, wd, W, H };
     const int32_t* pl = prims + (int64_t)job.prim_offset * (SNOW ? 3 : 5);
     if (SNOW) m_disc(mk, pl[i * 3], pl[i * 3 + 1], pl[i * 3 + 2], lane);
     else {
         const int ax = pl[i * 5], ay = pl[i * 5 + 1], bx = pl[i * 5 + 2], by = pl[i * 5 + 3], th = pl[i * 5 + 4];
         if (th <= 1) m_line_thin(mk, ax, ay, bx, by, lane);
-        else m_line_thick_t<true>(mk, ax, ay, bx, by, th, lane);
+        else m_line_thick(mk, ax, ay, bx, by, th, lane);
     }
 }
 
@@ -1522,6 +1337,52 @@ int grid_for(int64_t items, int64_t jobs)
     int64_t cap = (AWSEG_CUS * 8 + jobs - 1) / (jobs < 1 ? 1 : jobs);
     if (want > cap) want = cap;
     return (int)(want < 1 ? 1 : want);
+}
+
+// Launch plans, shared by the per-kind launchers and awseg_weather_batch (whose bytes are the per-kind launchers' by construction).
+// Fog strips (W % 4 == 0, W >= 16), n_frames foggy frames in the launch: two 256-thread blocks fit a CU (70 KB LDS ring each),
+// so the strip height is the one that makes the grid ONE round of them.  Few frames (the in-step case: 1-2 frames of a kind):
+// short strips — the halo rows triple the noise work, but the chip is otherwise idle and a wave's serial row walk is the
+// launch's duration; many frames: >= 24 rows per strip.  rows >= 0: the caller's strip height instead.
+struct fog_strip_plan { int rows, nbx, nby; };               // rows per strip; x blocks (60 quads each); y blocks (4 strips each)
+fog_strip_plan plan_fog_strips(int H, int W, int n_frames, int rows = -1)
+{
+    fog_strip_plan p;
+    p.nbx = ((W >> 2) + kFogStripQuads - 1) / kFogStripQuads;
+    p.rows = rows;
+    if (p.rows < 0) {
+        const int64_t per_round = (int64_t)AWSEG_CUS * 2 / p.nbx / n_frames;     // y-blocks available
+        p.rows = per_round >= 1 ? (int)((H + 4 * per_round - 1) / (4 * per_round)) : H;
+        const int min_rows = n_frames <= 2 ? 8 : 24;
+        if (p.rows < min_rows) p.rows = min_rows;
+    }
+    p.nby = p.rows >= 1 ? ((H + p.rows - 1) / p.rows + 3) / 4 : 0;
+    return p;
+}
+
+// 3 x 3 streak strips: a block is 64 quads wide and four strips of strip_rows<1> rows high.
+dim3 streak_strip_grid(int H, int W, int n_frames)
+{
+    const int nr = strip_rows<1>::value;
+    return dim3((W + 255) / 256, (H + 4 * nr - 1) / (4 * nr), n_frames);
+}
+
+// Coverage pre-pass: zero n_maps maps, then (rasterise_coverage) one wave per primitive of a packed group of cnt frames whose
+// maps start at `bits`.  awseg_weather_batch clears rain's and snow's maps with one memset and rasterises the two groups.
+int clear_coverage(uint32_t* bits, int n_maps, int H, int wd, hipStream_t s)
+{
+    return hipMemsetAsync(bits, 0, (size_t)n_maps * H * wd * sizeof(uint32_t), s) == hipSuccess ? 0 : AWSEG_EINVAL;
+}
+template <bool SNOW>
+int rasterise_coverage(int H, int W, const job_pack<awseg_prim_job>& pk, int cnt, const int32_t* prims, uint32_t* bits, int wd, hipStream_t s)
+{
+    int maxp = 0;
+    for (int q = 0; q < cnt; ++q) maxp = pk.j[q].prim_count > maxp ? pk.j[q].prim_count : maxp;
+    if (maxp > 0) {
+        hipLaunchKernelGGL((raster_kernel<SNOW>), dim3((maxp + 3) / 4, cnt), dim3(256), 0, s, H, W, pk, prims, bits, wd);
+        AWSEG_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1587,27 +1448,16 @@ AWSEG_API int awseg_weather_batch(const uint8_t* imgs, int height, int width, co
     }
     if ((n_rain && !rain_drops) || (n_snow && !snow_flakes) || ((n_rain || n_snow) && !workspace)) return AWSEG_EINVAL;
     uint32_t* bits = reinterpret_cast<uint32_t*>(workspace);
-    // fog strip height: as fog_common (one round of two blocks per CU; short strips when few frames are foggy)
-    int fog_rows = 0, fog_nbx = 0, fog_nby = 0;
-    if (n_fog) {
-        fog_nbx = ((W >> 2) + kFogStripQuads - 1) / kFogStripQuads;
-        const int64_t per_round = (int64_t)AWSEG_CUS * 2 / fog_nbx / n_fog;
-        fog_rows = per_round >= 1 ? (int)((H + 4 * per_round - 1) / (4 * per_round)) : H;
-        const int min_rows = n_fog <= 2 ? 8 : 24;
-        if (fog_rows < min_rows) fog_rows = min_rows;
-        fog_nby = ((H + fog_rows - 1) / fog_rows + 3) / 4;
-    }
-    const int nr = strip_rows<1>::value;
-    const int st_nbx = (W + 255) / 256, st_nby = (H + 4 * nr - 1) / (4 * nr);
+    const fog_strip_plan fp = n_fog ? plan_fog_strips(H, W, n_fog) : fog_strip_plan{ 0, 0, 0 };
+    const dim3 sg = streak_strip_grid(H, W, 1);
     int pw_blocks = (int)((hw / 4 + kThreads - 1) / kThreads);         // pointwise kinds: grid-stride over pixel quads
     const int pw_cap = AWSEG_CUS * 8 / n_jobs > 64 ? AWSEG_CUS * 8 / n_jobs : 64;
     if (pw_blocks > pw_cap) pw_blocks = pw_cap;
     if ((hw & 3) != 0) return AWSEG_ERANGE;
     wb_table tab;
     tab.n = 0; tab.pad = 0;
-    job_pack<awseg_prim_job> rain_pk, snow_pk;
     awseg_prim_job rsel[kMaxJobs], ssel[kMaxJobs];
-    int rcnt = 0, scnt = 0, rmax = 0, smax = 0;
+    int rcnt = 0, scnt = 0;
     int next_block = 0;
     const int order[5] = { AWSEG_WEATHER_FOG, AWSEG_WEATHER_RAIN, AWSEG_WEATHER_SNOW, AWSEG_WEATHER_NIGHT, AWSEG_WEATHER_CLEAN };
     for (int o = 0; o < 5; ++o)
@@ -1615,33 +1465,24 @@ AWSEG_API int awseg_weather_batch(const uint8_t* imgs, int height, int width, co
             const awseg_weather_job& jb = jobs[i];
             if (jb.kind != order[o]) continue;
             wb_entry& e = tab.e[tab.n++];
-            e.kind = jb.kind; e.b0 = next_block; e.slot = 0; e.strip_rows = fog_rows;
+            e.kind = jb.kind; e.b0 = next_block; e.slot = 0; e.strip_rows = fp.rows;
             e.fog.image = jb.image; e.fog._pad = 0; e.fog.beta = jb.a; e.fog.atmos = jb.b; e.fog.seed = jb.seed;
             e.night.image = jb.image; e.night._pad = 0; e.night.brightness = jb.a; e.night.intensity = jb.b; e.night.seed = jb.seed;
             e.prim.image = jb.image; e.prim.prim_offset = jb.prim_offset; e.prim.prim_count = jb.prim_count; e.prim.blur_ksize = 3; e.prim.intensity = jb.a;
-            if (jb.kind == AWSEG_WEATHER_FOG) { e.nbx = fog_nbx; e.nby = fog_nby; }
+            if (jb.kind == AWSEG_WEATHER_FOG) { e.nbx = fp.nbx; e.nby = fp.nby; }
             else if (jb.kind == AWSEG_WEATHER_RAIN || jb.kind == AWSEG_WEATHER_SNOW) {
                 if (jb.prim_count < 0 || jb.prim_offset < 0) return AWSEG_EINVAL;
-                e.nbx = st_nbx; e.nby = st_nby;
-                if (jb.kind == AWSEG_WEATHER_RAIN) { e.slot = rcnt; rsel[rcnt++] = e.prim; rmax = jb.prim_count > rmax ? jb.prim_count : rmax; }
-                else { e.slot = n_rain + scnt; ssel[scnt++] = e.prim; smax = jb.prim_count > smax ? jb.prim_count : smax; }
+                e.nbx = (int)sg.x; e.nby = (int)sg.y;
+                if (jb.kind == AWSEG_WEATHER_RAIN) { e.slot = rcnt; rsel[rcnt++] = e.prim; }
+                else { e.slot = n_rain + scnt; ssel[scnt++] = e.prim; }
             }
             else { e.nbx = pw_blocks; e.nby = 1; }
             next_block += e.nbx * e.nby;
         }
-    if (n_rain + n_snow) {
-        if (hipMemsetAsync(bits, 0, (size_t)(n_rain + n_snow) * H * wd * sizeof(uint32_t), s) != hipSuccess) return AWSEG_EINVAL;
-        if (rcnt && rmax > 0) {
-            rain_pk = pack_jobs(rsel, 0, rcnt);
-            hipLaunchKernelGGL((raster_kernel<false>), dim3((rmax + 3) / 4, rcnt), dim3(256), 0, s, H, W, rain_pk, rain_drops, bits, wd);
-            AWSEG_LAUNCH_CHECK();
-        }
-        if (scnt && smax > 0) {
-            snow_pk = pack_jobs(ssel, 0, scnt);
-            hipLaunchKernelGGL((raster_kernel<true>), dim3((smax + 3) / 4, scnt), dim3(256), 0, s, H, W, snow_pk, snow_flakes, bits + (size_t)n_rain * H * wd, wd);
-            AWSEG_LAUNCH_CHECK();
-        }
-    }
+    // the rain frames' maps, then the snow frames' (wb_entry::slot)
+    if (n_rain + n_snow) { if (int rc = clear_coverage(bits, n_rain + n_snow, H, wd, s)) return rc; }
+    if (rcnt) { if (int rc = rasterise_coverage<false>(H, W, pack_jobs(rsel, 0, rcnt), rcnt, rain_drops, bits, wd, s)) return rc; }
+    if (scnt) { if (int rc = rasterise_coverage<true>(H, W, pack_jobs(ssel, 0, scnt), scnt, snow_flakes, bits + (size_t)n_rain * H * wd, wd, s)) return rc; }
     gauss_taps_f32 tf;
     for (int i = 0; i < 2 * FR + 1; ++i) tf.w[i] = (float)taps_host[i];
     const size_t lds = n_fog ? (size_t)kFogRing * 256 * sizeof(float4) : 0;
@@ -1706,24 +1547,14 @@ static int fog_common(int mode, const uint8_t* imgs, int H, int W, const awseg_f
         else if (mode == 0) AWSEG_FOG(true, 0);      // depth-only request keeps the float64 pipeline
         else {
             const char* sr_env = getenv("AWSEG_FOG_STRIP_ROWS");             // rows per strip; 0: the tile kernel (read per call: tests vary it)
-            int strip_rows = sr_env ? atoi(sr_env) : -1;
-            if (strip_rows < 0) {
-                // two 256-thread blocks fit a CU (70 KB LDS ring each): the strip height that makes the grid ONE round of them
-                const int64_t per_round = (int64_t)AWSEG_CUS * 2 / (((W >> 2) + kFogStripQuads - 1) / kFogStripQuads) / cnt;   // y-blocks (4 strips each) available
-                strip_rows = per_round >= 1 ? (int)((H + 4 * per_round - 1) / (4 * per_round)) : H;
-                // few frames per launch (the in-step case: 1-2 frames of a kind): short strips — the halo rows triple the noise work,
-                // but the chip is otherwise idle and a wave's serial row walk is the launch's duration; many frames: >= 24 rows per strip
-                const int min_rows = cnt <= 2 ? 8 : 24;
-                if (strip_rows < min_rows) strip_rows = min_rows;
-            }
-            const bool strip_ok = strip_rows >= 1 && (W & 3) == 0 && W >= 16 && (((uintptr_t)imgs & 3) == 0) &&
+            // the strip form takes widths of whole quads and aligned buffers; everything else is the tile kernel's
+            const bool strip_ok = (W & 3) == 0 && W >= 16 && (((uintptr_t)imgs & 3) == 0) &&
                                   (!out || ((uintptr_t)out & 3) == 0) && (!norm_out || ((uintptr_t)norm_out & 15) == 0);
-            const int strips = strip_ok ? (H + strip_rows - 1) / strip_rows : 0;
-            if (strip_ok && (strips + 3) / 4 <= 65535) {
+            const fog_strip_plan fp = strip_ok ? plan_fog_strips(H, W, cnt, sr_env ? atoi(sr_env) : -1) : fog_strip_plan{ 0, 0, 0 };
+            if (fp.rows >= 1 && fp.nby <= 65535) {
                 const size_t lds = (size_t)kFogRing * 256 * sizeof(float4);
                 if (hipFuncSetAttribute(reinterpret_cast<const void*>(fog_strip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return AWSEG_EINVAL;   // per launch: per device
-                dim3 sgrid(((W >> 2) + kFogStripQuads - 1) / kFogStripQuads, (strips + 3) / 4, cnt);
-                hipLaunchKernelGGL(fog_strip_kernel, sgrid, dim3(256), lds, s, imgs, H, W, pk, j0, tf, out, norm_out, depth_out, nc, strip_rows);
+                hipLaunchKernelGGL(fog_strip_kernel, dim3(fp.nbx, fp.nby, cnt), dim3(256), lds, s, imgs, H, W, pk, j0, tf, out, norm_out, depth_out, nc, fp.rows);
             }
             else hipLaunchKernelGGL(fog_fast_kernel, grid, dim3(kFogFastThreads), 0, s, imgs, H, W, pk, j0, tf, out, norm_out, depth_out, nc);
         }
@@ -1808,6 +1639,7 @@ static int streak_common(bool snow, const uint8_t* imgs, int H, int W, const aws
     if (!imgs || !jobs || (!out && !norm_out) || H < 1 || W < 1 || n_jobs < 0) return AWSEG_EINVAL;
     if (norm_out && (!mean_host || !std_host)) return AWSEG_EINVAL;
     if (n_jobs == 0) return 0;
+    if (!bits) return AWSEG_EINVAL;                  // the blur kernels read the coverage maps the pre-pass writes there
     if (n_jobs > 65535) return AWSEG_ERANGE;
     if (out == imgs) return AWSEG_EINVAL;            // the blur reads neighbours: not in-place safe
     if (((uintptr_t)imgs & 3) || (out && ((uintptr_t)out & 3)) || (norm_out && ((uintptr_t)norm_out & 15))) return AWSEG_EALIGN;
@@ -1824,38 +1656,19 @@ static int streak_common(bool snow, const uint8_t* imgs, int H, int W, const aws
             if (take) sel[cnt++] = jobs[j];
             if (cnt == kMaxJobs || (j == n_jobs && cnt > 0)) {
                 const job_pack<awseg_prim_job> pk = pack_jobs(sel, 0, cnt);
-                dim3 grid((W + BTW - 1) / BTW, (H + BTH - 1) / BTH, cnt);
-                if (bits) {
-                    // the group's coverage maps live at the start of the workspace (groups run back to back on the stream)
-                    int maxp = 0;
-                    for (int q = 0; q < cnt; ++q) maxp = sel[q].prim_count > maxp ? sel[q].prim_count : maxp;
-                    if (hipMemsetAsync(bits, 0, (size_t)cnt * H * wd * sizeof(uint32_t), s) != hipSuccess) return AWSEG_EINVAL;
-                    if (maxp > 0) {
-                        dim3 rgrid((maxp + 3) / 4, cnt);
-                        if (snow) hipLaunchKernelGGL((raster_kernel<true>), rgrid, dim3(256), 0, s, H, W, pk, prims, bits, wd);
-                        else hipLaunchKernelGGL((raster_kernel<false>), rgrid, dim3(256), 0, s, H, W, pk, prims, bits, wd);
-                        AWSEG_LAUNCH_CHECK();
-                    }
-                    static const bool tiles = getenv("AWSEG_STREAK_TILES") != nullptr;   // measurements: the tile kernel on the coverage map
-                    const int nr = want7 ? strip_rows<3>::value : strip_rows<1>::value;
-                    dim3 sgrid((W + 255) / 256, (H + 4 * nr - 1) / (4 * nr), cnt);
-                    if (tiles || sgrid.y > 65535 || want7) {            // 7x7 as a strip needs 222 registers (two waves per SIMD): 303 us against 161
-                        if (!snow) hipLaunchKernelGGL((streak_kernel<false, 1, true>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(3, 0.5), out, norm_out, nc, bits, wd);
-                        else if (!want7) hipLaunchKernelGGL((streak_kernel<true, 1, true>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(3, 1.0), out, norm_out, nc, bits, wd);
-                        else hipLaunchKernelGGL((streak_kernel<true, 3, true>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(7, 1.0), out, norm_out, nc, bits, wd);
-                    }
-#define AWSEG_STRIP(SN, RV, TAPS)                                                                                                       \
+                // the group's coverage maps live at the start of the workspace (groups run back to back on the stream)
+                if (int rc = clear_coverage(bits, cnt, H, wd, s)) return rc;
+                if (int rc = snow ? rasterise_coverage<true>(H, W, pk, cnt, prims, bits, wd, s) : rasterise_coverage<false>(H, W, pk, cnt, prims, bits, wd, s)) return rc;
+                const dim3 sgrid = streak_strip_grid(H, W, cnt);
+#define AWSEG_STRIP(SN, TAPS)                                                                                                          \
     do {                                                                                                                              \
-        if ((W & 3) == 0 && W >= 16) hipLaunchKernelGGL((streak_strip_kernel<SN, RV, true>), sgrid, dim3(256), 0, s, imgs, H, W, pk, TAPS, out, norm_out, nc, bits, wd); \
-        else hipLaunchKernelGGL((streak_strip_kernel<SN, RV, false>), sgrid, dim3(256), 0, s, imgs, H, W, pk, TAPS, out, norm_out, nc, bits, wd);                          \
+        if ((W & 3) == 0 && W >= 16) hipLaunchKernelGGL((streak_strip_kernel<SN, 1, true>), sgrid, dim3(256), 0, s, imgs, H, W, pk, TAPS, out, norm_out, nc, bits, wd); \
+        else hipLaunchKernelGGL((streak_strip_kernel<SN, 1, false>), sgrid, dim3(256), 0, s, imgs, H, W, pk, TAPS, out, norm_out, nc, bits, wd);                          \
     } while (0)
-                    else if (!snow) AWSEG_STRIP(false, 1, make_blur(3, 0.5));
-                    else if (!want7) AWSEG_STRIP(true, 1, make_blur(3, 1.0));
+                if (want7) hipLaunchKernelGGL(snow7_tile_kernel, dim3((W + BTW - 1) / BTW, (H + BTH - 1) / BTH, cnt), dim3(kSThreads), 0, s, imgs, H, W, pk, make_blur(7, 1.0), out, norm_out, nc, bits, wd);
+                else if (!snow) AWSEG_STRIP(false, make_blur(3, 0.5));
+                else AWSEG_STRIP(true, make_blur(3, 1.0));
 #undef AWSEG_STRIP
-                }
-                else if (!snow) hipLaunchKernelGGL((streak_kernel<false, 1, false>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(3, 0.5), out, norm_out, nc, bits, wd);
-                else if (!want7) hipLaunchKernelGGL((streak_kernel<true, 1, false>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(3, 1.0), out, norm_out, nc, bits, wd);
-                else hipLaunchKernelGGL((streak_kernel<true, 3, false>), grid, dim3(kSThreads), 0, s, imgs, H, W, pk, prims, make_blur(7, 1.0), out, norm_out, nc, bits, wd);
                 AWSEG_LAUNCH_CHECK();
                 cnt = 0;
             }

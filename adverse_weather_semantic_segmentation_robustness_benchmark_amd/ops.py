@@ -1036,36 +1036,26 @@ def weather_batch(imgs: torch.Tensor, jobs: np.ndarray, rain_drops: Optional[np.
     return rc == 0
 
 
-def _streak_workspace(imgs: torch.Tensor, n_jobs: int, h: int, w: int, prepass: bool):
-    """Coverage-map scratch of the rain / snow launchers (awseg_streak_workspace); None = rasterise inside the blur kernel."""
-    if not prepass or n_jobs < 1:
-        return None
-    return N.workspace.get(imgs.device, N.lib().awseg_streak_workspace(n_jobs, h, w), tag="streak")
-
-
-def rain(imgs: torch.Tensor, jobs: np.ndarray, drops: np.ndarray, out=None, norm_out=None, mean=None, std=None,
-         prepass: bool = True) -> None:
-    """_apply_rain (PKG/data/preprocessing.py:125-168).  prepass: rasterise the drops once per frame into a coverage bit map
-    (a second small kernel) instead of in every tile they touch — same bytes out."""
+def _streak(entry: str, imgs: torch.Tensor, jobs: np.ndarray, prims: np.ndarray, out, norm_out, mean, std) -> None:
+    """awseg_rain_apply / awseg_snow_apply: the primitives are rasterised once per frame into a coverage bit map (a small kernel
+    in front, its scratch from awseg_streak_workspace), the blur kernels are pure stencils."""
     imgs = imgs.contiguous()
     _, h, w, _ = imgs.shape
     jd = N.host_jobs(jobs)
-    pd = torch.from_numpy(np.ascontiguousarray(drops, dtype=np.int32)).to(imgs.device, non_blocking=True)
+    pd = torch.from_numpy(np.ascontiguousarray(prims, dtype=np.int32)).to(imgs.device, non_blocking=True)
     m, s = _mean_std(mean, std)
-    N.call("awseg_rain_apply", N.ptr(imgs), h, w, jd, len(jobs), N.ptr(pd), N.ptr(out), N.ptr(norm_out),
-                                     N.host(m), N.host(s), N.ptr(_streak_workspace(imgs, len(jobs), h, w, prepass)), N.stream())
+    ws = N.workspace.get(imgs.device, N.lib().awseg_streak_workspace(len(jobs), h, w), tag="streak") if len(jobs) else None
+    N.call(entry, N.ptr(imgs), h, w, jd, len(jobs), N.ptr(pd), N.ptr(out), N.ptr(norm_out), N.host(m), N.host(s), N.ptr(ws), N.stream())
 
 
-def snow(imgs: torch.Tensor, jobs: np.ndarray, flakes: np.ndarray, out=None, norm_out=None, mean=None, std=None,
-         prepass: bool = True) -> None:
+def rain(imgs: torch.Tensor, jobs: np.ndarray, drops: np.ndarray, out=None, norm_out=None, mean=None, std=None) -> None:
+    """_apply_rain (PKG/data/preprocessing.py:125-168)."""
+    _streak("awseg_rain_apply", imgs, jobs, drops, out, norm_out, mean, std)
+
+
+def snow(imgs: torch.Tensor, jobs: np.ndarray, flakes: np.ndarray, out=None, norm_out=None, mean=None, std=None) -> None:
     """_apply_snow (PKG/data/preprocessing.py:170-202)."""
-    imgs = imgs.contiguous()
-    _, h, w, _ = imgs.shape
-    jd = N.host_jobs(jobs)
-    pd = torch.from_numpy(np.ascontiguousarray(flakes, dtype=np.int32)).to(imgs.device, non_blocking=True)
-    m, s = _mean_std(mean, std)
-    N.call("awseg_snow_apply", N.ptr(imgs), h, w, jd, len(jobs), N.ptr(pd), N.ptr(out), N.ptr(norm_out),
-                                     N.host(m), N.host(s), N.ptr(_streak_workspace(imgs, len(jobs), h, w, prepass)), N.stream())
+    _streak("awseg_snow_apply", imgs, jobs, flakes, out, norm_out, mean, std)
 
 
 _DENSITY_TABLE = {"fog": (0.5, 0.5), "rain": (0.3, 0.2), "snow": (0.3, 0.2)}   # trainer.py:501-509, else (0.1, 0)

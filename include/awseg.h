@@ -304,7 +304,8 @@ int awseg_weather_batch(const uint8_t* imgs, int height, int width, const awseg_
  * sigma 0.5, BORDER_REFLECT_101, float32; quantise.  drops: device int32[n,5],
  * jobs[j] (host) names its slice.  OpenCV's rasteriser is not available offline: the
  * coverage rule is stated in oracle/awseg_oracle.c (parity unpinned).
- * out must not alias imgs.
+ * out must not alias imgs.  workspace (required; NULL with n_jobs > 0 is AWSEG_EINVAL):
+ * awseg_streak_workspace(n_jobs, height, width) bytes of device scratch, dword aligned.
  */
 int awseg_rain_apply(const uint8_t* imgs, int height, int width,
                      const awseg_prim_job* jobs, int n_jobs, const int32_t* drops,
@@ -312,9 +313,8 @@ int awseg_rain_apply(const uint8_t* imgs, int height, int width,
                      const float* mean_host, const float* std_host,
                      void* workspace, awseg_stream_t stream);
 
-/* Device scratch for awseg_rain_apply / awseg_snow_apply: with a workspace of this many bytes the primitives of a frame are
- * rasterised ONCE into a 1-bit coverage map (one wave per primitive) and the blur kernel is a pure stencil; with
- * workspace == NULL every 64x32 tile rasterises the primitives that touch it.  Same bytes out either way. */
+/* Bytes of device scratch awseg_rain_apply / awseg_snow_apply need: the primitives of a frame are rasterised ONCE into a 1-bit
+ * coverage map there (one wave per primitive) and the blur kernels are pure stencils that read it. */
 int64_t awseg_streak_workspace(int n_jobs, int height, int width);
 
 /* ------------------------------------------------------------------------- *
@@ -322,7 +322,7 @@ int64_t awseg_streak_workspace(int n_jobs, int height, int width);
  * ------------------------------------------------------------------------- *
  * v = clip(v + 0.2I, 0, 1); filled discs (x,y,r) of 1.0; Gaussian blur ksize 3
  * or 7, sigma 1.0, BORDER_REFLECT_101, float32; quantise.  flakes: device
- * int32[n,3].  out must not alias imgs.
+ * int32[n,3].  out must not alias imgs.  workspace: required, as for awseg_rain_apply.
  */
 int awseg_snow_apply(const uint8_t* imgs, int height, int width,
                      const awseg_prim_job* jobs, int n_jobs, const int32_t* flakes,

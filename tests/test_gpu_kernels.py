@@ -263,43 +263,45 @@ def test_rain_snow_vs_oracle(ops, oracle, hw):
     i1, drops1 = oracle.draw_rain(h, w, None)
     jobs, prims = ops.prim_jobs([0, 1], [i0, i1], [drops0, drops1])
     out = torch.zeros(2, h, w, 3, dtype=torch.uint8, device="cuda")
-    # prepass=True: coverage bit map rasterised once per frame + pure-stencil blur; False: rasteriser inside every tile
-    for prepass in (True, False):
-        out.zero_()
-        ops.rain(dev(imgs), jobs, prims, out=out, prepass=prepass)
-        for b, (i, dr) in enumerate(((i0, drops0), (i1, drops1))):
-            ref = oracle.rain(imgs[b], i, dr)
-            assert (out[b].cpu().numpy() != ref).sum() == 0, prepass
+    ops.rain(dev(imgs), jobs, prims, out=out)
+    for b, (i, dr) in enumerate(((i0, drops0), (i1, drops1))):
+        ref = oracle.rain(imgs[b], i, dr)
+        assert (out[b].cpu().numpy() != ref).sum() == 0
     s0, fl0, k0 = oracle.draw_snow(h, w, 0.5)
     s1, fl1, _ = oracle.draw_snow(h, w, None)
     for ks in ((3, 7), (7, 3)):
         jobs, prims = ops.prim_jobs([0, 1], [s0, s1], [fl0, fl1], ks)
-        for prepass in (True, False):
-            out.zero_()
-            ops.snow(dev(imgs), jobs, prims, out=out, prepass=prepass)
-            assert np.array_equal(out[0].cpu().numpy(), oracle.snow(imgs[0], s0, fl0, ks[0])), prepass
-            assert np.array_equal(out[1].cpu().numpy(), oracle.snow(imgs[1], s1, fl1, ks[1])), prepass
+        out.zero_()
+        ops.snow(dev(imgs), jobs, prims, out=out)
+        assert np.array_equal(out[0].cpu().numpy(), oracle.snow(imgs[0], s0, fl0, ks[0]))
+        assert np.array_equal(out[1].cpu().numpy(), oracle.snow(imgs[1], s1, fl1, ks[1]))
 
 
-def test_rain_snow_coverage_prepass_equals_in_tile_rasteriser_at_full_size(ops):
+def test_rain_snow_equal_the_oracle_at_full_size(ops, oracle):
     """1024x2048 frames, interior tiles with the aligned staging path, thick and thin drops, both flake sizes, fused normalise:
-    the two forms of the kernel must agree byte for byte (and float for float)."""
+    the bytes are the CPU oracle's, and the normalised planes are the oracle's normalise of those bytes, float for float."""
     from adverse_weather_semantic_segmentation_robustness_benchmark_amd.data import preprocessing as P
     B, h, w = 3, 1024, 2048
     np.random.seed(11)
     imgs = torch.randint(0, 255, (B, h, w, 3), dtype=torch.uint8, device="cuda")
+    host = imgs.cpu().numpy()
     rd = [P.draw_rain(h, w, v) for v in (0.2, 0.5, 0.8)]
     rj, rp = ops.prim_jobs(list(range(B)), [d[0] for d in rd], [d[1] for d in rd])
-    a, b = torch.zeros_like(imgs), torch.zeros_like(imgs)
-    na, nb = torch.zeros(B, 3, h, w, device="cuda"), torch.zeros(B, 3, h, w, device="cuda")
-    ops.rain(imgs, rj, rp, out=a, norm_out=na, prepass=True)
-    ops.rain(imgs, rj, rp, out=b, norm_out=nb, prepass=False)
-    assert torch.equal(a, b) and torch.equal(na, nb) and not torch.equal(a, imgs)
+    a, na = torch.zeros_like(imgs), torch.zeros(B, 3, h, w, device="cuda")
+    ops.rain(imgs, rj, rp, out=a, norm_out=na)
+    assert not torch.equal(a, imgs)
+    for b in range(B):
+        ref = oracle.rain(host[b], rd[b][0], rd[b][1])
+        assert np.array_equal(a[b].cpu().numpy(), ref), b
+        assert np.array_equal(na[b].cpu().numpy(), oracle.normalize(ref)), b
     sd = [P.draw_snow(h, w, v) for v in (0.2, 0.5, 0.8)]
-    sj, sp = ops.prim_jobs(list(range(B)), [d[0] for d in sd], [d[1] for d in sd], [3, 7, 3])
-    ops.snow(imgs, sj, sp, out=a, norm_out=na, prepass=True)
-    ops.snow(imgs, sj, sp, out=b, norm_out=nb, prepass=False)
-    assert torch.equal(a, b) and torch.equal(na, nb)
+    ks = [3, 7, 3]
+    sj, sp = ops.prim_jobs(list(range(B)), [d[0] for d in sd], [d[1] for d in sd], ks)
+    ops.snow(imgs, sj, sp, out=a, norm_out=na)
+    for b in range(B):
+        ref = oracle.snow(host[b], sd[b][0], sd[b][1], ks[b])
+        assert np.array_equal(a[b].cpu().numpy(), ref), b
+        assert np.array_equal(na[b].cpu().numpy(), oracle.normalize(ref)), b
 
 
 def test_philox_modes_are_deterministic_and_plausible(ops):
@@ -318,6 +320,16 @@ def test_philox_modes_are_deterministic_and_plausible(ops):
     f = ops.fog_density_field(["fog", "rain", "clean"], h, w, "cuda", 7)
     assert 0.5 <= f[0].min().item() and f[0].max().item() < 1.0 and abs(f[0].mean().item() - 0.75) < 0.01
     assert 0.2 <= f[1].min().item() and f[1].max().item() < 0.5 and f[2].max().item() < 0.1
+
+
+def test_philox_fog_takes_frames_narrower_than_a_pixel_quad(ops):
+    """W < 4: no strip plan is made (its x-block count would be zero, and the launcher used to divide by it); the tile kernel runs."""
+    imgs = torch.randint(0, 255, (1, 5, 3, 3), dtype=torch.uint8, device="cuda")
+    a, b = torch.zeros_like(imgs), torch.zeros_like(imgs)
+    d = torch.zeros(1, 5, 3, dtype=torch.float64, device="cuda")
+    ops.fog(imgs, ops.fog_jobs([0], [0.5], seeds=[3]), out=a, depth_out=d)
+    ops.fog(imgs, ops.fog_jobs([0], [0.5], seeds=[3]), out=b)
+    assert torch.equal(a, b) and not torch.equal(a, imgs) and d.min().item() >= 1.0
 
 
 def _philox4x32_7(seed, ctr, stream):

@@ -37,16 +37,14 @@ def main():
     variants["no drops"] = [d[1][:0] for d in rd]
     for name, drops in variants.items():
         rj, rp = ops.prim_jobs(idx, [d[0] for d in rd], drops)
-        for pre in (True, False):
-            ms = timed(lambda: ops.rain(imgs, rj, rp, norm_out=norm, prepass=pre))
-            print(f"rain, {name:18s} prepass={pre!s:5s} {ms * 1e3:8.1f} us   {15 * H * W * B / ms / 1e6:8.1f} GB/s")
+        ms = timed(lambda: ops.rain(imgs, rj, rp, norm_out=norm))
+        print(f"rain, {name:18s} {ms * 1e3:8.1f} us   {15 * H * W * B / ms / 1e6:8.1f} GB/s")
     sd = [P.draw_snow(H, W, 0.5) for _ in range(B)]
     for name, fl in (("drawn flakes", [d[1] for d in sd]), ("no flakes", [d[1][:0] for d in sd])):
         for ks in (3, 7):
             sj, sp = ops.prim_jobs(idx, [d[0] for d in sd], fl, [ks] * B)
-            for pre in (True, False):
-                ms = timed(lambda: ops.snow(imgs, sj, sp, norm_out=norm, prepass=pre))
-                print(f"snow k{ks}, {name:14s} prepass={pre!s:5s} {ms * 1e3:8.1f} us   {15 * H * W * B / ms / 1e6:8.1f} GB/s")
+            ms = timed(lambda: ops.snow(imgs, sj, sp, norm_out=norm))
+            print(f"snow k{ks}, {name:14s} {ms * 1e3:8.1f} us   {15 * H * W * B / ms / 1e6:8.1f} GB/s")
 
 
 if __name__ == "__main__":
