@@ -165,8 +165,42 @@ void attention_d32_kernel(const float* __restrict__ q, const float* __restrict__
 // operands instead of 24-bit, everything else as the kernel above (transposed scores, in-register softmax, the
 // probability tile reused as the B operand).  tests/test_gpu_kernels.py measures both kernels against a float64
 // reference: their errors are of the same order (a few 1e-7 relative), two orders inside the 1e-4 gate.
-// The probabilities are produced pre-scaled by 2^15 (folded into the exponent: exp2(s - m + 15)) so that every one that
-// matters is a NORMAL f16 number; the scale cancels in O / l.  Any finite float32 q, k, v: see the range guard below.
+// The probabilities are produced pre-scaled (folded into the exponent) so that every one that matters is a NORMAL f16
+// number; the scale cancels in O / l.  Any finite float32 q, k, v: see the range guard below.
+//
+// STALE INTEGER MAXIMUM (the in-range passes of both split kernels; the float32 kernel above, the bf16 instance and the
+// SCALED passes of the range guard keep the exact running maximum, exp2(s - m + 15)).  Softmax does not care which constant
+// is subtracted as long as it is the same for all keys of a query between two rescales, and the loop is bound by its vector
+// instruction count, so the constant is chosen to cost none in the common tile:
+//   * per query a stale m, an INTEGER in log2 units with |m| <= 2048 — exact in f16 — which enters the score product as one
+//     more k-slice: A = ones in slot 0 of both lane halves, B = -m in the slot of half 0 and the pre-scale exponent
+//     kPre = 15 - kTau in the slot of half 1: one extra v_mfma_f32_32x32x16_f16 per tile, on a pipe with slack, and the
+//     accumulator leaves the MFMA as s' = s - m + kPre.  p = exp2(s') directly: no subtraction, no m_new, no alpha.
+//   * common path: the lane's register maximum of s' against 15 (i.e. s - m > kTau), one ballot.  Rare path (wave-uniform,
+//     ballot != 0 or the first tile): the halves of a query agree on the tile maximum through the shuffle,
+//     m += d, d = max(0, ceil(max s' - kPre)) (an integer: alpha = 2^-d is exact), om / oc / l *= alpha, the B fragment is
+//     rebuilt and this tile's exponents become s' - d.  A lane whose query did not move has d = 0, alpha = 1 exactly.
+//   * each half-wave lane sums its own 16 keys into a partial l; the halves are joined once behind the loop.
+//   * a query whose m would leave [-2048, 2048] (or is not finite) flags the block: nothing is stored and the whole block
+//     runs again with the exact-maximum arithmetic (block-uniform, like the range guard).
+// Per tile of the prepared-image loop (gfx950 disassembly, v_ mnemonics other than v_mfma): 111 vector instructions beside 12
+// MFMAs before, 76 beside 13 now (in-block loop 110 -> 78); 130 -> 140 and 142 -> 162 VGPRs, three waves per SIMD as before.
+// The other form of the subtraction, the score accumulator initialised to -m from a register tile, costs no MFMA but 85 vector
+// instructions: hipcc ties the MFMA's destination to its C operand and copies the tile with eight v_mov_b64 per tile.  Measured
+// equal within 0.5 % (stage 1: 0.895 against 0.900 ms; parent 0.992), so the form with fewer vector instructions stays.
+// DESIGN.md 5b and profiles/attention_stale_max.log have the counters and the step-level figures.
+// Precision.  After a rescale m = ceil(exact running maximum), later the maximum may rise by up to kTau before the next one:
+// m - 1 < running maximum <= m + kTau.  The row's largest probability is therefore in (2^(kPre - 1), 2^15] operand units where
+// the exact form has it at 2^15 exactly: at worst kTau + 1 bits of pre-scale are given up, none of the top (p <= 2^15 <
+// 65 504 always).  kTau = 4 (kPre = 11), from a numpy emulation of this loop (tools/attention_stale_rate.py, figures in
+// profiles/attention_stale_max.log): on standard normal q, k (the tests' inputs) the rare path runs in 0.2-0.3 % of the
+// wave-tiles behind the first at kTau = 4, 1.5-9 % at 3, 5-31 % at 2, and at 6 or 8 there is nothing left to win for the two
+// or four further bits; the bench model's stage-1 / stage-2 q, k (random weights: a flat softmax) never rescale at any kTau,
+// and scores of +-90 bits (the tests' x 8 inputs) rescale in 60-100 % of the wave-tiles at every kTau.  What it costs: p - f16(p) is
+// a normal f16 for p >= 2^-3, so with the exact maximum every probability above 2^-18 of the row maximum keeps 22 bits; here
+// that is guaranteed above 2^-13 (2^-(17 - kTau)) and typically holds above 2^-17.  Below, the absolute floor 2^-25 operand
+// units (f16 subnormals are kept) is worth < 2^-35 of the row maximum instead of < 2^-40: 2 048 such keys together stay
+// below float32 rounding of the row sum.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -213,6 +247,58 @@ __device__ __forceinline__ void split8(const float* x, h8& hi, h8& lo)
     for (int i = 0; i < 4; ++i) { unsigned h, l; split_pair(x[2 * i], x[2 * i + 1], h, l); H[i] = h; L[i] = l; }
     hi = __builtin_bit_cast(h8, H); lo = __builtin_bit_cast(h8, L);
 }
+// ---- the stale-maximum softmax step shared by both split kernels (see the header): identical arithmetic, identical bits
+constexpr float kTau = 4.0f;                 // headroom of the stale maximum, log2 units
+constexpr float kPre = 15.0f - kTau;         // probability pre-scale exponent of the stale-maximum loop
+constexpr float kStaleLimit = 2048.0f;       // integers up to here are exact in f16
+struct stale_max { float m, l; u32x4 mb; bool oor; };       // stale maximum, this lane half's partial row sum, B fragment of the -m slice
+// (the empty asm statements make the two fragments' constant registers opaque: hipcc otherwise rebuilds them with five v_mov per tile)
+__device__ __forceinline__ h8 stale_ones() { u32x4 o = {0x3c00u, 0u, 0u, 0u}; asm volatile("" : "+v"(o)); return __builtin_bit_cast(h8, o); }
+__device__ __forceinline__ unsigned stale_slice(float m, int hk)
+{
+    return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(hk ? kPre : -m, 0.f));       // integers: exact
+}
+__device__ __forceinline__ void stale_init(stale_max& st, int hk)
+{
+    st.m = 0.f; st.l = 0.f; st.oor = false;
+    st.mb = u32x4{stale_slice(0.f, hk), 0u, 0u, 0u};
+    asm volatile("" : "+v"(st.mb));
+}
+// sm, scx: the score accumulators with the -m slice already in sm.  Leaves p = exp2(s - m + kPre) for the (possibly moved) m.
+__device__ __forceinline__ void stale_softmax(const f32x16& sm, const f32x16& scx, bool first, int hk, stale_max& st, f32x16& om, f32x16& oc, float* p)
+{
+    float s[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) s[r] = fmaf(scx[r], kLoInv, sm[r]);
+    float mt = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+#pragma unroll
+    for (int r = 4; r < 16; r += 4) mt = fmaxf(mt, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
+    if (first || __builtin_amdgcn_ballot_w64(mt > 15.0f) != 0) {          // wave-uniform
+        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+        float d = __builtin_ceilf(mt - kPre);                              // the tile's ceil(max s) - m
+        if (!first) d = fmaxf(d, 0.f);                                     // (the first tile sets m, down as well as up)
+        float mn = st.m + d;
+        if (!(__builtin_fabsf(mn) <= kStaleLimit)) {                       // also NaN / Inf: the block goes to the exact loop
+            st.oor = true;
+            mn = st.m; d = 0.f;                                            // (whatever this pass computes from here on is discarded)
+        }
+        if (!first) {
+            const float alpha = __builtin_ldexpf(1.0f, -(int)d);           // exact, 0 once d passes the exponent range
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { om[r] *= alpha; oc[r] *= alpha; }
+            st.l *= alpha;
+        }
+        st.m = mn;
+        st.mb[0] = stale_slice(mn, hk);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[r] -= d;
+    }
+    float ls = p[0] = __builtin_amdgcn_exp2f(s[0]);
+#pragma unroll
+    for (int r = 1; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r]); ls += p[r]; }
+    st.l += ls;
+}
+
 // k-slot of tile key `key` in the PV product: element j of lane half h of k-step s is accumulator row
 // 16 s + 8 (j >> 2) + 4 h + (j & 3) (the C/D layout read as an operand); slot = 16 s + 8 h + j
 __device__ __forceinline__ constexpr int pv_slot(int key)
@@ -253,7 +339,8 @@ __device__ __forceinline__ h8 pack8_bf16(const float* x)
 // returns true (block-uniform) when the optimistic pass met an out-of-range operand and stored nothing.
 // BF16: ONE bf16 MFMA per product tile (q, k, v and the probabilities rounded to bf16, float32 accumulation and softmax):
 // BASELINE config 5's bf16 MFMA path; no range guard (bf16 has float32's exponent range).
-template <bool SCALED, bool BF16 = false>
+// STALE: the stale-integer-maximum loop (in-range float32-grade pass only); sMax[3] reports a query whose maximum left its range.
+template <bool SCALED, bool BF16 = false, bool STALE = false>
 __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                                 float* __restrict__ out, int nq, int nkv, int heads, float scale_log2e, int kvp,
                                                 _Float16 (*sK)[TK * SROW], _Float16 (*sV)[D * SROW], unsigned* sMax, const attn_scales sc)
@@ -335,6 +422,9 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
 #pragma unroll
     for (int r = 0; r < 16; ++r) { om[r] = 0.f; oc[r] = 0.f; }
     float m_run = -1e30f, l_run = 0.f;
+    stale_max st;
+    stale_init(st, hk);
+    const h8 ones = stale_ones();
     const int a_off = li * SROW + 8 * hk;
 
     for (int t = 0; t < ntiles; ++t) {
@@ -344,6 +434,7 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
         f32x16 sm, scx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sm[r] = 0.f; scx[r] = 0.f; }
+        if (STALE) sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, __builtin_bit_cast(h8, st.mb), sm, 0, 0, 0);       // - m + kPre
         if (BF16) {
             sm = MFMA_BF(kh0, qh[0], sm);
             sm = MFMA_BF(kh1, qh[1], sm);
@@ -358,28 +449,33 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
         const h8* vr = reinterpret_cast<const h8*>(&sV[buf][a_off]);
         const h8 vh0 = vr[0], vh1 = vr[2], vl0 = vr[4], vl1 = vr[6];
         // ---- online softmax, one query per lane
-        float s[16];
+        float p[16];
+        if (STALE) {
+            stale_softmax(sm, scx, t == 0, hk, st, om, oc, p);
+        } else {
+            float s[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = fmaf(scx[r], kLoInv, sm[r]);
-            if (SCALED) s[r] = s[r] * sc.bq * sc.bk;
-        }
-        float mt = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+            for (int r = 0; r < 16; ++r) {
+                s[r] = fmaf(scx[r], kLoInv, sm[r]);
+                if (SCALED) s[r] = s[r] * sc.bq * sc.bk;
+            }
+            float mt = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
 #pragma unroll
-        for (int r = 4; r < 16; r += 4) mt = fmaxf(mt, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        const float m_sh = m_new - 15.0f;                  // probabilities scaled by 2^15 (see the header)
-        float p[16], ls = 0.f;
+            for (int r = 4; r < 16; r += 4) mt = fmaxf(mt, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
+            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            const float m_new = fmaxf(m_run, mt);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            const float m_sh = m_new - 15.0f;                  // probabilities scaled by 2^15 (see the header)
+            float ls = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r] - m_sh); ls += p[r]; }
-        ls += __shfl_xor(ls, 32, 64);
-        l_run = l_run * alpha + ls;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+            for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r] - m_sh); ls += p[r]; }
+            ls += __shfl_xor(ls, 32, 64);
+            l_run = l_run * alpha + ls;
+            m_run = m_new;
+            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { om[r] *= alpha; oc[r] *= alpha; }
+                for (int r = 0; r < 16; ++r) { om[r] *= alpha; oc[r] *= alpha; }
+            }
         }
         // ---- O^T += V^T P^T: the probability tile, split, is the B operand: registers 8 s .. 8 s + 7 = k-step s
         // The probabilities are pre-scaled to (0, 2^15], so their low parts need no scaling: p - f16(p) is a normal f16
@@ -422,9 +518,12 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
         if (qmax >= kSplitLimit) atomicMax(&sMax[0], __builtin_bit_cast(unsigned, qmax));
         if (kmax >= kSplitLimit) atomicMax(&sMax[1], __builtin_bit_cast(unsigned, kmax));
         if (vmax >= kSplitLimit) atomicMax(&sMax[2], __builtin_bit_cast(unsigned, vmax));
+        if (STALE && st.oor) sMax[3] = 1u;
         __syncthreads();
         if ((sMax[0] | sMax[1] | sMax[2]) != 0u) return true;
+        if (STALE && sMax[3] != 0u) return true;
     }
+    if (STALE) l_run = st.l + __shfl_xor(st.l, 32, 64);        // the two halves of a query: joined once
     const int qi = q0 + li;
     if (qi < nq) {
         const float inv = 1.0f / l_run;
@@ -454,10 +553,14 @@ void attention_d32_split_kernel(const float* __restrict__ q, const float* __rest
 {
     __shared__ __attribute__((aligned(16))) _Float16 sK[2][TK * SROW];      // [key][hi d 0..31 | lo d 0..31]
     __shared__ __attribute__((aligned(16))) _Float16 sV[2][D * SROW];       // [d][hi slot 0..31 | lo slot 0..31]
-    __shared__ unsigned sMax[3];                                             // max |q*scale|, |k|, |v| bits, when >= 2^15
-    if (threadIdx.x < 3) sMax[threadIdx.x] = 0u;                             // ordered by the pass's first barrier
+    __shared__ unsigned sMax[4];                                             // max |q*scale|, |k|, |v| bits, when >= 2^15; [3]: a stale maximum left its range
+    if (threadIdx.x < 4) sMax[threadIdx.x] = 0u;                             // ordered by the pass's first barrier
     const attn_scales one = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-    if (!attn_split_pass<false>(q, k, v, out, nq, nkv, heads, scale_log2e, kvp, sK, sV, sMax, one)) return;
+    if (!attn_split_pass<false, false, true>(q, k, v, out, nq, nkv, heads, scale_log2e, kvp, sK, sV, sMax, one)) return;
+    if ((sMax[0] | sMax[1] | sMax[2]) == 0u) {                               // operands in range, a score maximum beyond +-2048: the exact-maximum loop
+        attn_split_pass<false>(q, k, v, out, nq, nkv, heads, scale_log2e, kvp, sK, sV, sMax, one);
+        return;
+    }
     const int eq = guard_exponent(sMax[0]), ek = guard_exponent(sMax[1]), ev = guard_exponent(sMax[2]);
     auto p2 = [](int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); };            // |e| <= 114
     const attn_scales sc = {p2(-eq), p2(-ek), p2(-ev), p2(eq), p2(ek), p2(ev)};
@@ -533,8 +636,9 @@ void attn_kv_image_kernel(const float* __restrict__ k, const float* __restrict__
     }
 }
 
-// SCALED: some operand carries a power-of-two scale (sc); QGUARD: track max|q| and report a block whose q left the range
-template <bool SCALED, bool QGUARD>
+// SCALED: some operand carries a power-of-two scale (sc); QGUARD: track max|q| and report a block whose q left the range;
+// STALE: the stale-integer-maximum loop (unscaled pass only), sMax[1] reports a query whose maximum left its range
+template <bool SCALED, bool QGUARD, bool STALE>
 __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q, const _Float16* __restrict__ img_bh, float* __restrict__ out,
                                                     int nq, int nkv, int heads, float scale_log2e, _Float16 (*sKV)[IMG_TILE_HALFS],
                                                     unsigned* sMax, const attn_scales sc)
@@ -581,6 +685,9 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
 #pragma unroll
     for (int r = 0; r < 16; ++r) { om[r] = 0.f; oc[r] = 0.f; }
     float m_run = -1e30f, l_run = 0.f;
+    stale_max st;
+    stale_init(st, hk);
+    const h8 ones = stale_ones();
     const int a_off = li * SROW + 8 * hk;
 
     for (int t = 0; t < ntiles; ++t) {
@@ -591,6 +698,7 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
         f32x16 sm, scx;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sm[r] = 0.f; scx[r] = 0.f; }
+        if (STALE) sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(ones, __builtin_bit_cast(h8, st.mb), sm, 0, 0, 0);       // - m + kPre
         sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh0, qh[0], sm, 0, 0, 0);
         scx = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh0, ql[0], scx, 0, 0, 0);
         sm = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh1, qh[1], sm, 0, 0, 0);
@@ -599,28 +707,33 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
         scx = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl1, qh[1], scx, 0, 0, 0);
         const h8* vr = reinterpret_cast<const h8*>(&sKV[buf][TK * SROW + a_off]);
         const h8 vh0 = vr[0], vh1 = vr[2], vl0 = vr[4], vl1 = vr[6];
-        float s[16];
+        float p[16];
+        if (STALE) {
+            stale_softmax(sm, scx, t == 0, hk, st, om, oc, p);
+        } else {
+            float s[16];
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = fmaf(scx[r], kLoInv, sm[r]);
-            if (SCALED) s[r] = s[r] * sc.bq * sc.bk;
-        }
-        float mt = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
+            for (int r = 0; r < 16; ++r) {
+                s[r] = fmaf(scx[r], kLoInv, sm[r]);
+                if (SCALED) s[r] = s[r] * sc.bq * sc.bk;
+            }
+            float mt = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
 #pragma unroll
-        for (int r = 4; r < 16; r += 4) mt = fmaxf(mt, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
-        mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
-        const float m_new = fmaxf(m_run, mt);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        const float m_sh = m_new - 15.0f;
-        float p[16], ls = 0.f;
+            for (int r = 4; r < 16; r += 4) mt = fmaxf(mt, fmaxf(fmaxf(s[r], s[r + 1]), fmaxf(s[r + 2], s[r + 3])));
+            mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
+            const float m_new = fmaxf(m_run, mt);
+            const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+            const float m_sh = m_new - 15.0f;
+            float ls = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r] - m_sh); ls += p[r]; }
-        ls += __shfl_xor(ls, 32, 64);
-        l_run = l_run * alpha + ls;
-        m_run = m_new;
-        if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
+            for (int r = 0; r < 16; ++r) { p[r] = __builtin_amdgcn_exp2f(s[r] - m_sh); ls += p[r]; }
+            ls += __shfl_xor(ls, 32, 64);
+            l_run = l_run * alpha + ls;
+            m_run = m_new;
+            if (__builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) { om[r] *= alpha; oc[r] *= alpha; }
+                for (int r = 0; r < 16; ++r) { om[r] *= alpha; oc[r] *= alpha; }
+            }
         }
         h8 ph0, pl0, ph1, pl1;
         split8_unscaled(p, ph0, pl0);
@@ -637,9 +750,12 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
 
     if (QGUARD) {
         if (qmax >= kSplitLimit) atomicMax(&sMax[0], __builtin_bit_cast(unsigned, qmax));
+        if (STALE && st.oor) sMax[1] = 1u;
         __syncthreads();
         if (sMax[0] != 0u) return true;
+        if (STALE && sMax[1] != 0u) return true;
     }
+    if (STALE) l_run = st.l + __shfl_xor(st.l, 32, 64);        // the two halves of a query: joined once
     const int qi = q0 + li;
     if (qi < nq) {
         const float inv = 1.0f / l_run;
@@ -660,21 +776,25 @@ void attention_d32_split_img_kernel(const float* __restrict__ q, const _Float16*
                                     float* __restrict__ out, int nq, int nkv, int heads, float scale_log2e)
 {
     __shared__ __attribute__((aligned(16))) _Float16 sKV[2][IMG_TILE_HALFS];
-    __shared__ unsigned sMax[1];
+    __shared__ unsigned sMax[2];                                     // max |q*scale| bits when >= 2^15; [1]: a stale maximum left its range
     const int h = blockIdx.y, b = blockIdx.z;
-    if (threadIdx.x == 0) sMax[0] = 0u;                              // ordered by the pass's first barrier
+    if (threadIdx.x < 2) sMax[threadIdx.x] = 0u;                     // ordered by the pass's first barrier
     const _Float16* img_bh = img + ((size_t)b * heads + h) * (size_t)(nkv / TK) * IMG_TILE_HALFS;
     const int ek = exps[((size_t)b * heads + h) * 2], ev = exps[((size_t)b * heads + h) * 2 + 1];
     auto p2 = [](int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); };
     attn_scales sc = {1.f, p2(-ek), p2(-ev), 1.f, p2(ek), p2(ev)};
     bool redo;
-    if ((ek | ev) == 0) redo = attn_split_pass_img<false, true>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
-    else redo = attn_split_pass_img<true, true>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
+    if ((ek | ev) == 0) redo = attn_split_pass_img<false, true, true>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
+    else redo = attn_split_pass_img<true, true, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
     if (!redo) return;
+    __syncthreads();
+    if (sMax[0] == 0u) {                                             // q in range, a score maximum beyond +-2048: the exact-maximum loop
+        attn_split_pass_img<false, false, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
+        return;
+    }
     const int eq = guard_exponent(sMax[0]);
     sc.sq = p2(-eq); sc.bq = p2(eq);
-    __syncthreads();
-    attn_split_pass_img<true, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
+    attn_split_pass_img<true, false, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
 }
 
 __global__ __launch_bounds__(AT, 2)

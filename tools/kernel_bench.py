@@ -369,6 +369,7 @@ def main():
         qh, kh, vh = (t.view(B, -1, nh, 32).transpose(1, 2) for t in (qa, ka, va))
         cases[name + " [torch SDPA]"] = (lambda: torch.nn.functional.scaled_dot_product_attention(qh, kh, vh, scale=32 ** -0.5), "mfma", fl)
     attn_case("attention d32 stage1 (131072 q x 2048 k, 1 head)", 1, (H // 4) * (W // 4), (H // 32) * (W // 32))
+    attn_case("attention d32 stage2 (32768 q x 2048 k, 2 heads)", 2, (H // 8) * (W // 8), (H // 32) * (W // 32))
     attn_case("attention d32 stage3 (8192 q x 2048 k, 5 heads)", 5, (H // 16) * (W // 16), (H // 32) * (W // 32))
 
     a_lo = torch.randn(B, H // 16, W // 16, 256, device=dev); hi48 = torch.randn(B, H // 4, W // 4, 48, device=dev); w304 = torch.randn(9, 304, device=dev)
