@@ -1,4 +1,5 @@
-"""ctypes binding of ``libawseg_hip.so`` (the C ABI declared in ``include/awseg.h``).
+"""ctypes binding of ``libawseg_hip.so`` (the C ABI declared in ``include/awseg.h`` and, for the input-restoration entry
+points, in ``include/awseg_restore.h``).
 
 This is the only door between the Python host code and the HIP kernels.  There is no CPU
 fallback anywhere behind it: if the library is missing or a kernel is asked to run on
@@ -146,6 +147,14 @@ SIGNATURES = {
     "awseg_image_quality": (c_i, [c_p, c_p, c_i, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_p, c_p, c_f, c_f, c_p, c_p, c_i, c_p, c_p, c_p]),
 }
 
+# name -> (restype, argtypes); every symbol include/awseg_restore.h declares.  A table of its own, bound by lib() like the one above
+# and called through the same call() / try_call(): the extension header is hashed on its own (awseg_restore_header_hash).
+EXTENSION_SIGNATURES = {
+    "awseg_restore_header_hash": (C.c_uint64, []),
+    "awseg_dehaze_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "awseg_dehaze": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+}
+
 
 class AwsegError(RuntimeError):
     pass
@@ -164,9 +173,10 @@ def lib() -> C.CDLL:
                 "adverse_weather_semantic_segmentation_robustness_benchmark_amd.csrc.build` "
                 "(there is no CPU fallback for the HIP hot path)")
         handle = C.CDLL(str(LIB_PATH))
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)          # AttributeError here == header/library drift
-            fn.restype, fn.argtypes = res, args
+        for table in (SIGNATURES, EXTENSION_SIGNATURES):
+            for name, (res, args) in table.items():
+                fn = getattr(handle, name)      # AttributeError here == header/library drift
+                fn.restype, fn.argtypes = res, args
         # a library built from another state of include/awseg.h takes other arguments than these bindings pass: refuse it
         # (a stale .so next to newer sources is exactly how that happens; the symbols above may all still exist)
         header = LIB_PATH.parent.parent / "include" / "awseg.h"
@@ -176,6 +186,13 @@ def lib() -> C.CDLL:
             if built != header_hash():
                 raise AwsegError(f"{LIB_PATH} was built from another include/awseg.h than the one beside it (ABI drift): rebuild it with "
                                  "`python -m adverse_weather_semantic_segmentation_robustness_benchmark_amd.csrc.build`")
+        extension = header.with_name("awseg_restore.h")
+        built = int(handle.awseg_restore_header_hash())
+        if built and extension.exists():
+            from .csrc.build import RESTORE_HEADER, header_hash
+            if built != header_hash(RESTORE_HEADER):
+                raise AwsegError(f"{LIB_PATH} was built from another include/awseg_restore.h than the one beside it (ABI drift): rebuild "
+                                 "it with `python -m adverse_weather_semantic_segmentation_robustness_benchmark_amd.csrc.build`")
         _lib = handle
     return _lib
 

@@ -17,22 +17,25 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent
 PKG = CSRC.parent
 LIB = PKG / "libawseg_hip.so"
-SOURCES = ["core.hip", "metrics.hip", "weather.hip", "loss.hip", "heads.hip", "backbone.hip", "depth.hip", "wino.hip", "gemm.hip", "attn.hip", "gemm_split.hip", "gemm_split3.hip", "wino_split.hip", "depthfuse.hip", "mixffn.hip", "dwtrain.hip", "bntrain.hip", "smallops.hip", "calib.hip", "consistency.hip", "deptheval.hip", "failure.hip", "boundary.hip", "bootstrap.hip", "strata.hip", "quality.hip", "segments.hip", "weightgrid.hip"]
+SOURCES = ["core.hip", "metrics.hip", "weather.hip", "loss.hip", "heads.hip", "backbone.hip", "depth.hip", "wino.hip", "gemm.hip", "attn.hip", "gemm_split.hip", "gemm_split3.hip", "wino_split.hip", "depthfuse.hip", "mixffn.hip", "dwtrain.hip", "bntrain.hip", "smallops.hip", "calib.hip", "consistency.hip", "deptheval.hip", "failure.hip", "boundary.hip", "bootstrap.hip", "strata.hip", "quality.hip", "segments.hip", "weightgrid.hip", "dehaze.hip"]
 ARCH = "gfx950"
 # per-file extras.  wino.hip: the SLP vectoriser packs the scalar inverse transform of the fused-head epilogue into
 # v_pk_add_f32 fed by ~220 v_mov (and spills); the kernel packs by hand where adjacent registers make it free.
 HEADER = PKG.parent / "include" / "awseg.h"
+RESTORE_HEADER = PKG.parent / "include" / "awseg_restore.h"     # the extension entry points (dehaze.hip), hashed on their own
 
 
-def header_hash() -> int:
+def header_hash(path: Path = HEADER) -> int:
     """60 bits of sha256(include/awseg.h): compiled into the library (awseg_header_hash) and compared by _native.lib() when it loads
-    it, so that a library built from another state of the ABI is refused instead of being called with the wrong arguments."""
+    it, so that a library built from another state of the ABI is refused instead of being called with the wrong arguments.
+    `path` = RESTORE_HEADER: the same for include/awseg_restore.h (awseg_restore_header_hash)."""
     import hashlib
-    return int(hashlib.sha256(HEADER.read_bytes()).hexdigest()[:15], 16)
+    return int(hashlib.sha256(path.read_bytes()).hexdigest()[:15], 16)
 
 
 EXTRA_FLAGS = {"attn.hip": ["-DAWSEG_ATTN_SPLIT_WAVES=" + os.environ.get("AWSEG_ATTN_SPLIT_WAVES", "2")], "wino.hip": ["-fno-slp-vectorize"], "wino_split.hip": ["-fno-slp-vectorize"],
-               "core.hip": ["-DAWSEG_HEADER_HASH=0x%xULL" % header_hash()]}
+               "core.hip": ["-DAWSEG_HEADER_HASH=0x%xULL" % header_hash()],
+               "dehaze.hip": ["-DAWSEG_RESTORE_HEADER_HASH=0x%xULL" % header_hash(RESTORE_HEADER)]}
 
 
 def hipcc() -> str:
@@ -60,7 +63,7 @@ def needs_build() -> bool:
     if not STAMP.exists() or STAMP.read_text() != _flag_stamp():
         return True
     t = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [HEADER]
+    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [HEADER, RESTORE_HEADER]
     return any(d.stat().st_mtime > t for d in deps)
 
 

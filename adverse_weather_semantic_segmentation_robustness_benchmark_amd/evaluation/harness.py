@@ -28,10 +28,10 @@ import torch.nn.functional as F
 from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
-from .metrics import (ConfidenceCalibration, RobustnessMetrics, bootstrap_metrics_from_replicates, boundary_metrics_from_stats,
-                      calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats, failure_metrics_from_stats, iou_from_counts,
-                      quality_metrics_from_stats, segment_metrics_from_stats, segment_options, severity_sweep_results,
-                      weight_grid_metrics_from_stats)
+from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMetrics, bootstrap_metrics_from_replicates,
+                      boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats,
+                      failure_metrics_from_stats, iou_from_counts, quality_metrics_from_stats, restoration_metrics_from_stats,
+                      segment_metrics_from_stats, segment_options, severity_sweep_results, weight_grid_metrics_from_stats)
 
 logger = logging.getLogger(__name__)
 
@@ -280,6 +280,47 @@ def check_quality_budget(terms: int) -> None:
     _check_budget(terms, ops.IQ_TERM_BUDGET, "image-quality counters hold {} pixel-channels")
 
 
+RESTORATION_KEYS = ("radius", "omega", "t_min", "airlight_min", "refine")
+RESTORATION_REFINE = {"opening": 1, "none": 0}
+
+
+def restoration_option(config, images=None):
+    """`evaluation.restoration` (default off): 'dark_channel', or a dict with any of `radius` (an integer in [1, 15], default 7),
+    `omega`, `t_min`, `airlight_min` (numbers in (0, 1], defaults 0.95, 0.1, 0.1) and `refine` ('opening', the default, or 'none'):
+    every selected frame is dehazed by the dark-channel prior and scored a second time.
+    `evaluation.restoration_conditions`: the weather conditions whose frames are restored, a list of names; absent: all of them,
+    'clean' included (a blind front-end does not know the weather); checked also when the option is off.  `images`, when given, is
+    a batch of frames: they must be float32 [B, 3, H, W].
+    -> None when absent, else {'radius', 'omega', 't_min', 'airlight_min', 'refine' (0 / 1), 'conditions' (a list, or None = all)}."""
+    names = _cfg(config, "evaluation.restoration_conditions", None)
+    if names is not None:
+        if isinstance(names, (str, bytes, dict)) or not isinstance(names, (list, tuple)) or not names \
+                or any(not isinstance(n, str) or not n for n in names):
+            raise ValueError(f"evaluation.restoration_conditions is a non-empty list of condition names, got {names!r}")
+        names = [str(n) for n in names]
+    spec = _cfg(config, "evaluation.restoration", None)
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec != "dark_channel":
+            raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict of its parameters, got {spec!r}")
+        spec = {}
+    if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS):
+        raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict with keys among {list(RESTORATION_KEYS)}, got {spec!r}")
+    kw = {k: v for k, v in spec.items() if k != "refine"}
+    refine = spec.get("refine", "opening")
+    if not isinstance(refine, str) or refine not in RESTORATION_REFINE:
+        raise ValueError(f"evaluation.restoration.refine is 'opening' or 'none', got {refine!r}")
+    try:
+        opt = ops.dehaze_parameters(refine=RESTORATION_REFINE[refine], **kw)
+    except ValueError as e:
+        raise ValueError(f"evaluation.restoration: {e}") from None
+    if images is not None:
+        check_frames("restoration", images)
+    opt["conditions"] = names
+    return opt
+
+
 BOOTSTRAP_MAX_REPLICATES = 65536
 
 
@@ -342,6 +383,7 @@ COUNTERS = (
     ("quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality counters"),
     ("segments", ("stats", "oob"), None, None, "prediction map value outside [0, num_classes) in the segment counters"),
     ("weight_grid", ("stats",), None, None, None),
+    ("restoration", ("counts", "oob", "stats"), None, None, "label outside [0, num_classes) in the confusion counters of the restored frames"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
     ("paired", ("stats", "oob", "sources"), None, None, "prediction map value outside [0, num_classes) in the consistency counters"),
 )
@@ -374,7 +416,7 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None, change=None, quality=None, segments=None, weight_grid=None):
+                 boundary=None, bootstrap=None, change=None, quality=None, segments=None, weight_grid=None, restoration=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -473,6 +515,16 @@ class EvalState:
             self.weight_grid = {"pairs": pairs, "configured_index": int(weight_grid["configured_index"]),
                                 "condition": weight_grid["condition"],
                                 "stats": ops.new_weight_grid_stats(1 + len(conditions), pairs.shape[0], metrics.num_classes, device)}
+        # restored frames (off unless restoration = restoration_option(config)): a SECOND confusion accumulator over this run's slots
+        # for the forward on the dehazed frames, and the dehazing counters int64 [slot, AWSEG_DEHAZE_ROW].  'conditions': the weather
+        # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
+        self.restoration = None
+        if restoration is not None:
+            params = ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS})
+            acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
+            self.restoration = {"params": params, "acc": acc, "counts": acc.counts, "oob": acc.oob,
+                                "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]},
+                                "stats": ops.new_dehaze_stats(device, 1 + len(conditions))}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -593,6 +645,25 @@ class EvalState:
             rows = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
         twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
         ops.image_quality(images, twins, rows, q["stats"], cond=cond, oob=q["oob"])
+
+    def update_restoration(self, model, images, labels, kinds, cond) -> None:
+        """The batch's frames of the selected weather conditions (`kinds`: the loader's names, before a sweep's slot names), dehazed,
+        through one more forward into the second confusion accumulator.  Nothing else sees the restored frames."""
+        rs = self.restoration
+        check_frames("restoration", images)
+        keep = [i for i, k in enumerate(kinds) if rs["conditions"] is None or str(k) in rs["conditions"]]
+        if not keep:
+            return
+        if len(keep) < images.shape[0]:
+            idx = torch.tensor(keep, dtype=torch.int64).to(images.device, non_blocking=True)
+            images, labels, cond = images.index_select(0, idx), labels.index_select(0, idx), cond.index_select(0, idx)
+        restored, _ = ops.dehaze(images, rs["stats"], cond, **rs["params"])
+        if self.auroc is not None:                                    # the ensemble
+            model.forward_eval(restored, labels, rs["counts"], rs["oob"], cond, want_logits=False, want_pred=False, stats=None)
+        else:
+            logits = model(restored)["segmentation"].float().contiguous()
+            ops.combine_argmax_confusion(logits, None, 3, want_logits=False, label=labels.contiguous(), counts=rs["counts"],
+                                         oob=rs["oob"], cond=cond)
 
     def update_change(self, images, pred, labels, frame_ref, cond, num_classes: int) -> None:
         """A variant batch is split into change strata against its sources' clean frames and counted against their clean maps.
@@ -734,6 +805,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
     batch's prediction map is kept (clean) or compared with its sources' clean maps (variants).
     Depth metrics (st.depth): `depth` is the batch's target float32 [B, H, W]; the depth maps are scored in one pass and not kept."""
     pred_out = rows = None                                            # rows: st.frame_ref of a sweep's batch
+    kinds = conds                                                     # the loader's names (a sweep renames conds to its slots)
     if st.sweep is not None:
         if sources is None or severity is None:
             raise ValueError("a severity sweep needs the paired loader's 'source' and 'severity' for every batch")
@@ -838,6 +910,8 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         if st.change is not None:
             st.update_change(images, pred_out, labels, rows, cond, metrics.num_classes)
         st.update_consistency(pred_out, labels, sources, rows, cond, metrics.num_classes)
+    if st.restoration is not None:                                    # after everything above: one more forward, on the dehazed frames
+        st.update_restoration(model, images, labels, kinds, cond)
     st.samples += images.size(0)
 
 
@@ -866,7 +940,7 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    depth=depth_options(config), failure=failure_option(config),
                    boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config),
                    quality=quality_options(config), segments=segment_option(config),
-                   weight_grid=weight_grid_option(config, model))
+                   weight_grid=weight_grid_option(config, model), restoration=restoration_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -945,6 +1019,11 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         # after the sweep results: the matched-damage keys read miou_clean and miou_<kind>_s<j>
         results.update(quality_metrics_from_stats(q["stats"].cpu().numpy(), st.acc.conditions, st.sweep.kinds, st.sweep.levels, results,
                                                   q["targets"], metrics.compute_robustness_degradation_ratio))
+    if st.restoration is not None:
+        rs = st.restoration
+        results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), rs["stats"].cpu().numpy(),
+                                                      st.acc.conditions, metrics.num_classes, **sweep_kw,
+                                                      degradation=metrics.compute_robustness_degradation_ratio))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -755,6 +755,78 @@ def quality_metrics_from_stats(stats, slots: List[str], kinds, levels: int, resu
     return res
 
 
+def restoration_metrics_from_stats(restored, plain, stats, conditions: List[str], num_classes: int, kinds=None, levels: int = 0,
+                                   degradation=None) -> Dict[str, float]:
+    """Result keys of the dehazing front-end.  `restored`, `plain`: the confusion counters int64
+    [1 + len(conditions), C * C] of the forward on the restored frames and of the ordinary one; `stats`: the dehazing counters int64
+    [1 + len(conditions), AWSEG_DEHAZE_ROW] (include/awseg_restore.h); slot 0 = every restored frame, slot 1 + k = conditions[k].
+    Host only, float64 on exact integer sums; every value a float.  With <n> a condition (under a severity sweep its slots
+    'clean', '<kind>_s<j>', and each '<kind>' from the summed counters of its levels), for every <n> with restored frames:
+      miou_<n>_restored                         mIoU of the restored frames, as miou_<n> is of the plain ones
+      restoration_gain_<n>                      miou_<n>_restored - miou_<n> on the same frames; not clamped: a loss is negative
+      airlight_<n>                              the mean over the three channels of the frames' mean airlight
+      transmission_mean_<n>                     the mean transmission t over the restored pixels
+    over slot 0: overall_miou_restored, mean_restoration_gain (against the plain counters summed over the conditions that have
+    restored frames: the same frames when every frame carries a condition of the list), mean_airlight, mean_transmission;
+      restoration_clean_cost                    miou_clean - miou_clean_restored: what the front-end costs where nothing was wrong
+      robustness_degradation_<n>_restored       degradation(plain miou_clean, miou_<n>_restored), <n> != clean
+      restoration_nonfinite_values, restoration_airlight_floored_frames    slot 0, only when non-zero
+    A ratio without a denominator is absent, not 0: no restored frame, no key.  degradation:
+    RobustnessMetrics.compute_robustness_degradation_ratio unless given."""
+    conditions, C = list(conditions), int(num_classes)
+    n = 1 + len(conditions)
+    conf = {}
+    for what, a in (("restored", restored), ("plain", plain)):
+        a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.int64)
+        if a.shape != (n, C * C):
+            raise ValueError(f"{what} confusion counters must be int64 [{n}, {C * C}], got {a.shape}")
+        conf[what] = a
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.shape != (n, ops.DEHAZE_ROW):
+        raise ValueError(f"dehaze stats must be int64 [{n}, {ops.DEHAZE_ROW}], got {raw.shape}")
+    degradation = degradation or RobustnessMetrics().compute_robustness_degradation_ratio
+
+    def miou(counts) -> Optional[float]:
+        return float(iou_from_counts(torch.from_numpy(counts.copy()), C)["mean_iou"]) if counts.sum() > 0 else None
+
+    named = [(name, [1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        named.append((kind, [1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels) + 1)]))
+    res: Dict[str, float] = {}
+    clean_plain = miou(conf["plain"][1 + conditions.index("clean")]) if "clean" in conditions else None
+    same_frames = np.zeros(C * C, dtype=np.int64)                           # plain counters of the conditions that were restored
+    rows = [(None, conf["restored"][0], None, raw[0])]
+    for name, idx in named:
+        rows.append((name, conf["restored"][idx].sum(0), conf["plain"][idx].sum(0), raw[idx].sum(0)))
+        if len(idx) == 1 and conf["restored"][idx[0]].sum() > 0:
+            same_frames += conf["plain"][idx[0]]
+    for name, r_counts, p_counts, row in rows:
+        dec = {f: int(v) for f, v in ops.dehaze_stats_to_numpy(row).items()}
+
+        def key(metric, name=name):
+            return f"mean_{metric}" if name is None else f"{metric}_{name}"
+        r = miou(r_counts)
+        if r is not None:
+            res["overall_miou_restored" if name is None else f"miou_{name}_restored"] = r
+            p = miou(same_frames if name is None else p_counts)
+            if p is not None:
+                res[key("restoration_gain")] = r - p
+            if name is not None and name != "clean" and clean_plain is not None:
+                res[f"robustness_degradation_{name}_restored"] = float(degradation(clean_plain, r))
+        if dec["frames"] > 0:
+            res[key("airlight")] = float(sum(dec[f"sum_airlight_{c}"] for c in range(3)) * ops.DEHAZE_UNIT / (3.0 * dec["frames"]))
+        if dec["pixels"] > 0:
+            res["mean_transmission" if name is None else f"transmission_mean_{name}"] = float(dec["sum_transmission"] * ops.DEHAZE_UNIT
+                                                                                              / dec["pixels"])
+    if clean_plain is not None and "miou_clean_restored" in res:
+        res["restoration_clean_cost"] = clean_plain - res["miou_clean_restored"]
+    for k, field in (("restoration_nonfinite_values", "nonfinite_values"), ("restoration_airlight_floored_frames", "airlight_floored_frames")):
+        v = int(ops.dehaze_stats_to_numpy(raw[0])[field])
+        if v:
+            res[k] = float(v)
+    return res
+
+
 def weight_grid_row_miou(inter, lab, prd) -> Optional[float]:
     """mIoU from the marginals of one grid point (int64 [C] each: hits, labelled, predicted): iou_from_counts' expressions (int64 /
     int64 true-divide to float32, mean over the classes with a non-empty union), so the configured point reproduces the pooled

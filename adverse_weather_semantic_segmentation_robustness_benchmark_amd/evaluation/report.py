@@ -58,9 +58,35 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += change_section(results)
     if any(re.match(r"mse_.+_s\d+$", k) for k in results):
         lines += quality_section(results)
+    if "overall_miou_restored" in results:
+        lines += restoration_section(results)
     if "bootstrap_replicates" in results:
         lines += bootstrap_section(results)
     return "\n".join(lines)
+
+
+def restoration_section(results: Dict[str, Any]) -> list:
+    """Input restoration (evaluation.restoration): one line per condition with the mIoU of the frames as they came, of the same
+    frames dehazed by the dark-channel prior, the difference, and the mean transmission the front-end estimated."""
+    names = [m.group(1) for k in results for m in [re.match(r"miou_(.+)_restored$", k)] if m]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    lines = ["", "## Input Restoration", "", "Every selected frame dehazed by the dark-channel prior in front of the model and scored "
+             "again.  Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); mean t: the mean "
+             "estimated transmission (1 = nothing removed).", "",
+             "| Condition | Plain mIoU | Restored mIoU | Gain | Mean t | Airlight | Degradation restored |", "|---" * 7 + "|"]
+    for n in names:
+        lines.append(f"| {n} | {cell('miou_' + n)} | {cell('miou_' + n + '_restored')} | {cell('restoration_gain_' + n)} | "
+                     f"{cell('transmission_mean_' + n)} | {cell('airlight_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |")
+    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_transmission')} | "
+                 f"{cell('mean_airlight')} | - |")
+    extra = [f"- **Clean cost** (plain - restored mIoU of the clean frames): {results['restoration_clean_cost']:.3f}"] \
+        if "restoration_clean_cost" in results else []
+    extra += [f"- **{title}**: {int(results[key])}" for key, title in (("restoration_nonfinite_values", "Input values that are not finite"),
+                                                                      ("restoration_airlight_floored_frames", "Frames whose airlight hit the floor"))
+              if key in results]
+    return lines + ([""] + extra if extra else [])
 
 
 def quality_section(results: Dict[str, Any]) -> list:

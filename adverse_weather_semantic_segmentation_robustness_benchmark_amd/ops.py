@@ -616,6 +616,95 @@ def image_quality_to_numpy(stats) -> dict:
     return {f: raw[..., i] for i, f in enumerate(IQ_FIELDS)}
 
 
+# ----------------------------------------------------------------------------- dehazing (include/awseg_restore.h)
+DEHAZE_FIELDS = ("frames", "sum_airlight_0", "sum_airlight_1", "sum_airlight_2", "pixels", "sum_transmission", "nonfinite_values",
+                 "airlight_floored_frames")
+DEHAZE_ROW = len(DEHAZE_FIELDS)        # AWSEG_DEHAZE_ROW
+DEHAZE_UNIT = 2.0 ** -16               # the airlight and transmission sums are int64 in fixed point: exact, order-independent
+DEHAZE_TILE_H, DEHAZE_TILE_W = 32, 64  # AWSEG_DEHAZE_TILE_H, AWSEG_DEHAZE_TILE_W: pixels per block
+DEHAZE_MAX_RADIUS = 15                 # AWSEG_DEHAZE_MAX_RADIUS
+DEHAZE_FRAME_RECORD = 1064             # AWSEG_DEHAZE_FRAME_RECORD: workspace bytes per frame beside its H * W bins
+DEHAZE_DEFAULTS = {"radius": 7, "omega": 0.95, "t_min": 0.1, "airlight_min": 0.1, "refine": 1}
+
+
+def new_dehaze_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, DEHAZE_ROW]: per slot the row DEHAZE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_dehaze_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), DEHAZE_ROW, dtype=torch.int64, device=device)
+
+
+def dehaze_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, refine=1) -> dict:
+    """The checked parameters of dehaze(): radius an integer in [1, 15]; omega, t_min, airlight_min numbers in (0, 1] (also as
+    float32); refine 0 or 1.  ValueError otherwise."""
+    def integer(name, v, lo, hi):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"dehaze: {name} is an integer in [{lo}, {hi}], got {v!r}")
+        return int(v)
+
+    def unit(name, v):
+        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
+        f = float(np.float32(v)) if ok else 0.0
+        if not (ok and 0.0 < f <= 1.0):
+            raise ValueError(f"dehaze: {name} is a number in (0, 1] (also as float32), got {v!r}")
+        return f
+    return {"radius": integer("radius", radius, 1, DEHAZE_MAX_RADIUS), "omega": unit("omega", omega), "t_min": unit("t_min", t_min),
+            "airlight_min": unit("airlight_min", airlight_min), "refine": integer("refine", refine, 0, 1)}
+
+
+def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 7,
+           omega: float = 0.95, t_min: float = 0.1, airlight_min: float = 0.1, refine: int = 1, mean=None, std=None,
+           out: Optional[torch.Tensor] = None):
+    """Dark-channel-prior dehazing (He, Sun, Tang 2009) of the loader's normalised float32 frames `image` [B, 3, H, W], as
+    include/awseg_restore.h defines it step by step: -> (restored float32 [B, 3, H, W], airlight float32 [B, 3]).  `stats`
+    (new_dehaze_stats; slot 0 + slot 1 + cond[b], cond device int32 [B]) takes the counters of DEHAZE_FIELDS; without it they go
+    to a tensor nobody reads.  `refine` 1: the transmission comes from the morphological opening of the normalised dark channel,
+    0: from He's patch minimum.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`: where the restored frames
+    go (contiguous, not `image`)."""
+    if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
+        raise ValueError(f"dehaze: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
+    b, _, h, w = (int(d) for d in image.shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"dehaze: frames of at least one pixel, got {tuple(image.shape)}")
+    if b > 65535 or h * w >= 2 ** 31:
+        raise ValueError(f"dehaze: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
+    p = dehaze_parameters(radius, omega, t_min, airlight_min, refine)
+    if (mean is None) != (std is None):
+        raise ValueError("dehaze: mean and std come together")
+    m, s = _mean_std(mean, std)
+    m, s = m.reshape(-1), s.reshape(-1)
+    if m.size != 3 or s.size != 3 or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
+        raise ValueError(f"dehaze: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
+    if stats is None:
+        stats = new_dehaze_stats(image.device, 1)
+    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != DEHAZE_ROW:
+        raise ValueError(f"stats must be int64 [slots, {DEHAZE_ROW}] (new_dehaze_stats), got {stats.dtype} {tuple(stats.shape)}")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    image = image.contiguous()
+    if out is None:
+        out = torch.empty_like(image)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
+        raise ValueError(f"dehaze: out is a contiguous float32 tensor of the frames' shape, got {out.dtype} {tuple(out.shape)}")
+    if b and out.data_ptr() == image.data_ptr():
+        raise ValueError("dehaze: out must not be the input (a block reads its neighbours' pixels)")
+    airlight = torch.empty(b, 3, dtype=torch.float32, device=image.device)
+    if b == 0:
+        return out, airlight
+    ws = N.workspace.get(image.device, N.lib().awseg_dehaze_workspace(b, h, w), tag="dehaze")
+    N.call("awseg_dehaze", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), p["radius"], p["omega"], p["t_min"], p["airlight_min"],
+           p["refine"], N.ptr(cond), N.ptr(out), N.ptr(airlight), N.ptr(stats), stats.shape[0], N.ptr(ws), N.stream())
+    return out, airlight
+
+
+def dehaze_stats_to_numpy(stats) -> dict:
+    """int64 [..., DEHAZE_ROW] -> {field: int64 [...]} for DEHAZE_FIELDS; the four sums stay in units of DEHAZE_UNIT."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != DEHAZE_ROW:
+        raise ValueError(f"dehaze rows hold {DEHAZE_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(DEHAZE_FIELDS)}
+
+
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

@@ -1,0 +1,71 @@
+/*
+ * awseg_restore.h — input-restoration entry points of libawseg_hip.so.  An extension header: same conventions as
+ * awseg.h (device pointers unless documented "host", stream-ordered, no allocation, no synchronisation, 0 / hipError_t / AWSEG_E*),
+ * whose types and error codes it uses.  awseg_abi_version stays what awseg.h says; the bindings keep these symbols in a table of
+ * their own (_native.EXTENSION_SIGNATURES).
+ */
+#ifndef AWSEG_RESTORE_H
+#define AWSEG_RESTORE_H
+
+#include "awseg.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* 60 bits of sha256 of THIS file as it was when the library was built, as awseg_header_hash is of awseg.h: a binding that finds
+ * another hash beside the library refuses to call the entry points below. */
+uint64_t awseg_restore_header_hash(void);
+
+/* ------------------------------------------------------------------------- *
+ *  Dark-channel-prior dehazing (He, Sun, Tang 2009) of the frames the model sees, as a blind front-end of the evaluation
+ *       replaces nothing: the reference has no restoration baseline
+ * ------------------------------------------------------------------------- *
+ * awseg_dehaze: image float32 [B, 3, H, W], the loader's normalised frames; mean, std: HOST float32[3] (they travel in the kernel
+ * arguments).  radius r in [1, 15] (windows are (2r+1)^2, clipped to the frame: positions outside take part in no minimum and no
+ * maximum), omega, t_min, airlight_min in (0, 1], refine 0 or 1.  Every step is one float32 operation with the parenthesisation
+ * given (the library is built without FMA contraction, float32 and float64 division are correctly rounded), so numpy gives the
+ * same bits.  Per frame b, pixel p, channel c:
+ *     v_c  = fminf(fmaxf(image[b,c,p] * std[c] + mean[c], 0), 1)         (NaN -> 0; every input value that is not finite is counted)
+ *   pass A   m = fminf(fminf(v_0, v_1), v_2);  dark = window minimum of m;  bin = (int)(dark * 255.0f), one uint8 per pixel in the
+ *            workspace and one count in the frame's 256-bin histogram
+ *   pass B   n_top = (H*W + 999) / 1000 (integers);  b* = the largest bin with sum_{k >= b*} hist[k] >= n_top;  over the pixels with
+ *            bin >= b*:  S_c += (int64) rintf(v_c * 65536.0f),  N += 1;
+ *            a_c = (float)((double) S_c / ((double) N * 65536.0));  A_c = fmaxf(a_c, airlight_min);  the frame's airlight "hit the
+ *            floor" when a_c < airlight_min for some c
+ *   pass C   n = fminf(fminf(v_0 / A_0, v_1 / A_1), v_2 / A_2);  e = window minimum of n;
+ *            o = e (refine 0), or the window maximum of e (refine 1: the morphological opening of n);
+ *            t = fmaxf(1.0f - omega * o, t_min);
+ *            J_c = fminf(fmaxf((v_c - A_c) / t + A_c, 0), 1);   restored[b,c,p] = (J_c - mean[c]) / std[c]
+ * restored float32 [B, 3, H, W] (must not overlap image: a block reads its neighbours' pixels); airlight float32 [B][3] = A.
+ * stats int64 [n_slots][AWSEG_DEHAZE_ROW] (accumulated, never cleared), slot rule of every other counter: frame b into slot 0 and
+ * into slot 1 + cond[b] when 0 <= cond[b] < n_slots - 1 (cond device int32[B] or NULL: slot 0 only).  Row:
+ *     [0] frames   [1..3] sum of rintf(A_c * 65536.0f), c = 0, 1, 2   [4] pixels   [5] sum of rintf(t * 65536.0f)
+ *     [6] input values that are not finite   [7] frames whose airlight hit the floor
+ * Integer sums only: independent of the grid, additive over launches and ranks.  A term is at most 2^16 units, so a stats tensor
+ * holds 2^46 pixels before a sum could wrap.
+ * Three kernels: A and C are tile kernels, a block owns AWSEG_DEHAZE_TILE_H x AWSEG_DEHAZE_TILE_W pixels and stages them with a halo
+ * of r (A; C with refine 0) or 2 r (C with refine 1) in LDS, separable window passes there; B walks the bin map.  16-byte loads and
+ * stores when W % 4 == 0 and image and restored are 16-byte aligned (four bins then travel as one 32-bit word), scalar ones otherwise.
+ * workspace: awseg_dehaze_workspace(batch, height, width) bytes
+ *     = batch * (AWSEG_DEHAZE_FRAME_RECORD + height * width):
+ * per frame a record of 256 uint32 histogram words and five int64 (S_0, S_1, S_2, N, non-finite values), then one uint8 bin per
+ * pixel; 8-byte aligned (AWSEG_EALIGN otherwise).  The launcher clears the records on the stream.
+ * AWSEG_EINVAL for a NULL pointer (cond excepted), channels != 3, a size < 1 (batch < 0), n_slots < 1, a parameter outside the
+ * ranges above (NaN included), a std that is not finite and > 0 or a non-finite mean; AWSEG_ERANGE for batch > 65535 or
+ * H * W >= 2^31; batch == 0 returns 0. */
+#define AWSEG_DEHAZE_ROW           8
+#define AWSEG_DEHAZE_TILE_H        32
+#define AWSEG_DEHAZE_TILE_W        64
+#define AWSEG_DEHAZE_MAX_RADIUS    15
+#define AWSEG_DEHAZE_FRAME_RECORD  1064
+int64_t awseg_dehaze_workspace(int64_t batch, int64_t height, int64_t width);
+int awseg_dehaze(const float* image, int64_t batch, int channels, int64_t height, int64_t width,
+                 const float* mean, const float* std, int radius, float omega, float t_min, float airlight_min, int refine,
+                 const int32_t* cond, float* restored, float* airlight, int64_t* stats, int n_slots,
+                 void* workspace, awseg_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* AWSEG_RESTORE_H */

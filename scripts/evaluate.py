@@ -22,7 +22,7 @@ from adverse_weather_semantic_segmentation_robustness_benchmark_amd import paral
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.data.loader import CityscapesKITTIDataset, create_dataloader
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.harness import evaluate_model
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.metrics import RobustnessMetrics
-from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.report import generate_evaluation_report
+from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.report import generate_evaluation_report, restoration_section
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.utils.checkpoint import load_model_state
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.models.model import DeepLabV3PlusModel, EnsembleModel, SegFormerModel
 from adverse_weather_semantic_segmentation_robustness_benchmark_amd.utils.config import (create_default_config, get_device_config, load_config,
@@ -135,6 +135,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
                     help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
                          "(sets evaluation.image_quality_targets)")
+    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel",),
+                    help="dehaze every frame by the dark-channel prior in front of the model and score it a second time: plain and "
+                         "restored mIoU, the gain and the mean transmission per condition (sets evaluation.restoration)")
+    ap.add_argument("--restoration-conditions", type=str, default=None, metavar="A,B",
+                    help="restore only the frames of these comma-separated weather conditions (default: all, clean included; sets "
+                         "evaluation.restoration_conditions)")
+    ap.add_argument("--restoration-refine", type=str, default=None, choices=("opening", "none"),
+                    help="transmission from the morphological opening of the normalised dark channel (default) or from He's plain "
+                         "patch minimum (sets evaluation.restoration.refine)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -151,6 +160,16 @@ def apply_bootstrap_options(args, config) -> None:
                       ("bootstrap_seed", "evaluation.bootstrap_seed")):
         if getattr(args, flag) is not None:
             config.set(key, getattr(args, flag))
+
+
+def apply_restoration_options(args, config) -> None:
+    """--restoration / --restoration-conditions / --restoration-refine into the configuration (the harness checks them)."""
+    if args.restoration_refine is not None and args.restoration is None:
+        raise ValueError("--restoration-refine needs --restoration dark_channel")
+    if args.restoration is not None:
+        config.set("evaluation.restoration", args.restoration if args.restoration_refine is None else {"refine": args.restoration_refine})
+    if args.restoration_conditions is not None:
+        config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
 
 
 def main():
@@ -185,6 +204,7 @@ def main():
         if args.image_quality_targets is not None:
             config.set("evaluation.image_quality_targets", parse_image_quality_targets(args.image_quality_targets))
         apply_bootstrap_options(args, config)
+        apply_restoration_options(args, config)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",
@@ -203,6 +223,10 @@ def main():
                     logger.info("%s: %s", k, " ".join(f"{x:.4f}" for x in v))
                 else:
                     logger.info("%s: %.4f", k, v)
+            if "overall_miou_restored" in plain:                       # --restoration: plain / restored / gain / mean t per condition
+                for line in restoration_section(plain):
+                    if line:
+                        logger.info("%s", line)
     except Exception as e:  # noqa: BLE001 - the reference converts failures to exit code 1 (evaluate.py:506-508)
         logger.error("Evaluation failed: %s", e)
         raise SystemExit(1)

@@ -190,6 +190,17 @@ def main():
         lambda: ops.image_quality(chg_var, chg_clean, fref, iqst, cond=cond, oob=iqoob), "hbm", 24 * px * B)
     cases["image quality, independent random frames"] = (
         lambda: ops.image_quality(iq_rand[0], iq_rand[1], fref, iqst, cond=cond, oob=iqoob), "hbm", 24 * px * B)
+    # dehazing front-end (evaluation.restoration): dark channel + airlight + recovery, three kernels per launch.  24 B/px is the
+    # least a dehazer moves (the frame in, the frame out); the passes read the frame three times over plus the tiles' halos, and take
+    # ~100 LDS reads per pixel for the window minima and maxima at r = 7, so "of peak" says how far from a copy the stencil is.
+    # Yardsticks on the same tensors: image quality above (an issue-bound stencil) and normalize (a streaming pass)
+    dz_out, dzst = torch.empty_like(chg_var), ops.new_dehaze_stats(dev, 6)
+    for tag, frames in (("rendered-like frames", chg_var), ("independent random frames", iq_rand[0])):
+        for refine in (1, 0):
+            cases[f"dehaze r=7 refine={refine}, {tag}"] = (
+                lambda frames=frames, refine=refine: ops.dehaze(frames, dzst, cond, radius=7, refine=refine, out=dz_out), "hbm", 24 * px * B)
+    cases["dehaze r=15 refine=1, rendered-like frames"] = (
+        lambda: ops.dehaze(chg_var, dzst, cond, radius=15, refine=1, out=dz_out), "hbm", 24 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
