@@ -153,6 +153,9 @@ EXTENSION_SIGNATURES = {
     "awseg_restore_header_hash": (C.c_uint64, []),
     "awseg_dehaze_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "awseg_dehaze": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "awseg_dehaze_guided_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "awseg_dehaze_guided": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i,
+                                  c_p, c_p]),
 }
 
 

@@ -30,7 +30,8 @@ from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMetrics, bootstrap_metrics_from_replicates,
                       boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats,
-                      failure_metrics_from_stats, iou_from_counts, quality_metrics_from_stats, restoration_metrics_from_stats,
+                      failure_metrics_from_stats, iou_from_counts, guided_metrics_from_stats, quality_metrics_from_stats,
+                      restoration_metrics_from_stats, restored_quality_metrics_from_stats,
                       segment_metrics_from_stats, segment_options, severity_sweep_results, weight_grid_metrics_from_stats)
 
 logger = logging.getLogger(__name__)
@@ -282,16 +283,20 @@ def check_quality_budget(terms: int) -> None:
 
 RESTORATION_KEYS = ("radius", "omega", "t_min", "airlight_min", "refine")
 RESTORATION_REFINE = {"opening": 1, "none": 0}
+RESTORATION_GUIDED_KEYS = ("guided_radius", "guided_eps")               # only under refine: guided (awseg_dehaze_guided)
 
 
 def restoration_option(config, images=None):
     """`evaluation.restoration` (default off): 'dark_channel', or a dict with any of `radius` (an integer in [1, 15], default 7),
-    `omega`, `t_min`, `airlight_min` (numbers in (0, 1], defaults 0.95, 0.1, 0.1) and `refine` ('opening', the default, or 'none'):
+    `omega`, `t_min`, `airlight_min` (numbers in (0, 1], defaults 0.95, 0.1, 0.1) and `refine` ('opening', the default, 'none', or
+    'guided': the guided-filter refinement of DESIGN.md 10n-bis, which alone takes `guided_radius`, an integer in [1, 32], default
+    min(4 radius, 32), and `guided_eps`, a number in [1e-4, 1], default 1e-3):
     every selected frame is dehazed by the dark-channel prior and scored a second time.
     `evaluation.restoration_conditions`: the weather conditions whose frames are restored, a list of names; absent: all of them,
     'clean' included (a blind front-end does not know the weather); checked also when the option is off.  `images`, when given, is
     a batch of frames: they must be float32 [B, 3, H, W].
-    -> None when absent, else {'radius', 'omega', 't_min', 'airlight_min', 'refine' (0 / 1), 'conditions' (a list, or None = all)}."""
+    -> None when absent, else {'radius', 'omega', 't_min', 'airlight_min', 'refine' (0 / 1), 'conditions' (a list, or None = all)};
+    under 'guided': {'radius', 'omega', 't_min', 'airlight_min', 'guided_radius', 'guided_eps', 'refine': 'guided', 'conditions'}."""
     names = _cfg(config, "evaluation.restoration_conditions", None)
     if names is not None:
         if isinstance(names, (str, bytes, dict)) or not isinstance(names, (list, tuple)) or not names \
@@ -305,14 +310,22 @@ def restoration_option(config, images=None):
         if spec != "dark_channel":
             raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict of its parameters, got {spec!r}")
         spec = {}
-    if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS):
-        raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict with keys among {list(RESTORATION_KEYS)}, got {spec!r}")
+    if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS) - set(RESTORATION_GUIDED_KEYS):
+        raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict with keys among "
+                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)}, got {spec!r}")
     kw = {k: v for k, v in spec.items() if k != "refine"}
     refine = spec.get("refine", "opening")
-    if not isinstance(refine, str) or refine not in RESTORATION_REFINE:
-        raise ValueError(f"evaluation.restoration.refine is 'opening' or 'none', got {refine!r}")
+    if not isinstance(refine, str) or (refine not in RESTORATION_REFINE and refine != "guided"):
+        raise ValueError(f"evaluation.restoration.refine is 'opening', 'none' or 'guided', got {refine!r}")
+    if refine != "guided" and set(kw) & set(RESTORATION_GUIDED_KEYS):
+        raise ValueError(f"evaluation.restoration: {sorted(set(kw) & set(RESTORATION_GUIDED_KEYS))} belong to refine: guided, got "
+                         f"refine: {refine}")
     try:
-        opt = ops.dehaze_parameters(refine=RESTORATION_REFINE[refine], **kw)
+        if refine == "guided":
+            opt = ops.dehaze_guided_parameters(**kw)
+            opt["refine"] = "guided"
+        else:
+            opt = ops.dehaze_parameters(refine=RESTORATION_REFINE[refine], **kw)
     except ValueError as e:
         raise ValueError(f"evaluation.restoration: {e}") from None
     if images is not None:
@@ -384,6 +397,9 @@ COUNTERS = (
     ("segments", ("stats", "oob"), None, None, "prediction map value outside [0, num_classes) in the segment counters"),
     ("weight_grid", ("stats",), None, None, None),
     ("restoration", ("counts", "oob", "stats"), None, None, "label outside [0, num_classes) in the confusion counters of the restored frames"),
+    ("restoration_guided", ("stats",), None, None, None),
+    ("restored_quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality "
+                                                                          "counters of the restored frames"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
     ("paired", ("stats", "oob", "sources"), None, None, "prediction map value outside [0, num_classes) in the consistency counters"),
 )
@@ -520,11 +536,23 @@ class EvalState:
         # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
         self.restoration = None
         if restoration is not None:
-            params = ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS})
+            guided = restoration["refine"] == "guided"
+            params = (ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
+                      else ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS}))
             acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
             self.restoration = {"params": params, "acc": acc, "counts": acc.counts, "oob": acc.oob,
                                 "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]},
                                 "stats": ops.new_dehaze_stats(device, 1 + len(conditions))}
+        # under refine: guided the counters of the filter, int64 [slot, AWSEG_GUIDED_ROW] (None otherwise: awseg_dehaze runs)
+        self.restoration_guided = None
+        if restoration is not None and restoration["refine"] == "guided":
+            self.restoration_guided = {"stats": ops.new_guided_stats(device, 1 + len(conditions))}
+        # fidelity of the restored frames (only when the sweep, the image-quality counters and the restoration are all on): a SECOND
+        # image-quality tensor, the restored frames against the same kept clean frames; the clean batch against its own kept rows
+        self.restored_quality = None
+        if restoration is not None and self.quality is not None:
+            self.restored_quality = {"terms": 0, "stats": ops.new_image_quality_stats(device, 1 + len(conditions)),
+                                     "oob": torch.zeros(1, dtype=torch.int64, device=device)}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -646,9 +674,10 @@ class EvalState:
         twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
         ops.image_quality(images, twins, rows, q["stats"], cond=cond, oob=q["oob"])
 
-    def update_restoration(self, model, images, labels, kinds, cond) -> None:
+    def update_restoration(self, model, images, labels, kinds, cond, rows=None) -> None:
         """The batch's frames of the selected weather conditions (`kinds`: the loader's names, before a sweep's slot names), dehazed,
-        through one more forward into the second confusion accumulator.  Nothing else sees the restored frames."""
+        through one more forward into the second confusion accumulator.  Nothing else sees the restored frames, but the second
+        image-quality tensor when it is on (`rows`: frame_ref's rows of the batch's sources in the kept clean frames)."""
         rs = self.restoration
         check_frames("restoration", images)
         keep = [i for i, k in enumerate(kinds) if rs["conditions"] is None or str(k) in rs["conditions"]]
@@ -657,7 +686,21 @@ class EvalState:
         if len(keep) < images.shape[0]:
             idx = torch.tensor(keep, dtype=torch.int64).to(images.device, non_blocking=True)
             images, labels, cond = images.index_select(0, idx), labels.index_select(0, idx), cond.index_select(0, idx)
-        restored, _ = ops.dehaze(images, rs["stats"], cond, **rs["params"])
+            if rows is not None:
+                rows = rows.index_select(0, idx) if torch.is_tensor(rows) else [rows[i] for i in keep]
+        if self.restoration_guided is not None:
+            restored, _ = ops.dehaze_guided(images, rs["stats"], self.restoration_guided["stats"], cond, **rs["params"])
+        else:
+            restored, _ = ops.dehaze(images, rs["stats"], cond, **rs["params"])
+        if self.restored_quality is not None:
+            # (the rows a last variant batch has just released still hold their frames: nothing writes them before the next batch)
+            rq = self.restored_quality
+            check_quality_budget(rq["terms"] + restored.numel())
+            rq["terms"] += restored.numel()
+            if not torch.is_tensor(rows):
+                rows = torch.tensor(rows, dtype=torch.int32).to(images.device, non_blocking=True)
+            twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
+            ops.image_quality(restored, twins, rows, rq["stats"], cond=cond, oob=rq["oob"])
         if self.auroc is not None:                                    # the ensemble
             model.forward_eval(restored, labels, rs["counts"], rs["oob"], cond, want_logits=False, want_pred=False, stats=None)
         else:
@@ -911,7 +954,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_change(images, pred_out, labels, rows, cond, metrics.num_classes)
         st.update_consistency(pred_out, labels, sources, rows, cond, metrics.num_classes)
     if st.restoration is not None:                                    # after everything above: one more forward, on the dehazed frames
-        st.update_restoration(model, images, labels, kinds, cond)
+        st.update_restoration(model, images, labels, kinds, cond, rows)
     st.samples += images.size(0)
 
 
@@ -1024,6 +1067,12 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), rs["stats"].cpu().numpy(),
                                                       st.acc.conditions, metrics.num_classes, **sweep_kw,
                                                       degradation=metrics.compute_robustness_degradation_ratio))
+        if st.restoration_guided is not None:
+            results.update(guided_metrics_from_stats(st.restoration_guided["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
+            results["restoration_refine"] = "guided"
+        if st.restored_quality is not None:
+            results.update(restored_quality_metrics_from_stats(st.restored_quality["stats"].cpu().numpy(), q["stats"].cpu().numpy(),
+                                                               st.acc.conditions, st.sweep.kinds, st.sweep.levels))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -827,6 +827,75 @@ def restoration_metrics_from_stats(restored, plain, stats, conditions: List[str]
     return res
 
 
+def guided_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0) -> Dict[str, float]:
+    """Result keys of the guided-filter refinement from its counters int64 [1 + len(conditions),
+    AWSEG_GUIDED_ROW] (include/awseg_restore.h; slot 0 = every restored frame, slot 1 + k = conditions[k]).  Host only, float64 on
+    exact integer sums; every value a float.  With <n> a condition (under a sweep its slots and each '<kind>' from the summed counters
+    of its levels), for every <n> with restored pixels:
+      transmission_refinement_<n>        mean |t - t_patch|: how far the filter moved the patch transmission fmaxf(p, t_min)
+      transmission_clamped_fraction_<n>  share of the pixels whose filter output q was above 1 or below t_min
+    and over slot 0 mean_transmission_refinement, mean_transmission_clamped_fraction.  No pixel, no key."""
+    conditions = list(conditions)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.shape != (1 + len(conditions), ops.GUIDED_ROW):
+        raise ValueError(f"guided stats must be int64 [{1 + len(conditions)}, {ops.GUIDED_ROW}], got {raw.shape}")
+    named = [(None, raw[0])] + [(name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        named.append((kind, raw[[1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels) + 1)]].sum(0)))
+    res: Dict[str, float] = {}
+    for name, row in named:
+        dec = {f: int(v) for f, v in ops.guided_stats_to_numpy(row).items()}
+        if dec["pixels"] <= 0:
+            continue
+        moved = float(dec["sum_transmission_moved"] * ops.DEHAZE_UNIT / dec["pixels"])
+        clamped = float((dec["above_one_pixels"] + dec["below_floor_pixels"]) / dec["pixels"])
+        res["mean_transmission_refinement" if name is None else f"transmission_refinement_{name}"] = moved
+        res["mean_transmission_clamped_fraction" if name is None else f"transmission_clamped_fraction_{name}"] = clamped
+    return res
+
+
+IQ_PLAIN_STEMS = ("mse", "psnr", "mean_abs_change", "ssim", "ssim_luminance", "ssim_contrast")
+
+
+def restored_quality_metrics_from_stats(restored, plain, slots: List[str], kinds, levels: int) -> Dict[str, float]:
+    """Fidelity of the restored frames: `restored`, `plain` image-quality counters int64 [1 + len(slots), AWSEG_IQ_ROW] of the
+    restored frames and of the corrupted ones against the same clean twins.  The clean slot of `restored` holds the restored clean
+    frames against themselves-before (the clean slot of `plain` is empty).  Host only; every value a float.  With <stem> one of
+    IQ_PLAIN_STEMS and <n> a '<kind>_s<j>' or a '<kind>' (summed counters of its levels), from quality_metrics_from_stats:
+      <stem>_<n>_restored                   that key of the restored counters
+      restoration_psnr_gain_<n>, restoration_ssim_gain_<n>     restored - plain on the same frames
+      mean_<stem>_restored, mean_restoration_psnr_gain, mean_restoration_ssim_gain     pooled over the corrupted frames that were
+                                            restored (the clean ones left out; the plain side over the same slots)
+      psnr_clean_restored, ssim_clean_restored                 what the front-end does to a frame that needed nothing
+    The mIoU-at-equal-SSIM interpolation is not repeated.  A ratio without a denominator is absent, not 0."""
+    slots, kinds, levels = list(slots), list(kinds), int(levels)
+    r = np.asarray(restored.cpu().numpy() if isinstance(restored, torch.Tensor) else restored, dtype=np.int64).copy()
+    p = np.asarray(plain.cpu().numpy() if isinstance(plain, torch.Tensor) else plain, dtype=np.int64).copy()
+    for what, a in (("restored", r), ("plain", p)):
+        if a.shape != (1 + len(slots), ops.IQ_ROW):
+            raise ValueError(f"{what} image-quality stats must be int64 [{1 + len(slots)}, {ops.IQ_ROW}], got {a.shape}")
+    res: Dict[str, float] = {}
+    if "clean" in slots:
+        row = r[1 + slots.index("clean")]
+        own = quality_metrics_from_stats(np.stack([row, row]), ["clean_s1"], ["clean"], 1, {})
+        res.update({f"{stem}_clean_restored": own[f"{stem}_clean"] for stem in ("psnr", "ssim") if f"{stem}_clean" in own})
+    level_slots = [1 + slots.index(f"{kind}_s{j}") for kind in kinds for j in range(1, levels + 1)]
+    done = [i for i in level_slots if r[i].any()]
+    r[0], p[0] = r[done].sum(0), p[done].sum(0)                              # pooled: the corrupted frames that were restored
+    after, before = quality_metrics_from_stats(r, slots, kinds, levels, {}), quality_metrics_from_stats(p, slots, kinds, levels, {})
+    names = [f"{kind}_s{j}" for kind in kinds for j in range(1, levels + 1)] + kinds
+    for stem in IQ_PLAIN_STEMS:
+        for key in [f"{stem}_{n}" for n in names] + [f"mean_{stem}"]:
+            if key in after:
+                res[f"{key}_restored"] = after[key]
+    for stem in ("psnr", "ssim"):
+        for n in names + [None]:
+            key = f"mean_{stem}" if n is None else f"{stem}_{n}"
+            if key in after and key in before:
+                res[f"mean_restoration_{stem}_gain" if n is None else f"restoration_{stem}_gain_{n}"] = after[key] - before[key]
+    return res
+
+
 def weight_grid_row_miou(inter, lab, prd) -> Optional[float]:
     """mIoU from the marginals of one grid point (int64 [C] each: hits, labelled, predicted): iou_from_counts' expressions (int64 /
     int64 true-divide to float32, mean over the classes with a non-empty union), so the configured point reproduces the pooled

@@ -74,13 +74,35 @@ def restoration_section(results: Dict[str, Any]) -> list:
         return f"{results[key]:.3f}" if key in results else "-"
     lines = ["", "## Input Restoration", "", "Every selected frame dehazed by the dark-channel prior in front of the model and scored "
              "again.  Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); mean t: the mean "
-             "estimated transmission (1 = nothing removed).", "",
-             "| Condition | Plain mIoU | Restored mIoU | Gain | Mean t | Airlight | Degradation restored |", "|---" * 7 + "|"]
+             "estimated transmission (1 = nothing removed).", ""]
+    # under refine: guided two more cells per line (how far the filter moved the patch transmission, the share of clamped pixels);
+    # with the image-quality counters two more (PSNR and SSIM of the restored frames against the clean twins, with the gain over
+    # the corrupted ones)
+    guided = any(k.startswith("transmission_refinement_") for k in results)
+    fidelity = any(re.match(r"(psnr|ssim)_.+_restored$", k) for k in results)
+    head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain", "Mean t", "Airlight", "Degradation restored"]
+    head += ["Refinement", "Clamped"] * guided + ["PSNR restored (gain)", "SSIM restored (gain)"] * fidelity
+    if "restoration_refine" in results:
+        lines += [f"Transmission refinement: {results['restoration_refine']} filter (DESIGN.md 10n-bis).", ""]
+    lines += ["| " + " | ".join(head) + " |", "|---" * len(head) + "|"]
+
+    def more(n):
+        cells = []
+        if guided:
+            cells += [cell("mean_transmission_refinement" if n is None else f"transmission_refinement_{n}"),
+                      cell("mean_transmission_clamped_fraction" if n is None else f"transmission_clamped_fraction_{n}")]
+        if fidelity:
+            for stem, fmt in (("psnr", ".2f"), ("ssim", ".3f")):
+                key = f"mean_{stem}_restored" if n is None else f"{stem}_{n}_restored"
+                gain = f"mean_restoration_{stem}_gain" if n is None else f"restoration_{stem}_gain_{n}"
+                cells.append(format(results[key], fmt) + (f" ({results[gain]:+{fmt}})" if gain in results else "") if key in results else "-")
+        return "".join(f" {c} |" for c in cells)
     for n in names:
         lines.append(f"| {n} | {cell('miou_' + n)} | {cell('miou_' + n + '_restored')} | {cell('restoration_gain_' + n)} | "
-                     f"{cell('transmission_mean_' + n)} | {cell('airlight_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |")
+                     f"{cell('transmission_mean_' + n)} | {cell('airlight_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |"
+                     + more(n))
     lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_transmission')} | "
-                 f"{cell('mean_airlight')} | - |")
+                 f"{cell('mean_airlight')} | - |" + more(None))
     extra = [f"- **Clean cost** (plain - restored mIoU of the clean frames): {results['restoration_clean_cost']:.3f}"] \
         if "restoration_clean_cost" in results else []
     extra += [f"- **{title}**: {int(results[key])}" for key, title in (("restoration_nonfinite_values", "Input values that are not finite"),

@@ -652,29 +652,21 @@ def dehaze_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, refine=
             "airlight_min": unit("airlight_min", airlight_min), "refine": integer("refine", refine, 0, 1)}
 
 
-def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 7,
-           omega: float = 0.95, t_min: float = 0.1, airlight_min: float = 0.1, refine: int = 1, mean=None, std=None,
-           out: Optional[torch.Tensor] = None):
-    """Dark-channel-prior dehazing (He, Sun, Tang 2009) of the loader's normalised float32 frames `image` [B, 3, H, W], as
-    include/awseg_restore.h defines it step by step: -> (restored float32 [B, 3, H, W], airlight float32 [B, 3]).  `stats`
-    (new_dehaze_stats; slot 0 + slot 1 + cond[b], cond device int32 [B]) takes the counters of DEHAZE_FIELDS; without it they go
-    to a tensor nobody reads.  `refine` 1: the transmission comes from the morphological opening of the normalised dark channel,
-    0: from He's patch minimum.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`: where the restored frames
-    go (contiguous, not `image`)."""
+def _dehaze_buffers(who: str, image, stats, cond, mean, std, out):
+    """The checks dehaze() and dehaze_guided() share -> (contiguous image, B, H, W, mean, std, stats, out, airlight [B, 3])."""
     if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
-        raise ValueError(f"dehaze: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
+        raise ValueError(f"{who}: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
     b, _, h, w = (int(d) for d in image.shape)
     if h < 1 or w < 1:
-        raise ValueError(f"dehaze: frames of at least one pixel, got {tuple(image.shape)}")
+        raise ValueError(f"{who}: frames of at least one pixel, got {tuple(image.shape)}")
     if b > 65535 or h * w >= 2 ** 31:
-        raise ValueError(f"dehaze: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
-    p = dehaze_parameters(radius, omega, t_min, airlight_min, refine)
+        raise ValueError(f"{who}: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
     if (mean is None) != (std is None):
-        raise ValueError("dehaze: mean and std come together")
+        raise ValueError(f"{who}: mean and std come together")
     m, s = _mean_std(mean, std)
     m, s = m.reshape(-1), s.reshape(-1)
     if m.size != 3 or s.size != 3 or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
-        raise ValueError(f"dehaze: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
+        raise ValueError(f"{who}: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
     if stats is None:
         stats = new_dehaze_stats(image.device, 1)
     if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != DEHAZE_ROW:
@@ -685,10 +677,23 @@ def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Opti
     if out is None:
         out = torch.empty_like(image)
     if out.dtype != torch.float32 or tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
-        raise ValueError(f"dehaze: out is a contiguous float32 tensor of the frames' shape, got {out.dtype} {tuple(out.shape)}")
+        raise ValueError(f"{who}: out is a contiguous float32 tensor of the frames' shape, got {out.dtype} {tuple(out.shape)}")
     if b and out.data_ptr() == image.data_ptr():
-        raise ValueError("dehaze: out must not be the input (a block reads its neighbours' pixels)")
-    airlight = torch.empty(b, 3, dtype=torch.float32, device=image.device)
+        raise ValueError(f"{who}: out must not be the input (a block reads its neighbours' pixels)")
+    return image, b, h, w, m, s, stats, out, torch.empty(b, 3, dtype=torch.float32, device=image.device)
+
+
+def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 7,
+           omega: float = 0.95, t_min: float = 0.1, airlight_min: float = 0.1, refine: int = 1, mean=None, std=None,
+           out: Optional[torch.Tensor] = None):
+    """Dark-channel-prior dehazing (He, Sun, Tang 2009) of the loader's normalised float32 frames `image` [B, 3, H, W], as
+    include/awseg_restore.h defines it step by step: -> (restored float32 [B, 3, H, W], airlight float32 [B, 3]).  `stats`
+    (new_dehaze_stats; slot 0 + slot 1 + cond[b], cond device int32 [B]) takes the counters of DEHAZE_FIELDS; without it they go
+    to a tensor nobody reads.  `refine` 1: the transmission comes from the morphological opening of the normalised dark channel,
+    0: from He's patch minimum.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`: where the restored frames
+    go (contiguous, not `image`)."""
+    p = dehaze_parameters(radius, omega, t_min, airlight_min, refine)
+    image, b, h, w, m, s, stats, out, airlight = _dehaze_buffers("dehaze", image, stats, cond, mean, std, out)
     if b == 0:
         return out, airlight
     ws = N.workspace.get(image.device, N.lib().awseg_dehaze_workspace(b, h, w), tag="dehaze")
@@ -703,6 +708,85 @@ def dehaze_stats_to_numpy(stats) -> dict:
     if raw.shape[-1] != DEHAZE_ROW:
         raise ValueError(f"dehaze rows hold {DEHAZE_ROW} counters, got {raw.shape[-1]}")
     return {f: raw[..., i] for i, f in enumerate(DEHAZE_FIELDS)}
+
+
+# ------------------------------------------------ guided-filter transmission (include/awseg_restore.h)
+GUIDED_FIELDS = ("above_one_pixels", "below_floor_pixels", "sum_transmission_moved", "pixels")
+GUIDED_ROW = len(GUIDED_FIELDS)        # AWSEG_GUIDED_ROW
+GUIDED_MAX_RADIUS = 32                 # AWSEG_GUIDED_MAX_RADIUS
+GUIDED_EPS_RANGE = (1e-4, 1.0)         # as float32: what the launcher accepts
+GUIDED_DEFAULT_EPS = 1e-3
+
+
+def new_guided_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, GUIDED_ROW]: per slot the row GUIDED_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate);
+    sum_transmission_moved is in units of DEHAZE_UNIT."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_guided_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), GUIDED_ROW, dtype=torch.int64, device=device)
+
+
+def default_guided_radius(radius: int) -> int:
+    return min(4 * int(radius), GUIDED_MAX_RADIUS)
+
+
+def dehaze_guided_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, guided_radius=None, guided_eps=GUIDED_DEFAULT_EPS) -> dict:
+    """The checked parameters of dehaze_guided(): those of dehaze_parameters (without refine); guided_radius an integer in [1, 32]
+    (None: min(4 radius, 32)); guided_eps a number in [1e-4, 1] as float32.  ValueError otherwise."""
+    p = dehaze_parameters(radius, omega, t_min, airlight_min, 0)
+    del p["refine"]
+    if guided_radius is None:
+        guided_radius = default_guided_radius(p["radius"])
+    if isinstance(guided_radius, (bool, np.bool_)) or not isinstance(guided_radius, (int, np.integer)) \
+            or not 1 <= int(guided_radius) <= GUIDED_MAX_RADIUS:
+        raise ValueError(f"dehaze_guided: guided_radius is an integer in [1, {GUIDED_MAX_RADIUS}], got {guided_radius!r}")
+    ok = not isinstance(guided_eps, (bool, np.bool_, str, bytes)) and isinstance(guided_eps, (int, float, np.integer, np.floating))
+    eps = float(np.float32(guided_eps)) if ok else 0.0
+    if not (ok and float(np.float32(GUIDED_EPS_RANGE[0])) <= eps <= GUIDED_EPS_RANGE[1]):
+        raise ValueError(f"dehaze_guided: guided_eps is a number in [1e-4, 1] (also as float32), got {guided_eps!r}")
+    p["guided_radius"], p["guided_eps"] = int(guided_radius), eps
+    return p
+
+
+def dehaze_guided_workspace_bytes(b: int, h: int, w: int) -> int:
+    """The closed form of awseg_dehaze_guided_workspace: the records and bin map of awseg_dehaze, then three float32 maps, every
+    region rounded up to 8 bytes."""
+    b, h, w = max(int(b), 1), max(int(h), 1), max(int(w), 1)
+    ceil8 = lambda x: (x + 7) & ~7                                      # noqa: E731
+    return ceil8(b * (DEHAZE_FRAME_RECORD + h * w)) + 3 * ceil8(4 * b * h * w)
+
+
+def dehaze_guided(image: torch.Tensor, stats: Optional[torch.Tensor] = None, guided_stats: Optional[torch.Tensor] = None,
+                  cond: Optional[torch.Tensor] = None, *, radius: int = 7, omega: float = 0.95, t_min: float = 0.1,
+                  airlight_min: float = 0.1, guided_radius: Optional[int] = None, guided_eps: float = GUIDED_DEFAULT_EPS, mean=None,
+                  std=None, out: Optional[torch.Tensor] = None, transmission: bool = False):
+    """dehaze() with the guided-filter refinement of the transmission (He, Sun, Tang 2010/2013): the patch transmission filtered
+    over (2 guided_radius + 1)^2 windows with the frame's luma as the guide, as include/awseg_restore.h defines it step by step
+    -> (restored float32 [B, 3, H, W], airlight float32 [B, 3][, t float32 [B, H, W] when `transmission`]).  `stats` as for
+    dehaze(); `guided_stats` (new_guided_stats, the same slots) takes the counters of GUIDED_FIELDS.  guided_radius None:
+    min(4 radius, 32).  There is no CPU path."""
+    p = dehaze_guided_parameters(radius, omega, t_min, airlight_min, guided_radius, guided_eps)
+    image, b, h, w, m, s, stats, out, airlight = _dehaze_buffers("dehaze_guided", image, stats, cond, mean, std, out)
+    if guided_stats is None:
+        guided_stats = new_guided_stats(image.device, stats.shape[0])
+    if guided_stats.dim() != 2 or guided_stats.dtype != torch.int64 or tuple(guided_stats.shape) != (stats.shape[0], GUIDED_ROW):
+        raise ValueError(f"guided_stats must be int64 [{stats.shape[0]}, {GUIDED_ROW}] (new_guided_stats, the slots of stats), got "
+                         f"{guided_stats.dtype} {tuple(guided_stats.shape)}")
+    t = torch.empty(b, h, w, dtype=torch.float32, device=image.device) if transmission else None
+    if b:
+        ws = N.workspace.get(image.device, N.lib().awseg_dehaze_guided_workspace(b, h, w), tag="dehaze_guided")
+        N.call("awseg_dehaze_guided", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), p["radius"], p["omega"], p["t_min"],
+               p["airlight_min"], p["guided_radius"], p["guided_eps"], N.ptr(cond), N.ptr(out), N.ptr(airlight), N.ptr(t), N.ptr(stats),
+               N.ptr(guided_stats), stats.shape[0], N.ptr(ws), N.stream())
+    return (out, airlight, t) if transmission else (out, airlight)
+
+
+def guided_stats_to_numpy(stats) -> dict:
+    """int64 [..., GUIDED_ROW] -> {field: int64 [...]} for GUIDED_FIELDS."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != GUIDED_ROW:
+        raise ValueError(f"guided rows hold {GUIDED_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(GUIDED_FIELDS)}
 
 
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent

@@ -65,6 +65,55 @@ int awseg_dehaze(const float* image, int64_t batch, int channels, int64_t height
                  const int32_t* cond, float* restored, float* airlight, int64_t* stats, int n_slots,
                  void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  The same front-end with the guided-filter refinement of the transmission (He, Sun, Tang, "Guided Image Filtering", 2010/2013):
+ *  the patch transmission filtered with the frame's own luma as the guide
+ *       replaces nothing: the reference has no restoration baseline
+ * ------------------------------------------------------------------------- *
+ * awseg_dehaze_guided: image, mean, std, radius, omega, t_min, airlight_min, cond, restored, airlight, stats, n_slots as for
+ * awseg_dehaze (which this entry point leaves as it is); guided_radius R in [1, AWSEG_GUIDED_MAX_RADIUS], guided_eps eps in
+ * [1e-4, 1].  v_c, pass A, pass B and A_c are those of awseg_dehaze.  Then, one float32 operation per step, parenthesised as written,
+ * no contraction:
+ *     n = fminf(fminf(v_0 / A_0, v_1 / A_1), v_2 / A_2);   e = (2r+1)^2 window minimum of n (pass C with refine 0)
+ *     p = 1.0f - omega * e                                  (the raw patch transmission, before any clamp)
+ *     g = (0.299f * v_0 + 0.587f * v_1) + 0.114f * v_2      (the guide)
+ *   the box sum S(x) of a map x over (2R+1)^2 windows, positions outside the frame being +0.0f:
+ *     h[y,x] = ((x[y,x-R] + x[y,x-R+1]) + ...) + x[y,x+R]   left to right, 2R additions
+ *     S[y,x] = ((h[y-R,x] + h[y-R+1,x]) + ...) + h[y+R,x]   top to bottom, 2R additions (rows outside the frame are rows of +0.0f)
+ *     N[y,x] = (rows of the window inside the frame) * (columns of the window inside the frame), as float32 (exact);  M(x) = S(x) / N
+ *   The order of the additions is part of the contract: a sliding-window or a tree sum gives other bits.
+ *     mg = M(g);  mp = M(p);  mgg = M(g * g);  mgp = M(g * p)          (the products are taken per position, before the sums)
+ *     var = mgg - mg * mg;  cov = mgp - mg * mp;  a = cov / (var + eps);  b = mp - a * mg
+ *     q = M(a) * g + M(b)
+ *     t = fmaxf(fminf(q, 1.0f), t_min);   J_c and restored[b,c,p] from t as in pass C;   transmission[b,p] = t
+ * The lower bound of eps keeps var + eps > 0 under float32 cancellation (on values in [0, 1] the rounding of a window sum is about
+ * 65 * 2^-24).  transmission float32 [B, H, W] or NULL (then t is not stored).
+ * stats: the row of awseg_dehaze with the refined t in [5].  guided_stats int64 [n_slots][AWSEG_GUIDED_ROW], the same slot rule,
+ * accumulated and never cleared:
+ *     [0] pixels with q > 1.0f   [1] pixels with q < t_min   [2] sum of rintf(fabsf(t - fmaxf(p, t_min)) * 65536.0f): how far the
+ *     filter moved the patch transmission   [3] pixels
+ * Integer sums only.
+ * Five kernels on the stream: A and B of awseg_dehaze; a coarse pass (pass C's staging and window minimum) that stores p; a
+ * coefficient kernel (a block owns AWSEG_DEHAZE_TILE_H x AWSEG_DEHAZE_TILE_W pixels, stages g and p with a halo of R, forms the four
+ * box sums one after another through one row-sum buffer, stores a and b); a final kernel (stages a and b with a halo of R, forms
+ * M(a), M(b), then t, J, the outputs and the counters).  16-byte loads and stores of the frames when W % 4 == 0 and image, restored
+ * and transmission are 16-byte aligned, scalar ones otherwise.
+ * workspace: awseg_dehaze_guided_workspace(batch, height, width) bytes
+ *     = ceil8(batch * (AWSEG_DEHAZE_FRAME_RECORD + height * width)) + 3 * ceil8(4 * batch * height * width),   ceil8(x) = (x + 7) & ~7:
+ * the records and the bin map of awseg_dehaze, then the float32 maps p, a, b, [B, H, W] each, every region beginning on an 8-byte
+ * boundary; 8-byte aligned (AWSEG_EALIGN otherwise).
+ * Refusals: those of awseg_dehaze with the same codes; also AWSEG_EINVAL for guided_radius outside [1, AWSEG_GUIDED_MAX_RADIUS],
+ * guided_eps outside [1e-4, 1] (NaN included) and a NULL guided_stats.  batch == 0 returns 0 and launches nothing. */
+#define AWSEG_GUIDED_ROW         4
+#define AWSEG_GUIDED_MAX_RADIUS  32
+int64_t awseg_dehaze_guided_workspace(int64_t batch, int64_t height, int64_t width);
+int awseg_dehaze_guided(const float* image, int64_t batch, int channels, int64_t height, int64_t width,
+                        const float* mean, const float* std, int radius, float omega, float t_min, float airlight_min,
+                        int guided_radius, float guided_eps, const int32_t* cond,
+                        float* restored, float* airlight, float* transmission /* [B,H,W] or NULL */,
+                        int64_t* stats /* [n_slots][AWSEG_DEHAZE_ROW] */, int64_t* guided_stats /* [n_slots][AWSEG_GUIDED_ROW] */,
+                        int n_slots, void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

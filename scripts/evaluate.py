@@ -141,9 +141,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--restoration-conditions", type=str, default=None, metavar="A,B",
                     help="restore only the frames of these comma-separated weather conditions (default: all, clean included; sets "
                          "evaluation.restoration_conditions)")
-    ap.add_argument("--restoration-refine", type=str, default=None, choices=("opening", "none"),
-                    help="transmission from the morphological opening of the normalised dark channel (default) or from He's plain "
-                         "patch minimum (sets evaluation.restoration.refine)")
+    ap.add_argument("--restoration-refine", type=str, default=None, choices=("opening", "none", "guided"),
+                    help="transmission from the morphological opening of the normalised dark channel (default), from He's plain "
+                         "patch minimum, or from the guided filter of the patch transmission (sets evaluation.restoration.refine)")
+    ap.add_argument("--restoration-guided-radius", type=int, default=None, metavar="R",
+                    help="window radius of the guided filter, 1 .. 32 (default min(4 radius, 32); needs --restoration-refine guided; "
+                         "sets evaluation.restoration.guided_radius)")
+    ap.add_argument("--restoration-guided-eps", type=float, default=None, metavar="EPS",
+                    help="regularisation of the guided filter, 1e-4 .. 1 (default 1e-3; needs --restoration-refine guided; sets "
+                         "evaluation.restoration.guided_eps)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -163,11 +169,17 @@ def apply_bootstrap_options(args, config) -> None:
 
 
 def apply_restoration_options(args, config) -> None:
-    """--restoration / --restoration-conditions / --restoration-refine into the configuration (the harness checks them)."""
+    """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* into the configuration (the harness
+    checks them)."""
     if args.restoration_refine is not None and args.restoration is None:
         raise ValueError("--restoration-refine needs --restoration dark_channel")
+    guided = {k: v for k, v in (("guided_radius", args.restoration_guided_radius), ("guided_eps", args.restoration_guided_eps))
+              if v is not None}
+    if guided and args.restoration_refine != "guided":
+        raise ValueError("--restoration-guided-radius and --restoration-guided-eps need --restoration-refine guided")
     if args.restoration is not None:
-        config.set("evaluation.restoration", args.restoration if args.restoration_refine is None else {"refine": args.restoration_refine})
+        config.set("evaluation.restoration", args.restoration if args.restoration_refine is None
+                   else {"refine": args.restoration_refine, **guided})
     if args.restoration_conditions is not None:
         config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
 
@@ -216,11 +228,15 @@ def main():
         results = evaluate_model(model, loader, metrics, device, config)
         if rank == 0:
             # (the weight sweep's grid and curves are lists of floats; every other value is a scalar)
-            plain = {k: [float(x) for x in v] if isinstance(v, (list, tuple)) else float(v) for k, v in results.items()}
+            # and restoration_refine, which names the refinement)
+            plain = {k: [float(x) for x in v] if isinstance(v, (list, tuple)) else v if isinstance(v, str) else float(v)
+                     for k, v in results.items()}
             generate_evaluation_report(plain, Path(args.output_dir))   # json + markdown, :277-392
             for k, v in plain.items():
                 if isinstance(v, list):
                     logger.info("%s: %s", k, " ".join(f"{x:.4f}" for x in v))
+                elif isinstance(v, str):
+                    logger.info("%s: %s", k, v)
                 else:
                     logger.info("%s: %.4f", k, v)
             if "overall_miou_restored" in plain:                       # --restoration: plain / restored / gain / mean t per condition

@@ -201,6 +201,15 @@ def main():
                 lambda frames=frames, refine=refine: ops.dehaze(frames, dzst, cond, radius=7, refine=refine, out=dz_out), "hbm", 24 * px * B)
     cases["dehaze r=15 refine=1, rendered-like frames"] = (
         lambda: ops.dehaze(chg_var, dzst, cond, radius=15, refine=1, out=dz_out), "hbm", 24 * px * B)
+    # the same front-end with the guided-filter transmission (refine: guided): five kernels per launch, ~1 300 float32 additions per
+    # pixel for the six box sums at R = 28 (their order is part of the contract), so the row is issue-bound, not HBM-bound: "of peak"
+    # is against the same 24 B/px.  Next to the opening and the image-quality rows above, on the same tensors
+    gfst = ops.new_guided_stats(dev, 6)
+    for tag, frames in (("rendered-like frames", chg_var), ("independent random frames", iq_rand[0])):
+        for gr in (28, 32):
+            cases[f"dehaze guided r=7 R={gr}, {tag}"] = (
+                lambda frames=frames, gr=gr: ops.dehaze_guided(frames, dzst, gfst, cond, radius=7, guided_radius=gr, out=dz_out),
+                "hbm", 24 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
