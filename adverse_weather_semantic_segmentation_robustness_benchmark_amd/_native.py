@@ -156,6 +156,8 @@ EXTENSION_SIGNATURES = {
     "awseg_dehaze_guided_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "awseg_dehaze_guided": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_i,
                                   c_p, c_p]),
+    "awseg_relight_workspace": (c_i64, [c_i64, c_i, c_i]),
+    "awseg_relight": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
 }
 
 

@@ -31,7 +31,7 @@ from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMetrics, bootstrap_metrics_from_replicates,
                       boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats,
                       failure_metrics_from_stats, iou_from_counts, guided_metrics_from_stats, quality_metrics_from_stats,
-                      restoration_metrics_from_stats, restored_quality_metrics_from_stats,
+                      relight_metrics_from_stats, restoration_metrics_from_stats, restored_quality_metrics_from_stats,
                       segment_metrics_from_stats, segment_options, severity_sweep_results, weight_grid_metrics_from_stats)
 
 logger = logging.getLogger(__name__)
@@ -284,6 +284,30 @@ def check_quality_budget(terms: int) -> None:
 RESTORATION_KEYS = ("radius", "omega", "t_min", "airlight_min", "refine")
 RESTORATION_REFINE = {"opening": 1, "none": 0}
 RESTORATION_GUIDED_KEYS = ("guided_radius", "guided_eps")               # only under refine: guided (awseg_dehaze_guided)
+RESTORATION_METHODS = ("dark_channel", "clahe")
+RESTORATION_RELIGHT_KEYS = ("grid", "clip_limit", "max_gain", "white_balance")      # only under method: clahe (awseg_relight)
+RESTORATION_WHITE_BALANCE = {"gray_world": True, "none": False}
+
+
+def _relight_option(spec: dict) -> dict:
+    """The dict of `evaluation.restoration` under method: clahe (without 'method') -> the checked option, without 'conditions'."""
+    foreign = sorted(set(spec) & (set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS)))
+    if foreign:
+        raise ValueError(f"evaluation.restoration: {foreign} belong to method: dark_channel, got method: clahe")
+    if set(spec) - set(RESTORATION_RELIGHT_KEYS):
+        raise ValueError(f"evaluation.restoration with method: clahe is a dict with keys among {list(RESTORATION_RELIGHT_KEYS)}, "
+                         f"got {spec!r}")
+    kw = dict(spec)
+    if "white_balance" in kw:
+        wb = kw["white_balance"]
+        if not isinstance(wb, str) or wb not in RESTORATION_WHITE_BALANCE:
+            raise ValueError(f"evaluation.restoration.white_balance is 'gray_world' or 'none', got {wb!r}")
+        kw["white_balance"] = RESTORATION_WHITE_BALANCE[wb]
+    try:
+        opt = ops.relight_parameters(**kw)
+    except ValueError as e:
+        raise ValueError(f"evaluation.restoration: {e}") from None
+    return {"method": "clahe", **opt}
 
 
 def restoration_option(config, images=None):
@@ -295,8 +319,14 @@ def restoration_option(config, images=None):
     `evaluation.restoration_conditions`: the weather conditions whose frames are restored, a list of names; absent: all of them,
     'clean' included (a blind front-end does not know the weather); checked also when the option is off.  `images`, when given, is
     a batch of frames: they must be float32 [B, 3, H, W].
+    Or 'clahe', or a dict with `method: clahe` and any of `grid` (n or [tiles_y, tiles_x], integers in [1, 16], default 8),
+    `clip_limit`, `max_gain` (numbers in [1, 64], defaults 2 and 8) and `white_balance` ('gray_world', the default, or 'none'):
+    every selected frame is relit by CLAHE on the luma with a grey-world white balance instead.  `method:
+    dark_channel` means what the absence of `method` means; the keys of one method are refused under the other.
     -> None when absent, else {'radius', 'omega', 't_min', 'airlight_min', 'refine' (0 / 1), 'conditions' (a list, or None = all)};
-    under 'guided': {'radius', 'omega', 't_min', 'airlight_min', 'guided_radius', 'guided_eps', 'refine': 'guided', 'conditions'}."""
+    under 'guided': {'radius', 'omega', 't_min', 'airlight_min', 'guided_radius', 'guided_eps', 'refine': 'guided', 'conditions'};
+    under 'clahe': {'method': 'clahe', 'grid' (ty, tx), 'clip_limit', 'max_gain', 'white_balance' (a bool), 'conditions'}.  Only
+    the last carries a 'method' key."""
     names = _cfg(config, "evaluation.restoration_conditions", None)
     if names is not None:
         if isinstance(names, (str, bytes, dict)) or not isinstance(names, (list, tuple)) or not names \
@@ -307,12 +337,26 @@ def restoration_option(config, images=None):
     if spec is None:
         return None
     if isinstance(spec, str):
-        if spec != "dark_channel":
-            raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict of its parameters, got {spec!r}")
-        spec = {}
+        if spec not in RESTORATION_METHODS:
+            raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe' or a dict of a method's parameters, got {spec!r}")
+        spec = {"method": spec}
+    if isinstance(spec, dict) and "method" in spec:
+        method = spec["method"]
+        if not isinstance(method, str) or method not in RESTORATION_METHODS:
+            raise ValueError(f"evaluation.restoration.method is 'dark_channel' or 'clahe', got {method!r}")
+        spec = {k: v for k, v in spec.items() if k != "method"}
+        if method == "clahe":
+            opt = _relight_option(spec)
+            if images is not None:
+                check_frames("restoration", images)
+            opt["conditions"] = names
+            return opt
+    if isinstance(spec, dict) and set(spec) & set(RESTORATION_RELIGHT_KEYS):
+        raise ValueError(f"evaluation.restoration: {sorted(set(spec) & set(RESTORATION_RELIGHT_KEYS))} belong to method: clahe, got "
+                         "method: dark_channel")
     if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS) - set(RESTORATION_GUIDED_KEYS):
-        raise ValueError(f"evaluation.restoration is 'dark_channel' or a dict with keys among "
-                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)}, got {spec!r}")
+        raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe' or a dict with keys among "
+                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)} (method: clahe: {list(RESTORATION_RELIGHT_KEYS)}), got {spec!r}")
     kw = {k: v for k, v in spec.items() if k != "refine"}
     refine = spec.get("refine", "opening")
     if not isinstance(refine, str) or (refine not in RESTORATION_REFINE and refine != "guided"):
@@ -398,6 +442,7 @@ COUNTERS = (
     ("weight_grid", ("stats",), None, None, None),
     ("restoration", ("counts", "oob", "stats"), None, None, "label outside [0, num_classes) in the confusion counters of the restored frames"),
     ("restoration_guided", ("stats",), None, None, None),
+    ("restoration_relight", ("stats",), None, None, None),
     ("restored_quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality "
                                                                           "counters of the restored frames"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
@@ -535,18 +580,27 @@ class EvalState:
         # for the forward on the dehazed frames, and the dehazing counters int64 [slot, AWSEG_DEHAZE_ROW].  'conditions': the weather
         # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
         self.restoration = None
+        relit = restoration is not None and restoration.get("method") == "clahe"
         if restoration is not None:
-            guided = restoration["refine"] == "guided"
-            params = (ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
+            guided = not relit and restoration["refine"] == "guided"
+            params = (ops.relight_parameters(**{k: restoration[k] for k in RESTORATION_RELIGHT_KEYS}) if relit
+                      else ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
                       else ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS}))
             acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
+            # under method: clahe there are no dehazing counters: 'stats' has no rows (the reduce and the result keys see nothing)
             self.restoration = {"params": params, "acc": acc, "counts": acc.counts, "oob": acc.oob,
                                 "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]},
-                                "stats": ops.new_dehaze_stats(device, 1 + len(conditions))}
+                                "stats": torch.zeros(0, ops.DEHAZE_ROW, dtype=torch.int64, device=device) if relit
+                                else ops.new_dehaze_stats(device, 1 + len(conditions))}
         # under refine: guided the counters of the filter, int64 [slot, AWSEG_GUIDED_ROW] (None otherwise: awseg_dehaze runs)
         self.restoration_guided = None
-        if restoration is not None and restoration["refine"] == "guided":
+        if restoration is not None and not relit and restoration["refine"] == "guided":
             self.restoration_guided = {"stats": ops.new_guided_stats(device, 1 + len(conditions))}
+        # under method: clahe the counters of the relighting, int64 [slot, AWSEG_RELIGHT_ROW] (None otherwise); awseg_relight
+        # produces the restored frames, everything behind it is the dehazer's second pass
+        self.restoration_relight = None
+        if relit:
+            self.restoration_relight = {"stats": ops.new_relight_stats(device, 1 + len(conditions))}
         # fidelity of the restored frames (only when the sweep, the image-quality counters and the restoration are all on): a SECOND
         # image-quality tensor, the restored frames against the same kept clean frames; the clean batch against its own kept rows
         self.restored_quality = None
@@ -674,6 +728,14 @@ class EvalState:
         twins = self.clean_frames["rows"].view((-1,) + tuple(images.shape[1:]))
         ops.image_quality(images, twins, rows, q["stats"], cond=cond, oob=q["oob"])
 
+    def check_relight_grid(self, images) -> None:
+        """Under method: clahe a tile is never empty: the grid may not have more tiles than the frames have rows or columns."""
+        if self.restoration_relight is not None and images.dim() == 4:
+            ty, tx = self.restoration["params"]["grid"]
+            if ty > images.shape[2] or tx > images.shape[3]:
+                raise ValueError(f"evaluation.restoration: a grid of {ty} x {tx} tiles does not fit frames of {images.shape[2]} x "
+                                 f"{images.shape[3]} pixels")
+
     def update_restoration(self, model, images, labels, kinds, cond, rows=None) -> None:
         """The batch's frames of the selected weather conditions (`kinds`: the loader's names, before a sweep's slot names), dehazed,
         through one more forward into the second confusion accumulator.  Nothing else sees the restored frames, but the second
@@ -688,7 +750,10 @@ class EvalState:
             images, labels, cond = images.index_select(0, idx), labels.index_select(0, idx), cond.index_select(0, idx)
             if rows is not None:
                 rows = rows.index_select(0, idx) if torch.is_tensor(rows) else [rows[i] for i in keep]
-        if self.restoration_guided is not None:
+        if self.restoration_relight is not None:
+            self.check_relight_grid(images)
+            restored, _ = ops.relight(images, self.restoration_relight["stats"], cond, **rs["params"])
+        elif self.restoration_guided is not None:
             restored, _ = ops.dehaze_guided(images, rs["stats"], self.restoration_guided["stats"], cond, **rs["params"])
         else:
             restored, _ = ops.dehaze(images, rs["stats"], cond, **rs["params"])
@@ -865,6 +930,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         check_frames("change_strata", images)
     if st.quality is not None:
         check_frames("image_quality", images)
+    st.check_relight_grid(images)                                     # before the forward: the first batch is refused as it comes
     bd, bs, sg = st.boundary, st.bootstrap, st.segments
     if bs is not None:
         if sources is None:
@@ -1064,9 +1130,13 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                   q["targets"], metrics.compute_robustness_degradation_ratio))
     if st.restoration is not None:
         rs = st.restoration
-        results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), rs["stats"].cpu().numpy(),
+        relit = st.restoration_relight is not None                 # no dehazing counters then: all-zero rows give no dehazing key
+        dehaze_stats = np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64) if relit else rs["stats"].cpu().numpy()
+        results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), dehaze_stats,
                                                       st.acc.conditions, metrics.num_classes, **sweep_kw,
                                                       degradation=metrics.compute_robustness_degradation_ratio))
+        if relit:
+            results.update(relight_metrics_from_stats(st.restoration_relight["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
         if st.restoration_guided is not None:
             results.update(guided_metrics_from_stats(st.restoration_guided["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
             results["restoration_refine"] = "guided"

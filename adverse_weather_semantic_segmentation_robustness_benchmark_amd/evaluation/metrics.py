@@ -854,6 +854,47 @@ def guided_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: 
     return res
 
 
+def relight_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0) -> Dict[str, Any]:
+    """Result keys of the night relighting (evaluation.restoration with method: clahe) from its counters int64
+    [1 + len(conditions), AWSEG_RELIGHT_ROW] (include/awseg_restore.h; slot 0 = every restored frame, slot 1 + k = conditions[k]).
+    Host only, float64 on exact integer sums; every value a float but restoration_method.  With <n> a condition (under a sweep its
+    slots and each '<kind>' from the summed counters of its levels; slot 0 under the prefix mean_ instead of the suffix):
+      luma_<n>, luma_<n>_restored        mean luma of the frames as they came and as they were restored (pixels > 0)
+      relight_gain_<n>                   their ratio, restored / plain (plain luma > 0)
+      white_balance_gain_{r,g,b}_<n>     the frames' mean grey-world gains (frames > 0)
+      relight_capped_fraction_<n>        share of the pixels whose luma gain was held at max_gain
+      relight_saturated_fraction_<n>     share of the channel values (3 per pixel) that left [0, 1] upwards and were clipped
+    and restoration_method = 'clahe'; restoration_nonfinite_values (slot 0) only when non-zero.  A ratio without a denominator is
+    absent, not 0."""
+    conditions = list(conditions)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.shape != (1 + len(conditions), ops.RELIGHT_ROW):
+        raise ValueError(f"relight stats must be int64 [{1 + len(conditions)}, {ops.RELIGHT_ROW}], got {raw.shape}")
+    named = [(None, raw[0])] + [(name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        named.append((kind, raw[[1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels) + 1)]].sum(0)))
+    res: Dict[str, Any] = {"restoration_method": "clahe"}
+    for name, row in named:
+        dec = {f: int(v) for f, v in ops.relight_stats_to_numpy(row).items()}
+
+        def key(metric, tail="", name=name):
+            return f"mean_{metric}{tail}" if name is None else f"{metric}_{name}{tail}"
+        if dec["frames"] > 0:
+            for c, ch in enumerate("rgb"):
+                res[key(f"white_balance_gain_{ch}")] = float(dec[f"sum_gain_{c}"] * ops.RELIGHT_UNIT / dec["frames"])
+        if dec["pixels"] > 0:
+            res[key("luma")] = float(dec["sum_luma"] * ops.RELIGHT_UNIT / dec["pixels"])
+            res[key("luma", "_restored")] = float(dec["sum_luma_restored"] * ops.RELIGHT_UNIT / dec["pixels"])
+            if dec["sum_luma"] > 0:
+                res[key("relight_gain")] = float(dec["sum_luma_restored"] / dec["sum_luma"])
+            res[key("relight_capped_fraction")] = float(dec["capped_pixels"] / dec["pixels"])
+            res[key("relight_saturated_fraction")] = float(dec["saturated_values"] / (3.0 * dec["pixels"]))
+    nonfinite = int(ops.relight_stats_to_numpy(raw[0])["nonfinite_values"])
+    if nonfinite:
+        res["restoration_nonfinite_values"] = float(nonfinite)
+    return res
+
+
 IQ_PLAIN_STEMS = ("mse", "psnr", "mean_abs_change", "ssim", "ssim_luminance", "ssim_contrast")
 
 

@@ -67,20 +67,32 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
 
 def restoration_section(results: Dict[str, Any]) -> list:
     """Input restoration (evaluation.restoration): one line per condition with the mIoU of the frames as they came, of the same
-    frames dehazed by the dark-channel prior, the difference, and the mean transmission the front-end estimated."""
+    frames dehazed by the dark-channel prior, the difference, and the mean transmission the front-end estimated.  Under method:
+    clahe (restoration_method in the results) the frames were relit instead and the luma gain stands where the mean transmission
+    does, the share of gain-capped pixels where the airlight does."""
     names = [m.group(1) for k in results for m in [re.match(r"miou_(.+)_restored$", k)] if m]
 
     def cell(key):
         return f"{results[key]:.3f}" if key in results else "-"
-    lines = ["", "## Input Restoration", "", "Every selected frame dehazed by the dark-channel prior in front of the model and scored "
-             "again.  Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); mean t: the mean "
-             "estimated transmission (1 = nothing removed).", ""]
+    relit = results.get("restoration_method") == "clahe"
+    lines = ["", "## Input Restoration", ""]
+    if relit:
+        lines += ["Method: clahe.  Every selected frame relit by contrast-limited adaptive histogram equalisation of the luma with a "
+                  "grey-world white balance in front of the model and scored again.  Gain: restored - plain mIoU on the same frames "
+                  "(negative: the front-end costs accuracy); luma gain: mean luma of the restored frames over that of the frames as "
+                  "they came; capped: share of the pixels whose gain was held at the limit.", ""]
+    else:
+        lines += ["Method: dark_channel.  Every selected frame dehazed by the dark-channel prior in front of the model and scored "
+                  "again.  Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); mean t: the mean "
+                  "estimated transmission (1 = nothing removed).", ""]
     # under refine: guided two more cells per line (how far the filter moved the patch transmission, the share of clamped pixels);
     # with the image-quality counters two more (PSNR and SSIM of the restored frames against the clean twins, with the gain over
     # the corrupted ones)
     guided = any(k.startswith("transmission_refinement_") for k in results)
     fidelity = any(re.match(r"(psnr|ssim)_.+_restored$", k) for k in results)
-    head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain", "Mean t", "Airlight", "Degradation restored"]
+    head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain"] + (["Luma gain", "Capped"] if relit else ["Mean t", "Airlight"]) \
+        + ["Degradation restored"]
+    fifth, sixth = ("relight_gain", "relight_capped_fraction") if relit else ("transmission_mean", "airlight")
     head += ["Refinement", "Clamped"] * guided + ["PSNR restored (gain)", "SSIM restored (gain)"] * fidelity
     if "restoration_refine" in results:
         lines += [f"Transmission refinement: {results['restoration_refine']} filter (DESIGN.md 10n-bis).", ""]
@@ -99,10 +111,15 @@ def restoration_section(results: Dict[str, Any]) -> list:
         return "".join(f" {c} |" for c in cells)
     for n in names:
         lines.append(f"| {n} | {cell('miou_' + n)} | {cell('miou_' + n + '_restored')} | {cell('restoration_gain_' + n)} | "
-                     f"{cell('transmission_mean_' + n)} | {cell('airlight_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |"
+                     f"{cell(fifth + '_' + n)} | {cell(sixth + '_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |"
                      + more(n))
-    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_transmission')} | "
-                 f"{cell('mean_airlight')} | - |" + more(None))
+    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_' + fifth if relit else 'mean_transmission')} | "
+                 f"{cell('mean_' + sixth)} | - |" + more(None))
+    if relit:
+        gains = [f"{results[k]:.3f}" for k in ("mean_white_balance_gain_r", "mean_white_balance_gain_g", "mean_white_balance_gain_b")
+                 if k in results]
+        if len(gains) == 3:
+            lines += ["", f"- **Mean white-balance gains** (r / g / b): {' / '.join(gains)}"]
     extra = [f"- **Clean cost** (plain - restored mIoU of the clean frames): {results['restoration_clean_cost']:.3f}"] \
         if "restoration_clean_cost" in results else []
     extra += [f"- **{title}**: {int(results[key])}" for key, title in (("restoration_nonfinite_values", "Input values that are not finite"),

@@ -652,8 +652,10 @@ def dehaze_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, refine=
             "airlight_min": unit("airlight_min", airlight_min), "refine": integer("refine", refine, 0, 1)}
 
 
-def _dehaze_buffers(who: str, image, stats, cond, mean, std, out):
-    """The checks dehaze() and dehaze_guided() share -> (contiguous image, B, H, W, mean, std, stats, out, airlight [B, 3])."""
+def _dehaze_buffers(who: str, image, stats, cond, mean, std, out, row: Optional[int] = None, new_stats=None):
+    """The checks dehaze(), dehaze_guided() and relight() share -> (contiguous image, B, H, W, mean, std, stats, out, airlight
+    [B, 3]).  `row`, `new_stats`: the width of a counter row and what makes one (default: the dehazer's)."""
+    row, new_stats = (DEHAZE_ROW, new_dehaze_stats) if row is None else (row, new_stats)
     if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
         raise ValueError(f"{who}: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
     b, _, h, w = (int(d) for d in image.shape)
@@ -668,9 +670,9 @@ def _dehaze_buffers(who: str, image, stats, cond, mean, std, out):
     if m.size != 3 or s.size != 3 or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
         raise ValueError(f"{who}: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
     if stats is None:
-        stats = new_dehaze_stats(image.device, 1)
-    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != DEHAZE_ROW:
-        raise ValueError(f"stats must be int64 [slots, {DEHAZE_ROW}] (new_dehaze_stats), got {stats.dtype} {tuple(stats.shape)}")
+        stats = new_stats(image.device, 1)
+    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != row:
+        raise ValueError(f"stats must be int64 [slots, {row}] ({new_stats.__name__}), got {stats.dtype} {tuple(stats.shape)}")
     if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
         raise ValueError("cond must be int32 [B]")
     image = image.contiguous()
@@ -787,6 +789,88 @@ def guided_stats_to_numpy(stats) -> dict:
     if raw.shape[-1] != GUIDED_ROW:
         raise ValueError(f"guided rows hold {GUIDED_ROW} counters, got {raw.shape[-1]}")
     return {f: raw[..., i] for i, f in enumerate(GUIDED_FIELDS)}
+
+
+# ------------------------------------------------ night relighting: CLAHE + grey world (include/awseg_restore.h)
+RELIGHT_FIELDS = ("frames", "sum_gain_0", "sum_gain_1", "sum_gain_2", "pixels", "sum_luma", "sum_luma_restored", "nonfinite_values",
+                  "capped_pixels", "saturated_values")
+RELIGHT_ROW = len(RELIGHT_FIELDS)      # AWSEG_RELIGHT_ROW
+RELIGHT_MAX_TILES = 16                 # AWSEG_RELIGHT_MAX_TILES
+RELIGHT_FRAME_RECORD = 48              # AWSEG_RELIGHT_FRAME_RECORD: workspace bytes per frame beside its tiles
+RELIGHT_TILE_BYTES = 1536              # AWSEG_RELIGHT_TILE_BYTES: 256 uint32 histogram words and 256 uint16 table entries per tile
+RELIGHT_RANGE = (1.0, 64.0)            # clip_limit and max_gain
+RELIGHT_UNIT = 2.0 ** -16              # the gain and luma sums are int64 in fixed point: exact, order-independent
+
+
+def new_relight_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, RELIGHT_ROW]: per slot the row RELIGHT_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_relight_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), RELIGHT_ROW, dtype=torch.int64, device=device)
+
+
+def relight_parameters(grid=(8, 8), clip_limit=2.0, max_gain=8.0, white_balance=True) -> dict:
+    """The checked parameters of relight(): grid an integer n (n x n tiles) or a pair (tiles_y, tiles_x) of integers in [1, 16];
+    clip_limit, max_gain numbers in [1, 64] (also as float32); white_balance a bool (or 0 / 1).  ValueError otherwise.
+    -> {'grid': (ty, tx), 'clip_limit', 'max_gain', 'white_balance': bool}."""
+    def tile_count(v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= RELIGHT_MAX_TILES:
+            raise ValueError(f"relight: grid is an integer or a pair of integers in [1, {RELIGHT_MAX_TILES}], got {grid!r}")
+        return int(v)
+
+    def bounded(name, v):
+        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
+        f = float(np.float32(v)) if ok else 0.0
+        if not (ok and RELIGHT_RANGE[0] <= f <= RELIGHT_RANGE[1]):
+            raise ValueError(f"relight: {name} is a number in [1, 64] (also as float32), got {v!r}")
+        return f
+    if isinstance(grid, (list, tuple)):
+        if len(grid) != 2:
+            raise ValueError(f"relight: grid is an integer or a pair of integers in [1, {RELIGHT_MAX_TILES}], got {grid!r}")
+        tiles = (tile_count(grid[0]), tile_count(grid[1]))
+    else:
+        tiles = (tile_count(grid),) * 2
+    if not isinstance(white_balance, (bool, np.bool_)) and not (isinstance(white_balance, (int, np.integer)) and white_balance in (0, 1)):
+        raise ValueError(f"relight: white_balance is a bool, got {white_balance!r}")
+    return {"grid": tiles, "clip_limit": bounded("clip_limit", clip_limit), "max_gain": bounded("max_gain", max_gain),
+            "white_balance": bool(white_balance)}
+
+
+def relight_workspace_bytes(b: int, tiles_y: int, tiles_x: int) -> int:
+    """The closed form of awseg_relight_workspace: per frame a record, and per tile a histogram and a table."""
+    b, tiles_y, tiles_x = max(int(b), 1), max(int(tiles_y), 1), max(int(tiles_x), 1)
+    return b * (RELIGHT_FRAME_RECORD + tiles_y * tiles_x * RELIGHT_TILE_BYTES)
+
+
+def relight(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, grid=(8, 8),
+            clip_limit: float = 2.0, max_gain: float = 8.0, white_balance=True, mean=None, std=None,
+            out: Optional[torch.Tensor] = None):
+    """Night relighting of the loader's normalised float32 frames `image` [B, 3, H, W]: contrast-limited adaptive histogram
+    equalisation of the luma (CLAHE, Zuiderveld 1994) on a `grid` of tiles with a grey-world white balance, as
+    include/awseg_restore.h defines it step by step -> (restored float32 [B, 3, H, W], gains float32 [B, 3]: the white-balance
+    gains).  `stats` (new_relight_stats; slot 0 + slot 1 + cond[b], cond device int32 [B]) takes the counters of RELIGHT_FIELDS;
+    without it they go to a tensor nobody reads.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`: where
+    the restored frames go (contiguous, not `image`).  The grid may not have more tiles than the frame has rows or columns.  There
+    is no CPU path."""
+    p = relight_parameters(grid, clip_limit, max_gain, white_balance)
+    image, b, h, w, m, s, stats, out, gains = _dehaze_buffers("relight", image, stats, cond, mean, std, out, RELIGHT_ROW, new_relight_stats)
+    ty, tx = p["grid"]
+    if ty > h or tx > w:
+        raise ValueError(f"relight: a grid of {ty} x {tx} tiles does not fit frames of {h} x {w} pixels (a tile is never empty)")
+    if b == 0:
+        return out, gains
+    ws = N.workspace.get(image.device, N.lib().awseg_relight_workspace(b, ty, tx), tag="relight")
+    N.call("awseg_relight", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), ty, tx, p["clip_limit"], p["max_gain"],
+           int(p["white_balance"]), N.ptr(cond), N.ptr(out), N.ptr(gains), N.ptr(stats), stats.shape[0], N.ptr(ws), N.stream())
+    return out, gains
+
+
+def relight_stats_to_numpy(stats) -> dict:
+    """int64 [..., RELIGHT_ROW] -> {field: int64 [...]} for RELIGHT_FIELDS; the gain and luma sums stay in units of RELIGHT_UNIT."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != RELIGHT_ROW:
+        raise ValueError(f"relight rows hold {RELIGHT_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(RELIGHT_FIELDS)}
 
 
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent

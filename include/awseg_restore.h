@@ -114,6 +114,71 @@ int awseg_dehaze_guided(const float* image, int64_t batch, int channels, int64_t
                         int64_t* stats /* [n_slots][AWSEG_DEHAZE_ROW] */, int64_t* guided_stats /* [n_slots][AWSEG_GUIDED_ROW] */,
                         int n_slots, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Night relighting: contrast-limited adaptive histogram equalisation of the luma (CLAHE; Zuiderveld 1994, the algorithm of
+ *  OpenCV's createCLAHE) with a grey-world white balance, the second blind front-end of the evaluation
+ *       replaces nothing: the reference has no restoration baseline
+ * ------------------------------------------------------------------------- *
+ * awseg_relight: image, mean, std (HOST float32[3]), cond, restored, stats, n_slots, workspace, stream as for awseg_dehaze (which
+ * this entry point leaves as it is).  tiles_y, tiles_x in [1, AWSEG_RELIGHT_MAX_TILES], tiles_y <= H, tiles_x <= W; clip_limit and
+ * max_gain in [1, 64]; white_balance 0 or 1.  Every step is one float32 operation with the parenthesisation given (no contraction,
+ * correctly rounded division) unless it is written in integers or in double, so numpy gives the same bits.  Frame b, pixel (y, x):
+ *   input    v_c = fminf(fmaxf(image[b,c,y,x] * std[c] + mean[c], 0), 1)   (NaN -> 0; every input value that is not finite is counted:
+ *            the v_c of awseg_dehaze);   l = (0.299f * v_0 + 0.587f * v_1) + 0.114f * v_2;   bin = min((int)(l * 255.0f), 255)
+ *   tiles    tile row i covers the rows [floor(i H / tiles_y), floor((i + 1) H / tiles_y)), tile column j the columns
+ *            [floor(j W / tiles_x), floor((j + 1) W / tiles_x)): tiles need not be equal and are never empty.  No padding and no
+ *            reflection: OpenCV pads the frame to a multiple of the grid, this does not, so the tables differ from OpenCV's wherever
+ *            the grid does not divide the frame.
+ *   pass A   per (frame, tile) the 256-bin histogram hist of bin (uint32); per frame S_c = sum of (int64) rintf(v_c * 65536.0f)
+ *            and the count of the input values that are not finite
+ *   pass B   per tile of n pixels, in integers except where written:
+ *              L = max(1, (int)((clip_limit * (float) n) / 256.0f));   E = sum_k max(hist[k] - L, 0)
+ *              h[k] = min(hist[k], L) + E / 256;   r = E % 256;   step = max(256 / r, 1) (r > 0):  h[0], h[step], h[2 step], ...
+ *              each get one more until r are given (ONE redistribution pass, OpenCV's)
+ *              cdf[k] = sum_{m <= k} h[m]  (cdf[255] == n);   lut[k] = (uint16)((cdf[k] * 65535 + n / 2) / n)  in 64-bit arithmetic
+ *            per frame:  m_c = (float)((double) S_c / ((double)(H * W) * 65536.0));   grey = ((m_0 + m_1) + m_2) / 3.0f;
+ *              k_c = fminf(fmaxf(grey / fmaxf(m_c, 1.0f / 256.0f), 0.25f), 4.0f), or 1.0f when white_balance == 0;  gains[b][c] = k_c
+ *   pass C   cy_i = (float)(y0_i + y1_i - 1) * 0.5f, the centre of tile row i = rows [y0_i, y1_i).  i0 = the largest i with
+ *            cy_i <= y (compared exactly, as integers: y0_i + y1_i - 1 <= 2 y).  None: i0 = i1 = 0, wy = 0.  i0 = tiles_y - 1: i1 = i0, wy = 0.  Otherwise i1 = i0 + 1 and
+ *            wy = ((float) y - cy_i0) / (cy_i1 - cy_i0).  Columns likewise: j0, j1, wx.
+ *            a, b, c, d = (float) lut[i0][j0][bin], lut[i0][j1][bin], lut[i1][j0][bin], lut[i1][j1][bin]
+ *              top = a + wx * (b - a);   bot = c + wx * (d - c);   l' = (top + wy * (bot - top)) / 65535.0f
+ *              raw = l' / fmaxf(l, 1.0f / 256.0f);   g = fminf(raw, max_gain)
+ *              u_c = (v_c * k_c) * g;   J_c = fminf(fmaxf(u_c, 0), 1);   restored[b,c,y,x] = (J_c - mean[c]) / std[c]
+ *            The table is indexed by the 8-bit bin, not interpolated within it: all pixels of one bin and one position weight get
+ *            one output luma.  The frames come from 8-bit renderings, so nothing is lost there.
+ * restored float32 [B, 3, H, W] (must not overlap image); gains float32 [B][3] = k.
+ * stats int64 [n_slots][AWSEG_RELIGHT_ROW] (accumulated, never cleared), the slot rule of awseg_dehaze (slot 0, and slot
+ * 1 + cond[b] when 0 <= cond[b] < n_slots - 1; cond device int32[B] or NULL).  Row:
+ *     [0] frames   [1..3] sum of rintf(k_c * 65536.0f), c = 0, 1, 2   [4] pixels   [5] sum of rintf(l * 65536.0f)
+ *     [6] sum of rintf(fminf(l_out, 1.0f) * 65536.0f), l_out = (0.299f * J_0 + 0.587f * J_1) + 0.114f * J_2
+ *     [7] input values that are not finite   [8] pixels with raw > max_gain   [9] channel values with u_c > 1.0f
+ * Integer sums only: independent of the grid, additive over launches and ranks.  A term is at most 2^18 units (a gain of 4), the
+ * per-pixel terms at most 2^16, so a stats tensor holds 2^46 pixels (and 2^44 frames) before a sum could wrap.
+ * On the stream: one clear of the records and histograms, then three kernels.  A and C are streaming passes over strips of rows
+ * (16-byte loads and stores when W % 4 == 0 and image and restored are 16-byte aligned, scalar ones otherwise; the same bits either
+ * way; a group of four pixels may straddle two tiles); A counts into LDS histograms and adds them to the tiles' words with integer
+ * atomics; B is one 256-thread block per tile and one more per frame for the gains and the frame's counters; C stages the tables
+ * of its two tile rows in LDS.
+ * workspace: awseg_relight_workspace(batch, tiles_y, tiles_x) bytes
+ *     = batch * (AWSEG_RELIGHT_FRAME_RECORD + tiles_y * tiles_x * AWSEG_RELIGHT_TILE_BYTES):
+ * the frames' records (int64 S_0, S_1, S_2, non-finite values; float32 k_0, k_1, k_2 and a pad), then every tile's 256 uint32
+ * histogram words, then every tile's 256 uint16 table entries; every region begins on an 8-byte boundary; 8-byte aligned
+ * (AWSEG_EALIGN otherwise).  The launcher clears the records and the histograms on the stream.
+ * AWSEG_EINVAL for a NULL pointer (cond excepted), channels != 3, a size < 1 (batch < 0), n_slots < 1, a grid outside
+ * [1, AWSEG_RELIGHT_MAX_TILES] or larger than the frame, clip_limit or max_gain outside [1, 64] (NaN included), white_balance other
+ * than 0 or 1, a std that is not finite and > 0 or a non-finite mean; AWSEG_ERANGE for batch > 65535 or H * W >= 2^31;
+ * batch == 0 returns 0 and launches nothing. */
+#define AWSEG_RELIGHT_ROW           10
+#define AWSEG_RELIGHT_MAX_TILES     16
+#define AWSEG_RELIGHT_FRAME_RECORD  48
+#define AWSEG_RELIGHT_TILE_BYTES    1536
+int64_t awseg_relight_workspace(int64_t batch, int tiles_y, int tiles_x);
+int awseg_relight(const float* image, int64_t batch, int channels, int64_t height, int64_t width,
+                  const float* mean, const float* std, int tiles_y, int tiles_x, float clip_limit, float max_gain,
+                  int white_balance, const int32_t* cond, float* restored, float* gains /* [B][3] */,
+                  int64_t* stats /* [n_slots][AWSEG_RELIGHT_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,9 +135,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
                     help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
                          "(sets evaluation.image_quality_targets)")
-    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel",),
-                    help="dehaze every frame by the dark-channel prior in front of the model and score it a second time: plain and "
-                         "restored mIoU, the gain and the mean transmission per condition (sets evaluation.restoration)")
+    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe"),
+                    help="restore every frame in front of the model and score it a second time: plain and restored mIoU and the gain "
+                         "per condition.  dark_channel: dehazing by the dark-channel prior (with the mean transmission); clahe: night "
+                         "relighting by CLAHE on the luma with a grey-world white balance (with the luma gain).  Sets "
+                         "evaluation.restoration")
     ap.add_argument("--restoration-conditions", type=str, default=None, metavar="A,B",
                     help="restore only the frames of these comma-separated weather conditions (default: all, clean included; sets "
                          "evaluation.restoration_conditions)")
@@ -150,6 +152,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--restoration-guided-eps", type=float, default=None, metavar="EPS",
                     help="regularisation of the guided filter, 1e-4 .. 1 (default 1e-3; needs --restoration-refine guided; sets "
                          "evaluation.restoration.guided_eps)")
+    ap.add_argument("--restoration-grid", type=str, default=None, metavar="N|TYxTX",
+                    help="tiles of the CLAHE grid, 8 or 8x8, 1 .. 16 each way (default 8; needs --restoration clahe; sets "
+                         "evaluation.restoration.grid)")
+    ap.add_argument("--restoration-clip-limit", type=float, default=None, metavar="C",
+                    help="clip limit of the tile histograms in multiples of the mean bin, 1 .. 64 (default 2; needs --restoration "
+                         "clahe; sets evaluation.restoration.clip_limit)")
+    ap.add_argument("--restoration-max-gain", type=float, default=None, metavar="G",
+                    help="largest luma gain of a pixel, 1 .. 64 (default 8; needs --restoration clahe; sets "
+                         "evaluation.restoration.max_gain)")
+    ap.add_argument("--restoration-white-balance", type=str, default=None, choices=("gray_world", "none"),
+                    help="white balance of the relit frames (default gray_world; needs --restoration clahe; sets "
+                         "evaluation.restoration.white_balance)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -168,9 +182,33 @@ def apply_bootstrap_options(args, config) -> None:
             config.set(key, getattr(args, flag))
 
 
+def parse_restoration_grid(text: str):
+    """'8' -> 8, '8x4' -> [8, 4] (tile rows x tile columns); ValueError otherwise.  The harness checks the range."""
+    parts = text.lower().split("x")
+    if len(parts) not in (1, 2) or not all(p.strip().isdigit() for p in parts):
+        raise ValueError(f"--restoration-grid is N or TYxTX (integers), got {text!r}")
+    values = [int(p) for p in parts]
+    return values[0] if len(values) == 1 else values
+
+
 def apply_restoration_options(args, config) -> None:
-    """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* into the configuration (the harness
-    checks them)."""
+    """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* and the flags of --restoration clahe
+    into the configuration (the harness checks them)."""
+    relight = {k: v for k, v in (("grid", args.restoration_grid), ("clip_limit", args.restoration_clip_limit),
+                                 ("max_gain", args.restoration_max_gain), ("white_balance", args.restoration_white_balance))
+               if v is not None}
+    if relight and args.restoration != "clahe":
+        raise ValueError("--restoration-grid, --restoration-clip-limit, --restoration-max-gain and --restoration-white-balance need "
+                         "--restoration clahe")
+    if args.restoration == "clahe":
+        if args.restoration_refine is not None or args.restoration_guided_radius is not None or args.restoration_guided_eps is not None:
+            raise ValueError("--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to clahe")
+        if "grid" in relight:
+            relight["grid"] = parse_restoration_grid(relight["grid"])
+        config.set("evaluation.restoration", {"method": "clahe", **relight} if relight else "clahe")
+        if args.restoration_conditions is not None:
+            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
+        return
     if args.restoration_refine is not None and args.restoration is None:
         raise ValueError("--restoration-refine needs --restoration dark_channel")
     guided = {k: v for k, v in (("guided_radius", args.restoration_guided_radius), ("guided_eps", args.restoration_guided_eps))

@@ -210,6 +210,18 @@ def main():
             cases[f"dehaze guided r=7 R={gr}, {tag}"] = (
                 lambda frames=frames, gr=gr: ops.dehaze_guided(frames, dzst, gfst, cond, radius=7, guided_radius=gr, out=dz_out),
                 "hbm", 24 * px * B)
+    # night relighting (evaluation.restoration: clahe): tile histograms + tables + interpolation, three kernels per launch.  The
+    # histogram pass reads the frame (12 B/px), the final pass reads and writes it (24 B/px): 36 B/px and no window work, so the row
+    # should sit near the streaming kernels, not near the dehazer.  Night-like: the rendered-like clean frames darkened by 0.4 and
+    # tinted by the renderer's night gains (0.8, 0.85, 1.2), which crowd a few bins of every tile's histogram
+    rl_mean = torch.tensor([0.485, 0.456, 0.406], device=dev).view(1, 3, 1, 1)
+    rl_std = torch.tensor([0.229, 0.224, 0.225], device=dev).view(1, 3, 1, 1)
+    rl_tint = torch.tensor([0.8, 0.85, 1.2], device=dev).view(1, 3, 1, 1)
+    rl_night = ((((chg_clean * rl_std + rl_mean).clamp_(0, 1) * 0.4 * rl_tint).clamp_(0, 1) - rl_mean) / rl_std).contiguous()
+    rlst = ops.new_relight_stats(dev, 6)
+    for tag, frames in (("rendered-like frames", chg_var), ("night-like frames", rl_night), ("independent random frames", iq_rand[0])):
+        cases[f"relight 8x8, {tag}"] = (
+            lambda frames=frames: ops.relight(frames, rlst, cond, grid=(8, 8), out=dz_out), "hbm", 36 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
