@@ -158,6 +158,8 @@ EXTENSION_SIGNATURES = {
                                   c_p, c_p]),
     "awseg_relight_workspace": (c_i64, [c_i64, c_i, c_i]),
     "awseg_relight": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "awseg_deocclude_workspace": (c_i64, [c_i64, c_i64, c_i64]),
+    "awseg_deocclude": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
 }
 
 

@@ -310,6 +310,7 @@ inline bool in_unit(float v) { return v > 0.0f && v <= 1.0f; }             // Na
     if (!awseg_aligned(workspace, 8)) return AWSEG_EALIGN;                                                                      \
     if (batch == 0) return 0
 
+#ifndef AWSEG_DEHAZE_TILES_NO_LAUNCHER                                     // deocclude.hip: uses neither, and would carry copies of A and B
 // Clears the frames' records and runs passes A and B on `s`: afterwards every record holds its frame's airlight sums and the bin
 // map is written.  Leaves g at geometry(radius, 0).
 inline int estimate_airlight(const float* image, int64_t batch, int H, int W, int radius, dz_args& g, bool vec, unsigned char* ws,
@@ -338,6 +339,7 @@ inline int estimate_airlight(const float* image, int64_t batch, int H, int W, in
     }
     return 0;
 }
+#endif  // AWSEG_DEHAZE_TILES_NO_LAUNCHER
 
 }  // namespace
 #endif  // AWSEG_DEHAZE_TILES_H

@@ -1,0 +1,443 @@
+// deocclude.hip — rain and snow removal in front of the model: bright occluders narrower than a window, found by the
+// white top-hat of every channel and filled from their unmasked neighbours; the arithmetic include/awseg_restore.h states step by
+// step: every output bit is what numpy gives.
+//
+// awseg_deocclude: two kernels on the caller's stream, no host synchronisation, no block waits for another.  Both run on the tiles
+// of the dehazer (dehaze_tiles.h, whose constants, v_c and reductions they share) and walk the three channels one after another
+// through one staged plane and one scratch plane, so that the LDS stays what one channel needs.
+//   detect_kernel   512 threads.  Per channel: stages v_c for the tile plus a halo of 2 r + d (+inf outside the frame), takes the (2r+1)^2 minimum
+//                   separably on the tile plus r + d, then the (2r+1)^2 maximum of the minima (-inf outside the frame) on the tile
+//                   plus d, and folds v_c - o_c and v_c into the running minima h and b, which a thread keeps in registers for its
+//                   (at most 5) positions of the tile plus d.  Then the seeds go to LDS, are dilated separably by d and written as
+//                   the mask.  Counts frames, pixels, seeds and the input values that are not finite.
+//   fill_kernel     256 threads.  Per channel: stages one word per position of the tile plus r: q_c with bit 24 set where the position is inside
+//                   the frame and unmasked, 0 elsewhere.  A row sum of at most 31 such words keeps the sum of q (< 2^21) and the
+//                   count (< 2^5) apart; the column pass unpacks them before it adds.  Then J_c and the normalised output for the
+//                   tile's pixels.  Counts the masked pixels, those left unfilled and the change.
+// LDS: detect [TH + 2 halo][TW + 2 pad] + [TH + 2 halo][TW + 2 (r + d)] floats (pad = halo rounded up to whole float4s): 52.6 KB
+// at r = 9, d = 1 (three resident blocks per CU, 24 waves), 86.8 KB at r = 15, d = 2 (one, 8 waves); fill [TH + 2 r][TW + 2 pad + TW] words: 30.4 KB at
+// r = 9, 39.7 KB at r = 15.
+#define AWSEG_DEHAZE_TILES_NO_LAUNCHER                                     // the constants, v_c and the reductions only
+#include "dehaze_tiles.h"
+
+// The window loops: 2 r taps beside the first, two per trip (minima, maxima and integer sums do not mind the order), four trips
+// unrolled, so that eight LDS reads are in flight where a plain loop waits for each.
+#define AWSEG_TAPS _Pragma("unroll 4")
+
+namespace {
+
+constexpr int kDRow = AWSEG_DEOCCLUDE_ROW;
+constexpr int kMaxDilate = AWSEG_DEOCCLUDE_MAX_DILATE;
+constexpr int kDetectThreads = 512;                                        // the detection kernel: twice the waves per staged tile
+constexpr int kDetectWaves = kDetectThreads / AWSEG_WAVE;
+constexpr int kRing = ((kTH + 2 * kMaxDilate) * (kTW + 2 * kMaxDilate) + kDetectThreads - 1) / kDetectThreads;    // positions of the tile plus d per thread
+constexpr uint32_t kOne = 1u << 24, kSumMask = kOne - 1;                   // the count above the sum of q in a staged word
+static_assert((2 * AWSEG_DEHAZE_MAX_RADIUS + 1) * 65536 < (int)kOne, "a row sum of q stays below the count");
+static_assert(kTH * kTW % kThreads == 0, "every thread owns the same number of pixels");
+
+struct dc_args {
+    float mean[3], std[3];
+    float threshold, bright_min;
+    int r, d;
+    int halo, pad, sw, rows, q, c1, c2;                                    // detection, see geometry()
+    int fpad, fsw, frows;                                                  // fill
+};
+
+// Detection: halo = 2 r + d pixels staged around the tile, pad = halo rounded up to whole float4s, sw staged columns, rows staged
+// rows; q = r + d: the ring of minima the maximum pass reads; c1 = TW + 2 q; c2 = TW + 2 d: the columns the seeds are needed on.
+// Fill: a halo of r, fpad, fsw and frows likewise.
+void geometry(int r, int d, dc_args& g)
+{
+    g.r = r;
+    g.d = d;
+    g.halo = 2 * r + d;
+    g.pad = (g.halo + 3) & ~3;
+    g.sw = kTW + 2 * g.pad;
+    g.rows = kTH + 2 * g.halo;
+    g.q = r + d;
+    g.c1 = kTW + 2 * g.q;
+    g.c2 = kTW + 2 * d;
+    g.fpad = (r + 3) & ~3;
+    g.fsw = kTW + 2 * g.fpad;
+    g.frows = kTH + 2 * r;
+}
+size_t detect_lds(const dc_args& g) { return (size_t)g.rows * (g.sw + g.c1) * sizeof(float); }
+size_t fill_lds(const dc_args& g) { return (size_t)g.frows * (g.fsw + kTW) * sizeof(uint32_t); }
+
+// a[c] of a kernel argument without an indexed (scratch) copy of it
+__device__ __forceinline__ float pick(const float (&a)[3], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : a[2]; }
+
+// b0 [g.rows][g.sw] = v_c over the tile and its halo, +inf outside the frame; `bad` += the tile's own values that are not finite.
+template <bool VEC>
+__device__ __forceinline__ void stage_channel(const float* __restrict__ plane, int H, int W, int y0, int x0, const dc_args& g, float sd,
+                                              float mean, float* __restrict__ b0, uint32_t& bad)
+{
+    const int tid = threadIdx.x;
+    if constexpr (VEC) {
+        const int groups = g.sw / 4;
+        for (int i = tid; i < g.rows * groups; i += kDetectThreads) {
+            const int row = i / groups, col = (i - row * groups) * 4;
+            const int yy = y0 - g.halo + row, xx = x0 - g.pad + col;         // W % 4 == 0 and (x0 - pad) % 4 == 0: a group is inside or outside
+            float4 o = { INFINITY, INFINITY, INFINITY, INFINITY };
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const float4 a = *reinterpret_cast<const float4*>(plane + (int64_t)yy * W + xx);
+                if (row >= g.halo && row < g.halo + kTH && col >= g.pad && col < g.pad + kTW)
+                    bad += not_finite(a.x) + not_finite(a.y) + not_finite(a.z) + not_finite(a.w);
+                o = { unit(a.x, sd, mean), unit(a.y, sd, mean), unit(a.z, sd, mean), unit(a.w, sd, mean) };
+            }
+            *reinterpret_cast<float4*>(b0 + row * g.sw + col) = o;
+        }
+    } else {
+        for (int i = tid; i < g.rows * g.sw; i += kDetectThreads) {
+            const int row = i / g.sw, col = i - row * g.sw;
+            const int yy = y0 - g.halo + row, xx = x0 - g.pad + col;
+            float o = INFINITY;
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const float a = plane[(int64_t)yy * W + xx];
+                if (row >= g.halo && row < g.halo + kTH && col >= g.pad && col < g.pad + kTW) bad += not_finite(a);
+                o = unit(a, sd, mean);
+            }
+            b0[row * g.sw + col] = o;
+        }
+    }
+}
+
+// One row of counters into slot 0 and the frame's own slot.
+__device__ __forceinline__ void add_row(int64_t* __restrict__ stats, int n_slots, const int32_t* __restrict__ cond, int64_t img,
+                                        const long long (&row)[kDRow])
+{
+    int slot = -1;
+    if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
+#pragma unroll
+    for (int k = 0; k < kDRow; ++k) {
+        if (!row[k]) continue;
+        atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row[k]);
+        if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kDRow + k], (unsigned long long)row[k]);
+    }
+}
+
+// Pass A.  grid = (tiles_x * tiles_y, B).
+template <bool VEC>
+__global__ __launch_bounds__(kDetectThreads)
+void detect_kernel(const float* __restrict__ image, int H, int W, int tiles_x, const dc_args g, const int32_t* __restrict__ cond,
+                   uint8_t* __restrict__ mask, int64_t* __restrict__ stats, int n_slots)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    float* b0 = reinterpret_cast<float*>(lds_raw);                         // [rows][sw]
+    float* b1 = b0 + g.rows * g.sw;                                        // [rows][c1]
+    __shared__ long long red[kDetectWaves][3];
+    const int64_t img = blockIdx.y, hw = (int64_t)H * W;
+    const int tid = threadIdx.x, taps = 2 * g.r;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * kTH, x0 = tx * kTW;
+    const float* frame = image + img * 3 * hw;
+    const int eh = kTH + 2 * g.d, n_e = eh * g.c2;                          // the tile plus d: where the seeds are needed
+    const int rows_e = kTH + 2 * g.q;
+    float h[kRing], b[kRing];
+#pragma unroll
+    for (int k = 0; k < kRing; ++k) h[k] = b[k] = INFINITY;
+    uint32_t bad = 0;
+    for (int c = 0; c < 3; ++c) {
+        stage_channel<VEC>(frame + c * hw, H, W, y0, x0, g, pick(g.std, c), pick(g.mean, c), b0, bad);
+        __syncthreads();
+        float v[kRing];                                                    // v_c at this thread's positions, before b0 is reused
+#pragma unroll
+        for (int k = 0; k < kRing; ++k) {
+            const int idx = tid + k * kDetectThreads;
+            v[k] = INFINITY;
+            if (idx < n_e) {
+                const int i = idx / g.c2, j = idx - i * g.c2;
+                v[k] = b0[(g.halo - g.d + i) * g.sw + (g.pad - g.d) + j];
+            }
+        }
+        // minimum along the row: column j of b1 is pixel x0 - q + j
+        for (int i = tid; i < g.rows * g.c1; i += kDetectThreads) {
+            const int row = i / g.c1, j = i - row * g.c1;
+            const float* p = b0 + row * g.sw + (g.pad - g.halo) + j;
+            float m = p[0];
+            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k], p[k + 1]));
+            b1[i] = m;
+        }
+        __syncthreads();
+        // minimum down the column: row ii of b0 [rows_e][c1] is pixel row y0 - q + ii; positions outside the frame take part in no maximum
+        for (int i = tid; i < rows_e * g.c1; i += kDetectThreads) {
+            const int ii = i / g.c1, j = i - ii * g.c1;
+            const float* p = b1 + i;
+            float m = p[0];
+            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k * g.c1], p[(k + 1) * g.c1]));
+            const int yy = y0 - g.q + ii, xx = x0 - g.q + j;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) m = -INFINITY;
+            b0[i] = m;
+        }
+        __syncthreads();
+        // maximum along the row: column j of b1 [rows_e][c2] is pixel x0 - d + j
+        for (int i = tid; i < rows_e * g.c2; i += kDetectThreads) {
+            const int ii = i / g.c2, j = i - ii * g.c2;
+            const float* p = b0 + ii * g.c1 + j;
+            float m = p[0];
+            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fmaxf(m, fmaxf(p[k], p[k + 1]));
+            b1[i] = m;
+        }
+        __syncthreads();
+        // maximum down the column at this thread's positions: o_c, folded into the running minima.  The next channel's staging
+        // writes b0 only, and its row pass writes b1 after a barrier.
+#pragma unroll
+        for (int k = 0; k < kRing; ++k) {
+            const int idx = tid + k * kDetectThreads;
+            if (idx < n_e) {
+                const float* p = b1 + idx;
+                float m = p[0];
+                AWSEG_TAPS for (int t = 1; t <= taps; t += 2) m = fmaxf(m, fmaxf(p[t * g.c2], p[(t + 1) * g.c2]));
+                h[k] = fminf(h[k], v[k] - m);
+                b[k] = fminf(b[k], v[k]);
+            }
+        }
+    }
+    // the seeds on the tile plus d (0 outside the frame), dilated by d along the row, then down the column
+    uint32_t* s0 = reinterpret_cast<uint32_t*>(b0);                        // [eh][c2]
+    uint32_t* s1 = reinterpret_cast<uint32_t*>(b1);                        // [eh][kTW]
+    long long n_seed = 0, n_px = 0;
+#pragma unroll
+    for (int k = 0; k < kRing; ++k) {
+        const int idx = tid + k * kDetectThreads;
+        if (idx < n_e) {
+            const int i = idx / g.c2, j = idx - i * g.c2;
+            const int yy = y0 - g.d + i, xx = x0 - g.d + j;
+            const bool inside = yy >= 0 && yy < H && xx >= 0 && xx < W;
+            const bool seed = inside && h[k] > g.threshold && b[k] >= g.bright_min;
+            s0[idx] = seed ? 1u : 0u;
+            if (seed && i >= g.d && i < g.d + kTH && j >= g.d && j < g.d + kTW) n_seed += 1;
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < eh * kTW; i += kDetectThreads) {
+        const int ii = i / kTW, j = i - ii * kTW;
+        const uint32_t* p = s0 + ii * g.c2 + j;
+        uint32_t m = p[0];
+        for (int k = 1; k <= 2 * g.d; ++k) m |= p[k];
+        s1[i] = m;
+    }
+    __syncthreads();
+    uint8_t* mk = mask + img * hw;
+    if constexpr (VEC) {
+        for (int i = tid; i < kTH * (kTW / 4); i += kDetectThreads) {
+            const int row = i / (kTW / 4), col = (i - row * (kTW / 4)) * 4;
+            const int yy = y0 + row, xx = x0 + col;
+            if (yy < H && xx < W) {
+                uint4 m = *reinterpret_cast<const uint4*>(s1 + row * kTW + col);
+                for (int k = 1; k <= 2 * g.d; ++k) {
+                    const uint4 w = *reinterpret_cast<const uint4*>(s1 + (row + k) * kTW + col);
+                    m.x |= w.x; m.y |= w.y; m.z |= w.z; m.w |= w.w;
+                }
+                *reinterpret_cast<uint32_t*>(mk + (int64_t)yy * W + xx) = m.x | (m.y << 8) | (m.z << 16) | (m.w << 24);
+                n_px += 4;
+            }
+        }
+    } else {
+        for (int i = tid; i < kTH * kTW; i += kDetectThreads) {
+            const int row = i / kTW, col = i - row * kTW;
+            const int yy = y0 + row, xx = x0 + col;
+            if (yy < H && xx < W) {
+                uint32_t m = s1[i];
+                for (int k = 1; k <= 2 * g.d; ++k) m |= s1[i + k * kTW];
+                mk[(int64_t)yy * W + xx] = (uint8_t)m;
+                n_px += 1;
+            }
+        }
+    }
+    const int lane = tid & (AWSEG_WAVE - 1), wave = tid / AWSEG_WAVE;
+    n_seed = wave_sum_i64(n_seed);
+    n_px = wave_sum_i64(n_px);
+    bad = awseg_wave_sum_u32(bad);
+    if (lane == 0) { red[wave][0] = n_px; red[wave][1] = n_seed; red[wave][2] = (long long)bad; }
+    __syncthreads();
+    if (tid == 0) {
+        long long row[kDRow] = { 0, 0, 0, 0, 0, 0, 0 };
+        for (int w = 0; w < kDetectWaves; ++w) { row[1] += red[w][0]; row[2] += red[w][1]; row[6] += red[w][2]; }
+        if (blockIdx.x == 0) row[0] = 1;                                   // the frame, once
+        add_row(stats, n_slots, cond, img, row);
+    }
+}
+
+// J_c and the normalised output of one pixel from its window's S_c and N.  `first` (0 or 1): the channel that counts the pixel itself.
+// The counters are a thread's own: at most 8 pixels and 24 changes of at most 2^16, so 32 bits hold them.
+__device__ __forceinline__ float fill_pixel(float x, uint32_t masked, uint32_t S, uint32_t N, float sd, float mean, uint32_t first,
+                                            uint32_t& n_masked, uint32_t& n_unfilled, uint32_t& change)
+{
+    const float v = unit(x, sd, mean);
+    const bool filled = masked != 0u && N > 0u;
+    const float J = filled ? (float)((double)S / ((double)(N > 0u ? N : 1u) * 65536.0)) : v;
+    const int32_t moved = (int32_t)rintf(J * 65536.0f) - (int32_t)rintf(v * 65536.0f);       // 0 where J is v
+    n_masked += masked != 0u ? first : 0u;
+    n_unfilled += masked != 0u && N == 0u ? first : 0u;
+    change += (uint32_t)(moved < 0 ? -moved : moved);
+    return (J - mean) / sd;
+}
+
+__device__ __forceinline__ uint32_t fill_word(float x, uint32_t masked, float sd, float mean)
+{
+    return masked ? 0u : ((uint32_t)(int32_t)rintf(unit(x, sd, mean) * 65536.0f) | kOne);
+}
+
+// Pass B.  grid = (tiles_x * tiles_y, B).
+template <bool VEC>
+__global__ __launch_bounds__(kThreads)
+void fill_kernel(const float* __restrict__ image, int H, int W, int tiles_x, const dc_args g, const uint8_t* __restrict__ mask,
+                 const int32_t* __restrict__ cond, float* __restrict__ restored, int64_t* __restrict__ stats, int n_slots)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    uint32_t* p0 = reinterpret_cast<uint32_t*>(lds_raw);                   // [frows][fsw]: q | count, 0 where masked or outside
+    uint32_t* r0 = p0 + g.frows * g.fsw;                                   // [frows][kTW]: their row sums
+    __shared__ long long red[kWaves][3];
+    const int64_t img = blockIdx.y, hw = (int64_t)H * W;
+    const int tid = threadIdx.x, taps = 2 * g.r;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int y0 = ty * kTH, x0 = tx * kTW;
+    const uint8_t* mk = mask + img * hw;
+    uint32_t n_masked = 0, n_unfilled = 0, change = 0;
+    for (int c = 0; c < 3; ++c) {
+        const float* plane = image + (img * 3 + c) * hw;
+        float* out = restored + (img * 3 + c) * hw;
+        const float sd = pick(g.std, c), mean = pick(g.mean, c);
+        const uint32_t first = c == 0 ? 1u : 0u;
+        if constexpr (VEC) {
+            const int groups = g.fsw / 4;
+            for (int i = tid; i < g.frows * groups; i += kThreads) {
+                const int row = i / groups, col = (i - row * groups) * 4;
+                const int yy = y0 - g.r + row, xx = x0 - g.fpad + col;
+                uint4 o = { 0u, 0u, 0u, 0u };
+                if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                    const int64_t p = (int64_t)yy * W + xx;
+                    const float4 a = *reinterpret_cast<const float4*>(plane + p);
+                    const uint32_t m = *reinterpret_cast<const uint32_t*>(mk + p);
+                    o = { fill_word(a.x, m & 0xFFu, sd, mean), fill_word(a.y, (m >> 8) & 0xFFu, sd, mean),
+                          fill_word(a.z, (m >> 16) & 0xFFu, sd, mean), fill_word(a.w, m >> 24, sd, mean) };
+                }
+                *reinterpret_cast<uint4*>(p0 + row * g.fsw + col) = o;
+            }
+        } else {
+            for (int i = tid; i < g.frows * g.fsw; i += kThreads) {
+                const int row = i / g.fsw, col = i - row * g.fsw;
+                const int yy = y0 - g.r + row, xx = x0 - g.fpad + col;
+                uint32_t o = 0u;
+                if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                    const int64_t p = (int64_t)yy * W + xx;
+                    o = fill_word(plane[p], mk[p], sd, mean);
+                }
+                p0[row * g.fsw + col] = o;
+            }
+        }
+        __syncthreads();
+        for (int i = tid; i < g.frows * kTW; i += kThreads) {              // sums along the row: at most 31 words, sum and count stay apart
+            const int row = i / kTW, j = i - row * kTW;
+            const uint32_t* p = p0 + row * g.fsw + (g.fpad - g.r) + j;
+            uint32_t s = p[0];
+            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) s += p[k] + p[k + 1];
+            r0[i] = s;
+        }
+        __syncthreads();
+        // sums down the column, unpacked, and the pixels.  The next channel's staging writes p0 only, and its row pass writes r0
+        // after a barrier.
+        if constexpr (VEC) {
+            for (int i = tid; i < kTH * (kTW / 4); i += kThreads) {
+                const int row = i / (kTW / 4), col = (i - row * (kTW / 4)) * 4;
+                const int yy = y0 + row, xx = x0 + col;
+                if (yy < H && xx < W) {
+                    uint4 S = { 0u, 0u, 0u, 0u }, N = { 0u, 0u, 0u, 0u };
+                    AWSEG_TAPS for (int k = 0; k <= taps; ++k) {
+                        const uint4 w = *reinterpret_cast<const uint4*>(r0 + (row + k) * kTW + col);
+                        S.x += w.x & kSumMask; S.y += w.y & kSumMask; S.z += w.z & kSumMask; S.w += w.w & kSumMask;
+                        N.x += w.x >> 24; N.y += w.y >> 24; N.z += w.z >> 24; N.w += w.w >> 24;
+                    }
+                    const int64_t p = (int64_t)yy * W + xx;
+                    const float4 a = *reinterpret_cast<const float4*>(plane + p);
+                    const uint32_t m = *reinterpret_cast<const uint32_t*>(mk + p);
+                    *reinterpret_cast<float4*>(out + p) = { fill_pixel(a.x, m & 0xFFu, S.x, N.x, sd, mean, first, n_masked, n_unfilled, change),
+                                                            fill_pixel(a.y, (m >> 8) & 0xFFu, S.y, N.y, sd, mean, first, n_masked, n_unfilled, change),
+                                                            fill_pixel(a.z, (m >> 16) & 0xFFu, S.z, N.z, sd, mean, first, n_masked, n_unfilled, change),
+                                                            fill_pixel(a.w, m >> 24, S.w, N.w, sd, mean, first, n_masked, n_unfilled, change) };
+                }
+            }
+        } else {
+            for (int i = tid; i < kTH * kTW; i += kThreads) {
+                const int row = i / kTW, col = i - row * kTW;
+                const int yy = y0 + row, xx = x0 + col;
+                if (yy < H && xx < W) {
+                    uint32_t S = 0u, N = 0u;
+                    AWSEG_TAPS for (int k = 0; k <= taps; ++k) {
+                        const uint32_t w = r0[i + k * kTW];
+                        S += w & kSumMask;
+                        N += w >> 24;
+                    }
+                    const int64_t p = (int64_t)yy * W + xx;
+                    out[p] = fill_pixel(plane[p], mk[p], S, N, sd, mean, first, n_masked, n_unfilled, change);
+                }
+            }
+        }
+    }
+    const int lane = tid & (AWSEG_WAVE - 1), wave = tid / AWSEG_WAVE;
+    n_masked = awseg_wave_sum_u32(n_masked);                               // a wave's sums: at most 64 * 24 * 2^16 < 2^32
+    n_unfilled = awseg_wave_sum_u32(n_unfilled);
+    change = awseg_wave_sum_u32(change);
+    if (lane == 0) { red[wave][0] = n_masked; red[wave][1] = n_unfilled; red[wave][2] = change; }
+    __syncthreads();
+    if (tid == 0) {
+        long long row[kDRow] = { 0, 0, 0, 0, 0, 0, 0 };
+        for (int w = 0; w < kWaves; ++w) { row[3] += red[w][0]; row[4] += red[w][1]; row[5] += red[w][2]; }
+        add_row(stats, n_slots, cond, img, row);
+    }
+}
+
+inline bool in_closed_unit(float v) { return v >= 0.0f && v <= 1.0f; }      // NaN fails
+
+}  // namespace
+
+AWSEG_API int64_t awseg_deocclude_workspace(int64_t batch, int64_t height, int64_t width)
+{
+    (void)batch; (void)height; (void)width;
+    return 0;                                                              // the mask is all that one kernel leaves for the other
+}
+
+AWSEG_API int awseg_deocclude(const float* image, int64_t batch, int channels, int64_t height, int64_t width, const float* mean,
+                              const float* std, int radius, float threshold, float bright_min, int dilate, const int32_t* cond,
+                              float* restored, uint8_t* mask, int64_t* stats, int n_slots, void* workspace, awseg_stream_t stream)
+{
+    if (!image || !mean || !std || !restored || !mask || !stats) return AWSEG_EINVAL;        // workspace: no bytes, so NULL will do
+    if (channels != 3 || batch < 0 || height < 1 || width < 1 || n_slots < 1) return AWSEG_EINVAL;
+    if (radius < 1 || radius > AWSEG_DEHAZE_MAX_RADIUS || dilate < 0 || dilate > kMaxDilate) return AWSEG_EINVAL;
+    if (!in_unit(threshold) || !in_closed_unit(bright_min)) return AWSEG_EINVAL;
+    dc_args g = {};
+    for (int c = 0; c < 3; ++c) {
+        if (!(std[c] > 0.0f && std[c] <= FLT_MAX) || !is_finite(mean[c])) return AWSEG_EINVAL;
+        g.mean[c] = mean[c];
+        g.std[c] = std[c];
+    }
+    g.threshold = threshold;
+    g.bright_min = bright_min;
+    if (batch > 65535 || height > INT32_MAX / width) return AWSEG_ERANGE;      // grid.y; H * W >= 2^31
+    if (workspace && !awseg_aligned(workspace, 8)) return AWSEG_EALIGN;
+    if (batch == 0) return 0;
+    hipStream_t s = awseg_s(stream);
+    const int H = (int)height, W = (int)width;
+    const int tiles_x = (W + kTW - 1) / kTW, tiles = tiles_x * ((H + kTH - 1) / kTH);
+    const bool vec = (W % 4 == 0) && awseg_aligned(image, 16) && awseg_aligned(restored, 16) && awseg_aligned(mask, 4);
+    geometry(radius, dilate, g);
+    dim3 grid((unsigned)tiles, (unsigned)batch);
+    {
+        auto kern = vec ? detect_kernel<true> : detect_kernel<false>;
+        const size_t lds = detect_lds(g);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return AWSEG_EINVAL;
+        hipLaunchKernelGGL(kern, grid, dim3(kDetectThreads), lds, s, image, H, W, tiles_x, g, cond, mask, stats, n_slots);
+        AWSEG_LAUNCH_CHECK();
+    }
+    {
+        auto kern = vec ? fill_kernel<true> : fill_kernel<false>;
+        const size_t lds = fill_lds(g);
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+            return AWSEG_EINVAL;
+        hipLaunchKernelGGL(kern, grid, dim3(kThreads), lds, s, image, H, W, tiles_x, g, (const uint8_t*)mask, cond, restored, stats, n_slots);
+        AWSEG_LAUNCH_CHECK();
+    }
+    return 0;
+}

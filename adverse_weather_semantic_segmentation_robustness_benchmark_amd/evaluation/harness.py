@@ -29,7 +29,8 @@ from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMetrics, bootstrap_metrics_from_replicates,
-                      boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, depth_metrics_from_stats,
+                      boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, deocclude_metrics_from_stats,
+                      depth_metrics_from_stats,
                       failure_metrics_from_stats, iou_from_counts, guided_metrics_from_stats, quality_metrics_from_stats,
                       relight_metrics_from_stats, restoration_metrics_from_stats, restored_quality_metrics_from_stats,
                       segment_metrics_from_stats, segment_options, severity_sweep_results, weight_grid_metrics_from_stats)
@@ -284,9 +285,11 @@ def check_quality_budget(terms: int) -> None:
 RESTORATION_KEYS = ("radius", "omega", "t_min", "airlight_min", "refine")
 RESTORATION_REFINE = {"opening": 1, "none": 0}
 RESTORATION_GUIDED_KEYS = ("guided_radius", "guided_eps")               # only under refine: guided (awseg_dehaze_guided)
-RESTORATION_METHODS = ("dark_channel", "clahe")
+RESTORATION_METHODS = ("dark_channel", "clahe", "tophat")
 RESTORATION_RELIGHT_KEYS = ("grid", "clip_limit", "max_gain", "white_balance")      # only under method: clahe (awseg_relight)
 RESTORATION_WHITE_BALANCE = {"gray_world": True, "none": False}
+# only under method: tophat (awseg_deocclude); `radius` is a key of the dark channel as well and belongs to the method named
+RESTORATION_DEOCCLUDE_KEYS = ("radius", "threshold", "bright_min", "dilate")
 
 
 def _relight_option(spec: dict) -> dict:
@@ -294,6 +297,9 @@ def _relight_option(spec: dict) -> dict:
     foreign = sorted(set(spec) & (set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS)))
     if foreign:
         raise ValueError(f"evaluation.restoration: {foreign} belong to method: dark_channel, got method: clahe")
+    foreign = sorted(set(spec) & set(RESTORATION_DEOCCLUDE_KEYS))
+    if foreign:
+        raise ValueError(f"evaluation.restoration: {foreign} belong to method: tophat, got method: clahe")
     if set(spec) - set(RESTORATION_RELIGHT_KEYS):
         raise ValueError(f"evaluation.restoration with method: clahe is a dict with keys among {list(RESTORATION_RELIGHT_KEYS)}, "
                          f"got {spec!r}")
@@ -310,6 +316,25 @@ def _relight_option(spec: dict) -> dict:
     return {"method": "clahe", **opt}
 
 
+def _deocclude_option(spec: dict) -> dict:
+    """The dict of `evaluation.restoration` under method: tophat (without 'method') -> the checked option, without 'conditions'."""
+    own = set(RESTORATION_DEOCCLUDE_KEYS)
+    foreign = sorted(set(spec) & ((set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS)) - own))
+    if foreign:
+        raise ValueError(f"evaluation.restoration: {foreign} belong to method: dark_channel, got method: tophat")
+    foreign = sorted(set(spec) & set(RESTORATION_RELIGHT_KEYS))
+    if foreign:
+        raise ValueError(f"evaluation.restoration: {foreign} belong to method: clahe, got method: tophat")
+    if set(spec) - own:
+        raise ValueError(f"evaluation.restoration with method: tophat is a dict with keys among {list(RESTORATION_DEOCCLUDE_KEYS)}, "
+                         f"got {spec!r}")
+    try:
+        opt = ops.deocclude_parameters(**spec)
+    except ValueError as e:
+        raise ValueError(f"evaluation.restoration: {e}") from None
+    return {"method": "tophat", **opt}
+
+
 def restoration_option(config, images=None):
     """`evaluation.restoration` (default off): 'dark_channel', or a dict with any of `radius` (an integer in [1, 15], default 7),
     `omega`, `t_min`, `airlight_min` (numbers in (0, 1], defaults 0.95, 0.1, 0.1) and `refine` ('opening', the default, 'none', or
@@ -321,12 +346,17 @@ def restoration_option(config, images=None):
     a batch of frames: they must be float32 [B, 3, H, W].
     Or 'clahe', or a dict with `method: clahe` and any of `grid` (n or [tiles_y, tiles_x], integers in [1, 16], default 8),
     `clip_limit`, `max_gain` (numbers in [1, 64], defaults 2 and 8) and `white_balance` ('gray_world', the default, or 'none'):
-    every selected frame is relit by CLAHE on the luma with a grey-world white balance instead.  `method:
-    dark_channel` means what the absence of `method` means; the keys of one method are refused under the other.
+    every selected frame is relit by CLAHE on the luma with a grey-world white balance instead.
+    Or 'tophat', or a dict with `method: tophat` and any of `radius` (an integer in [1, 15], default 9), `threshold` (a number in
+    (0, 1], default 0.06), `bright_min` (a number in [0, 1], default 0.5) and `dilate` (an integer in [0, 2], default 1): the bright
+    occluders of rain and snow are masked by the white top-hat and filled from their neighbours instead.  `method:
+    dark_channel` means what the absence of `method` means; the keys of one method are refused under another (`radius` belongs to
+    the method named).
     -> None when absent, else {'radius', 'omega', 't_min', 'airlight_min', 'refine' (0 / 1), 'conditions' (a list, or None = all)};
     under 'guided': {'radius', 'omega', 't_min', 'airlight_min', 'guided_radius', 'guided_eps', 'refine': 'guided', 'conditions'};
-    under 'clahe': {'method': 'clahe', 'grid' (ty, tx), 'clip_limit', 'max_gain', 'white_balance' (a bool), 'conditions'}.  Only
-    the last carries a 'method' key."""
+    under 'clahe': {'method': 'clahe', 'grid' (ty, tx), 'clip_limit', 'max_gain', 'white_balance' (a bool), 'conditions'};
+    under 'tophat': {'method': 'tophat', 'radius', 'threshold', 'bright_min', 'dilate', 'conditions'}.  Only the last two carry a
+    'method' key."""
     names = _cfg(config, "evaluation.restoration_conditions", None)
     if names is not None:
         if isinstance(names, (str, bytes, dict)) or not isinstance(names, (list, tuple)) or not names \
@@ -338,15 +368,15 @@ def restoration_option(config, images=None):
         return None
     if isinstance(spec, str):
         if spec not in RESTORATION_METHODS:
-            raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe' or a dict of a method's parameters, got {spec!r}")
+            raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat' or a dict of a method's parameters, got {spec!r}")
         spec = {"method": spec}
     if isinstance(spec, dict) and "method" in spec:
         method = spec["method"]
         if not isinstance(method, str) or method not in RESTORATION_METHODS:
-            raise ValueError(f"evaluation.restoration.method is 'dark_channel' or 'clahe', got {method!r}")
+            raise ValueError(f"evaluation.restoration.method is 'dark_channel', 'clahe' or 'tophat', got {method!r}")
         spec = {k: v for k, v in spec.items() if k != "method"}
-        if method == "clahe":
-            opt = _relight_option(spec)
+        if method in ("clahe", "tophat"):
+            opt = _relight_option(spec) if method == "clahe" else _deocclude_option(spec)
             if images is not None:
                 check_frames("restoration", images)
             opt["conditions"] = names
@@ -354,9 +384,13 @@ def restoration_option(config, images=None):
     if isinstance(spec, dict) and set(spec) & set(RESTORATION_RELIGHT_KEYS):
         raise ValueError(f"evaluation.restoration: {sorted(set(spec) & set(RESTORATION_RELIGHT_KEYS))} belong to method: clahe, got "
                          "method: dark_channel")
+    if isinstance(spec, dict) and set(spec) & set(RESTORATION_DEOCCLUDE_KEYS[1:]):
+        raise ValueError(f"evaluation.restoration: {sorted(set(spec) & set(RESTORATION_DEOCCLUDE_KEYS[1:]))} belong to method: tophat, "
+                         "got method: dark_channel")
     if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS) - set(RESTORATION_GUIDED_KEYS):
-        raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe' or a dict with keys among "
-                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)} (method: clahe: {list(RESTORATION_RELIGHT_KEYS)}), got {spec!r}")
+        raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat' or a dict with keys among "
+                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)} (method: clahe: {list(RESTORATION_RELIGHT_KEYS)}; method: "
+                         f"tophat: {list(RESTORATION_DEOCCLUDE_KEYS)}), got {spec!r}")
     kw = {k: v for k, v in spec.items() if k != "refine"}
     refine = spec.get("refine", "opening")
     if not isinstance(refine, str) or (refine not in RESTORATION_REFINE and refine != "guided"):
@@ -443,6 +477,7 @@ COUNTERS = (
     ("restoration", ("counts", "oob", "stats"), None, None, "label outside [0, num_classes) in the confusion counters of the restored frames"),
     ("restoration_guided", ("stats",), None, None, None),
     ("restoration_relight", ("stats",), None, None, None),
+    ("restoration_deocclude", ("stats",), None, None, None),
     ("restored_quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality "
                                                                           "counters of the restored frames"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
@@ -581,26 +616,33 @@ class EvalState:
         # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
         self.restoration = None
         relit = restoration is not None and restoration.get("method") == "clahe"
+        tophat = restoration is not None and restoration.get("method") == "tophat"
         if restoration is not None:
-            guided = not relit and restoration["refine"] == "guided"
+            guided = not relit and not tophat and restoration["refine"] == "guided"
             params = (ops.relight_parameters(**{k: restoration[k] for k in RESTORATION_RELIGHT_KEYS}) if relit
+                      else ops.deocclude_parameters(**{k: restoration[k] for k in RESTORATION_DEOCCLUDE_KEYS}) if tophat
                       else ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
                       else ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS}))
             acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
-            # under method: clahe there are no dehazing counters: 'stats' has no rows (the reduce and the result keys see nothing)
+            # under method: clahe and method: tophat there are no dehazing counters: 'stats' has no rows (the reduce and the result keys see nothing)
             self.restoration = {"params": params, "acc": acc, "counts": acc.counts, "oob": acc.oob,
                                 "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]},
-                                "stats": torch.zeros(0, ops.DEHAZE_ROW, dtype=torch.int64, device=device) if relit
+                                "stats": torch.zeros(0, ops.DEHAZE_ROW, dtype=torch.int64, device=device) if relit or tophat
                                 else ops.new_dehaze_stats(device, 1 + len(conditions))}
         # under refine: guided the counters of the filter, int64 [slot, AWSEG_GUIDED_ROW] (None otherwise: awseg_dehaze runs)
         self.restoration_guided = None
-        if restoration is not None and not relit and restoration["refine"] == "guided":
+        if restoration is not None and not relit and not tophat and restoration["refine"] == "guided":
             self.restoration_guided = {"stats": ops.new_guided_stats(device, 1 + len(conditions))}
         # under method: clahe the counters of the relighting, int64 [slot, AWSEG_RELIGHT_ROW] (None otherwise); awseg_relight
         # produces the restored frames, everything behind it is the dehazer's second pass
         self.restoration_relight = None
         if relit:
             self.restoration_relight = {"stats": ops.new_relight_stats(device, 1 + len(conditions))}
+        # under method: tophat the counters of the occluder removal, int64 [slot, AWSEG_DEOCCLUDE_ROW] (None otherwise); awseg_deocclude
+        # produces the restored frames, everything behind it is the dehazer's second pass.  The mask is not kept
+        self.restoration_deocclude = None
+        if tophat:
+            self.restoration_deocclude = {"stats": ops.new_deocclude_stats(device, 1 + len(conditions))}
         # fidelity of the restored frames (only when the sweep, the image-quality counters and the restoration are all on): a SECOND
         # image-quality tensor, the restored frames against the same kept clean frames; the clean batch against its own kept rows
         self.restored_quality = None
@@ -753,6 +795,8 @@ class EvalState:
         if self.restoration_relight is not None:
             self.check_relight_grid(images)
             restored, _ = ops.relight(images, self.restoration_relight["stats"], cond, **rs["params"])
+        elif self.restoration_deocclude is not None:
+            restored, _ = ops.deocclude(images, self.restoration_deocclude["stats"], cond, **rs["params"])
         elif self.restoration_guided is not None:
             restored, _ = ops.dehaze_guided(images, rs["stats"], self.restoration_guided["stats"], cond, **rs["params"])
         else:
@@ -1131,12 +1175,15 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
     if st.restoration is not None:
         rs = st.restoration
         relit = st.restoration_relight is not None                 # no dehazing counters then: all-zero rows give no dehazing key
-        dehaze_stats = np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64) if relit else rs["stats"].cpu().numpy()
+        tophat = st.restoration_deocclude is not None              # nor then
+        dehaze_stats = np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64) if relit or tophat else rs["stats"].cpu().numpy()
         results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), dehaze_stats,
                                                       st.acc.conditions, metrics.num_classes, **sweep_kw,
                                                       degradation=metrics.compute_robustness_degradation_ratio))
         if relit:
             results.update(relight_metrics_from_stats(st.restoration_relight["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
+        if tophat:
+            results.update(deocclude_metrics_from_stats(st.restoration_deocclude["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
         if st.restoration_guided is not None:
             results.update(guided_metrics_from_stats(st.restoration_guided["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
             results["restoration_refine"] = "guided"

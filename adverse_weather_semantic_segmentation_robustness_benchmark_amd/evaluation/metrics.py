@@ -895,6 +895,42 @@ def relight_metrics_from_stats(stats, conditions: List[str], kinds=None, levels:
     return res
 
 
+def deocclude_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0) -> Dict[str, Any]:
+    """Result keys of the rain and snow removal (evaluation.restoration with method: tophat) from its counters int64
+    [1 + len(conditions), AWSEG_DEOCCLUDE_ROW] (include/awseg_restore.h; slot 0 = every restored frame, slot 1 + k = conditions[k]).
+    Host only, float64 on exact integer sums; every value a float but restoration_method.  With <n> a condition (under a sweep its
+    slots and each '<kind>' from the summed counters of its levels; slot 0 under the prefix mean_ instead of the suffix):
+      occluder_fraction_<n>              masked pixels / pixels
+      occluder_seed_fraction_<n>         seed pixels (before the dilation) / pixels
+      occluder_unfilled_fraction_<n>     masked pixels without an unmasked neighbour in their window / masked pixels
+      occluder_change_<n>                mean absolute change per masked channel value (3 per masked pixel), in [0, 1]
+    and restoration_method = 'tophat'; restoration_nonfinite_values (slot 0) only when non-zero.  A ratio without a denominator is
+    absent, not 0."""
+    conditions = list(conditions)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.shape != (1 + len(conditions), ops.DEOCCLUDE_ROW):
+        raise ValueError(f"deocclude stats must be int64 [{1 + len(conditions)}, {ops.DEOCCLUDE_ROW}], got {raw.shape}")
+    named = [(None, raw[0])] + [(name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        named.append((kind, raw[[1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels) + 1)]].sum(0)))
+    res: Dict[str, Any] = {"restoration_method": "tophat"}
+    for name, row in named:
+        dec = {f: int(v) for f, v in ops.deocclude_stats_to_numpy(row).items()}
+
+        def key(metric, name=name):
+            return f"mean_{metric}" if name is None else f"{metric}_{name}"
+        if dec["pixels"] > 0:
+            res[key("occluder_fraction")] = float(dec["masked_pixels"] / dec["pixels"])
+            res[key("occluder_seed_fraction")] = float(dec["seed_pixels"] / dec["pixels"])
+        if dec["masked_pixels"] > 0:
+            res[key("occluder_unfilled_fraction")] = float(dec["unfilled_pixels"] / dec["masked_pixels"])
+            res[key("occluder_change")] = float(dec["sum_change"] * ops.DEOCCLUDE_UNIT / (3.0 * dec["masked_pixels"]))
+    nonfinite = int(ops.deocclude_stats_to_numpy(raw[0])["nonfinite_values"])
+    if nonfinite:
+        res["restoration_nonfinite_values"] = float(nonfinite)
+    return res
+
+
 IQ_PLAIN_STEMS = ("mse", "psnr", "mean_abs_change", "ssim", "ssim_luminance", "ssim_contrast")
 
 

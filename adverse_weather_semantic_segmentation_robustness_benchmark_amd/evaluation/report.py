@@ -69,14 +69,21 @@ def restoration_section(results: Dict[str, Any]) -> list:
     """Input restoration (evaluation.restoration): one line per condition with the mIoU of the frames as they came, of the same
     frames dehazed by the dark-channel prior, the difference, and the mean transmission the front-end estimated.  Under method:
     clahe (restoration_method in the results) the frames were relit instead and the luma gain stands where the mean transmission
-    does, the share of gain-capped pixels where the airlight does."""
+    does, the share of gain-capped pixels where the airlight does; under method: tophat the occluders of rain and snow were masked
+    and filled, and the masked share of the pixels and the mean change of a masked value stand in those two columns."""
     names = [m.group(1) for k in results for m in [re.match(r"miou_(.+)_restored$", k)] if m]
 
     def cell(key):
         return f"{results[key]:.3f}" if key in results else "-"
     relit = results.get("restoration_method") == "clahe"
+    tophat = results.get("restoration_method") == "tophat"
     lines = ["", "## Input Restoration", ""]
-    if relit:
+    if tophat:
+        lines += ["Method: tophat.  In every selected frame the bright occluders of rain and snow were masked by the white top-hat of "
+                  "all three channels and filled from their unmasked neighbours in front of the model, and the frame scored again.  "
+                  "Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); occluders: share of the "
+                  "pixels that were masked; change: mean absolute change of a masked channel value.", ""]
+    elif relit:
         lines += ["Method: clahe.  Every selected frame relit by contrast-limited adaptive histogram equalisation of the luma with a "
                   "grey-world white balance in front of the model and scored again.  Gain: restored - plain mIoU on the same frames "
                   "(negative: the front-end costs accuracy); luma gain: mean luma of the restored frames over that of the frames as "
@@ -90,9 +97,10 @@ def restoration_section(results: Dict[str, Any]) -> list:
     # the corrupted ones)
     guided = any(k.startswith("transmission_refinement_") for k in results)
     fidelity = any(re.match(r"(psnr|ssim)_.+_restored$", k) for k in results)
-    head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain"] + (["Luma gain", "Capped"] if relit else ["Mean t", "Airlight"]) \
-        + ["Degradation restored"]
-    fifth, sixth = ("relight_gain", "relight_capped_fraction") if relit else ("transmission_mean", "airlight")
+    head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain"] \
+        + (["Occluders", "Change"] if tophat else ["Luma gain", "Capped"] if relit else ["Mean t", "Airlight"]) + ["Degradation restored"]
+    fifth, sixth = (("occluder_fraction", "occluder_change") if tophat else ("relight_gain", "relight_capped_fraction") if relit
+                    else ("transmission_mean", "airlight"))
     head += ["Refinement", "Clamped"] * guided + ["PSNR restored (gain)", "SSIM restored (gain)"] * fidelity
     if "restoration_refine" in results:
         lines += [f"Transmission refinement: {results['restoration_refine']} filter (DESIGN.md 10n-bis).", ""]
@@ -113,13 +121,15 @@ def restoration_section(results: Dict[str, Any]) -> list:
         lines.append(f"| {n} | {cell('miou_' + n)} | {cell('miou_' + n + '_restored')} | {cell('restoration_gain_' + n)} | "
                      f"{cell(fifth + '_' + n)} | {cell(sixth + '_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |"
                      + more(n))
-    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_' + fifth if relit else 'mean_transmission')} | "
+    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_' + fifth if relit or tophat else 'mean_transmission')} | "
                  f"{cell('mean_' + sixth)} | - |" + more(None))
     if relit:
         gains = [f"{results[k]:.3f}" for k in ("mean_white_balance_gain_r", "mean_white_balance_gain_g", "mean_white_balance_gain_b")
                  if k in results]
         if len(gains) == 3:
             lines += ["", f"- **Mean white-balance gains** (r / g / b): {' / '.join(gains)}"]
+    if tophat and "mean_occluder_unfilled_fraction" in results:
+        lines += ["", f"- **Masked pixels left unfilled** (no unmasked pixel in their window): {results['mean_occluder_unfilled_fraction']:.3f}"]
     extra = [f"- **Clean cost** (plain - restored mIoU of the clean frames): {results['restoration_clean_cost']:.3f}"] \
         if "restoration_clean_cost" in results else []
     extra += [f"- **{title}**: {int(results[key])}" for key, title in (("restoration_nonfinite_values", "Input values that are not finite"),

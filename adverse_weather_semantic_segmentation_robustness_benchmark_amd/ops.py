@@ -873,6 +873,77 @@ def relight_stats_to_numpy(stats) -> dict:
     return {f: raw[..., i] for i, f in enumerate(RELIGHT_FIELDS)}
 
 
+# ------------------------------------------------ rain and snow removal: top-hat mask + masked fill (include/awseg_restore.h)
+DEOCCLUDE_FIELDS = ("frames", "pixels", "seed_pixels", "masked_pixels", "unfilled_pixels", "sum_change", "nonfinite_values")
+DEOCCLUDE_ROW = len(DEOCCLUDE_FIELDS)  # AWSEG_DEOCCLUDE_ROW
+DEOCCLUDE_MAX_DILATE = 2               # AWSEG_DEOCCLUDE_MAX_DILATE
+DEOCCLUDE_UNIT = 2.0 ** -16            # the change sum is int64 in fixed point: exact, order-independent
+DEOCCLUDE_DEFAULTS = {"radius": 9, "threshold": 0.06, "bright_min": 0.5, "dilate": 1}    # the prototype's: a stated choice, not a tuned one
+
+
+def new_deocclude_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, DEOCCLUDE_ROW]: per slot the row DEOCCLUDE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_deocclude_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), DEOCCLUDE_ROW, dtype=torch.int64, device=device)
+
+
+def deocclude_parameters(radius=9, threshold=0.06, bright_min=0.5, dilate=1) -> dict:
+    """The checked parameters of deocclude(): radius an integer in [1, 15]; threshold a number in (0, 1], bright_min one in [0, 1]
+    (also as float32); dilate an integer in [0, 2].  ValueError otherwise."""
+    def integer(name, v, lo, hi):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+            raise ValueError(f"deocclude: {name} is an integer in [{lo}, {hi}], got {v!r}")
+        return int(v)
+
+    def unit(name, v, open_below):
+        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
+        f = float(np.float32(v)) if ok else -1.0
+        if not (ok and (0.0 < f if open_below else 0.0 <= f) and f <= 1.0):
+            raise ValueError(f"deocclude: {name} is a number in {'(' if open_below else '['}0, 1] (also as float32), got {v!r}")
+        return f
+    return {"radius": integer("radius", radius, 1, DEHAZE_MAX_RADIUS), "threshold": unit("threshold", threshold, True),
+            "bright_min": unit("bright_min", bright_min, False), "dilate": integer("dilate", dilate, 0, DEOCCLUDE_MAX_DILATE)}
+
+
+def deocclude_workspace_bytes(b: int, h: int, w: int) -> int:
+    """The closed form of awseg_deocclude_workspace: nothing.  The mask is all one kernel leaves for the other, and it is an output."""
+    return 0
+
+
+def deocclude(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 9,
+              threshold: float = 0.06, bright_min: float = 0.5, dilate: int = 1, mean=None, std=None,
+              out: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+    """Rain and snow removal from the loader's normalised float32 frames `image` [B, 3, H, W]: the pixels where the white top-hat
+    ((2 radius + 1)^2 windows) of all three channels exceeds `threshold` and the darkest channel is at least `bright_min`, dilated
+    by `dilate`, are replaced by the mean of the unmasked pixels of their window, as include/awseg_restore.h defines it step by
+    step -> (restored float32 [B, 3, H, W], mask uint8 [B, H, W]: 1 where a pixel was taken for an occluder).  `stats`
+    (new_deocclude_stats; slot 0 + slot 1 + cond[b], cond device int32 [B]) takes the counters of DEOCCLUDE_FIELDS; without it they
+    go to a tensor nobody reads.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`, `mask`: where the
+    restored frames and the mask go (contiguous; `out` not `image`).  There is no CPU path."""
+    p = deocclude_parameters(radius, threshold, bright_min, dilate)
+    image, b, h, w, m, s, stats, out, _ = _dehaze_buffers("deocclude", image, stats, cond, mean, std, out, DEOCCLUDE_ROW, new_deocclude_stats)
+    if mask is None:
+        mask = torch.empty(b, h, w, dtype=torch.uint8, device=image.device)
+    if mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w) or not mask.is_contiguous() or mask.device != image.device:
+        raise ValueError(f"deocclude: mask is a contiguous uint8 tensor [B, H, W] on the frames' device, got {mask.dtype} {tuple(mask.shape)}")
+    if b == 0:
+        return out, mask
+    need = N.lib().awseg_deocclude_workspace(b, h, w)                  # 0: the launcher takes NULL for a workspace of no bytes
+    ws = N.workspace.get(image.device, need, tag="deocclude") if need else None
+    N.call("awseg_deocclude", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), p["radius"], p["threshold"], p["bright_min"], p["dilate"],
+           N.ptr(cond), N.ptr(out), N.ptr(mask), N.ptr(stats), stats.shape[0], N.ptr(ws), N.stream())
+    return out, mask
+
+
+def deocclude_stats_to_numpy(stats) -> dict:
+    """int64 [..., DEOCCLUDE_ROW] -> {field: int64 [...]} for DEOCCLUDE_FIELDS; the change sum stays in units of DEOCCLUDE_UNIT."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != DEOCCLUDE_ROW:
+        raise ValueError(f"deocclude rows hold {DEOCCLUDE_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(DEOCCLUDE_FIELDS)}
+
+
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

@@ -179,6 +179,59 @@ int awseg_relight(const float* image, int64_t batch, int channels, int64_t heigh
                   int white_balance, const int32_t* cond, float* restored, float* gains /* [B][3] */,
                   int64_t* stats /* [n_slots][AWSEG_RELIGHT_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Rain and snow removal: bright occluders narrower than a window found by the morphological white top-hat of every channel and
+ *  filled from their unmasked neighbours, the third blind front-end of the evaluation
+ *       replaces nothing: the reference has no restoration baseline
+ * ------------------------------------------------------------------------- *
+ * awseg_deocclude: image, mean, std (HOST float32[3]), cond, restored, stats, n_slots, workspace, stream as for awseg_dehaze (which
+ * this entry point leaves as it is).  radius r in [1, AWSEG_DEHAZE_MAX_RADIUS], threshold in (0, 1], bright_min in [0, 1], dilate d
+ * in [0, AWSEG_DEOCCLUDE_MAX_DILATE].  Every float step is one float32 operation with the parenthesisation given (no contraction);
+ * everything else is written in integers or in double, so numpy gives the same bits.  All windows are clipped to the frame:
+ * positions outside take part in no minimum, no maximum and no sum.  Frame b, pixel p, channel c:
+ *   input    v_c = fminf(fmaxf(image[b,c,p] * std[c] + mean[c], 0), 1)     (NaN -> 0; every input value that is not finite is counted:
+ *            the v_c of awseg_dehaze)
+ *   pass A   e_c = (2r+1)^2 window minimum of v_c;   o_c = (2r+1)^2 window maximum of e_c   (the opening of v_c: o_c <= v_c)
+ *            h = fminf(fminf(v_0 - o_0, v_1 - o_1), v_2 - o_2)             (the smallest of the three white top-hats)
+ *            b = fminf(fminf(v_0, v_1), v_2)
+ *            seed = (h > threshold) && (b >= bright_min)      a near-white occluder lifts all three channels over their opened
+ *                                                             background, a thin coloured object does not
+ *            mask = (2d+1)^2 window maximum of seed           (covers the blurred rim);   mask[b,p] = 0 or 1, one uint8
+ *   pass B   q_c = (int32) rintf(v_c * 65536.0f)
+ *            over the (2r+1)^2 window: N = the count of the positions with mask == 0, S_c = the integer sum of q_c over them
+ *            (S_c <= 961 * 2^16 < 2^26; integers, so the order is free)
+ *            mask == 1 and N > 0:   J_c = (float)((double) S_c / ((double) N * 65536.0))
+ *            mask == 1 and N == 0:  J_c = v_c   (the pixel is "left unfilled")
+ *            mask == 0:             J_c = v_c
+ *            restored[b,c,p] = (J_c - mean[c]) / std[c]
+ * restored float32 [B, 3, H, W] (must not overlap image: a block reads its neighbours' pixels); mask uint8 [B, H, W].
+ * stats int64 [n_slots][AWSEG_DEOCCLUDE_ROW] (accumulated, never cleared), the slot rule of awseg_dehaze (slot 0, and slot
+ * 1 + cond[b] when 0 <= cond[b] < n_slots - 1; cond device int32[B] or NULL).  Row:
+ *     [0] frames   [1] pixels   [2] seed pixels   [3] masked pixels   [4] masked pixels left unfilled
+ *     [5] sum over the masked pixels and the channels of |(int64) rintf(J_c * 65536.0f) - q_c|   [6] input values that are not finite
+ * Integer sums only: independent of the grid, additive over launches and ranks.  A term is at most 3 * 2^16 units, so a stats
+ * tensor holds 2^44 pixels before a sum could wrap.
+ * Two kernels on the stream, both on the AWSEG_DEHAZE_TILE_H x AWSEG_DEHAZE_TILE_W tiles of awseg_dehaze.  The detection kernel
+ * walks the three channels one after another through one staged plane with a halo of 2 r + d (at most 32) and one scratch plane,
+ * separable row and column passes in LDS, keeping the running minimum of the top-hats in registers; then it dilates the seeds and
+ * writes the mask.  The fill kernel walks the channels again with a halo of r: it stages q_c of the unmasked positions with their
+ * count in the upper bits of the same word, and forms separable integer window sums.  16-byte loads and stores of the frames and
+ * 32-bit ones of the mask when W % 4 == 0, image and restored are 16-byte aligned and mask is 4-byte aligned, scalar ones
+ * otherwise; the same bits either way.
+ * workspace: awseg_deocclude_workspace(batch, height, width) bytes = 0: the only thing one kernel leaves for the other is the mask,
+ * which is an output.  So the pointer may be NULL, as a buffer of no bytes is; one that is given is 8-byte aligned as elsewhere
+ * (AWSEG_EALIGN otherwise) and never dereferenced.
+ * AWSEG_EINVAL for a NULL pointer (cond and workspace excepted), channels != 3, a size < 1 (batch < 0), n_slots < 1, a parameter outside the
+ * ranges above (NaN included), a std that is not finite and > 0 or a non-finite mean; AWSEG_ERANGE for batch > 65535 or
+ * H * W >= 2^31; batch == 0 returns 0 and launches nothing. */
+#define AWSEG_DEOCCLUDE_ROW         7
+#define AWSEG_DEOCCLUDE_MAX_DILATE  2
+int64_t awseg_deocclude_workspace(int64_t batch, int64_t height, int64_t width);
+int awseg_deocclude(const float* image, int64_t batch, int channels, int64_t height, int64_t width,
+                    const float* mean, const float* std, int radius, float threshold, float bright_min, int dilate,
+                    const int32_t* cond, float* restored, uint8_t* mask /* [B,H,W] */,
+                    int64_t* stats /* [n_slots][AWSEG_DEOCCLUDE_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

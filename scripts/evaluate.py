@@ -135,11 +135,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
                     help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
                          "(sets evaluation.image_quality_targets)")
-    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe"),
+    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe", "tophat"),
                     help="restore every frame in front of the model and score it a second time: plain and restored mIoU and the gain "
                          "per condition.  dark_channel: dehazing by the dark-channel prior (with the mean transmission); clahe: night "
-                         "relighting by CLAHE on the luma with a grey-world white balance (with the luma gain).  Sets "
-                         "evaluation.restoration")
+                         "relighting by CLAHE on the luma with a grey-world white balance (with the luma gain); tophat: rain "
+                         "and snow removal, the bright occluders masked by the white top-hat and filled from their neighbours (with "
+                         "the masked share of the pixels).  Sets evaluation.restoration")
     ap.add_argument("--restoration-conditions", type=str, default=None, metavar="A,B",
                     help="restore only the frames of these comma-separated weather conditions (default: all, clean included; sets "
                          "evaluation.restoration_conditions)")
@@ -164,6 +165,18 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--restoration-white-balance", type=str, default=None, choices=("gray_world", "none"),
                     help="white balance of the relit frames (default gray_world; needs --restoration clahe; sets "
                          "evaluation.restoration.white_balance)")
+    ap.add_argument("--restoration-radius", type=int, default=None, metavar="R",
+                    help="window radius, 1 .. 15: of the top-hat and the fill under --restoration tophat (default 9), of the dark "
+                         "channel under --restoration dark_channel (default 7); sets evaluation.restoration.radius")
+    ap.add_argument("--restoration-threshold", type=float, default=None, metavar="T",
+                    help="smallest top-hat of all three channels that makes a pixel an occluder, in (0, 1] (default 0.06; needs "
+                         "--restoration tophat; sets evaluation.restoration.threshold)")
+    ap.add_argument("--restoration-bright-min", type=float, default=None, metavar="B",
+                    help="smallest value of the darkest channel of an occluder, 0 .. 1 (default 0.5; needs --restoration tophat; sets "
+                         "evaluation.restoration.bright_min)")
+    ap.add_argument("--restoration-dilate", type=int, default=None, metavar="D",
+                    help="pixels the occluder mask is grown by to cover the blurred rim, 0 .. 2 (default 1; needs --restoration "
+                         "tophat; sets evaluation.restoration.dilate)")
     ap.add_argument("--bootstrap", type=int, default=None, metavar="N",
                     help="paired frame bootstrap with N replicates (1 .. 65536): percentile intervals and standard errors of every "
                          "mIoU and degradation (sets evaluation.bootstrap_replicates)")
@@ -193,13 +206,29 @@ def parse_restoration_grid(text: str):
 
 def apply_restoration_options(args, config) -> None:
     """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* and the flags of --restoration clahe
-    into the configuration (the harness checks them)."""
+    and --restoration tophat into the configuration (the harness checks them)."""
+    tophat = {k: v for k, v in (("threshold", args.restoration_threshold), ("bright_min", args.restoration_bright_min),
+                                ("dilate", args.restoration_dilate)) if v is not None}
+    if tophat and args.restoration != "tophat":
+        raise ValueError("--restoration-threshold, --restoration-bright-min and --restoration-dilate need --restoration tophat")
+    if args.restoration_radius is not None and args.restoration not in ("tophat", "dark_channel"):
+        raise ValueError("--restoration-radius needs --restoration tophat or --restoration dark_channel")
+    if args.restoration == "tophat":
+        if args.restoration_refine is not None or args.restoration_guided_radius is not None or args.restoration_guided_eps is not None:
+            raise ValueError("--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to tophat")
+        if args.restoration_radius is not None:
+            tophat["radius"] = args.restoration_radius
     relight = {k: v for k, v in (("grid", args.restoration_grid), ("clip_limit", args.restoration_clip_limit),
                                  ("max_gain", args.restoration_max_gain), ("white_balance", args.restoration_white_balance))
                if v is not None}
     if relight and args.restoration != "clahe":
         raise ValueError("--restoration-grid, --restoration-clip-limit, --restoration-max-gain and --restoration-white-balance need "
                          "--restoration clahe")
+    if args.restoration == "tophat":
+        config.set("evaluation.restoration", {"method": "tophat", **tophat} if tophat else "tophat")
+        if args.restoration_conditions is not None:
+            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
+        return
     if args.restoration == "clahe":
         if args.restoration_refine is not None or args.restoration_guided_radius is not None or args.restoration_guided_eps is not None:
             raise ValueError("--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to clahe")
@@ -216,8 +245,9 @@ def apply_restoration_options(args, config) -> None:
     if guided and args.restoration_refine != "guided":
         raise ValueError("--restoration-guided-radius and --restoration-guided-eps need --restoration-refine guided")
     if args.restoration is not None:
-        config.set("evaluation.restoration", args.restoration if args.restoration_refine is None
-                   else {"refine": args.restoration_refine, **guided})
+        spec = {**({} if args.restoration_refine is None else {"refine": args.restoration_refine}), **guided,
+                **({} if args.restoration_radius is None else {"radius": args.restoration_radius})}
+        config.set("evaluation.restoration", spec if spec else args.restoration)
     if args.restoration_conditions is not None:
         config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
 

@@ -1,0 +1,358 @@
+"""-m gpu: awseg_deocclude against the numpy model of tests/deocclude_ref.py, bit for bit (restored frames, mask, counter rows: the
+header states every operation, so there is no tolerance); its launches replayed inside the fenced arena of tests/fenced.py with the
+prototypes of include/awseg_restore.h; and the harness option `evaluation.restoration: tophat` end to end."""
+import ctypes
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from tests import deocclude_ref as D
+from tests import fenced
+
+pytestmark = pytest.mark.gpu
+RESTORE_HEADER = Path(__file__).resolve().parents[1] / "include" / "awseg_restore.h"
+CASES = D.gpu_cases()
+
+
+@pytest.fixture(scope="module")
+def P(native):
+    from types import SimpleNamespace
+    import adverse_weather_semantic_segmentation_robustness_benchmark_amd as pkg
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd import ops
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd.data import loader
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation import harness, metrics
+    return SimpleNamespace(pkg=pkg, ops=ops, N=native, loader=loader, harness=harness, metrics=metrics, RobustnessMetrics=pkg.RobustnessMetrics)
+
+
+def on_device(x: np.ndarray, shift: int = 0) -> torch.Tensor:
+    """x on the device, `shift` float32 elements past a 16-byte boundary."""
+    buf = torch.empty(x.size + 4, dtype=torch.float32, device="cuda")
+    assert buf.data_ptr() % 16 == 0
+    t = buf[shift:shift + x.size].view(x.shape)
+    t.copy_(torch.from_numpy(x))
+    assert t.data_ptr() % 16 == 4 * shift
+    return t
+
+
+def same_bits(got: torch.Tensor, want: np.ndarray) -> bool:
+    return got.cpu().numpy().tobytes() == np.ascontiguousarray(want).tobytes()
+
+
+def differing(got: torch.Tensor, want: np.ndarray) -> str:
+    raw = got.cpu().numpy()
+    diff = np.nonzero(raw.view(np.int32) != want.view(np.int32)) if raw.dtype == np.float32 else np.nonzero(raw != want)
+    return "" if diff[0].size == 0 else f"{diff[0].size} of {want.size} values differ, first at {[int(d[0]) for d in diff]}"
+
+
+@pytest.mark.parametrize("name,x,kw,shift", CASES, ids=[c[0] for c in CASES])
+def test_deocclude_equals_the_numpy_model_bit_for_bit(P, name, x, kw, shift):
+    b, _, h, w = x.shape
+    cond = np.arange(b, dtype=np.int32) % 2                             # two slots wherever there are two frames
+    want, want_mask, want_stats = D.deocclude(x, cond=cond, n_slots=3, **kw)
+    stats = P.ops.new_deocclude_stats("cuda", 3)
+    out = on_device(np.zeros_like(x), shift)
+    mask = torch.full((b, h, w), 7, dtype=torch.uint8, device="cuda")
+    got, got_mask = P.ops.deocclude(on_device(x, shift), stats, torch.from_numpy(cond).cuda(), out=out, mask=mask, **kw)
+    torch.cuda.synchronize()
+    assert got.data_ptr() == out.data_ptr() and got_mask.data_ptr() == mask.data_ptr()
+    print(name, "model", want_stats[0].tolist(), "device", stats[0].cpu().numpy().tolist())
+    assert not differing(got_mask, want_mask), "mask: " + differing(got_mask, want_mask)
+    assert stats.cpu().numpy().tolist() == want_stats.tolist()
+    assert not differing(got, want), "restored: " + differing(got, want)
+    assert want_stats[0, D.MASKED] > 0 and bool(torch.isfinite(got).all())
+    if "unfilled" in name:
+        assert want_stats[0, D.UNFILLED] > 0
+    if "NaN" in name:
+        assert want_stats[0, D.NONFINITE] == 3
+    if b > 1:
+        assert want_stats[1, D.FRAMES] > 0 and want_stats[2, D.FRAMES] > 0 and want_stats[1].tolist() != want_stats[2].tolist()
+
+
+def test_both_paths_give_the_same_bits(P):
+    _, x, kw, _ = CASES[1]
+    a, am = P.ops.deocclude(on_device(x, 0), out=on_device(np.zeros_like(x), 0), **kw)
+    s, sm = P.ops.deocclude(on_device(x, 1), out=on_device(np.zeros_like(x), 1), **kw)
+    assert torch.equal(a, s) and torch.equal(am, sm) and int(am.sum()) > 0
+    # a mask that is not 4-byte aligned takes the scalar path as well
+    buf = torch.zeros(x.shape[0] * x.shape[2] * x.shape[3] + 4, dtype=torch.uint8, device="cuda")
+    odd = buf[1:1 + am.numel()].view(am.shape)
+    assert odd.data_ptr() % 4 == 1
+    o, om = P.ops.deocclude(on_device(x, 0), out=on_device(np.zeros_like(x), 0), mask=odd, **kw)
+    assert torch.equal(o, a) and torch.equal(om, am) and int(buf[0]) == 0 and int(buf[1 + am.numel():].sum()) == 0
+
+
+def test_other_parameters_and_normalisations_reach_the_kernel(P):
+    x = D.occluder_batch((2, 3, 33, 65), 11)
+    mean, std = np.array([0.4, 0.5, 0.45], np.float32), np.array([0.25, 0.2, 0.3], np.float32)
+    kw = {"radius": 4, "threshold": 0.11, "bright_min": 0.35, "dilate": 2}
+    want, want_mask, want_stats = D.deocclude(x, mean=mean, std=std, **kw)
+    stats = P.ops.new_deocclude_stats("cuda", 1)
+    got, got_mask = P.ops.deocclude(on_device(x), stats, mean=mean, std=std, **kw)
+    assert same_bits(got, want) and same_bits(got_mask, want_mask) and stats.cpu().numpy().tolist() == want_stats.tolist()
+    assert want_stats[0, D.MASKED] > 0 and D.deocclude(x, **kw)[0].tobytes() != want.tobytes()
+    for other in ({"threshold": 0.5}, {"bright_min": 0.9}, {"dilate": 0}, {"radius": 1}):
+        assert D.deocclude(x, mean=mean, std=std, **{**kw, **other})[1].tobytes() != want_mask.tobytes(), other
+
+
+def test_two_launches_into_one_stats_tensor_add_up(P):
+    x, y = D.occluder_batch((3, 3, 33, 65), 5), D.occluder_batch((3, 3, 33, 65), 6)
+    cond = np.array([1, -1, 0], np.int32)
+    first = D.deocclude(x, cond=cond, n_slots=3)[2]
+    second = D.deocclude(y, cond=cond[::-1], n_slots=3)[2]
+    stats = P.ops.new_deocclude_stats("cuda", 3)
+    P.ops.deocclude(on_device(x), stats, torch.from_numpy(cond).cuda())
+    assert stats.cpu().numpy().tolist() == first.tolist()
+    assert first[1].tolist() != first[2].tolist() and first[1, D.FRAMES] == first[2, D.FRAMES] == 1 and first[0, D.FRAMES] == 3
+    P.ops.deocclude(on_device(y), stats, torch.from_numpy(cond[::-1].copy()).cuda())
+    assert stats.cpu().numpy().tolist() == (first + second).tolist()
+    lone = P.ops.new_deocclude_stats("cuda", 2)                        # a condition that is no slot reaches slot 0 only
+    P.ops.deocclude(on_device(x), lone, torch.tensor([5, 1, -3], dtype=torch.int32, device="cuda"))
+    assert lone[0].cpu().numpy().tolist() == first[0].tolist() and not lone[1].any()
+
+
+def test_an_empty_batch_launches_nothing(P):
+    stats = P.ops.new_deocclude_stats("cuda", 2)
+    out, mask = P.ops.deocclude(torch.zeros(0, 3, 8, 12, device="cuda"), stats)
+    torch.cuda.synchronize()
+    assert tuple(out.shape) == (0, 3, 8, 12) and tuple(mask.shape) == (0, 8, 12) and not stats.any()
+    x = on_device(D.occluder_batch((1, 3, 8, 12), 1))
+    keep, keep_mask = torch.full_like(x, 7.0), torch.full((1, 8, 12), 7, dtype=torch.uint8, device="cuda")
+    mean, std = D.IMAGENET_MEAN.copy(), D.IMAGENET_STD.copy()
+    rc = P.N.lib().awseg_deocclude(P.N.ptr(x), 0, 3, 8, 12, P.N.host(mean), P.N.host(std), 9, 0.06, 0.5, 1, None, P.N.ptr(keep),
+                                   P.N.ptr(keep_mask), P.N.ptr(stats), 2, None, P.N.stream())
+    torch.cuda.synchronize()
+    assert rc == 0 and bool((keep == 7.0).all()) and bool((keep_mask == 7).all()) and not stats.any()
+
+
+def test_the_launcher_refuses_every_invalid_argument_with_its_code(P):
+    """On device buffers: a refusal comes before any launch, so outputs and counters stay as they were."""
+    b, h, w = 2, 8, 12
+    x = on_device(D.occluder_batch((b, 3, h, w), 2))
+    restored, mask = torch.full_like(x, 7.0), torch.full((b, h, w), 7, dtype=torch.uint8, device="cuda")
+    stats = P.ops.new_deocclude_stats("cuda", 2)
+    ws = torch.zeros(16, dtype=torch.uint8, device="cuda")
+    cond = torch.zeros(b, dtype=torch.int32, device="cuda")
+    mean, std = D.IMAGENET_MEAN.copy(), D.IMAGENET_STD.copy()
+    bad_std, bad_mean = np.array([0.2, -0.1, 0.2], np.float32), np.array([0.4, np.nan, 0.4], np.float32)
+    ptr, host = P.N.ptr, P.N.host
+    good = {"image": ptr(x), "batch": b, "channels": 3, "height": h, "width": w, "mean": host(mean), "std": host(std), "radius": 9,
+            "threshold": 0.06, "bright_min": 0.5, "dilate": 1, "cond": ptr(cond), "restored": ptr(restored), "mask": ptr(mask),
+            "stats": ptr(stats), "n_slots": 2, "workspace": ptr(ws), "stream": P.N.stream()}
+    lib = P.N.lib()
+    for name, value in [("image", None), ("mean", None), ("std", None), ("restored", None), ("mask", None), ("stats", None),
+                        ("channels", 1), ("batch", -1), ("height", 0), ("width", 0), ("n_slots", 0), ("radius", 0), ("radius", 16),
+                        ("threshold", 0.0), ("threshold", 1.5), ("threshold", float("nan")), ("bright_min", -0.5), ("bright_min", 1.5),
+                        ("bright_min", float("nan")), ("dilate", -1), ("dilate", 3), ("std", host(bad_std)), ("mean", host(bad_mean))]:
+        assert lib.awseg_deocclude(*dict(good, **{name: value}).values()) == -1, (name, value)
+    assert lib.awseg_deocclude(*dict(good, batch=65536).values()) == -2
+    assert lib.awseg_deocclude(*dict(good, height=1 << 16, width=1 << 15).values()) == -2
+    assert lib.awseg_deocclude(*dict(good, workspace=ctypes.c_void_p(ws.data_ptr() + 4)).values()) == -3
+    torch.cuda.synchronize()
+    assert bool((restored == 7.0).all()) and bool((mask == 7).all()) and not stats.any()
+    for kw in ({"radius": 16}, {"threshold": 0}, {"bright_min": 1.5}, {"dilate": 3}, {"out": x}, {"mask": torch.zeros(b, h, w, device="cuda")}):
+        with pytest.raises(ValueError):
+            P.ops.deocclude(x, **kw)
+    assert lib.awseg_deocclude(*good.values()) == 0 and lib.awseg_deocclude(*dict(good, workspace=None, cond=None).values()) == 0
+    torch.cuda.synchronize()
+    assert int(stats[0, D.FRAMES]) == 2 * b and not bool((mask == 7).any())
+
+
+# --------------------------------------------------------------------------------------------------------------------- fences
+@pytest.mark.parametrize("shift", [0, 1], ids=["aligned", "4 bytes off alignment"])
+def test_fenced_replay_writes_nothing_outside_its_buffers(P, monkeypatch, shift):
+    """The launch of ops.deocclude recorded and replayed by tests/fenced.py with the prototypes of both headers: 64 KiB of fence
+    around restored, the mask and the counter rows; the outputs poisoned with three bytes.  No fence byte changes, every output bit
+    equals the plain run whatever the poison, no output element is left unwritten, and the input is untouched.  There is no
+    workspace to fence: awseg_deocclude_workspace is 0 and the launcher gets NULL."""
+    protos = {**fenced.parse_header(), **fenced.parse_header(RESTORE_HEADER)}
+    assert [p.name for p in protos["awseg_deocclude"]][-2:] == ["workspace", "stream"] and protos["awseg_deocclude"][0].const
+    monkeypatch.setattr(fenced, "parse_header", lambda path=None: protos)         # record() asks it for the launchers' parameters
+    _, frames, kw, _ = CASES[1]                                         # 2 x 3 x 40 x 72
+    b, _, h, w = frames.shape
+    x = on_device(frames, shift)
+    cond = torch.tensor([0, 1], dtype=torch.int32, device="cuda")
+    stats = P.ops.new_deocclude_stats("cuda", 3)
+    stats[1, 1] = 17                                                  # an accumulator: what it held stays
+    out = on_device(np.zeros((b, 3, h, w), np.float32), shift)
+    trace = fenced.Trace()
+    with fenced.record(trace):
+        restored, mask = P.ops.deocclude(x, stats, cond, out=out, **kw)
+    torch.cuda.synchronize()
+    want, want_mask, want_stats = D.deocclude(frames, cond=[0, 1], n_slots=3, **kw)
+    want_stats[1, 1] += 17
+    assert same_bits(restored, want) and same_bits(mask, want_mask) and stats.cpu().numpy().tolist() == want_stats.tolist()
+    assert [l.name for l in trace.launches] == ["awseg_deocclude"]
+    assert P.N.lib().awseg_deocclude_workspace(b, h, w) == P.ops.deocclude_workspace_bytes(b, h, w) == 0
+    assert [buf.requested for buf in trace.buffers.values() if buf.requested is not None] == []
+
+    slots = fenced.plan(trace, protos, inout=("stats",))
+    kinds = {"/".join(sorted(s.params)): s.kind for s in slots}
+    assert kinds == {"image": "in", "cond": "in", "restored": "out", "mask": "out", "stats": "inout"}
+    replay = fenced.Replay(trace, slots, "cuda", protos=protos)
+    for s in slots:
+        if s.params & {"image", "restored"}:
+            assert s.region.view.data_ptr() % 16 == 4 * shift
+    after = {}
+    for byte in (0x00, 0xFF, 0x7F):
+        replay.run(byte)
+        damage = replay.arena.check()
+        assert not damage, f"poison {byte:#04x}: bytes outside a region changed: {damage}"
+        for s in slots:
+            if s.kind == "in":
+                assert torch.equal(s.region.view, s.initial), f"input {s.region.name} was modified"
+            if s.kind in ("out", "inout"):
+                assert torch.equal(s.region.view, s.final), f"poison {byte:#04x}: {s.region.name} differs from the plain run"
+        after[byte] = {id(s): s.region.view.clone() for s in slots if s.kind == "out"}
+    for s in slots:
+        if s.kind == "out":
+            left = fenced.unwritten(after[0x00][id(s)], after[0xFF][id(s)], s.elem)
+            assert left.numel() == 0, f"{left.numel()} elements of {s.region.name} were never written"
+
+
+# ----------------------------------------------------------------------------------------------------------------- end to end
+def _run(P, model, ds, restoration=None, frames=None, **state):
+    """eval_batch over ds -> (state, results).  `frames`: what each batch's images are replaced with."""
+    metrics = P.RobustnessMetrics(19, ds.weather_conditions)
+    st = P.harness.EvalState(metrics, ds.weather_conditions, "cuda", 15, True, restoration=restoration, **state)
+    for batch in ds.batches(2):
+        images = batch["image"]
+        if frames is not None:
+            images = frames(images, st.acc.cond_ids(batch["weather_condition"]))
+        P.harness.eval_batch(model, st, images, batch["label"], batch["weather_condition"], metrics)
+    return st, P.harness.finalize(st, metrics)
+
+
+OCCLUDER_STEMS = ("occluder_", "mean_occluder_")
+
+
+@pytest.fixture(scope="module")
+def tiny(P):
+    """A tiny random-weight ensemble and four frames (clean, rain, snow, fog) at 64 x 128, with the plain run every case compares to."""
+    from tests.test_gpu_paired import _dataset, _model
+    model = _model()
+    ds = _dataset(P, n=4, hw=(64, 128), kinds=("rain", "snow", "fog"), schedule="round_robin")
+    st_off, off = _run(P, model, ds)
+    return model, ds, st_off, off
+
+
+def test_harness_scores_the_deoccluded_frames_a_second_time(P, tiny):
+    model, ds, st_off, off = tiny
+    conditions = list(ds.weather_conditions)
+    option = P.harness.restoration_option({"evaluation.restoration": {"method": "tophat", "radius": 7}})
+    st_on, on = _run(P, model, ds, option)
+
+    # off: nothing allocated, and key for key, bit for bit what the on-run reports for everything that existed before
+    assert st_off.restoration is None and st_off.restoration_deocclude is None and st_off.restoration_relight is None
+    new = set(on) - set(off)
+    assert set(off) <= set(on) and all(repr(on[k]) == repr(off[k]) for k in off)
+    assert torch.equal(st_on.acc.counts, st_off.acc.counts) and torch.equal(st_on.ece, st_off.ece)
+    assert new and all("restor" in k or k.startswith(OCCLUDER_STEMS) for k in new)
+    assert not any("airlight" in k or "transmission" in k or "relight" in k or "luma" in k for k in on)
+    assert on["restoration_method"] == "tophat"
+    # no dehazing, guided or relighting counters are allocated
+    assert st_on.restoration["stats"].numel() == 0 and st_on.restoration_guided is None and st_on.restoration_relight is None
+
+    # the second accumulator is a plain evaluation of ops.deocclude's frames
+    hand = P.ops.new_deocclude_stats("cuda", 1 + len(conditions))
+    st_hand, by_hand = _run(P, model, ds, frames=lambda x, cond: P.ops.deocclude(x, hand, cond, radius=7)[0])
+    rs = st_on.restoration
+    assert torch.equal(rs["counts"], st_hand.acc.counts) and int(rs["counts"].sum()) > 0
+    assert torch.equal(st_on.restoration_deocclude["stats"], hand) and int(rs["oob"].item()) == 0
+    assert int(hand[0, D.FRAMES]) == len(ds) and int(hand[0, D.PIXELS]) == len(ds) * 64 * 128
+
+    # every key of the option
+    assert repr(on["overall_miou_restored"]) == repr(by_hand["overall_miou"])
+    want = P.metrics.deocclude_metrics_from_stats(hand.cpu().numpy(), conditions)
+    assert {k: on[k] for k in want} == want
+    for c in conditions:
+        assert repr(on[f"miou_{c}_restored"]) == repr(by_hand[f"miou_{c}"])
+        assert on[f"restoration_gain_{c}"] == on[f"miou_{c}_restored"] - on[f"miou_{c}"]
+        assert 0.0 <= on[f"occluder_seed_fraction_{c}"] <= on[f"occluder_fraction_{c}"] <= 1.0
+        assert f"robustness_degradation_{c}_restored" in on or c == "clean"
+    assert on["restoration_clean_cost"] == on["miou_clean"] - on["miou_clean_restored"]
+    same_frames = P.metrics.iou_from_counts(st_on.acc.counts[1:].sum(0), 19)["mean_iou"]
+    assert on["mean_restoration_gain"] == on["overall_miou_restored"] - same_frames
+    from adverse_weather_semantic_segmentation_robustness_benchmark_amd.evaluation.report import report_markdown
+    text = report_markdown({k: v if isinstance(v, str) else float(v) for k, v in on.items()})
+    assert "## Input Restoration" in text and "Method: tophat" in text and "| Occluders | Change |" in text
+    assert all(f"| {c} | {on[f'miou_{c}']:.3f} | {on[f'miou_{c}_restored']:.3f} | {on[f'restoration_gain_{c}']:.3f} | "
+               f"{on[f'occluder_fraction_{c}']:.3f} |" in text for c in conditions)
+
+    # [rain, snow], the obvious use: the other slots' restored counters stay at zero
+    only = P.harness.restoration_option({"evaluation.restoration": {"method": "tophat", "radius": 7},
+                                         "evaluation.restoration_conditions": ["rain", "snow"]})
+    st_rs, res_rs = _run(P, model, ds, only)
+    picked = [1 + conditions.index(c) for c in ("rain", "snow")]
+    others = [i for i in range(1, 1 + len(conditions)) if i not in picked]
+    assert not st_rs.restoration["counts"][others].any() and not st_rs.restoration_deocclude["stats"][others].any()
+    assert torch.equal(st_rs.restoration_deocclude["stats"][picked], hand[picked])
+    assert torch.equal(st_rs.restoration_deocclude["stats"][0], hand[picked].sum(0))
+    assert "miou_rain_restored" in res_rs and "miou_clean_restored" not in res_rs and "occluder_fraction_fog" not in res_rs
+    assert torch.equal(st_rs.acc.counts, st_off.acc.counts)
+    st_on.all_reduce()                                                 # the table-driven reduce takes the new entry's tensors
+
+
+@pytest.mark.parametrize("spec", ["dark_channel", {"refine": "guided"}, "clahe"], ids=["dark_channel", "guided", "clahe"])
+def test_the_other_methods_report_what_they_reported(P, tiny, spec):
+    """Under dark_channel and clahe nothing new is allocated or launched, and the result dict is, key for key and bit for bit, the
+    plain run's keys plus what the method's own launcher and host functions give by hand."""
+    model, ds, st_off, off = tiny
+    conditions = list(ds.weather_conditions)
+    option = P.harness.restoration_option({"evaluation.restoration": spec})
+    st, res = _run(P, model, ds, option)
+    assert st.restoration_deocclude is None and not any(k.startswith(OCCLUDER_STEMS) for k in res)
+    assert res.get("restoration_method") in (None, "clahe") and all(repr(res[k]) == repr(off[k]) for k in off)
+    n = 1 + len(conditions)
+    if spec == "clahe":
+        hand = P.ops.new_relight_stats("cuda", n)
+        frames = lambda x, cond: P.ops.relight(x, hand, cond)[0]                               # noqa: E731
+    elif spec == "dark_channel":
+        hand = P.ops.new_dehaze_stats("cuda", n)
+        frames = lambda x, cond: P.ops.dehaze(x, hand, cond)[0]                                # noqa: E731
+    else:
+        hand, filt = P.ops.new_dehaze_stats("cuda", n), P.ops.new_guided_stats("cuda", n)
+        frames = lambda x, cond: P.ops.dehaze_guided(x, hand, filt, cond)[0]                   # noqa: E731
+    st_hand, by_hand = _run(P, model, ds, frames=frames)
+    kw = {"degradation": P.RobustnessMetrics(19, conditions).compute_robustness_degradation_ratio}
+    dehaze_rows = np.zeros((n, P.ops.DEHAZE_ROW), np.int64) if spec == "clahe" else hand.cpu().numpy()
+    want = dict(off)
+    want.update(P.metrics.restoration_metrics_from_stats(st_hand.acc.counts.cpu().numpy(), st_off.acc.counts.cpu().numpy(), dehaze_rows,
+                                                         conditions, 19, **kw))
+    if spec == "clahe":
+        want.update(P.metrics.relight_metrics_from_stats(hand.cpu().numpy(), conditions))
+    if isinstance(spec, dict):
+        want.update(P.metrics.guided_metrics_from_stats(filt.cpu().numpy(), conditions))
+        want["restoration_refine"] = "guided"
+    assert set(res) == set(want) and all(repr(res[k]) == repr(want[k]) for k in want)
+
+
+def test_harness_measures_the_fidelity_of_the_deoccluded_frames(P):
+    from tests.test_gpu_dehaze_guided import _sweep_run
+    from tests.test_gpu_paired import _model
+    from tests.test_gpu_quality import _dataset
+    model = _model()
+    ds = _dataset(P, n=2, hw=(64, 128), kinds=("rain", "snow"))
+    slots = ds.sweep.slots()
+    quality = {"targets": [0.9, 0.75, 0.5]}
+    option = P.harness.restoration_option({"evaluation.restoration": "tophat"})
+    st, on, batches = _sweep_run(P, model, ds, True, quality=quality, restoration=option)
+    clean = {s: img[i] for img, _, sources, severity in batches if severity == 0 for i, s in enumerate(sources)}
+    second = P.ops.new_image_quality_stats("cuda", 1 + len(slots))
+    filled = P.ops.new_deocclude_stats("cuda", 1 + len(slots))
+    oob = torch.zeros(1, dtype=torch.int64, device="cuda")
+    for img, names, sources, severity in batches:
+        cond = st.acc.cond_ids([P.loader.slot_name(n, severity) for n in names])
+        restored = P.ops.deocclude(img, filled, cond, **st.restoration["params"])[0]
+        twins = torch.stack([clean[s] for s in sources])
+        P.ops.image_quality(restored, twins, torch.arange(len(sources), dtype=torch.int32, device="cuda"), second, cond=cond, oob=oob)
+    assert torch.equal(st.restored_quality["stats"], second) and torch.equal(st.restoration_deocclude["stats"], filled)
+    kinds = sorted({s.rsplit("_s", 1)[0] for s in slots if "_s" in s})
+    want = P.metrics.restored_quality_metrics_from_stats(second.cpu().numpy(), st.quality["stats"].cpu().numpy(), slots, kinds, 2)
+    assert want and {k: on[k] for k in want} == want and on["restoration_method"] == "tophat"
+    for n in (f"{kinds[0]}_s1", f"{kinds[0]}_s2", kinds[0]):
+        assert f"psnr_{n}_restored" in on and f"ssim_{n}_restored" in on and f"restoration_psnr_gain_{n}" in on
+        assert f"restoration_ssim_gain_{n}" in on and f"occluder_fraction_{n}" in on
+    pooled = P.metrics.deocclude_metrics_from_stats(filled.cpu().numpy(), slots, kinds=kinds, levels=2)
+    assert {k: on[k] for k in pooled} == pooled

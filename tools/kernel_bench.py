@@ -222,6 +222,16 @@ def main():
     for tag, frames in (("rendered-like frames", chg_var), ("night-like frames", rl_night), ("independent random frames", iq_rand[0])):
         cases[f"relight 8x8, {tag}"] = (
             lambda frames=frames: ops.relight(frames, rlst, cond, grid=(8, 8), out=dz_out), "hbm", 36 * px * B)
+    # rain and snow removal (evaluation.restoration: tophat): top-hat mask + masked fill, two kernels per launch.  The detection
+    # kernel reads the frame and writes the mask (13 B/px), the fill kernel reads both and writes the frame (25 B/px): 38 B/px, but
+    # detection takes three channels of separable minima and maxima where the dehazer's recovery pass takes one (~8 r LDS reads per
+    # pixel and channel), so the row is bound by LDS and vector issue and "of peak" says how far from a copy the stencil is.  The
+    # 16 x 16 flakes of the rendered-like frames are occluders at r = 9 and r = 15; the random frames mask most pixels
+    dost, do_mask = ops.new_deocclude_stats(dev, 6), torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    for tag, frames in (("rendered-like frames", chg_var), ("independent random frames", iq_rand[0])):
+        for r in (9, 15):
+            cases[f"deocclude r={r} d=1, {tag}"] = (
+                lambda frames=frames, r=r: ops.deocclude(frames, dost, cond, radius=r, out=dz_out, mask=do_mask), "hbm", 38 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
