@@ -160,6 +160,9 @@ EXTENSION_SIGNATURES = {
     "awseg_relight": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
     "awseg_deocclude_workspace": (c_i64, [c_i64, c_i64, c_i64]),
     "awseg_deocclude": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),
+    "awseg_weather_estimate_workspace": (c_i64, [c_i64]),
+    "awseg_weather_estimate": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_i,
+                                     c_p, c_p]),
 }
 
 

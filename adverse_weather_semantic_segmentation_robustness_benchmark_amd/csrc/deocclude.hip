@@ -4,7 +4,8 @@
 //
 // awseg_deocclude: two kernels on the caller's stream, no host synchronisation, no block waits for another.  Both run on the tiles
 // of the dehazer (dehaze_tiles.h, whose constants, v_c and reductions they share) and walk the three channels one after another
-// through one staged plane and one scratch plane, so that the LDS stays what one channel needs.
+// through one staged plane and one scratch plane, so that the LDS stays what one channel needs.  The detection kernel's geometry,
+// staging and window passes live in deocclude_tiles.h, which estimate.hip (awseg_weather_estimate) shares.
 //   detect_kernel   512 threads.  Per channel: stages v_c for the tile plus a halo of 2 r + d (+inf outside the frame), takes the (2r+1)^2 minimum
 //                   separably on the tile plus r + d, then the (2r+1)^2 maximum of the minima (-inf outside the frame) on the tile
 //                   plus d, and folds v_c - o_c and v_c into the running minima h and b, which a thread keeps in registers for its
@@ -17,90 +18,18 @@
 // LDS: detect [TH + 2 halo][TW + 2 pad] + [TH + 2 halo][TW + 2 (r + d)] floats (pad = halo rounded up to whole float4s): 52.6 KB
 // at r = 9, d = 1 (three resident blocks per CU, 24 waves), 86.8 KB at r = 15, d = 2 (one, 8 waves); fill [TH + 2 r][TW + 2 pad + TW] words: 30.4 KB at
 // r = 9, 39.7 KB at r = 15.
-#define AWSEG_DEHAZE_TILES_NO_LAUNCHER                                     // the constants, v_c and the reductions only
-#include "dehaze_tiles.h"
-
-// The window loops: 2 r taps beside the first, two per trip (minima, maxima and integer sums do not mind the order), four trips
-// unrolled, so that eight LDS reads are in flight where a plain loop waits for each.
-#define AWSEG_TAPS _Pragma("unroll 4")
+#include "deocclude_tiles.h"                                              // the geometry, the staging and the window passes
 
 namespace {
 
 constexpr int kDRow = AWSEG_DEOCCLUDE_ROW;
 constexpr int kMaxDilate = AWSEG_DEOCCLUDE_MAX_DILATE;
-constexpr int kDetectThreads = 512;                                        // the detection kernel: twice the waves per staged tile
-constexpr int kDetectWaves = kDetectThreads / AWSEG_WAVE;
 constexpr int kRing = ((kTH + 2 * kMaxDilate) * (kTW + 2 * kMaxDilate) + kDetectThreads - 1) / kDetectThreads;    // positions of the tile plus d per thread
 constexpr uint32_t kOne = 1u << 24, kSumMask = kOne - 1;                   // the count above the sum of q in a staged word
 static_assert((2 * AWSEG_DEHAZE_MAX_RADIUS + 1) * 65536 < (int)kOne, "a row sum of q stays below the count");
 static_assert(kTH * kTW % kThreads == 0, "every thread owns the same number of pixels");
 
-struct dc_args {
-    float mean[3], std[3];
-    float threshold, bright_min;
-    int r, d;
-    int halo, pad, sw, rows, q, c1, c2;                                    // detection, see geometry()
-    int fpad, fsw, frows;                                                  // fill
-};
-
-// Detection: halo = 2 r + d pixels staged around the tile, pad = halo rounded up to whole float4s, sw staged columns, rows staged
-// rows; q = r + d: the ring of minima the maximum pass reads; c1 = TW + 2 q; c2 = TW + 2 d: the columns the seeds are needed on.
-// Fill: a halo of r, fpad, fsw and frows likewise.
-void geometry(int r, int d, dc_args& g)
-{
-    g.r = r;
-    g.d = d;
-    g.halo = 2 * r + d;
-    g.pad = (g.halo + 3) & ~3;
-    g.sw = kTW + 2 * g.pad;
-    g.rows = kTH + 2 * g.halo;
-    g.q = r + d;
-    g.c1 = kTW + 2 * g.q;
-    g.c2 = kTW + 2 * d;
-    g.fpad = (r + 3) & ~3;
-    g.fsw = kTW + 2 * g.fpad;
-    g.frows = kTH + 2 * r;
-}
-size_t detect_lds(const dc_args& g) { return (size_t)g.rows * (g.sw + g.c1) * sizeof(float); }
 size_t fill_lds(const dc_args& g) { return (size_t)g.frows * (g.fsw + kTW) * sizeof(uint32_t); }
-
-// a[c] of a kernel argument without an indexed (scratch) copy of it
-__device__ __forceinline__ float pick(const float (&a)[3], int c) { return c == 0 ? a[0] : c == 1 ? a[1] : a[2]; }
-
-// b0 [g.rows][g.sw] = v_c over the tile and its halo, +inf outside the frame; `bad` += the tile's own values that are not finite.
-template <bool VEC>
-__device__ __forceinline__ void stage_channel(const float* __restrict__ plane, int H, int W, int y0, int x0, const dc_args& g, float sd,
-                                              float mean, float* __restrict__ b0, uint32_t& bad)
-{
-    const int tid = threadIdx.x;
-    if constexpr (VEC) {
-        const int groups = g.sw / 4;
-        for (int i = tid; i < g.rows * groups; i += kDetectThreads) {
-            const int row = i / groups, col = (i - row * groups) * 4;
-            const int yy = y0 - g.halo + row, xx = x0 - g.pad + col;         // W % 4 == 0 and (x0 - pad) % 4 == 0: a group is inside or outside
-            float4 o = { INFINITY, INFINITY, INFINITY, INFINITY };
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const float4 a = *reinterpret_cast<const float4*>(plane + (int64_t)yy * W + xx);
-                if (row >= g.halo && row < g.halo + kTH && col >= g.pad && col < g.pad + kTW)
-                    bad += not_finite(a.x) + not_finite(a.y) + not_finite(a.z) + not_finite(a.w);
-                o = { unit(a.x, sd, mean), unit(a.y, sd, mean), unit(a.z, sd, mean), unit(a.w, sd, mean) };
-            }
-            *reinterpret_cast<float4*>(b0 + row * g.sw + col) = o;
-        }
-    } else {
-        for (int i = tid; i < g.rows * g.sw; i += kDetectThreads) {
-            const int row = i / g.sw, col = i - row * g.sw;
-            const int yy = y0 - g.halo + row, xx = x0 - g.pad + col;
-            float o = INFINITY;
-            if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const float a = plane[(int64_t)yy * W + xx];
-                if (row >= g.halo && row < g.halo + kTH && col >= g.pad && col < g.pad + kTW) bad += not_finite(a);
-                o = unit(a, sd, mean);
-            }
-            b0[row * g.sw + col] = o;
-        }
-    }
-}
 
 // One row of counters into slot 0 and the frame's own slot.
 __device__ __forceinline__ void add_row(int64_t* __restrict__ stats, int n_slots, const int32_t* __restrict__ cond, int64_t img,
@@ -127,12 +56,11 @@ void detect_kernel(const float* __restrict__ image, int H, int W, int tiles_x, c
     float* b1 = b0 + g.rows * g.sw;                                        // [rows][c1]
     __shared__ long long red[kDetectWaves][3];
     const int64_t img = blockIdx.y, hw = (int64_t)H * W;
-    const int tid = threadIdx.x, taps = 2 * g.r;
+    const int tid = threadIdx.x;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int y0 = ty * kTH, x0 = tx * kTW;
     const float* frame = image + img * 3 * hw;
     const int eh = kTH + 2 * g.d, n_e = eh * g.c2;                          // the tile plus d: where the seeds are needed
-    const int rows_e = kTH + 2 * g.q;
     float h[kRing], b[kRing];
 #pragma unroll
     for (int k = 0; k < kRing; ++k) h[k] = b[k] = INFINITY;
@@ -150,45 +78,15 @@ void detect_kernel(const float* __restrict__ image, int H, int W, int tiles_x, c
                 v[k] = b0[(g.halo - g.d + i) * g.sw + (g.pad - g.d) + j];
             }
         }
-        // minimum along the row: column j of b1 is pixel x0 - q + j
-        for (int i = tid; i < g.rows * g.c1; i += kDetectThreads) {
-            const int row = i / g.c1, j = i - row * g.c1;
-            const float* p = b0 + row * g.sw + (g.pad - g.halo) + j;
-            float m = p[0];
-            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k], p[k + 1]));
-            b1[i] = m;
-        }
-        __syncthreads();
-        // minimum down the column: row ii of b0 [rows_e][c1] is pixel row y0 - q + ii; positions outside the frame take part in no maximum
-        for (int i = tid; i < rows_e * g.c1; i += kDetectThreads) {
-            const int ii = i / g.c1, j = i - ii * g.c1;
-            const float* p = b1 + i;
-            float m = p[0];
-            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k * g.c1], p[(k + 1) * g.c1]));
-            const int yy = y0 - g.q + ii, xx = x0 - g.q + j;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) m = -INFINITY;
-            b0[i] = m;
-        }
-        __syncthreads();
-        // maximum along the row: column j of b1 [rows_e][c2] is pixel x0 - d + j
-        for (int i = tid; i < rows_e * g.c2; i += kDetectThreads) {
-            const int ii = i / g.c2, j = i - ii * g.c2;
-            const float* p = b0 + ii * g.c1 + j;
-            float m = p[0];
-            AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fmaxf(m, fmaxf(p[k], p[k + 1]));
-            b1[i] = m;
-        }
-        __syncthreads();
+        minimum_passes(H, W, y0, x0, g, b0, b1);                           // e_c on the tile plus q, -inf outside the frame
+        maximum_row_pass(g, b0, b1);
         // maximum down the column at this thread's positions: o_c, folded into the running minima.  The next channel's staging
         // writes b0 only, and its row pass writes b1 after a barrier.
 #pragma unroll
         for (int k = 0; k < kRing; ++k) {
             const int idx = tid + k * kDetectThreads;
             if (idx < n_e) {
-                const float* p = b1 + idx;
-                float m = p[0];
-                AWSEG_TAPS for (int t = 1; t <= taps; t += 2) m = fmaxf(m, fmaxf(p[t * g.c2], p[(t + 1) * g.c2]));
-                h[k] = fminf(h[k], v[k] - m);
+                h[k] = fminf(h[k], v[k] - maximum_down(b1, idx, g));
                 b[k] = fminf(b[k], v[k]);
             }
         }

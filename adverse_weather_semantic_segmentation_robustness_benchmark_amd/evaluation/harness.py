@@ -29,7 +29,7 @@ from .. import _native as N
 from .. import ops, parallel
 from ..data.loader import resolve_severities, slot_name
 from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMetrics, bootstrap_metrics_from_replicates,
-                      boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, deocclude_metrics_from_stats,
+                      boundary_metrics_from_stats, calibration_from_stats, change_metrics_from_stats, deocclude_metrics_from_stats, estimate_metrics_from_stats,
                       depth_metrics_from_stats,
                       failure_metrics_from_stats, iou_from_counts, guided_metrics_from_stats, quality_metrics_from_stats,
                       relight_metrics_from_stats, restoration_metrics_from_stats, restored_quality_metrics_from_stats,
@@ -290,6 +290,11 @@ RESTORATION_RELIGHT_KEYS = ("grid", "clip_limit", "max_gain", "white_balance")  
 RESTORATION_WHITE_BALANCE = {"gray_world": True, "none": False}
 # only under method: tophat (awseg_deocclude); `radius` is a key of the dark channel as well and belongs to the method named
 RESTORATION_DEOCCLUDE_KEYS = ("radius", "threshold", "bright_min", "dilate")
+# under method: auto (awseg_weather_estimate) the three methods above are chosen per frame: the keys of that level,
+# the keys of `estimator`, and the route a rule that knew the weather would take (names outside the map: none)
+RESTORATION_AUTO_KEYS = ("route", "estimator", "dark_channel", "clahe", "tophat")
+RESTORATION_ROUTES = ("estimated", "oracle")
+RESTORATION_ESTIMATOR_KEYS = tuple(ops.ESTIMATE_DEFAULTS)
 
 
 def _relight_option(spec: dict) -> dict:
@@ -335,6 +340,43 @@ def _deocclude_option(spec: dict) -> dict:
     return {"method": "tophat", **opt}
 
 
+def _auto_option(spec: dict) -> dict:
+    """The dict of `evaluation.restoration` under method: auto (without 'method') -> the checked option, without 'conditions':
+    {'method': 'auto', 'route', 'estimator', 'dark_channel', 'clahe', 'tophat'}, the last three what restoration_option gives for
+    that method alone (without 'conditions')."""
+    levels = {"dark_channel": set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS), "clahe": set(RESTORATION_RELIGHT_KEYS),
+              "tophat": set(RESTORATION_DEOCCLUDE_KEYS), "estimator": set(RESTORATION_ESTIMATOR_KEYS)}
+    for key in sorted(set(spec) - set(RESTORATION_AUTO_KEYS)):
+        homes = [name for name, keys in levels.items() if key in keys]
+        if homes:
+            raise ValueError(f"evaluation.restoration: {key!r} belongs under {' or '.join(repr(h) for h in homes)} with method: auto, "
+                             "not beside them")
+        raise ValueError(f"evaluation.restoration with method: auto is a dict with keys among {list(RESTORATION_AUTO_KEYS)}, got {spec!r}")
+    route = spec.get("route", "estimated")
+    if not isinstance(route, str) or route not in RESTORATION_ROUTES:
+        raise ValueError(f"evaluation.restoration.route is 'estimated' or 'oracle', got {route!r}")
+    opt = {"method": "auto", "route": route}
+    est = spec.get("estimator", {})
+    if not isinstance(est, dict) or set(est) - set(RESTORATION_ESTIMATOR_KEYS):
+        raise ValueError(f"evaluation.restoration.estimator is a dict with keys among {list(RESTORATION_ESTIMATOR_KEYS)}, got {est!r}")
+    try:
+        opt["estimator"] = ops.weather_estimate_parameters(**est)
+    except ValueError as e:
+        raise ValueError(f"evaluation.restoration.estimator: {e}") from None
+    for method in RESTORATION_METHODS:
+        sub = spec.get(method, {})
+        if not isinstance(sub, dict) or set(sub) & ({"method"} | set(RESTORATION_AUTO_KEYS)):
+            raise ValueError(f"evaluation.restoration.{method} is a dict of that method's parameters, got {sub!r}")
+        if method == "dark_channel" and sub.get("refine") == "guided":
+            raise ValueError("evaluation.restoration.dark_channel: refine: guided is not available under method: auto")
+        try:
+            one = restoration_option({"evaluation.restoration": {"method": method, **sub}})
+        except ValueError as e:
+            raise ValueError(str(e).replace("evaluation.restoration", f"evaluation.restoration.{method}", 1)) from None
+        opt[method] = {k: v for k, v in one.items() if k not in ("method", "conditions")}
+    return opt
+
+
 def restoration_option(config, images=None):
     """`evaluation.restoration` (default off): 'dark_channel', or a dict with any of `radius` (an integer in [1, 15], default 7),
     `omega`, `t_min`, `airlight_min` (numbers in (0, 1], defaults 0.95, 0.1, 0.1) and `refine` ('opening', the default, 'none', or
@@ -356,7 +398,13 @@ def restoration_option(config, images=None):
     under 'guided': {'radius', 'omega', 't_min', 'airlight_min', 'guided_radius', 'guided_eps', 'refine': 'guided', 'conditions'};
     under 'clahe': {'method': 'clahe', 'grid' (ty, tx), 'clip_limit', 'max_gain', 'white_balance' (a bool), 'conditions'};
     under 'tophat': {'method': 'tophat', 'radius', 'threshold', 'bright_min', 'dilate', 'conditions'}.  Only the last two carry a
-    'method' key."""
+    'method' key, and 'auto':
+    'auto', or a dict with `method: auto` and any of `route` ('estimated', the default: every selected frame goes to the method the
+    weather estimate of DESIGN.md 10q names for it, or to none; 'oracle': to the method ops.ESTIMATE_EXPECTED_ROUTE names for its true
+    condition, the upper bound), `estimator` (a dict of the estimate's parameters: `radius`, `threshold`, `bright_min`, `cast_max`, `luma_max`,
+    `dark_min`, `seed_min`; ops.ESTIMATE_DEFAULTS) and `dark_channel`, `clahe`, `tophat` (each a dict of that method's parameters as
+    above, its defaults when absent; `refine: guided` is refused).  A key of one level is refused at another.
+    -> {'method': 'auto', 'route', 'estimator', 'dark_channel', 'clahe', 'tophat', 'conditions'}."""
     names = _cfg(config, "evaluation.restoration_conditions", None)
     if names is not None:
         if isinstance(names, (str, bytes, dict)) or not isinstance(names, (list, tuple)) or not names \
@@ -367,16 +415,17 @@ def restoration_option(config, images=None):
     if spec is None:
         return None
     if isinstance(spec, str):
-        if spec not in RESTORATION_METHODS:
-            raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat' or a dict of a method's parameters, got {spec!r}")
+        if spec not in RESTORATION_METHODS and spec != "auto":
+            raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat', 'auto' or a dict of a method's parameters, "
+                             f"got {spec!r}")
         spec = {"method": spec}
     if isinstance(spec, dict) and "method" in spec:
         method = spec["method"]
-        if not isinstance(method, str) or method not in RESTORATION_METHODS:
-            raise ValueError(f"evaluation.restoration.method is 'dark_channel', 'clahe' or 'tophat', got {method!r}")
+        if not isinstance(method, str) or (method not in RESTORATION_METHODS and method != "auto"):
+            raise ValueError(f"evaluation.restoration.method is 'dark_channel', 'clahe', 'tophat' or 'auto', got {method!r}")
         spec = {k: v for k, v in spec.items() if k != "method"}
-        if method in ("clahe", "tophat"):
-            opt = _relight_option(spec) if method == "clahe" else _deocclude_option(spec)
+        if method in ("clahe", "tophat", "auto"):
+            opt = _relight_option(spec) if method == "clahe" else _deocclude_option(spec) if method == "tophat" else _auto_option(spec)
             if images is not None:
                 check_frames("restoration", images)
             opt["conditions"] = names
@@ -478,6 +527,7 @@ COUNTERS = (
     ("restoration_guided", ("stats",), None, None, None),
     ("restoration_relight", ("stats",), None, None, None),
     ("restoration_deocclude", ("stats",), None, None, None),
+    ("restoration_estimate", ("stats",), None, None, None),
     ("restored_quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality "
                                                                           "counters of the restored frames"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
@@ -615,11 +665,13 @@ class EvalState:
         # for the forward on the dehazed frames, and the dehazing counters int64 [slot, AWSEG_DEHAZE_ROW].  'conditions': the weather
         # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
         self.restoration = None
+        auto = restoration is not None and restoration.get("method") == "auto"
         relit = restoration is not None and restoration.get("method") == "clahe"
         tophat = restoration is not None and restoration.get("method") == "tophat"
         if restoration is not None:
-            guided = not relit and not tophat and restoration["refine"] == "guided"
-            params = (ops.relight_parameters(**{k: restoration[k] for k in RESTORATION_RELIGHT_KEYS}) if relit
+            guided = not relit and not tophat and not auto and restoration["refine"] == "guided"
+            params = (None if auto
+                      else ops.relight_parameters(**{k: restoration[k] for k in RESTORATION_RELIGHT_KEYS}) if relit
                       else ops.deocclude_parameters(**{k: restoration[k] for k in RESTORATION_DEOCCLUDE_KEYS}) if tophat
                       else ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
                       else ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS}))
@@ -631,18 +683,31 @@ class EvalState:
                                 else ops.new_dehaze_stats(device, 1 + len(conditions))}
         # under refine: guided the counters of the filter, int64 [slot, AWSEG_GUIDED_ROW] (None otherwise: awseg_dehaze runs)
         self.restoration_guided = None
-        if restoration is not None and not relit and not tophat and restoration["refine"] == "guided":
+        if restoration is not None and not relit and not tophat and not auto and restoration["refine"] == "guided":
             self.restoration_guided = {"stats": ops.new_guided_stats(device, 1 + len(conditions))}
         # under method: clahe the counters of the relighting, int64 [slot, AWSEG_RELIGHT_ROW] (None otherwise); awseg_relight
         # produces the restored frames, everything behind it is the dehazer's second pass
         self.restoration_relight = None
-        if relit:
+        if relit or auto:
             self.restoration_relight = {"stats": ops.new_relight_stats(device, 1 + len(conditions))}
         # under method: tophat the counters of the occluder removal, int64 [slot, AWSEG_DEOCCLUDE_ROW] (None otherwise); awseg_deocclude
         # produces the restored frames, everything behind it is the dehazer's second pass.  The mask is not kept
         self.restoration_deocclude = None
-        if tophat:
+        if tophat or auto:
             self.restoration_deocclude = {"stats": ops.new_deocclude_stats(device, 1 + len(conditions))}
+        # under method: auto all three methods' counters above are allocated, each sees the frames routed to it, and
+        # the counters of the weather estimate, int64 [slot, AWSEG_ESTIMATE_ROW], see every selected frame.  'route': 'estimated'
+        # or 'oracle'; 'params': the estimator's and each method's; 'host', 'event': the pinned buffer the routes are copied to and
+        # the event behind that copy (estimated only); 'pending': the estimate of the batch in flight; 'readbacks': how many batches'
+        # routes the host has waited for
+        self.restoration_estimate = None
+        if auto:
+            self.restoration_estimate = {"stats": ops.new_estimate_stats(device, 1 + len(conditions)), "route": restoration["route"],
+                                         "params": {"estimator": ops.weather_estimate_parameters(**restoration["estimator"]),
+                                                    "dark_channel": ops.dehaze_parameters(**{k: restoration["dark_channel"][k] for k in RESTORATION_KEYS}),
+                                                    "clahe": ops.relight_parameters(**{k: restoration["clahe"][k] for k in RESTORATION_RELIGHT_KEYS}),
+                                                    "tophat": ops.deocclude_parameters(**{k: restoration["tophat"][k] for k in RESTORATION_DEOCCLUDE_KEYS})},
+                                         "host": None, "event": None, "pending": None, "readbacks": 0}
         # fidelity of the restored frames (only when the sweep, the image-quality counters and the restoration are all on): a SECOND
         # image-quality tensor, the restored frames against the same kept clean frames; the clean batch against its own kept rows
         self.restored_quality = None
@@ -773,10 +838,74 @@ class EvalState:
     def check_relight_grid(self, images) -> None:
         """Under method: clahe a tile is never empty: the grid may not have more tiles than the frames have rows or columns."""
         if self.restoration_relight is not None and images.dim() == 4:
-            ty, tx = self.restoration["params"]["grid"]
+            auto = self.restoration_estimate
+            ty, tx = (self.restoration["params"] if auto is None else auto["params"]["clahe"])["grid"]
             if ty > images.shape[2] or tx > images.shape[3]:
                 raise ValueError(f"evaluation.restoration: a grid of {ty} x {tx} tiles does not fit frames of {images.shape[2]} x "
                                  f"{images.shape[3]} pixels")
+
+    def _selected(self, kinds):
+        """The batch's frames of the selected weather conditions: their indices."""
+        rs = self.restoration
+        return [i for i, k in enumerate(kinds) if rs["conditions"] is None or str(k) in rs["conditions"]]
+
+    def begin_estimate(self, images, kinds, cond) -> None:
+        """Under method: auto, at the top of the batch and before its forward is enqueued: the weather estimate of the selected
+        frames into its counters.  With route: estimated the routes start on their way to a pinned host buffer and an event is
+        recorded behind the copy; update_restoration waits for that event, after the plain forward has been enqueued, so the host
+        waits for the estimator and not for the forward.  With route: oracle nothing is read back."""
+        es = self.restoration_estimate
+        check_frames("restoration", images)
+        keep = self._selected(kinds)
+        es["pending"] = None
+        if not keep:
+            return
+        if len(keep) < images.shape[0]:
+            idx = torch.tensor(keep, dtype=torch.int64).to(images.device, non_blocking=True)
+            images, cond = images.index_select(0, idx), cond.index_select(0, idx)
+        route, _ = ops.weather_estimate(images, es["stats"], cond, **es["params"]["estimator"])
+        es["pending"] = {"frames": len(keep)}
+        if es["route"] == "estimated":
+            if es["host"] is None or es["host"].numel() < len(keep):
+                es["host"] = torch.empty(len(keep), dtype=torch.int32).pin_memory()
+                es["event"] = torch.cuda.Event()
+            es["host"][:len(keep)].copy_(route, non_blocking=True)
+            es["event"].record()
+
+    def _routes(self, kinds) -> list:
+        """The route (an index into ops.ESTIMATE_ROUTES) of every selected frame of the batch in flight: the estimate's, read back
+        here (the one host synchronisation the option adds: on the estimator's event), or under route: oracle the one
+        ops.ESTIMATE_EXPECTED_ROUTE names for the frame's true condition."""
+        es = self.restoration_estimate
+        pending, es["pending"] = es["pending"], None
+        if pending is None or pending["frames"] != len(kinds):
+            raise ValueError("evaluation.restoration: method: auto needs the batch's weather estimate (begin_estimate) before its routes")
+        if es["route"] == "oracle":
+            return [ops.ESTIMATE_ROUTES.index(ops.ESTIMATE_EXPECTED_ROUTE.get(str(k), "none")) for k in kinds]
+        es["event"].synchronize()
+        es["readbacks"] += 1
+        return [int(r) for r in es["host"][:len(kinds)].tolist()]
+
+    def _restore_by_route(self, images, cond, routes):
+        """The frames grouped by route, each group through its method into that method's own counters, written back into one batch;
+        the frames routed to none are copied as they are."""
+        es, n = self.restoration_estimate, images.shape[0]
+        run = {"dark_channel": lambda x, c: ops.dehaze(x, self.restoration["stats"], c, **es["params"]["dark_channel"])[0],
+               "clahe": lambda x, c: ops.relight(x, self.restoration_relight["stats"], c, **es["params"]["clahe"])[0],
+               "tophat": lambda x, c: ops.deocclude(x, self.restoration_deocclude["stats"], c, **es["params"]["tophat"])[0]}
+        restored = None
+        for r, name in enumerate(ops.ESTIMATE_ROUTES):
+            members = [i for i, v in enumerate(routes) if v == r]
+            if not members:
+                continue
+            if len(members) == n:                                     # the whole batch takes one route
+                return images if name == "none" else run[name](images, cond)
+            if restored is None:
+                restored = torch.empty_like(images)
+            idx = torch.tensor(members, dtype=torch.int64).to(images.device, non_blocking=True)
+            group = images.index_select(0, idx)
+            restored.index_copy_(0, idx, group if name == "none" else run[name](group, cond.index_select(0, idx)))
+        return restored
 
     def update_restoration(self, model, images, labels, kinds, cond, rows=None) -> None:
         """The batch's frames of the selected weather conditions (`kinds`: the loader's names, before a sweep's slot names), dehazed,
@@ -784,7 +913,7 @@ class EvalState:
         image-quality tensor when it is on (`rows`: frame_ref's rows of the batch's sources in the kept clean frames)."""
         rs = self.restoration
         check_frames("restoration", images)
-        keep = [i for i, k in enumerate(kinds) if rs["conditions"] is None or str(k) in rs["conditions"]]
+        keep = self._selected(kinds)
         if not keep:
             return
         if len(keep) < images.shape[0]:
@@ -792,7 +921,10 @@ class EvalState:
             images, labels, cond = images.index_select(0, idx), labels.index_select(0, idx), cond.index_select(0, idx)
             if rows is not None:
                 rows = rows.index_select(0, idx) if torch.is_tensor(rows) else [rows[i] for i in keep]
-        if self.restoration_relight is not None:
+        if self.restoration_estimate is not None:
+            self.check_relight_grid(images)
+            restored = self._restore_by_route(images, cond, self._routes([kinds[i] for i in keep]))
+        elif self.restoration_relight is not None:
             self.check_relight_grid(images)
             restored, _ = ops.relight(images, self.restoration_relight["stats"], cond, **rs["params"])
         elif self.restoration_deocclude is not None:
@@ -996,6 +1128,14 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         depth_kw = {"depth_stats": (depth, cond, st.depth["stats"], st.depth["min"]), "want_depth": False}
     if labels.dtype not in (torch.uint8, torch.int64):
         labels = labels.long()
+    if st.weight_grid is not None:                                    # before anything of the batch is counted
+        if st.auroc is None:
+            raise ValueError("the ensemble weight sweep needs the two-member ensemble")
+        if getattr(model, "ensemble_strategy", "weighted_average") != "weighted_average":
+            raise ValueError("the ensemble weight sweep needs model.ensemble_strategy weighted_average, got "
+                             f"{model.ensemble_strategy!r}")
+    if st.restoration_estimate is not None:                           # method: auto: the weather estimate, behind every check of the
+        st.begin_estimate(images, kinds, cond)                        # batch and ahead of its forward
     if st.auroc is not None:
         strategy = getattr(model, "ensemble_strategy", "weighted_average")
         fused_stats = metrics.num_classes == 19 and strategy != "max_confidence" and images[0, 0].numel() % 4 == 0
@@ -1011,9 +1151,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
                 st.update_calibration(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"], mode, w, T))
             else:
                 st.update_calibration(labels, cond, logits=res["segmentation"])
-        if st.weight_grid is not None:
-            if strategy != "weighted_average":
-                raise ValueError(f"the ensemble weight sweep needs model.ensemble_strategy weighted_average, got {strategy!r}")
+        if st.weight_grid is not None:                              # (its strategy was checked above)
             st.update_weight_grid(labels, cond, members=(res["segformer_seg"], res["deeplabv3plus_seg"]))
         if st.failure is not None:
             # max_confidence hands over its combined logits: the kernel does not know that rule
@@ -1032,8 +1170,6 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
             st.update_auroc(res["segformer_seg"], res["deeplabv3plus_seg"], labels)
             ops.ece_accumulate(res["segmentation"], labels, st.ece, st.edges, cond)
     else:
-        if st.weight_grid is not None:
-            raise ValueError("the ensemble weight sweep needs the two-member ensemble")
         out = model(images)
         logits = out["segmentation"].float().contiguous()
         if st.depth is not None:
@@ -1174,16 +1310,20 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                   q["targets"], metrics.compute_robustness_degradation_ratio))
     if st.restoration is not None:
         rs = st.restoration
-        relit = st.restoration_relight is not None                 # no dehazing counters then: all-zero rows give no dehazing key
-        tophat = st.restoration_deocclude is not None              # nor then
+        auto = st.restoration_estimate is not None                 # every method's counters, each over the frames routed to it
+        relit = st.restoration_relight is not None and not auto    # no dehazing counters then: all-zero rows give no dehazing key
+        tophat = st.restoration_deocclude is not None and not auto  # nor then
         dehaze_stats = np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64) if relit or tophat else rs["stats"].cpu().numpy()
         results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), dehaze_stats,
                                                       st.acc.conditions, metrics.num_classes, **sweep_kw,
                                                       degradation=metrics.compute_robustness_degradation_ratio))
-        if relit:
+        if relit or auto:
             results.update(relight_metrics_from_stats(st.restoration_relight["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
-        if tophat:
+        if tophat or auto:
             results.update(deocclude_metrics_from_stats(st.restoration_deocclude["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
+        if auto:                                                   # last: restoration_method and the non-finite count are the estimate's
+            results.update(estimate_metrics_from_stats(st.restoration_estimate["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw,
+                                                       route=st.restoration_estimate["route"]))
         if st.restoration_guided is not None:
             results.update(guided_metrics_from_stats(st.restoration_guided["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
             results["restoration_refine"] = "guided"

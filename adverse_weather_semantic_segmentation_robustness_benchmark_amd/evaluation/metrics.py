@@ -931,6 +931,70 @@ def deocclude_metrics_from_stats(stats, conditions: List[str], kinds=None, level
     return res
 
 
+def estimate_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0, route: str = "estimated") -> Dict[str, Any]:
+    """Result keys of the blind routing (evaluation.restoration with method: auto) from the counters of the weather
+    estimate, int64 [1 + len(conditions), AWSEG_ESTIMATE_ROW] (include/awseg_restore.h; slot 0 = every selected frame, slot 1 + k =
+    conditions[k]).  Host only, float64 on exact integer sums; every value a float but restoration_method and restoration_route.
+    With <n> a condition (under a sweep its slots and each '<kind>' from the summed counters of its levels; slot 0 under the prefix
+    mean_ instead of the suffix), for every <n> with frames:
+      route_{none,dark_channel,clahe,tophat}_fraction_<n>   share of the frames the ESTIMATE sent to that method: the rows of the
+                                         confusion table of estimated against true condition (under route: oracle the routes
+                                         applied are ops.ESTIMATE_EXPECTED_ROUTE's, these stay the estimate's)
+      route_accuracy_<n>                 share of the frames sent where ops.ESTIMATE_EXPECTED_ROUTE sends <n> ('<kind>_s<j>' counts as
+                                         its kind); only for the conditions the map names
+      route_accuracy                     the same pooled over the condition slots the map names
+      estimate_dark_channel_<n>, estimate_luma_<n>          mean dark channel and mean luma over the pixels
+      estimate_cast_<n>                  red over blue: the ratio of the channel sums 0 and 2 (absent when channel 2 sums to 0)
+      estimate_seed_fraction_<n>         top-hat seeds / pixels
+    and restoration_method = 'auto', restoration_route = `route`; restoration_nonfinite_values (slot 0) only when non-zero.  A ratio
+    without a denominator is absent, not 0."""
+    conditions = list(conditions)
+    raw = np.asarray(stats.cpu().numpy() if isinstance(stats, torch.Tensor) else stats, dtype=np.int64)
+    if raw.shape != (1 + len(conditions), ops.ESTIMATE_ROW):
+        raise ValueError(f"estimate stats must be int64 [{1 + len(conditions)}, {ops.ESTIMATE_ROW}], got {raw.shape}")
+    if route not in ("estimated", "oracle"):
+        raise ValueError(f"route is 'estimated' or 'oracle', got {route!r}")
+    kinds, levels = list(kinds or []), int(levels)
+
+    def expected(name):
+        """The route the map names for a condition, a sweep's slot or a kind; None when it names none."""
+        base = name.rsplit("_s", 1)[0] if kinds and name not in ops.ESTIMATE_EXPECTED_ROUTE and name.rsplit("_s", 1)[0] in kinds else name
+        return ops.ESTIMATE_EXPECTED_ROUTE.get(base)
+    named = [(None, raw[0])] + [(name, raw[1 + k]) for k, name in enumerate(conditions)]
+    for kind in kinds:
+        named.append((kind, raw[[1 + conditions.index(f"{kind}_s{j}") for j in range(1, levels + 1)]].sum(0)))
+    res: Dict[str, Any] = {"restoration_method": "auto", "restoration_route": route}
+    for name, row in named:
+        dec = {f: int(v) for f, v in ops.estimate_stats_to_numpy(row).items()}
+
+        def key(metric, name=name):
+            return f"mean_{metric}" if name is None else f"{metric}_{name}"
+        if dec["frames"] > 0:
+            for r in ops.ESTIMATE_ROUTES:
+                res[key(f"route_{r}_fraction")] = float(dec[f"routed_{r}"] / dec["frames"])
+            want = None if name is None else expected(name)
+            if want is not None:
+                res[f"route_accuracy_{name}"] = float(dec[f"routed_{want}"] / dec["frames"])
+        if dec["pixels"] > 0:
+            res[key("estimate_dark_channel")] = float(dec["sum_dark"] * ops.ESTIMATE_UNIT / dec["pixels"])
+            res[key("estimate_luma")] = float(dec["sum_luma"] * ops.ESTIMATE_UNIT / dec["pixels"])
+            res[key("estimate_seed_fraction")] = float(dec["seed_pixels"] / dec["pixels"])
+        if dec["sum_channel_2"] > 0:
+            res[key("estimate_cast")] = float(dec["sum_channel_0"] / dec["sum_channel_2"])
+    right = frames = 0
+    for k, name in enumerate(conditions):                                  # the slots themselves: a kind's sum would count them twice
+        want = expected(name)
+        if want is not None:
+            dec = ops.estimate_stats_to_numpy(raw[1 + k])
+            right, frames = right + int(dec[f"routed_{want}"]), frames + int(dec["frames"])
+    if frames > 0:
+        res["route_accuracy"] = float(right / frames)
+    nonfinite = int(ops.estimate_stats_to_numpy(raw[0])["nonfinite_values"])
+    if nonfinite:
+        res["restoration_nonfinite_values"] = float(nonfinite)
+    return res
+
+
 IQ_PLAIN_STEMS = ("mse", "psnr", "mean_abs_change", "ssim", "ssim_luminance", "ssim_contrast")
 
 

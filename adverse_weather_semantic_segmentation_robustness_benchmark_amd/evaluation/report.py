@@ -70,15 +70,27 @@ def restoration_section(results: Dict[str, Any]) -> list:
     frames dehazed by the dark-channel prior, the difference, and the mean transmission the front-end estimated.  Under method:
     clahe (restoration_method in the results) the frames were relit instead and the luma gain stands where the mean transmission
     does, the share of gain-capped pixels where the airlight does; under method: tophat the occluders of rain and snow were masked
-    and filled, and the masked share of the pixels and the mean change of a masked value stand in those two columns."""
+    and filled, and the masked share of the pixels and the mean change of a masked value stand in those two columns.  Under method:
+    auto each frame went to one of the three or to none: the two columns are the share of the frames routed where the condition's
+    name says they belong and the share routed to none, and a second table is the confusion table of the weather estimate."""
     names = [m.group(1) for k in results for m in [re.match(r"miou_(.+)_restored$", k)] if m]
 
     def cell(key):
         return f"{results[key]:.3f}" if key in results else "-"
     relit = results.get("restoration_method") == "clahe"
     tophat = results.get("restoration_method") == "tophat"
+    auto = results.get("restoration_method") == "auto"
     lines = ["", "## Input Restoration", ""]
-    if tophat:
+    if auto:
+        how = ("the method a weather estimate of its own pixels names (the mean dark channel, the red-to-blue ratio of the channel "
+               "means with the mean luma, the share of top-hat seeds; DESIGN.md 10q)"
+               if results.get("restoration_route") != "oracle" else
+               "the method its true condition names (route: oracle, the upper bound of the routing; the estimate is only counted)")
+        lines += [f"Method: auto, route: {results.get('restoration_route', 'estimated')}.  Every selected frame was sent to {how}: "
+                  "dark_channel, clahe, tophat or none, restored by it in front of the model, and scored again.  Gain: restored - "
+                  "plain mIoU on the same frames (negative: the front-end costs accuracy); routed right: share of the frames the "
+                  "estimate sent where the condition's name says they belong; to none: share it left as they came.", ""]
+    elif tophat:
         lines += ["Method: tophat.  In every selected frame the bright occluders of rain and snow were masked by the white top-hat of "
                   "all three channels and filled from their unmasked neighbours in front of the model, and the frame scored again.  "
                   "Gain: restored - plain mIoU on the same frames (negative: the front-end costs accuracy); occluders: share of the "
@@ -98,9 +110,10 @@ def restoration_section(results: Dict[str, Any]) -> list:
     guided = any(k.startswith("transmission_refinement_") for k in results)
     fidelity = any(re.match(r"(psnr|ssim)_.+_restored$", k) for k in results)
     head = ["Condition", "Plain mIoU", "Restored mIoU", "Gain"] \
-        + (["Occluders", "Change"] if tophat else ["Luma gain", "Capped"] if relit else ["Mean t", "Airlight"]) + ["Degradation restored"]
-    fifth, sixth = (("occluder_fraction", "occluder_change") if tophat else ("relight_gain", "relight_capped_fraction") if relit
-                    else ("transmission_mean", "airlight"))
+        + (["Routed right", "To none"] if auto else ["Occluders", "Change"] if tophat else ["Luma gain", "Capped"] if relit
+           else ["Mean t", "Airlight"]) + ["Degradation restored"]
+    fifth, sixth = (("route_accuracy", "route_none_fraction") if auto else ("occluder_fraction", "occluder_change") if tophat
+                    else ("relight_gain", "relight_capped_fraction") if relit else ("transmission_mean", "airlight"))
     head += ["Refinement", "Clamped"] * guided + ["PSNR restored (gain)", "SSIM restored (gain)"] * fidelity
     if "restoration_refine" in results:
         lines += [f"Transmission refinement: {results['restoration_refine']} filter (DESIGN.md 10n-bis).", ""]
@@ -121,8 +134,19 @@ def restoration_section(results: Dict[str, Any]) -> list:
         lines.append(f"| {n} | {cell('miou_' + n)} | {cell('miou_' + n + '_restored')} | {cell('restoration_gain_' + n)} | "
                      f"{cell(fifth + '_' + n)} | {cell(sixth + '_' + n)} | {cell('robustness_degradation_' + n + '_restored')} |"
                      + more(n))
-    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | {cell('mean_' + fifth if relit or tophat else 'mean_transmission')} | "
+    lines.append(f"| all | - | {cell('overall_miou_restored')} | {cell('mean_restoration_gain')} | "
+                 f"{cell('route_accuracy' if auto else 'mean_' + fifth if relit or tophat else 'mean_transmission')} | "
                  f"{cell('mean_' + sixth)} | - |" + more(None))
+    if auto:
+        routes = ("none", "dark_channel", "clahe", "tophat")
+        seen = [m.group(1) for k in results for m in [re.match(r"route_none_fraction_(.+)$", k)] if m]
+        lines += ["", "Estimated route against true condition (shares of the condition's frames), with the statistics the estimate "
+                  "decides on:", "", "| Condition | " + " | ".join(routes) + " | Dark channel | Luma | Red / blue | Seeds |",
+                  "|---" * 9 + "|"]
+        for n in seen:
+            lines.append(f"| {n} | " + " | ".join(cell(f"route_{r}_fraction_{n}") for r in routes)
+                         + f" | {cell('estimate_dark_channel_' + n)} | {cell('estimate_luma_' + n)} | {cell('estimate_cast_' + n)} | "
+                         + (f"{results['estimate_seed_fraction_' + n]:.5f}" if 'estimate_seed_fraction_' + n in results else "-") + " |")
     if relit:
         gains = [f"{results[k]:.3f}" for k in ("mean_white_balance_gain_r", "mean_white_balance_gain_g", "mean_white_balance_gain_b")
                  if k in results]

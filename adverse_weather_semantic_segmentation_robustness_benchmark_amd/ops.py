@@ -944,6 +944,118 @@ def deocclude_stats_to_numpy(stats) -> dict:
     return {f: raw[..., i] for i, f in enumerate(DEOCCLUDE_FIELDS)}
 
 
+# ------------------------------------------------ weather estimate: which front-end a frame needs (include/awseg_restore.h)
+ESTIMATE_FIELDS = ("frames", "pixels", "sum_dark", "sum_luma", "sum_channel_0", "sum_channel_1", "sum_channel_2", "seed_pixels",
+                   "nonfinite_values", "routed_none", "routed_dark_channel", "routed_clahe", "routed_tophat")
+ESTIMATE_ROW = len(ESTIMATE_FIELDS)    # AWSEG_ESTIMATE_ROW
+ESTIMATE_DESCRIPTORS = ("dark_channel", "luma", "mean_0", "mean_1", "mean_2", "seed_fraction")      # AWSEG_ESTIMATE_DESCRIPTORS of them
+ESTIMATE_FRAME_RECORD = 64             # AWSEG_ESTIMATE_FRAME_RECORD: workspace bytes per frame
+ESTIMATE_UNIT = 2.0 ** -16             # the dark-channel, luma and channel sums are int64 in fixed point: exact, order-independent
+ESTIMATE_ROUTES = ("none", "dark_channel", "clahe", "tophat")          # route 0 .. 3: the method a frame is sent to
+# the route a rule that knew the weather would take, by the condition's name (other names: none): what `route: oracle` applies and
+# what route_accuracy counts as right
+ESTIMATE_EXPECTED_ROUTE = {"clean": "none", "fog": "dark_channel", "night": "clahe", "rain": "tophat", "snow": "tophat"}
+# the prototype's thresholds on the renderer's street scenes at 256 x 512 and above: a stated choice, not a tuned one.  seed_min
+# depends on the resolution (the renderer's drop count does not grow with the frame)
+ESTIMATE_DEFAULTS = {"radius": 7, "threshold": 0.06, "bright_min": 0.5, "cast_max": 0.65, "luma_max": 0.5, "dark_min": 0.47,
+                     "seed_min": 0.001}
+
+
+def new_estimate_stats(device, n_slots: int = 1) -> torch.Tensor:
+    """int64 [n_slots, ESTIMATE_ROW]: per slot the row ESTIMATE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
+    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+        raise ValueError(f"new_estimate_stats: n_slots is an integer >= 1, got {n_slots!r}")
+    return torch.zeros(int(n_slots), ESTIMATE_ROW, dtype=torch.int64, device=device)
+
+
+def weather_estimate_parameters(radius=7, threshold=0.06, bright_min=0.5, cast_max=0.65, luma_max=0.5, dark_min=0.47,
+                                seed_min=0.001) -> dict:
+    """The checked parameters of weather_estimate(): radius an integer in [1, 15]; threshold a number in (0, 1], bright_min one in
+    [0, 1], cast_max in (0, 4], luma_max in (0, 1], dark_min and seed_min in [0, 1) (all also as float32; NaN is refused).
+    ValueError otherwise."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= DEHAZE_MAX_RADIUS:
+        raise ValueError(f"weather_estimate: radius is an integer in [1, {DEHAZE_MAX_RADIUS}], got {radius!r}")
+
+    def number(name, v, lo, hi, open_below=False, open_above=False):
+        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
+        f = float(np.float32(v)) if ok else float("nan")
+        if not (ok and (lo < f if open_below else lo <= f) and (f < hi if open_above else f <= hi)):
+            raise ValueError(f"weather_estimate: {name} is a number in {'(' if open_below else '['}{lo:g}, {hi:g}"
+                             f"{')' if open_above else ']'} (also as float32), got {v!r}")
+        return f
+    return {"radius": int(radius), "threshold": number("threshold", threshold, 0.0, 1.0, open_below=True),
+            "bright_min": number("bright_min", bright_min, 0.0, 1.0), "cast_max": number("cast_max", cast_max, 0.0, 4.0, open_below=True),
+            "luma_max": number("luma_max", luma_max, 0.0, 1.0, open_below=True),
+            "dark_min": number("dark_min", dark_min, 0.0, 1.0, open_above=True),
+            "seed_min": number("seed_min", seed_min, 0.0, 1.0, open_above=True)}
+
+
+def weather_estimate_workspace_bytes(b: int) -> int:
+    """The closed form of awseg_weather_estimate_workspace: one record per frame."""
+    return max(int(b), 0) * ESTIMATE_FRAME_RECORD
+
+
+def weather_estimate(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 7,
+                     threshold: float = 0.06, bright_min: float = 0.5, cast_max: float = 0.65, luma_max: float = 0.5,
+                     dark_min: float = 0.47, seed_min: float = 0.001, mean=None, std=None, route: Optional[torch.Tensor] = None,
+                     descriptors: Optional[torch.Tensor] = None):
+    """Which front-end each of the loader's normalised float32 frames `image` [B, 3, H, W] needs, from its pixels alone, as
+    include/awseg_restore.h defines it step by step -> (route int32 [B]: an index into ESTIMATE_ROUTES, descriptors float32 [B, 6]:
+    ESTIMATE_DESCRIPTORS).  A dark frame with a blue cast (mean_0 < cast_max * mean_2 and luma < luma_max) goes to clahe, else a
+    veiled one (dark_channel > dark_min) to dark_channel, else one with bright occluders (seed_fraction > seed_min; the seeds of
+    deocclude() at `radius`, `threshold`, `bright_min`) to tophat, else to none.  `stats` (new_estimate_stats; slot 0 + slot
+    1 + cond[b], cond device int32 [B]) takes the counters of ESTIMATE_FIELDS; without it they go to a tensor nobody reads.
+    `mean`, `std`: the loader's normalisation (default: ImageNet's).  `route`, `descriptors`: where the results go (contiguous, on
+    the frames' device).  The frames are read only.  There is no CPU path."""
+    p = weather_estimate_parameters(radius, threshold, bright_min, cast_max, luma_max, dark_min, seed_min)
+    if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
+        raise ValueError(f"weather_estimate: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
+    b, _, h, w = (int(d) for d in image.shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"weather_estimate: frames of at least one pixel, got {tuple(image.shape)}")
+    if b > 65535 or h * w >= 2 ** 31:
+        raise ValueError(f"weather_estimate: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
+    if (mean is None) != (std is None):
+        raise ValueError("weather_estimate: mean and std come together")
+    m, s = _mean_std(mean, std)
+    m, s = m.reshape(-1), s.reshape(-1)
+    if m.size != 3 or s.size != 3 or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
+        raise ValueError(f"weather_estimate: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
+    if stats is None:
+        stats = new_estimate_stats(image.device, 1)
+    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != ESTIMATE_ROW or not stats.is_contiguous():
+        raise ValueError(f"stats must be int64 [slots, {ESTIMATE_ROW}] (new_estimate_stats), got {stats.dtype} {tuple(stats.shape)}")
+    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
+        raise ValueError("cond must be int32 [B]")
+    image = image.contiguous()
+    if route is None:
+        route = torch.empty(b, dtype=torch.int32, device=image.device)
+    if route.dtype != torch.int32 or tuple(route.shape) != (b,) or not route.is_contiguous() or route.device != image.device:
+        raise ValueError(f"weather_estimate: route is a contiguous int32 tensor [B] on the frames' device, got {route.dtype} "
+                         f"{tuple(route.shape)}")
+    if descriptors is None:
+        descriptors = torch.empty(b, len(ESTIMATE_DESCRIPTORS), dtype=torch.float32, device=image.device)
+    if descriptors.dtype != torch.float32 or tuple(descriptors.shape) != (b, len(ESTIMATE_DESCRIPTORS)) \
+            or not descriptors.is_contiguous() or descriptors.device != image.device:
+        raise ValueError(f"weather_estimate: descriptors is a contiguous float32 tensor [B, {len(ESTIMATE_DESCRIPTORS)}] on the "
+                         f"frames' device, got {descriptors.dtype} {tuple(descriptors.shape)}")
+    if b == 0:
+        return route, descriptors
+    ws = N.workspace.get(image.device, N.lib().awseg_weather_estimate_workspace(b), tag="weather_estimate")
+    N.call("awseg_weather_estimate", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), p["radius"], p["threshold"], p["bright_min"],
+           p["cast_max"], p["luma_max"], p["dark_min"], p["seed_min"], N.ptr(cond), N.ptr(route), N.ptr(descriptors), N.ptr(stats),
+           stats.shape[0], N.ptr(ws), N.stream())
+    return route, descriptors
+
+
+def estimate_stats_to_numpy(stats) -> dict:
+    """int64 [..., ESTIMATE_ROW] -> {field: int64 [...]} for ESTIMATE_FIELDS; the five sums stay in units of ESTIMATE_UNIT."""
+    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+    if raw.shape[-1] != ESTIMATE_ROW:
+        raise ValueError(f"estimate rows hold {ESTIMATE_ROW} counters, got {raw.shape[-1]}")
+    return {f: raw[..., i] for i, f in enumerate(ESTIMATE_FIELDS)}
+
+
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

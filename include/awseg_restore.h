@@ -232,6 +232,64 @@ int awseg_deocclude(const float* image, int64_t batch, int channels, int64_t hei
                     const int32_t* cond, float* restored, uint8_t* mask /* [B,H,W] */,
                     int64_t* stats /* [n_slots][AWSEG_DEOCCLUDE_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Weather estimate: which of the three front-ends above a frame needs, decided per frame from its pixels alone, for the blind
+ *  routing of the evaluation
+ *       replaces nothing: the reference has no restoration baseline
+ * ------------------------------------------------------------------------- *
+ * awseg_weather_estimate: image, mean, std (HOST float32[3]), cond, stats, n_slots, workspace, stream as for awseg_dehaze (which
+ * this entry point leaves as it is, as it leaves awseg_relight and awseg_deocclude).  radius r in [1, AWSEG_DEHAZE_MAX_RADIUS],
+ * threshold in (0, 1], bright_min in [0, 1] (those of awseg_deocclude); cast_max in (0, 4], luma_max in (0, 1], dark_min in [0, 1),
+ * seed_min in [0, 1).  Every float step is one float32 operation with the parenthesisation given (no contraction); everything else
+ * is written in integers or in double, so numpy gives the same bits.  All windows are clipped to the frame.  Frame b, pixel p:
+ *   input    v_c = fminf(fmaxf(image[b,c,p] * std[c] + mean[c], 0), 1)     (NaN -> 0; every input value that is not finite is counted:
+ *            the v_c of awseg_dehaze)
+ *   pixel    e_c = (2r+1)^2 window minimum of v_c;   o_c = (2r+1)^2 window maximum of e_c
+ *            m = fminf(fminf(v_0, v_1), v_2);   h = fminf(fminf(v_0 - o_0, v_1 - o_1), v_2 - o_2)
+ *            seed = (h > threshold) && (m >= bright_min)                   (pass A of awseg_deocclude before the dilation)
+ *            dark = (2r+1)^2 window minimum of m                           (pass A of awseg_dehaze before the binning; the kernel forms
+ *                                                                          it as fminf(fminf(e_0, e_1), e_2): minima commute)
+ *            l = (0.299f * v_0 + 0.587f * v_1) + 0.114f * v_2
+ *   frame    Q_dark = sum of (int64) rintf(dark * 65536.0f);  Q_l from l and Q_c from v_c (c = 0, 1, 2) likewise;  N_seed = the
+ *            count of seeds;  the count of the input values that are not finite
+ *            P = (double)(H * W) * 65536.0;   D = (float)((double) Q_dark / P);   L = (float)((double) Q_l / P);
+ *            M_c = (float)((double) Q_c / P);   O = (float)((double) N_seed / (double)(H * W))
+ *   route    the first rule that matches, float32 compares (cast_max * M_2 is one float32 product):
+ *              1. (M_0 < cast_max * M_2) && (L < luma_max)  ->  2   a dark frame with a blue cast: awseg_relight
+ *              2. D > dark_min                              ->  1   a veil: awseg_dehaze
+ *              3. O > seed_min                              ->  3   bright occluders: awseg_deocclude
+ *              4. otherwise                                 ->  0   nothing
+ *            The veil comes before the occluders: a fog frame carries top-hat seeds of its own.
+ * route int32 [B]; descriptors float32 [B][AWSEG_ESTIMATE_DESCRIPTORS] = D, L, M_0, M_1, M_2, O.
+ * stats int64 [n_slots][AWSEG_ESTIMATE_ROW] (accumulated, never cleared), the slot rule of awseg_dehaze (slot 0, and slot
+ * 1 + cond[b] when 0 <= cond[b] < n_slots - 1; cond device int32[B] or NULL).  Row:
+ *     [0] frames   [1] pixels   [2] sum of Q_dark   [3] sum of Q_l   [4..6] sum of Q_c, c = 0, 1, 2   [7] seed pixels
+ *     [8] input values that are not finite   [9..12] frames routed to 0, 1, 2, 3
+ * Integer sums only: independent of the grid, additive over launches and ranks.  A term is at most 2^16 units, so a stats tensor
+ * holds 2^46 pixels before a sum could wrap.  With cond the true condition, [9..12] of the slots are the confusion table of the
+ * estimate.
+ * On the stream: one clear of the records, then two kernels.  The first runs on the AWSEG_DEHAZE_TILE_H x AWSEG_DEHAZE_TILE_W tiles
+ * of awseg_dehaze and is the detection kernel of awseg_deocclude at d = 0 without the dilation and the mask: the three channels one
+ * after another through one staged plane with a halo of 2 r and one scratch plane, separable passes in LDS, the running minima in
+ * registers, one block-level reduction and one 64-bit atomic per quantity and block into the frame's record.  The second, one
+ * thread per frame, forms the descriptors and the route and adds the frame's row to its slots.  16-byte loads when W % 4 == 0 and
+ * image is 16-byte aligned, scalar ones otherwise; the same bits either way.
+ * workspace: awseg_weather_estimate_workspace(batch) bytes = batch * AWSEG_ESTIMATE_FRAME_RECORD: per frame seven int64 (Q_dark,
+ * Q_l, Q_0, Q_1, Q_2, N_seed, non-finite values) and a pad; 8-byte aligned (AWSEG_EALIGN otherwise).  The launcher clears it on the
+ * stream.
+ * AWSEG_EINVAL for a NULL pointer (cond excepted), channels != 3, a size < 1 (batch < 0), n_slots < 1, a parameter outside the
+ * ranges above (NaN included), a std that is not finite and > 0 or a non-finite mean; AWSEG_ERANGE for batch > 65535 or
+ * H * W >= 2^31; batch == 0 returns 0 and launches nothing. */
+#define AWSEG_ESTIMATE_ROW           13
+#define AWSEG_ESTIMATE_DESCRIPTORS   6
+#define AWSEG_ESTIMATE_FRAME_RECORD  64
+int64_t awseg_weather_estimate_workspace(int64_t batch);
+int awseg_weather_estimate(const float* image, int64_t batch, int channels, int64_t height, int64_t width,
+                           const float* mean, const float* std, int radius, float threshold, float bright_min,
+                           float cast_max, float luma_max, float dark_min, float seed_min, const int32_t* cond,
+                           int32_t* route /* [B] */, float* descriptors /* [B][AWSEG_ESTIMATE_DESCRIPTORS] */,
+                           int64_t* stats /* [n_slots][AWSEG_ESTIMATE_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,12 +135,26 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
                     help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
                          "(sets evaluation.image_quality_targets)")
-    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe", "tophat"),
+    ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe", "tophat", "auto"),
                     help="restore every frame in front of the model and score it a second time: plain and restored mIoU and the gain "
                          "per condition.  dark_channel: dehazing by the dark-channel prior (with the mean transmission); clahe: night "
                          "relighting by CLAHE on the luma with a grey-world white balance (with the luma gain); tophat: rain "
                          "and snow removal, the bright occluders masked by the white top-hat and filled from their neighbours (with "
-                         "the masked share of the pixels).  Sets evaluation.restoration")
+                         "the masked share of the pixels); auto: one of the three, or none, per frame, chosen by a weather estimate "
+                         "from the frame's pixels alone (with the confusion table of the estimate).  Sets evaluation.restoration")
+    ap.add_argument("--restoration-route", type=str, default=None, choices=("estimated", "oracle"),
+                    help="what routes the frames under --restoration auto: the weather estimate (default), or oracle: the true "
+                         "condition, the upper bound (sets evaluation.restoration.route)")
+    ap.add_argument("--restoration-seed-min", type=float, default=None, metavar="X",
+                    help="share of top-hat seed pixels above which a frame goes to tophat, 0 .. 1 (default 0.001, chosen at 256 x 512 "
+                         "and above: it depends on the resolution; needs --restoration auto; sets "
+                         "evaluation.restoration.estimator.seed_min)")
+    ap.add_argument("--restoration-dark-min", type=float, default=None, metavar="X",
+                    help="mean dark channel above which a frame goes to dark_channel, 0 .. 1 (default 0.47; needs --restoration auto; "
+                         "sets evaluation.restoration.estimator.dark_min)")
+    ap.add_argument("--restoration-cast-max", type=float, default=None, metavar="X",
+                    help="red-to-blue ratio of the channel means below which a dark frame goes to clahe, 0 .. 4 (default 0.65; needs "
+                         "--restoration auto; sets evaluation.restoration.estimator.cast_max)")
     ap.add_argument("--restoration-conditions", type=str, default=None, metavar="A,B",
                     help="restore only the frames of these comma-separated weather conditions (default: all, clean included; sets "
                          "evaluation.restoration_conditions)")
@@ -206,7 +220,26 @@ def parse_restoration_grid(text: str):
 
 def apply_restoration_options(args, config) -> None:
     """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* and the flags of --restoration clahe
-    and --restoration tophat into the configuration (the harness checks them)."""
+    and --restoration tophat, and --restoration auto with its route and estimator flags, into the configuration (the harness
+    checks them)."""
+    estimator = {k: v for k, v in (("seed_min", args.restoration_seed_min), ("dark_min", args.restoration_dark_min),
+                                   ("cast_max", args.restoration_cast_max)) if v is not None}
+    if (estimator or args.restoration_route is not None) and args.restoration != "auto":
+        raise ValueError("--restoration-route, --restoration-seed-min, --restoration-dark-min and --restoration-cast-max need "
+                         "--restoration auto")
+    if args.restoration == "auto":
+        others = ("refine", "guided_radius", "guided_eps", "grid", "clip_limit", "max_gain", "white_balance", "radius", "threshold",
+                  "bright_min", "dilate")
+        given = [f"--restoration-{o.replace('_', '-')}" for o in others if getattr(args, f"restoration_{o}") is not None]
+        if given:
+            raise ValueError(f"{', '.join(given)}: under --restoration auto the methods' parameters are configuration only "
+                             "(evaluation.restoration.dark_channel / .clahe / .tophat)")
+        spec = {"method": "auto", **({} if args.restoration_route is None else {"route": args.restoration_route}),
+                **({"estimator": estimator} if estimator else {})}
+        config.set("evaluation.restoration", spec if len(spec) > 1 else "auto")
+        if args.restoration_conditions is not None:
+            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
+        return
     tophat = {k: v for k, v in (("threshold", args.restoration_threshold), ("bright_min", args.restoration_bright_min),
                                 ("dilate", args.restoration_dilate)) if v is not None}
     if tophat and args.restoration != "tophat":

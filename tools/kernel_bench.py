@@ -232,6 +232,17 @@ def main():
         for r in (9, 15):
             cases[f"deocclude r={r} d=1, {tag}"] = (
                 lambda frames=frames, r=r: ops.deocclude(frames, dost, cond, radius=r, out=dz_out, mask=do_mask), "hbm", 38 * px * B)
+    # weather estimate (evaluation.restoration: auto): the deoccluder's detection pass at d = 0 without the dilation and the mask, and
+    # the frame's sums instead of an output: 12 B/px in and nothing out, three channels of separable minima and maxima (~8 r LDS reads
+    # per pixel and channel), so the row is expected to be bound by LDS reads and vector issue like the deoccluder's (no counters were
+    # taken), and "of peak" says how far from a read of the frame it is.  Yardsticks on the same tensors: dehaze r=7 refine=1, deocclude r=9 and normalize
+    est_st = ops.new_estimate_stats(dev, 6)
+    est_route, est_desc = torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, 6, dtype=torch.float32, device=dev)
+    for tag, frames in (("rendered-like frames", chg_var), ("independent random frames", iq_rand[0])):
+        for r in (7, 15):
+            cases[f"weather estimate r={r}, {tag}"] = (
+                lambda frames=frames, r=r: ops.weather_estimate(frames, est_st, cond, radius=r, route=est_route, descriptors=est_desc),
+                "hbm", 12 * px * B)
     # stratified counters on the maps of the two consistency cases: 4 B/px (the consistency scan's three maps + the stratum byte).
     # Coherent: the stratum map of the case above; random: an independent stratum per pixel
     ops.change_strata(chg_var, chg_clean, fref, ops.DEFAULT_CHANGE_EDGES, out=smap_c, oob=soob)
