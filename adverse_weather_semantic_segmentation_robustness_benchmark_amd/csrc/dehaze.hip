@@ -98,14 +98,7 @@ void recover_kernel(const float* __restrict__ image, int H, int W, int tiles_x, 
             airlight[img * 3 + 1] = a1;
             airlight[img * 3 + 2] = a2;
         }
-        int slot = -1;
-        if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-#pragma unroll
-        for (int k = 0; k < kRow; ++k) {
-            if (!row[k]) continue;
-            atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row[k]);
-            if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kRow + k], (unsigned long long)row[k]);
-        }
+        add_row(stats, n_slots, cond, img, row);
     }
 }
 

@@ -320,20 +320,9 @@ void transmission_kernel(const float* __restrict__ image, int H, int W, int tile
             airlight[img * 3 + 1] = a1;
             airlight[img * 3 + 2] = a2;
         }
-        int slot = -1;
-        if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-#pragma unroll
-        for (int k = 0; k < kRow; ++k) {
-            if (!row_d[k]) continue;
-            atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row_d[k]);
-            if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kRow + k], (unsigned long long)row_d[k]);
-        }
-#pragma unroll
-        for (int k = 0; k < kGRow; ++k) {
-            if (!row_g[k]) continue;
-            atomicAdd((unsigned long long*)&guided_stats[k], (unsigned long long)row_g[k]);
-            if (slot > 0) atomicAdd((unsigned long long*)&guided_stats[(int64_t)slot * kGRow + k], (unsigned long long)row_g[k]);
-        }
+        const int slot = slot_of(n_slots, cond, img);                      // one read of cond for both rows
+        add_row(stats, slot, row_d);
+        add_row(guided_stats, slot, row_g);
     }
 }
 

@@ -4,20 +4,13 @@
 // one include/awseg_restore.h states; both translation units must produce the same bits from it.
 #ifndef AWSEG_DEHAZE_TILES_H
 #define AWSEG_DEHAZE_TILES_H
-#include "awseg_common.h"
-#include "../../include/awseg_restore.h"
-#include <float.h>
-#include <math.h>
+#include "restore_common.h"                                               // v_c, the reductions, the window minimum, the refusals
 
 namespace {
 
-constexpr int kTH = AWSEG_DEHAZE_TILE_H, kTW = AWSEG_DEHAZE_TILE_W;
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / AWSEG_WAVE;
 constexpr int kRow = AWSEG_DEHAZE_ROW;
 constexpr int kBins = 256;
 static_assert(kThreads == kBins, "one thread per histogram word");
-static_assert(kTW % 4 == 0, "a tile row is whole float4s");
 
 struct dz_record {                                                         // per frame, at the head of the workspace
     uint32_t hist[kBins];
@@ -45,22 +38,12 @@ void geometry(int r, int refine, dz_args& g)
 }
 size_t lds_bytes(const dz_args& g) { return (size_t)g.rows * (g.sw + g.c1) * sizeof(float); }
 
-__device__ __forceinline__ float unit(float x, float sd, float mean) { return fminf(fmaxf(x * sd + mean, 0.0f), 1.0f); }
-__device__ __forceinline__ uint32_t not_finite(float x) { return fabsf(x) <= FLT_MAX ? 0u : 1u; }
-
 template <bool DIV>
 __device__ __forceinline__ float min_of(float x0, float x1, float x2, const dz_args& g, float a0, float a1, float a2)
 {
     float v0 = unit(x0, g.std[0], g.mean[0]), v1 = unit(x1, g.std[1], g.mean[1]), v2 = unit(x2, g.std[2], g.mean[2]);
     if constexpr (DIV) { v0 = v0 / a0; v1 = v1 / a1; v2 = v2 / a2; }
     return fminf(fminf(v0, v1), v2);
-}
-
-__device__ __forceinline__ long long wave_sum_i64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
 }
 
 // b0 [g.rows][g.sw] = min_c over the tile and its halo, +inf outside the frame.  COUNT: `bad` += the tile's own values that are not finite.
@@ -115,30 +98,9 @@ template <bool REFINE>
 __device__ __forceinline__ void window_passes(int H, int W, int y0, int x0, const dz_args& g, float* __restrict__ b0, float* __restrict__ b1)
 {
     const int tid = threadIdx.x, taps = 2 * g.r;
-    __syncthreads();
-    // minimum along the row: column j of b1 is pixel x0 - q + j
-    for (int i = tid; i < g.rows * g.c1; i += kThreads) {
-        const int row = i / g.c1, j = i - row * g.c1;
-        const float* p = b0 + row * g.sw + (g.pad - g.halo) + j;
-        float m = p[0];
-        for (int k = 1; k <= taps; ++k) m = fminf(m, p[k]);
-        b1[i] = m;
-    }
-    __syncthreads();
-    // minimum down the column: row ii of the result is pixel row y0 - q + ii
     const int rows_e = kTH + 2 * g.q;
-    for (int i = tid; i < rows_e * g.c1; i += kThreads) {
-        const int ii = i / g.c1, j = i - ii * g.c1;
-        const float* p = b1 + i;
-        float m = p[0];
-        for (int k = 1; k <= taps; ++k) m = fminf(m, p[k * g.c1]);
-        if constexpr (REFINE) {                                            // positions outside the frame take part in no maximum
-            const int yy = y0 - g.q + ii, xx = x0 - g.q + j;
-            if (yy < 0 || yy >= H || xx < 0 || xx >= W) m = -INFINITY;
-        }
-        b0[i] = m;
-    }
     __syncthreads();
+    window_minimum<kThreads, REFINE, false>(H, W, y0, x0, g, b0, b1);   // the plain tap loops: see there
     if constexpr (REFINE) {
         for (int i = tid; i < rows_e * kTW; i += kThreads) {               // maximum along the row
             const int ii = i / kTW, j = i - ii * kTW;
@@ -287,30 +249,17 @@ __device__ __forceinline__ dz_pixel recover(float o, float x0, float x1, float x
     return recover_at(fmaxf(1.0f - g.omega * o, g.t_min), x0, x1, x2, g, a0, a1, a2, t_q);
 }
 
-inline bool is_finite(float v) { return v >= -FLT_MAX && v <= FLT_MAX; }
-inline bool in_unit(float v) { return v > 0.0f && v <= 1.0f; }             // NaN fails
-
-// The refusals awseg_dehaze and awseg_dehaze_guided share, in awseg_dehaze's order; fills g's normalisation and parameters.  The
-// caller has checked its own pointers and its own parameters (refine; the guided radius and eps) where the comment stands.
+// The refusals awseg_dehaze and awseg_dehaze_guided share; fills g's normalisation and parameters.  own_pointers and own_parameters:
+// what the one has and the other has not (refine; guided_stats, the guided radius and eps).
 #define AWSEG_DEHAZE_CHECKS(own_pointers, own_parameters)                                                                     \
-    if (!image || !mean || !std || !restored || !airlight || !stats || !workspace || !(own_pointers)) return AWSEG_EINVAL;      \
-    if (channels != 3 || batch < 0 || height < 1 || width < 1 || n_slots < 1) return AWSEG_EINVAL;                              \
-    if (radius < 1 || radius > AWSEG_DEHAZE_MAX_RADIUS || !(own_parameters)) return AWSEG_EINVAL;                               \
-    if (!in_unit(omega) || !in_unit(t_min) || !in_unit(airlight_min)) return AWSEG_EINVAL;                                      \
     dz_args g = {};                                                                                                             \
-    for (int c = 0; c < 3; ++c) {                                                                                               \
-        if (!(std[c] > 0.0f && std[c] <= FLT_MAX) || !is_finite(mean[c])) return AWSEG_EINVAL;                                  \
-        g.mean[c] = mean[c];                                                                                                    \
-        g.std[c] = std[c];                                                                                                      \
-    }                                                                                                                           \
+    AWSEG_RESTORE_CHECKS(g, restored && airlight && workspace && (own_pointers),                                                \
+                         radius >= 1 && radius <= AWSEG_DEHAZE_MAX_RADIUS && (own_parameters) && in_unit(omega) && in_unit(t_min) \
+                             && in_unit(airlight_min));                                                                         \
     g.omega = omega;                                                                                                            \
     g.t_min = t_min;                                                                                                            \
-    g.a_min = airlight_min;                                                                                                     \
-    if (batch > 65535 || height > INT32_MAX / width) return AWSEG_ERANGE;      /* grid.y; H * W >= 2^31 */                      \
-    if (!awseg_aligned(workspace, 8)) return AWSEG_EALIGN;                                                                      \
-    if (batch == 0) return 0
+    g.a_min = airlight_min
 
-#ifndef AWSEG_DEHAZE_TILES_NO_LAUNCHER                                     // deocclude.hip: uses neither, and would carry copies of A and B
 // Clears the frames' records and runs passes A and B on `s`: afterwards every record holds its frame's airlight sums and the bin
 // map is written.  Leaves g at geometry(radius, 0).
 inline int estimate_airlight(const float* image, int64_t batch, int H, int W, int radius, dz_args& g, bool vec, unsigned char* ws,
@@ -339,7 +288,6 @@ inline int estimate_airlight(const float* image, int64_t batch, int H, int W, in
     }
     return 0;
 }
-#endif  // AWSEG_DEHAZE_TILES_NO_LAUNCHER
 
 }  // namespace
 #endif  // AWSEG_DEHAZE_TILES_H

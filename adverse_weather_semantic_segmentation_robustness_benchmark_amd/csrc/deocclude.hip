@@ -3,7 +3,7 @@
 // step: every output bit is what numpy gives.
 //
 // awseg_deocclude: two kernels on the caller's stream, no host synchronisation, no block waits for another.  Both run on the tiles
-// of the dehazer (dehaze_tiles.h, whose constants, v_c and reductions they share) and walk the three channels one after another
+// of the dehazer (restore_common.h: the tile, v_c, the reductions and the window minimum) and walk the three channels one after another
 // through one staged plane and one scratch plane, so that the LDS stays what one channel needs.  The detection kernel's geometry,
 // staging and window passes live in deocclude_tiles.h, which estimate.hip (awseg_weather_estimate) shares.
 //   detect_kernel   512 threads.  Per channel: stages v_c for the tile plus a halo of 2 r + d (+inf outside the frame), takes the (2r+1)^2 minimum
@@ -30,20 +30,6 @@ static_assert((2 * AWSEG_DEHAZE_MAX_RADIUS + 1) * 65536 < (int)kOne, "a row sum 
 static_assert(kTH * kTW % kThreads == 0, "every thread owns the same number of pixels");
 
 size_t fill_lds(const dc_args& g) { return (size_t)g.frows * (g.fsw + kTW) * sizeof(uint32_t); }
-
-// One row of counters into slot 0 and the frame's own slot.
-__device__ __forceinline__ void add_row(int64_t* __restrict__ stats, int n_slots, const int32_t* __restrict__ cond, int64_t img,
-                                        const long long (&row)[kDRow])
-{
-    int slot = -1;
-    if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-#pragma unroll
-    for (int k = 0; k < kDRow; ++k) {
-        if (!row[k]) continue;
-        atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row[k]);
-        if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kDRow + k], (unsigned long long)row[k]);
-    }
-}
 
 // Pass A.  grid = (tiles_x * tiles_y, B).
 template <bool VEC>
@@ -78,7 +64,7 @@ void detect_kernel(const float* __restrict__ image, int H, int W, int tiles_x, c
                 v[k] = b0[(g.halo - g.d + i) * g.sw + (g.pad - g.d) + j];
             }
         }
-        minimum_passes(H, W, y0, x0, g, b0, b1);                           // e_c on the tile plus q, -inf outside the frame
+        window_minimum<kDetectThreads, true, true>(H, W, y0, x0, g, b0, b1);       // e_c on the tile plus q, -inf outside the frame
         maximum_row_pass(g, b0, b1);
         // maximum down the column at this thread's positions: o_c, folded into the running minima.  The next channel's staging
         // writes b0 only, and its row pass writes b1 after a barrier.
@@ -286,8 +272,6 @@ void fill_kernel(const float* __restrict__ image, int H, int W, int tiles_x, con
     }
 }
 
-inline bool in_closed_unit(float v) { return v >= 0.0f && v <= 1.0f; }      // NaN fails
-
 }  // namespace
 
 AWSEG_API int64_t awseg_deocclude_workspace(int64_t batch, int64_t height, int64_t width)
@@ -300,21 +284,12 @@ AWSEG_API int awseg_deocclude(const float* image, int64_t batch, int channels, i
                               const float* std, int radius, float threshold, float bright_min, int dilate, const int32_t* cond,
                               float* restored, uint8_t* mask, int64_t* stats, int n_slots, void* workspace, awseg_stream_t stream)
 {
-    if (!image || !mean || !std || !restored || !mask || !stats) return AWSEG_EINVAL;        // workspace: no bytes, so NULL will do
-    if (channels != 3 || batch < 0 || height < 1 || width < 1 || n_slots < 1) return AWSEG_EINVAL;
-    if (radius < 1 || radius > AWSEG_DEHAZE_MAX_RADIUS || dilate < 0 || dilate > kMaxDilate) return AWSEG_EINVAL;
-    if (!in_unit(threshold) || !in_closed_unit(bright_min)) return AWSEG_EINVAL;
     dc_args g = {};
-    for (int c = 0; c < 3; ++c) {
-        if (!(std[c] > 0.0f && std[c] <= FLT_MAX) || !is_finite(mean[c])) return AWSEG_EINVAL;
-        g.mean[c] = mean[c];
-        g.std[c] = std[c];
-    }
+    AWSEG_RESTORE_CHECKS(g, restored && mask,                                  // workspace: no bytes, so NULL will do
+                         radius >= 1 && radius <= AWSEG_DEHAZE_MAX_RADIUS && dilate >= 0 && dilate <= kMaxDilate && in_unit(threshold)
+                             && in_closed_unit(bright_min));
     g.threshold = threshold;
     g.bright_min = bright_min;
-    if (batch > 65535 || height > INT32_MAX / width) return AWSEG_ERANGE;      // grid.y; H * W >= 2^31
-    if (workspace && !awseg_aligned(workspace, 8)) return AWSEG_EALIGN;
-    if (batch == 0) return 0;
     hipStream_t s = awseg_s(stream);
     const int H = (int)height, W = (int)width;
     const int tiles_x = (W + kTW - 1) / kTW, tiles = tiles_x * ((H + kTH - 1) / kTH);

@@ -1,15 +1,11 @@
 // deocclude_tiles.h — what the detection kernel of deocclude.hip (awseg_deocclude) and the tile kernel of estimate.hip
 // (awseg_weather_estimate) share: the geometry of a 32 x 64 tile with a halo of 2 r + d, the staging of one
-// channel's v_c, and the separable window passes of the opening in LDS.  Every step is the one include/awseg_restore.h states; both
-// translation units must produce the same bits from it.  On top of dehaze_tiles.h (the constants, v_c and the reductions only).
+// channel's v_c, and the maximum passes of the opening in LDS.  Every step is the one include/awseg_restore.h states; both
+// translation units must produce the same bits from it.  On top of restore_common.h: the tile, v_c, the reductions and the window
+// minimum, which these kernels run at 512 threads with -inf outside the frame.
 #ifndef AWSEG_DEOCCLUDE_TILES_H
 #define AWSEG_DEOCCLUDE_TILES_H
-#define AWSEG_DEHAZE_TILES_NO_LAUNCHER                                     // the constants, v_c and the reductions only
-#include "dehaze_tiles.h"
-
-// The window loops: 2 r taps beside the first, two per trip (minima, maxima and integer sums do not mind the order), four trips
-// unrolled, so that eight LDS reads are in flight where a plain loop waits for each.
-#define AWSEG_TAPS _Pragma("unroll 4")
+#include "restore_common.h"
 
 namespace {
 
@@ -82,35 +78,7 @@ __device__ __forceinline__ void stage_channel(const float* __restrict__ plane, i
     }
 }
 
-// The window minimum e_c of the staged channel.  In: b0 [g.rows][g.sw] staged, behind a barrier.  Out: b0 [kTH + 2 q][c1] = e_c at
-// pixel (y0 - q + ii, x0 - q + j), -inf outside the frame (such positions take part in no maximum); ends with a barrier.
-__device__ __forceinline__ void minimum_passes(int H, int W, int y0, int x0, const dc_args& g, float* __restrict__ b0, float* __restrict__ b1)
-{
-    const int tid = threadIdx.x, taps = 2 * g.r;
-    const int rows_e = kTH + 2 * g.q;
-    // minimum along the row: column j of b1 is pixel x0 - q + j
-    for (int i = tid; i < g.rows * g.c1; i += kDetectThreads) {
-        const int row = i / g.c1, j = i - row * g.c1;
-        const float* p = b0 + row * g.sw + (g.pad - g.halo) + j;
-        float m = p[0];
-        AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k], p[k + 1]));
-        b1[i] = m;
-    }
-    __syncthreads();
-    // minimum down the column: row ii of b0 [rows_e][c1] is pixel row y0 - q + ii; positions outside the frame take part in no maximum
-    for (int i = tid; i < rows_e * g.c1; i += kDetectThreads) {
-        const int ii = i / g.c1, j = i - ii * g.c1;
-        const float* p = b1 + i;
-        float m = p[0];
-        AWSEG_TAPS for (int k = 1; k <= taps; k += 2) m = fminf(m, fminf(p[k * g.c1], p[(k + 1) * g.c1]));
-        const int yy = y0 - g.q + ii, xx = x0 - g.q + j;
-        if (yy < 0 || yy >= H || xx < 0 || xx >= W) m = -INFINITY;
-        b0[i] = m;
-    }
-    __syncthreads();
-}
-
-// The maximum of the minima along the row.  In: b0 of minimum_passes.  Out: b1 [kTH + 2 q][c2], column j = pixel x0 - d + j; ends
+// The maximum of the minima along the row.  In: b0 of window_minimum.  Out: b1 [kTH + 2 q][c2], column j = pixel x0 - d + j; ends
 // with a barrier.  The maximum down the column is the caller's: it takes it at its own positions only.
 __device__ __forceinline__ void maximum_row_pass(const dc_args& g, const float* __restrict__ b0, float* __restrict__ b1)
 {

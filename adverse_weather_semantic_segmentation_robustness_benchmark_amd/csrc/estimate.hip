@@ -69,7 +69,7 @@ void estimate_kernel(const float* __restrict__ image, int H, int W, int tiles_x,
             }
         }
         if (c == 0) sum[2] += q; else if (c == 1) sum[3] += q; else sum[4] += q;
-        minimum_passes(H, W, y0, x0, g, b0, b1);                           // e_c on the tile plus r, -inf outside the frame
+        window_minimum<kDetectThreads, true, true>(H, W, y0, x0, g, b0, b1);       // e_c on the tile plus r, -inf outside the frame
 #pragma unroll
         for (int k = 0; k < kPerThread; ++k) {
             const int idx = tid + k * kDetectThreads;
@@ -132,17 +132,9 @@ void route_kernel(const es_record* __restrict__ records, int batch, int64_t hw, 
     d[0] = D; d[1] = L; d[2] = M0; d[3] = M1; d[4] = M2; d[5] = O;
     long long row[kERow] = { 1, (long long)hw, rec.sum[0], rec.sum[1], rec.sum[2], rec.sum[3], rec.sum[4], rec.sum[5], rec.sum[6],
                              to == 0, to == 1, to == 2, to == 3 };
-    int slot = -1;
-    if (cond) { const int c = cond[b]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-#pragma unroll
-    for (int k = 0; k < kERow; ++k) {
-        if (!row[k]) continue;
-        atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row[k]);
-        if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kERow + k], (unsigned long long)row[k]);
-    }
+    add_row(stats, n_slots, cond, b, row);
 }
 
-inline bool in_closed_unit(float v) { return v >= 0.0f && v <= 1.0f; }      // NaN fails
 inline bool below_one(float v) { return v >= 0.0f && v < 1.0f; }
 
 }  // namespace
@@ -157,23 +149,12 @@ AWSEG_API int awseg_weather_estimate(const float* image, int64_t batch, int chan
                                      float dark_min, float seed_min, const int32_t* cond, int32_t* route, float* descriptors,
                                      int64_t* stats, int n_slots, void* workspace, awseg_stream_t stream)
 {
-    if (!image || !mean || !std || !route || !descriptors || !stats || !workspace) return AWSEG_EINVAL;
-    if (channels != 3 || batch < 0 || height < 1 || width < 1 || n_slots < 1) return AWSEG_EINVAL;
-    if (radius < 1 || radius > AWSEG_DEHAZE_MAX_RADIUS) return AWSEG_EINVAL;
-    if (!in_unit(threshold) || !in_closed_unit(bright_min) || !(cast_max > 0.0f && cast_max <= 4.0f) || !in_unit(luma_max)
-        || !below_one(dark_min) || !below_one(seed_min))
-        return AWSEG_EINVAL;
     dc_args g = {};
-    for (int c = 0; c < 3; ++c) {
-        if (!(std[c] > 0.0f && std[c] <= FLT_MAX) || !is_finite(mean[c])) return AWSEG_EINVAL;
-        g.mean[c] = mean[c];
-        g.std[c] = std[c];
-    }
+    AWSEG_RESTORE_CHECKS(g, route && descriptors && workspace,
+                         radius >= 1 && radius <= AWSEG_DEHAZE_MAX_RADIUS && in_unit(threshold) && in_closed_unit(bright_min)
+                             && cast_max > 0.0f && cast_max <= 4.0f && in_unit(luma_max) && below_one(dark_min) && below_one(seed_min));
     g.threshold = threshold;
     g.bright_min = bright_min;
-    if (batch > 65535 || height > INT32_MAX / width) return AWSEG_ERANGE;      // grid.y; H * W >= 2^31
-    if (!awseg_aligned(workspace, 8)) return AWSEG_EALIGN;
-    if (batch == 0) return 0;
     hipStream_t s = awseg_s(stream);
     const int H = (int)height, W = (int)width;
     const int tiles_x = (W + kTW - 1) / kTW, tiles = tiles_x * ((H + kTH - 1) / kTH);

@@ -16,15 +16,10 @@
 //                         interpolates, applies the gain and the white balance and adds its sums to the slots' rows.
 // The tile and band bounds travel in the kernel arguments (host integers: no division per pixel); a pixel finds its tile column
 // from a multiplied guess corrected against the bounds in LDS.
-#include "awseg_common.h"
-#include "../../include/awseg_restore.h"
-#include <float.h>
-#include <math.h>
+#include "restore_common.h"                                               // v_c, the reductions, the counter epilogue, the refusals
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / AWSEG_WAVE;
 constexpr int kBins = 256;
 constexpr int kRow = AWSEG_RELIGHT_ROW;
 constexpr int kMaxT = AWSEG_RELIGHT_MAX_TILES;
@@ -46,17 +41,8 @@ struct rl_args {
     float cy[kMaxT], cx[kMaxT];                                            // the tiles' centres
 };
 
-__device__ __forceinline__ float unit(float x, float sd, float mean) { return fminf(fmaxf(x * sd + mean, 0.0f), 1.0f); }
-__device__ __forceinline__ uint32_t not_finite(float x) { return fabsf(x) <= FLT_MAX ? 0u : 1u; }
 __device__ __forceinline__ float luma(float v0, float v1, float v2) { return (0.299f * v0 + 0.587f * v1) + 0.114f * v2; }
 __device__ __forceinline__ int bin_of(float l) { return min((int)(l * 255.0f), 255); }
-
-__device__ __forceinline__ long long wave_sum_i64(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // k with b[k] <= p < b[k + 1] among the n intervals of b (n + 1 non-decreasing bounds, b[0] <= p < b[n]; empty ones are stepped over).
 __device__ __forceinline__ int interval_of(const int* b, int n, int p, int guess)
@@ -139,19 +125,6 @@ void histogram_kernel(const float* __restrict__ image, int H, int W, const rl_ar
         for (int w = 0; w < kWaves; ++w) t += red[w][tid];
         long long* dst = tid < 3 ? &rec->sum[tid] : &rec->nonfinite;
         if (t) atomicAdd((unsigned long long*)dst, (unsigned long long)t);
-    }
-}
-
-__device__ __forceinline__ void add_row(int64_t* __restrict__ stats, int n_slots, const int32_t* __restrict__ cond, int64_t img,
-                                        const long long (&row)[kRow])
-{
-    int slot = -1;
-    if (cond) { const int c = cond[img]; if (c >= 0 && c + 1 < n_slots) slot = c + 1; }
-#pragma unroll
-    for (int k = 0; k < kRow; ++k) {
-        if (!row[k]) continue;
-        atomicAdd((unsigned long long*)&stats[k], (unsigned long long)row[k]);
-        if (slot > 0) atomicAdd((unsigned long long*)&stats[(int64_t)slot * kRow + k], (unsigned long long)row[k]);
     }
 }
 
@@ -319,7 +292,6 @@ void apply_kernel(const float* __restrict__ image, int H, int W, const rl_args g
     }
 }
 
-inline bool is_finite(float v) { return v >= -FLT_MAX && v <= FLT_MAX; }
 inline bool in_range(float v, float lo, float hi) { return v >= lo && v <= hi; }       // NaN fails
 
 // Strips per band: enough blocks to fill the chip `resident` times over the whole launch, at most one per row of the tallest band.
@@ -346,20 +318,11 @@ AWSEG_API int awseg_relight(const float* image, int64_t batch, int channels, int
                             const int32_t* cond, float* restored, float* gains, int64_t* stats, int n_slots, void* workspace,
                             awseg_stream_t stream)
 {
-    if (!image || !mean || !std || !restored || !gains || !stats || !workspace) return AWSEG_EINVAL;
-    if (channels != 3 || batch < 0 || height < 1 || width < 1 || n_slots < 1) return AWSEG_EINVAL;
-    if (tiles_y < 1 || tiles_y > kMaxT || tiles_x < 1 || tiles_x > kMaxT || tiles_y > height || tiles_x > width) return AWSEG_EINVAL;
-    if (!in_range(clip_limit, 1.0f, 64.0f) || !in_range(max_gain, 1.0f, 64.0f)) return AWSEG_EINVAL;
-    if (white_balance != 0 && white_balance != 1) return AWSEG_EINVAL;
     rl_args g = {};
-    for (int c = 0; c < 3; ++c) {
-        if (!(std[c] > 0.0f && std[c] <= FLT_MAX) || !is_finite(mean[c])) return AWSEG_EINVAL;
-        g.mean[c] = mean[c];
-        g.std[c] = std[c];
-    }
-    if (batch > 65535 || height > INT32_MAX / width) return AWSEG_ERANGE;      // grid.z; H * W >= 2^31
-    if (!awseg_aligned(workspace, 8)) return AWSEG_EALIGN;
-    if (batch == 0) return 0;
+    AWSEG_RESTORE_CHECKS(g, restored && gains && workspace,
+                         tiles_y >= 1 && tiles_y <= kMaxT && tiles_x >= 1 && tiles_x <= kMaxT && tiles_y <= height && tiles_x <= width
+                             && in_range(clip_limit, 1.0f, 64.0f) && in_range(max_gain, 1.0f, 64.0f)
+                             && (white_balance == 0 || white_balance == 1));
     hipStream_t s = awseg_s(stream);
     const int H = (int)height, W = (int)width;
     g.clip = clip_limit;

@@ -282,70 +282,89 @@ def check_quality_budget(terms: int) -> None:
     _check_budget(terms, ops.IQ_TERM_BUDGET, "image-quality counters hold {} pixel-channels")
 
 
-RESTORATION_KEYS = ("radius", "omega", "t_min", "airlight_min", "refine")
-RESTORATION_REFINE = {"opening": 1, "none": 0}
-RESTORATION_GUIDED_KEYS = ("guided_radius", "guided_eps")               # only under refine: guided (awseg_dehaze_guided)
-RESTORATION_METHODS = ("dark_channel", "clahe", "tophat")
-RESTORATION_RELIGHT_KEYS = ("grid", "clip_limit", "max_gain", "white_balance")      # only under method: clahe (awseg_relight)
-RESTORATION_WHITE_BALANCE = {"gray_world": True, "none": False}
-# only under method: tophat (awseg_deocclude); `radius` is a key of the dark channel as well and belongs to the method named
-RESTORATION_DEOCCLUDE_KEYS = ("radius", "threshold", "bright_min", "dilate")
+# `evaluation.restoration`: one entry per method, in the order of the routes, of the refusals and of the result keys.  'keys': its
+# config keys (`radius` is the dark channel's and the top-hat's and belongs to the method named); 'maps': the keys given by name
+# and what the names stand for (the first is the default); 'parameters': ops' check of them; 'new_stats': what makes its counters;
+# 'attr': the EvalState attribute they live in; 'run': (images, counters..., cond, **parameters) -> (restored frames, ...);
+# 'metrics': counters -> result keys (None: the dehazer's go through restoration_metrics_from_stats with the second confusion).
+RESTORATION = {
+    "dark_channel": {                                                  # awseg_dehaze, DESIGN.md 10n: also what no `method` means
+        "keys": ("radius", "omega", "t_min", "airlight_min", "refine"), "maps": {"refine": {"opening": 1, "none": 0}},
+        "parameters": ops.dehaze_parameters, "new_stats": ops.new_dehaze_stats, "attr": "restoration", "run": ops.dehaze, "metrics": None},
+    "clahe": {                                                         # awseg_relight, DESIGN.md 10o
+        "keys": ("grid", "clip_limit", "max_gain", "white_balance"), "maps": {"white_balance": {"gray_world": True, "none": False}},
+        "parameters": ops.relight_parameters, "new_stats": ops.new_relight_stats, "attr": "restoration_relight", "run": ops.relight,
+        "metrics": relight_metrics_from_stats},
+    "tophat": {                                                        # awseg_deocclude, DESIGN.md 10p
+        "keys": ("radius", "threshold", "bright_min", "dilate"), "maps": {},
+        "parameters": ops.deocclude_parameters, "new_stats": ops.new_deocclude_stats, "attr": "restoration_deocclude",
+        "run": ops.deocclude, "metrics": deocclude_metrics_from_stats},
+}
+# the dark channel under refine: guided (awseg_dehaze_guided): what runs in its place, the filter's counters
+# beside the dehazer's
+RESTORATION_GUIDED = {"keys": ("radius", "omega", "t_min", "airlight_min", "guided_radius", "guided_eps"),
+                      "parameters": ops.dehaze_guided_parameters, "new_stats": ops.new_guided_stats, "attr": "restoration_guided",
+                      "run": ops.dehaze_guided, "metrics": guided_metrics_from_stats}
+RESTORATION_METHODS = tuple(RESTORATION)
+RESTORATION_KEYS = RESTORATION["dark_channel"]["keys"]
+RESTORATION_REFINE = RESTORATION["dark_channel"]["maps"]["refine"]
+RESTORATION_GUIDED_KEYS = RESTORATION_GUIDED["keys"][4:]               # only under refine: guided
+RESTORATION_RELIGHT_KEYS = RESTORATION["clahe"]["keys"]
+RESTORATION_WHITE_BALANCE = RESTORATION["clahe"]["maps"]["white_balance"]
+RESTORATION_DEOCCLUDE_KEYS = RESTORATION["tophat"]["keys"]
 # under method: auto (awseg_weather_estimate) the three methods above are chosen per frame: the keys of that level,
 # the keys of `estimator`, and the route a rule that knew the weather would take (names outside the map: none)
-RESTORATION_AUTO_KEYS = ("route", "estimator", "dark_channel", "clahe", "tophat")
+RESTORATION_AUTO_KEYS = ("route", "estimator") + RESTORATION_METHODS
 RESTORATION_ROUTES = ("estimated", "oracle")
 RESTORATION_ESTIMATOR_KEYS = tuple(ops.ESTIMATE_DEFAULTS)
 
 
-def _relight_option(spec: dict) -> dict:
-    """The dict of `evaluation.restoration` under method: clahe (without 'method') -> the checked option, without 'conditions'."""
-    foreign = sorted(set(spec) & (set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS)))
-    if foreign:
-        raise ValueError(f"evaluation.restoration: {foreign} belong to method: dark_channel, got method: clahe")
-    foreign = sorted(set(spec) & set(RESTORATION_DEOCCLUDE_KEYS))
-    if foreign:
-        raise ValueError(f"evaluation.restoration: {foreign} belong to method: tophat, got method: clahe")
-    if set(spec) - set(RESTORATION_RELIGHT_KEYS):
-        raise ValueError(f"evaluation.restoration with method: clahe is a dict with keys among {list(RESTORATION_RELIGHT_KEYS)}, "
-                         f"got {spec!r}")
+def _method_keys(method: str) -> tuple:
+    """Every config key of a method."""
+    return RESTORATION[method]["keys"] + (RESTORATION_GUIDED_KEYS if method == "dark_channel" else ())
+
+
+
+def _method_option(method: str, spec) -> dict:
+    """`evaluation.restoration` under one method of the table (without 'method') -> the checked option, without 'conditions'."""
+    entry, own = RESTORATION[method], set(_method_keys(method))
+    for other in RESTORATION if isinstance(spec, dict) else ():
+        foreign = sorted(set(spec) & (set(_method_keys(other)) - own))
+        if foreign:
+            raise ValueError(f"evaluation.restoration: {foreign} belong to method: {other}, got method: {method}")
+    if not isinstance(spec, dict) or set(spec) - own:
+        if method != "dark_channel":
+            raise ValueError(f"evaluation.restoration with method: {method} is a dict with keys among {list(entry['keys'])}, got {spec!r}")
+        raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat' or a dict with keys among "
+                         f"{list(_method_keys(method))} (method: clahe: {list(RESTORATION_RELIGHT_KEYS)}; method: "
+                         f"tophat: {list(RESTORATION_DEOCCLUDE_KEYS)}), got {spec!r}")
     kw = dict(spec)
-    if "white_balance" in kw:
-        wb = kw["white_balance"]
-        if not isinstance(wb, str) or wb not in RESTORATION_WHITE_BALANCE:
-            raise ValueError(f"evaluation.restoration.white_balance is 'gray_world' or 'none', got {wb!r}")
-        kw["white_balance"] = RESTORATION_WHITE_BALANCE[wb]
+    for key, values in entry["maps"].items():
+        names = list(values) + ["guided"] * (key == "refine")
+        given = kw.get(key, names[0])
+        if not isinstance(given, str) or given not in names:
+            raise ValueError(f"evaluation.restoration.{key} is {', '.join(map(repr, names[:-1]))} or {names[-1]!r}, got {given!r}")
+        if key in kw and given in values:
+            kw[key] = values[given]
+    guided = kw.get("refine") == "guided"
+    if not guided and set(kw) & set(RESTORATION_GUIDED_KEYS):
+        raise ValueError(f"evaluation.restoration: {sorted(set(kw) & set(RESTORATION_GUIDED_KEYS))} belong to refine: guided, got "
+                         f"refine: {spec.get('refine', 'opening')}")
     try:
-        opt = ops.relight_parameters(**kw)
+        if guided:
+            opt = {**RESTORATION_GUIDED["parameters"](**{k: v for k, v in kw.items() if k != "refine"}), "refine": "guided"}
+        else:
+            opt = entry["parameters"](**kw)
     except ValueError as e:
         raise ValueError(f"evaluation.restoration: {e}") from None
-    return {"method": "clahe", **opt}
-
-
-def _deocclude_option(spec: dict) -> dict:
-    """The dict of `evaluation.restoration` under method: tophat (without 'method') -> the checked option, without 'conditions'."""
-    own = set(RESTORATION_DEOCCLUDE_KEYS)
-    foreign = sorted(set(spec) & ((set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS)) - own))
-    if foreign:
-        raise ValueError(f"evaluation.restoration: {foreign} belong to method: dark_channel, got method: tophat")
-    foreign = sorted(set(spec) & set(RESTORATION_RELIGHT_KEYS))
-    if foreign:
-        raise ValueError(f"evaluation.restoration: {foreign} belong to method: clahe, got method: tophat")
-    if set(spec) - own:
-        raise ValueError(f"evaluation.restoration with method: tophat is a dict with keys among {list(RESTORATION_DEOCCLUDE_KEYS)}, "
-                         f"got {spec!r}")
-    try:
-        opt = ops.deocclude_parameters(**spec)
-    except ValueError as e:
-        raise ValueError(f"evaluation.restoration: {e}") from None
-    return {"method": "tophat", **opt}
+    return opt if method == "dark_channel" else {"method": method, **opt}      # no `method`, no 'method' key
 
 
 def _auto_option(spec: dict) -> dict:
     """The dict of `evaluation.restoration` under method: auto (without 'method') -> the checked option, without 'conditions':
     {'method': 'auto', 'route', 'estimator', 'dark_channel', 'clahe', 'tophat'}, the last three what restoration_option gives for
     that method alone (without 'conditions')."""
-    levels = {"dark_channel": set(RESTORATION_KEYS) | set(RESTORATION_GUIDED_KEYS), "clahe": set(RESTORATION_RELIGHT_KEYS),
-              "tophat": set(RESTORATION_DEOCCLUDE_KEYS), "estimator": set(RESTORATION_ESTIMATOR_KEYS)}
+    levels = {**{method: _method_keys(method) for method in RESTORATION}, "estimator": RESTORATION_ESTIMATOR_KEYS}
     for key in sorted(set(spec) - set(RESTORATION_AUTO_KEYS)):
         homes = [name for name, keys in levels.items() if key in keys]
         if homes:
@@ -419,42 +438,13 @@ def restoration_option(config, images=None):
             raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat', 'auto' or a dict of a method's parameters, "
                              f"got {spec!r}")
         spec = {"method": spec}
+    method = RESTORATION_METHODS[0]
     if isinstance(spec, dict) and "method" in spec:
         method = spec["method"]
         if not isinstance(method, str) or (method not in RESTORATION_METHODS and method != "auto"):
             raise ValueError(f"evaluation.restoration.method is 'dark_channel', 'clahe', 'tophat' or 'auto', got {method!r}")
         spec = {k: v for k, v in spec.items() if k != "method"}
-        if method in ("clahe", "tophat", "auto"):
-            opt = _relight_option(spec) if method == "clahe" else _deocclude_option(spec) if method == "tophat" else _auto_option(spec)
-            if images is not None:
-                check_frames("restoration", images)
-            opt["conditions"] = names
-            return opt
-    if isinstance(spec, dict) and set(spec) & set(RESTORATION_RELIGHT_KEYS):
-        raise ValueError(f"evaluation.restoration: {sorted(set(spec) & set(RESTORATION_RELIGHT_KEYS))} belong to method: clahe, got "
-                         "method: dark_channel")
-    if isinstance(spec, dict) and set(spec) & set(RESTORATION_DEOCCLUDE_KEYS[1:]):
-        raise ValueError(f"evaluation.restoration: {sorted(set(spec) & set(RESTORATION_DEOCCLUDE_KEYS[1:]))} belong to method: tophat, "
-                         "got method: dark_channel")
-    if not isinstance(spec, dict) or set(spec) - set(RESTORATION_KEYS) - set(RESTORATION_GUIDED_KEYS):
-        raise ValueError(f"evaluation.restoration is 'dark_channel', 'clahe', 'tophat' or a dict with keys among "
-                         f"{list(RESTORATION_KEYS + RESTORATION_GUIDED_KEYS)} (method: clahe: {list(RESTORATION_RELIGHT_KEYS)}; method: "
-                         f"tophat: {list(RESTORATION_DEOCCLUDE_KEYS)}), got {spec!r}")
-    kw = {k: v for k, v in spec.items() if k != "refine"}
-    refine = spec.get("refine", "opening")
-    if not isinstance(refine, str) or (refine not in RESTORATION_REFINE and refine != "guided"):
-        raise ValueError(f"evaluation.restoration.refine is 'opening', 'none' or 'guided', got {refine!r}")
-    if refine != "guided" and set(kw) & set(RESTORATION_GUIDED_KEYS):
-        raise ValueError(f"evaluation.restoration: {sorted(set(kw) & set(RESTORATION_GUIDED_KEYS))} belong to refine: guided, got "
-                         f"refine: {refine}")
-    try:
-        if refine == "guided":
-            opt = ops.dehaze_guided_parameters(**kw)
-            opt["refine"] = "guided"
-        else:
-            opt = ops.dehaze_parameters(refine=RESTORATION_REFINE[refine], **kw)
-    except ValueError as e:
-        raise ValueError(f"evaluation.restoration: {e}") from None
+    opt = _auto_option(spec) if method == "auto" else _method_option(method, spec)
     if images is not None:
         check_frames("restoration", images)
     opt["conditions"] = names
@@ -664,50 +654,38 @@ class EvalState:
         # restored frames (off unless restoration = restoration_option(config)): a SECOND confusion accumulator over this run's slots
         # for the forward on the dehazed frames, and the dehazing counters int64 [slot, AWSEG_DEHAZE_ROW].  'conditions': the weather
         # conditions whose frames are restored (None: all); 'oob' is the second accumulator's
-        self.restoration = None
-        auto = restoration is not None and restoration.get("method") == "auto"
-        relit = restoration is not None and restoration.get("method") == "clahe"
-        tophat = restoration is not None and restoration.get("method") == "tophat"
-        if restoration is not None:
-            guided = not relit and not tophat and not auto and restoration["refine"] == "guided"
-            params = (None if auto
-                      else ops.relight_parameters(**{k: restoration[k] for k in RESTORATION_RELIGHT_KEYS}) if relit
-                      else ops.deocclude_parameters(**{k: restoration[k] for k in RESTORATION_DEOCCLUDE_KEYS}) if tophat
-                      else ops.dehaze_guided_parameters(**{k: restoration[k] for k in RESTORATION_KEYS[:4] + RESTORATION_GUIDED_KEYS}) if guided
-                      else ops.dehaze_parameters(**{k: restoration[k] for k in RESTORATION_KEYS}))
-            acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
-            # under method: clahe and method: tophat there are no dehazing counters: 'stats' has no rows (the reduce and the result keys see nothing)
-            self.restoration = {"params": params, "acc": acc, "counts": acc.counts, "oob": acc.oob,
-                                "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]},
-                                "stats": torch.zeros(0, ops.DEHAZE_ROW, dtype=torch.int64, device=device) if relit or tophat
-                                else ops.new_dehaze_stats(device, 1 + len(conditions))}
-        # under refine: guided the counters of the filter, int64 [slot, AWSEG_GUIDED_ROW] (None otherwise: awseg_dehaze runs)
-        self.restoration_guided = None
-        if restoration is not None and not relit and not tophat and not auto and restoration["refine"] == "guided":
-            self.restoration_guided = {"stats": ops.new_guided_stats(device, 1 + len(conditions))}
-        # under method: clahe the counters of the relighting, int64 [slot, AWSEG_RELIGHT_ROW] (None otherwise); awseg_relight
-        # produces the restored frames, everything behind it is the dehazer's second pass
-        self.restoration_relight = None
-        if relit or auto:
-            self.restoration_relight = {"stats": ops.new_relight_stats(device, 1 + len(conditions))}
-        # under method: tophat the counters of the occluder removal, int64 [slot, AWSEG_DEOCCLUDE_ROW] (None otherwise); awseg_deocclude
-        # produces the restored frames, everything behind it is the dehazer's second pass.  The mask is not kept
-        self.restoration_deocclude = None
-        if tophat or auto:
-            self.restoration_deocclude = {"stats": ops.new_deocclude_stats(device, 1 + len(conditions))}
-        # under method: auto all three methods' counters above are allocated, each sees the frames routed to it, and
-        # the counters of the weather estimate, int64 [slot, AWSEG_ESTIMATE_ROW], see every selected frame.  'route': 'estimated'
-        # or 'oracle'; 'params': the estimator's and each method's; 'host', 'event': the pinned buffer the routes are copied to and
-        # the event behind that copy (estimated only); 'pending': the estimate of the batch in flight; 'readbacks': how many batches'
-        # routes the host has waited for
+        # Every entry of RESTORATION keeps its counters, int64 [slot, row], in its own attribute ({'stats'}, None while it does not
+        # run): `restoration` the dehazer's (AWSEG_DEHAZE_ROW), `restoration_guided` the filter's under refine: guided,
+        # `restoration_relight` and `restoration_deocclude` those of method: clahe and method: tophat, whose frames go through the
+        # dehazer's second pass all the same; their masks and gains are not kept.  Without dehazing counters `restoration['stats']`
+        # has no rows (the reduce and the result keys see nothing).  Under method: auto all three methods' counters
+        # are allocated and each sees the frames routed to it
+        for entry in (*RESTORATION.values(), RESTORATION_GUIDED):
+            setattr(self, entry["attr"], None)
         self.restoration_estimate = None
-        if auto:
-            self.restoration_estimate = {"stats": ops.new_estimate_stats(device, 1 + len(conditions)), "route": restoration["route"],
-                                         "params": {"estimator": ops.weather_estimate_parameters(**restoration["estimator"]),
-                                                    "dark_channel": ops.dehaze_parameters(**{k: restoration["dark_channel"][k] for k in RESTORATION_KEYS}),
-                                                    "clahe": ops.relight_parameters(**{k: restoration["clahe"][k] for k in RESTORATION_RELIGHT_KEYS}),
-                                                    "tophat": ops.deocclude_parameters(**{k: restoration["tophat"][k] for k in RESTORATION_DEOCCLUDE_KEYS})},
-                                         "host": None, "event": None, "pending": None, "readbacks": 0}
+        self._restoration_method = None if restoration is None else restoration.get("method", RESTORATION_METHODS[0])
+        if restoration is not None:
+            auto, slots = self._restoration_method == "auto", 1 + len(conditions)
+            options = {m: restoration[m] for m in RESTORATION} if auto else {self._restoration_method: restoration}
+            params = {}
+            for method, opt in options.items():
+                entries = [RESTORATION[method]] + [RESTORATION_GUIDED] * (opt.get("refine") == "guided")      # the last runs
+                params[method] = entries[-1]["parameters"](**{k: opt[k] for k in entries[-1]["keys"]})
+                for entry in entries:
+                    setattr(self, entry["attr"], {"stats": entry["new_stats"](device, slots)})
+            acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
+            own = self.restoration or {"stats": torch.zeros(0, ops.DEHAZE_ROW, dtype=torch.int64, device=device)}
+            self.restoration = {"params": None if auto else params[self._restoration_method], "acc": acc, "counts": acc.counts,
+                                "oob": acc.oob, "stats": own["stats"],
+                                "conditions": None if restoration.get("conditions") is None else {str(c) for c in restoration["conditions"]}}
+            # the counters of the weather estimate, int64 [slot, AWSEG_ESTIMATE_ROW], see every selected frame.  'route': 'estimated'
+            # or 'oracle'; 'params': the estimator's and each method's; 'host', 'event': the pinned buffer the routes are copied to and
+            # the event behind that copy (estimated only); 'pending': the estimate of the batch in flight; 'readbacks': how many
+            # batches' routes the host has waited for
+            if auto:
+                self.restoration_estimate = {"stats": ops.new_estimate_stats(device, slots), "route": restoration["route"],
+                                             "params": {"estimator": ops.weather_estimate_parameters(**restoration["estimator"]), **params},
+                                             "host": None, "event": None, "pending": None, "readbacks": 0}
         # fidelity of the restored frames (only when the sweep, the image-quality counters and the restoration are all on): a SECOND
         # image-quality tensor, the restored frames against the same kept clean frames; the clean batch against its own kept rows
         self.restored_quality = None
@@ -886,25 +864,28 @@ class EvalState:
         es["readbacks"] += 1
         return [int(r) for r in es["host"][:len(kinds)].tolist()]
 
+    def _restore(self, method, images, cond, params):
+        """The frames through one method of the table (the guided dehazer where its counters are allocated) into its counters."""
+        entries = [RESTORATION[method]] + [RESTORATION_GUIDED] * (method == "dark_channel" and self.restoration_guided is not None)
+        return entries[-1]["run"](images, *(getattr(self, e["attr"])["stats"] for e in entries), cond, **params)[0]
+
     def _restore_by_route(self, images, cond, routes):
         """The frames grouped by route, each group through its method into that method's own counters, written back into one batch;
         the frames routed to none are copied as they are."""
         es, n = self.restoration_estimate, images.shape[0]
-        run = {"dark_channel": lambda x, c: ops.dehaze(x, self.restoration["stats"], c, **es["params"]["dark_channel"])[0],
-               "clahe": lambda x, c: ops.relight(x, self.restoration_relight["stats"], c, **es["params"]["clahe"])[0],
-               "tophat": lambda x, c: ops.deocclude(x, self.restoration_deocclude["stats"], c, **es["params"]["tophat"])[0]}
+        run = lambda name, x, c: self._restore(name, x, c, es["params"][name])      # noqa: E731
         restored = None
         for r, name in enumerate(ops.ESTIMATE_ROUTES):
             members = [i for i, v in enumerate(routes) if v == r]
             if not members:
                 continue
             if len(members) == n:                                     # the whole batch takes one route
-                return images if name == "none" else run[name](images, cond)
+                return images if name == "none" else run(name, images, cond)
             if restored is None:
                 restored = torch.empty_like(images)
             idx = torch.tensor(members, dtype=torch.int64).to(images.device, non_blocking=True)
             group = images.index_select(0, idx)
-            restored.index_copy_(0, idx, group if name == "none" else run[name](group, cond.index_select(0, idx)))
+            restored.index_copy_(0, idx, group if name == "none" else run(name, group, cond.index_select(0, idx)))
         return restored
 
     def update_restoration(self, model, images, labels, kinds, cond, rows=None) -> None:
@@ -921,18 +902,11 @@ class EvalState:
             images, labels, cond = images.index_select(0, idx), labels.index_select(0, idx), cond.index_select(0, idx)
             if rows is not None:
                 rows = rows.index_select(0, idx) if torch.is_tensor(rows) else [rows[i] for i in keep]
+        self.check_relight_grid(images)
         if self.restoration_estimate is not None:
-            self.check_relight_grid(images)
             restored = self._restore_by_route(images, cond, self._routes([kinds[i] for i in keep]))
-        elif self.restoration_relight is not None:
-            self.check_relight_grid(images)
-            restored, _ = ops.relight(images, self.restoration_relight["stats"], cond, **rs["params"])
-        elif self.restoration_deocclude is not None:
-            restored, _ = ops.deocclude(images, self.restoration_deocclude["stats"], cond, **rs["params"])
-        elif self.restoration_guided is not None:
-            restored, _ = ops.dehaze_guided(images, rs["stats"], self.restoration_guided["stats"], cond, **rs["params"])
         else:
-            restored, _ = ops.dehaze(images, rs["stats"], cond, **rs["params"])
+            restored = self._restore(self._restoration_method, images, cond, rs["params"])
         if self.restored_quality is not None:
             # (the rows a last variant batch has just released still hold their frames: nothing writes them before the next batch)
             rq = self.restored_quality
@@ -1310,23 +1284,20 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
                                                   q["targets"], metrics.compute_robustness_degradation_ratio))
     if st.restoration is not None:
         rs = st.restoration
-        auto = st.restoration_estimate is not None                 # every method's counters, each over the frames routed to it
-        relit = st.restoration_relight is not None and not auto    # no dehazing counters then: all-zero rows give no dehazing key
-        tophat = st.restoration_deocclude is not None and not auto  # nor then
-        dehaze_stats = np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64) if relit or tophat else rs["stats"].cpu().numpy()
+        # without dehazing counters (method: clahe, method: tophat) all-zero rows give no dehazing key
+        dehaze_stats = rs["stats"].cpu().numpy() if rs["stats"].shape[0] else np.zeros((1 + len(st.acc.conditions), ops.DEHAZE_ROW), np.int64)
         results.update(restoration_metrics_from_stats(rs["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), dehaze_stats,
                                                       st.acc.conditions, metrics.num_classes, **sweep_kw,
                                                       degradation=metrics.compute_robustness_degradation_ratio))
-        if relit or auto:
-            results.update(relight_metrics_from_stats(st.restoration_relight["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
-        if tophat or auto:
-            results.update(deocclude_metrics_from_stats(st.restoration_deocclude["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
-        if auto:                                                   # last: restoration_method and the non-finite count are the estimate's
+        for entry in (*RESTORATION.values(), RESTORATION_GUIDED):   # in the table's order: later keys overwrite earlier ones
+            held = getattr(st, entry["attr"])
+            if held is not None and entry["metrics"] is not None:
+                results.update(entry["metrics"](held["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
+        if st.restoration_guided is not None:
+            results["restoration_refine"] = "guided"
+        if st.restoration_estimate is not None:                    # last: restoration_method and the non-finite count are the estimate's
             results.update(estimate_metrics_from_stats(st.restoration_estimate["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw,
                                                        route=st.restoration_estimate["route"]))
-        if st.restoration_guided is not None:
-            results.update(guided_metrics_from_stats(st.restoration_guided["stats"].cpu().numpy(), st.acc.conditions, **sweep_kw))
-            results["restoration_refine"] = "guided"
         if st.restored_quality is not None:
             results.update(restored_quality_metrics_from_stats(st.restored_quality["stats"].cpu().numpy(), q["stats"].cpu().numpy(),
                                                                st.acc.conditions, st.sweep.kinds, st.sweep.levels))

@@ -627,35 +627,61 @@ DEHAZE_FRAME_RECORD = 1064             # AWSEG_DEHAZE_FRAME_RECORD: workspace by
 DEHAZE_DEFAULTS = {"radius": 7, "omega": 0.95, "t_min": 0.1, "airlight_min": 0.1, "refine": 1}
 
 
-def new_dehaze_stats(device, n_slots: int = 1) -> torch.Tensor:
-    """int64 [n_slots, DEHAZE_ROW]: per slot the row DEHAZE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
-    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
-        raise ValueError(f"new_dehaze_stats: n_slots is an integer >= 1, got {n_slots!r}")
-    return torch.zeros(int(n_slots), DEHAZE_ROW, dtype=torch.int64, device=device)
+def _stats_rows(name: str, fields, units: str = ""):
+    """-> (new_<name>_stats, <name>_stats_to_numpy) for the counter row `fields` of include/awseg_restore.h; `units`: what the
+    docstrings say about the row's fixed-point sums."""
+    row, upper = len(fields), name.upper()
+
+    def new_stats(device, n_slots: int = 1) -> torch.Tensor:
+        if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
+            raise ValueError(f"new_{name}_stats: n_slots is an integer >= 1, got {n_slots!r}")
+        return torch.zeros(int(n_slots), row, dtype=torch.int64, device=device)
+
+    def stats_to_numpy(stats) -> dict:
+        raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
+        if raw.shape[-1] != row:
+            raise ValueError(f"{name} rows hold {row} counters, got {raw.shape[-1]}")
+        return {f: raw[..., i] for i, f in enumerate(fields)}
+
+    new_stats.__name__ = new_stats.__qualname__ = f"new_{name}_stats"
+    new_stats.__doc__ = (f"int64 [n_slots, {upper}_ROW]: per slot the row {upper}_FIELDS of include/awseg_restore.h (zeroed: the launches "
+                         f"accumulate){units and '; ' + units}.")
+    stats_to_numpy.__name__ = stats_to_numpy.__qualname__ = f"{name}_stats_to_numpy"
+    stats_to_numpy.__doc__ = f"int64 [..., {upper}_ROW] -> {{field: int64 [...]}} for {upper}_FIELDS{units and '; ' + units}."
+    return new_stats, stats_to_numpy
+
+
+def _integer(who: str, name: str, v, lo: int, hi: int) -> int:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{who}: {name} is an integer in [{lo}, {hi}], got {v!r}")
+    return int(v)
+
+
+def _number(who: str, name: str, v, lo: float, hi: float, open_below: bool = False, open_above: bool = False) -> float:
+    """v as float32, in the interval from lo to hi (NaN is refused)."""
+    ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
+    f = float(np.float32(v)) if ok else float("nan")
+    if not (ok and (lo < f if open_below else lo <= f) and (f < hi if open_above else f <= hi)):
+        raise ValueError(f"{who}: {name} is a number in {'(' if open_below else '['}{lo:g}, {hi:g}{')' if open_above else ']'} "
+                         f"(also as float32), got {v!r}")
+    return f
+
+
+new_dehaze_stats, dehaze_stats_to_numpy = _stats_rows("dehaze", DEHAZE_FIELDS, "the four sums are in units of DEHAZE_UNIT")
 
 
 def dehaze_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, refine=1) -> dict:
     """The checked parameters of dehaze(): radius an integer in [1, 15]; omega, t_min, airlight_min numbers in (0, 1] (also as
     float32); refine 0 or 1.  ValueError otherwise."""
-    def integer(name, v, lo, hi):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"dehaze: {name} is an integer in [{lo}, {hi}], got {v!r}")
-        return int(v)
-
-    def unit(name, v):
-        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
-        f = float(np.float32(v)) if ok else 0.0
-        if not (ok and 0.0 < f <= 1.0):
-            raise ValueError(f"dehaze: {name} is a number in (0, 1] (also as float32), got {v!r}")
-        return f
-    return {"radius": integer("radius", radius, 1, DEHAZE_MAX_RADIUS), "omega": unit("omega", omega), "t_min": unit("t_min", t_min),
-            "airlight_min": unit("airlight_min", airlight_min), "refine": integer("refine", refine, 0, 1)}
+    unit = lambda name, v: _number("dehaze", name, v, 0.0, 1.0, open_below=True)      # noqa: E731
+    return {"radius": _integer("dehaze", "radius", radius, 1, DEHAZE_MAX_RADIUS), "omega": unit("omega", omega),
+            "t_min": unit("t_min", t_min), "airlight_min": unit("airlight_min", airlight_min),
+            "refine": _integer("dehaze", "refine", refine, 0, 1)}
 
 
-def _dehaze_buffers(who: str, image, stats, cond, mean, std, out, row: Optional[int] = None, new_stats=None):
-    """The checks dehaze(), dehaze_guided() and relight() share -> (contiguous image, B, H, W, mean, std, stats, out, airlight
-    [B, 3]).  `row`, `new_stats`: the width of a counter row and what makes one (default: the dehazer's)."""
-    row, new_stats = (DEHAZE_ROW, new_dehaze_stats) if row is None else (row, new_stats)
+def _restore_frames(who: str, image, stats, cond, mean, std, row: int, new_stats):
+    """The checks of the frames, the normalisation, the counters and the conditions that every restoration entry point makes ->
+    (contiguous image, B, H, W, mean, std, stats).  `row`, `new_stats`: the width of a counter row and what makes one."""
     if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
         raise ValueError(f"{who}: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
     b, _, h, w = (int(d) for d in image.shape)
@@ -675,14 +701,18 @@ def _dehaze_buffers(who: str, image, stats, cond, mean, std, out, row: Optional[
         raise ValueError(f"stats must be int64 [slots, {row}] ({new_stats.__name__}), got {stats.dtype} {tuple(stats.shape)}")
     if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
         raise ValueError("cond must be int32 [B]")
-    image = image.contiguous()
+    return image.contiguous(), b, h, w, m, s, stats
+
+
+def _restore_outputs(who: str, image, out):
+    """-> (`out` checked, or new frames like `image`; a new float32 [B, 3] for the per-frame side output)."""
     if out is None:
         out = torch.empty_like(image)
     if out.dtype != torch.float32 or tuple(out.shape) != tuple(image.shape) or not out.is_contiguous():
         raise ValueError(f"{who}: out is a contiguous float32 tensor of the frames' shape, got {out.dtype} {tuple(out.shape)}")
-    if b and out.data_ptr() == image.data_ptr():
+    if image.shape[0] and out.data_ptr() == image.data_ptr():
         raise ValueError(f"{who}: out must not be the input (a block reads its neighbours' pixels)")
-    return image, b, h, w, m, s, stats, out, torch.empty(b, 3, dtype=torch.float32, device=image.device)
+    return out, torch.empty(image.shape[0], 3, dtype=torch.float32, device=image.device)
 
 
 def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, *, radius: int = 7,
@@ -695,7 +725,8 @@ def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Opti
     0: from He's patch minimum.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`: where the restored frames
     go (contiguous, not `image`)."""
     p = dehaze_parameters(radius, omega, t_min, airlight_min, refine)
-    image, b, h, w, m, s, stats, out, airlight = _dehaze_buffers("dehaze", image, stats, cond, mean, std, out)
+    image, b, h, w, m, s, stats = _restore_frames("dehaze", image, stats, cond, mean, std, DEHAZE_ROW, new_dehaze_stats)
+    out, airlight = _restore_outputs("dehaze", image, out)
     if b == 0:
         return out, airlight
     ws = N.workspace.get(image.device, N.lib().awseg_dehaze_workspace(b, h, w), tag="dehaze")
@@ -704,28 +735,13 @@ def dehaze(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Opti
     return out, airlight
 
 
-def dehaze_stats_to_numpy(stats) -> dict:
-    """int64 [..., DEHAZE_ROW] -> {field: int64 [...]} for DEHAZE_FIELDS; the four sums stay in units of DEHAZE_UNIT."""
-    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
-    if raw.shape[-1] != DEHAZE_ROW:
-        raise ValueError(f"dehaze rows hold {DEHAZE_ROW} counters, got {raw.shape[-1]}")
-    return {f: raw[..., i] for i, f in enumerate(DEHAZE_FIELDS)}
-
-
 # ------------------------------------------------ guided-filter transmission (include/awseg_restore.h, DESIGN 10n-bis)
 GUIDED_FIELDS = ("above_one_pixels", "below_floor_pixels", "sum_transmission_moved", "pixels")
 GUIDED_ROW = len(GUIDED_FIELDS)        # AWSEG_GUIDED_ROW
 GUIDED_MAX_RADIUS = 32                 # AWSEG_GUIDED_MAX_RADIUS
 GUIDED_EPS_RANGE = (1e-4, 1.0)         # as float32: what the launcher accepts
 GUIDED_DEFAULT_EPS = 1e-3
-
-
-def new_guided_stats(device, n_slots: int = 1) -> torch.Tensor:
-    """int64 [n_slots, GUIDED_ROW]: per slot the row GUIDED_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate);
-    sum_transmission_moved is in units of DEHAZE_UNIT."""
-    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
-        raise ValueError(f"new_guided_stats: n_slots is an integer >= 1, got {n_slots!r}")
-    return torch.zeros(int(n_slots), GUIDED_ROW, dtype=torch.int64, device=device)
+new_guided_stats, guided_stats_to_numpy = _stats_rows("guided", GUIDED_FIELDS, "sum_transmission_moved is in units of DEHAZE_UNIT")
 
 
 def default_guided_radius(radius: int) -> int:
@@ -739,14 +755,12 @@ def dehaze_guided_parameters(radius=7, omega=0.95, t_min=0.1, airlight_min=0.1, 
     del p["refine"]
     if guided_radius is None:
         guided_radius = default_guided_radius(p["radius"])
-    if isinstance(guided_radius, (bool, np.bool_)) or not isinstance(guided_radius, (int, np.integer)) \
-            or not 1 <= int(guided_radius) <= GUIDED_MAX_RADIUS:
-        raise ValueError(f"dehaze_guided: guided_radius is an integer in [1, {GUIDED_MAX_RADIUS}], got {guided_radius!r}")
+    p["guided_radius"] = _integer("dehaze_guided", "guided_radius", guided_radius, 1, GUIDED_MAX_RADIUS)
     ok = not isinstance(guided_eps, (bool, np.bool_, str, bytes)) and isinstance(guided_eps, (int, float, np.integer, np.floating))
     eps = float(np.float32(guided_eps)) if ok else 0.0
     if not (ok and float(np.float32(GUIDED_EPS_RANGE[0])) <= eps <= GUIDED_EPS_RANGE[1]):
         raise ValueError(f"dehaze_guided: guided_eps is a number in [1e-4, 1] (also as float32), got {guided_eps!r}")
-    p["guided_radius"], p["guided_eps"] = int(guided_radius), eps
+    p["guided_eps"] = eps                                              # the bound is float32(1e-4), the text 1e-4: not _number's
     return p
 
 
@@ -768,7 +782,8 @@ def dehaze_guided(image: torch.Tensor, stats: Optional[torch.Tensor] = None, gui
     dehaze(); `guided_stats` (new_guided_stats, the same slots) takes the counters of GUIDED_FIELDS.  guided_radius None:
     min(4 radius, 32).  There is no CPU path."""
     p = dehaze_guided_parameters(radius, omega, t_min, airlight_min, guided_radius, guided_eps)
-    image, b, h, w, m, s, stats, out, airlight = _dehaze_buffers("dehaze_guided", image, stats, cond, mean, std, out)
+    image, b, h, w, m, s, stats = _restore_frames("dehaze_guided", image, stats, cond, mean, std, DEHAZE_ROW, new_dehaze_stats)
+    out, airlight = _restore_outputs("dehaze_guided", image, out)
     if guided_stats is None:
         guided_stats = new_guided_stats(image.device, stats.shape[0])
     if guided_stats.dim() != 2 or guided_stats.dtype != torch.int64 or tuple(guided_stats.shape) != (stats.shape[0], GUIDED_ROW):
@@ -783,14 +798,6 @@ def dehaze_guided(image: torch.Tensor, stats: Optional[torch.Tensor] = None, gui
     return (out, airlight, t) if transmission else (out, airlight)
 
 
-def guided_stats_to_numpy(stats) -> dict:
-    """int64 [..., GUIDED_ROW] -> {field: int64 [...]} for GUIDED_FIELDS."""
-    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
-    if raw.shape[-1] != GUIDED_ROW:
-        raise ValueError(f"guided rows hold {GUIDED_ROW} counters, got {raw.shape[-1]}")
-    return {f: raw[..., i] for i, f in enumerate(GUIDED_FIELDS)}
-
-
 # ------------------------------------------------ night relighting: CLAHE + grey world (include/awseg_restore.h, DESIGN 10o)
 RELIGHT_FIELDS = ("frames", "sum_gain_0", "sum_gain_1", "sum_gain_2", "pixels", "sum_luma", "sum_luma_restored", "nonfinite_values",
                   "capped_pixels", "saturated_values")
@@ -800,13 +807,7 @@ RELIGHT_FRAME_RECORD = 48              # AWSEG_RELIGHT_FRAME_RECORD: workspace b
 RELIGHT_TILE_BYTES = 1536              # AWSEG_RELIGHT_TILE_BYTES: 256 uint32 histogram words and 256 uint16 table entries per tile
 RELIGHT_RANGE = (1.0, 64.0)            # clip_limit and max_gain
 RELIGHT_UNIT = 2.0 ** -16              # the gain and luma sums are int64 in fixed point: exact, order-independent
-
-
-def new_relight_stats(device, n_slots: int = 1) -> torch.Tensor:
-    """int64 [n_slots, RELIGHT_ROW]: per slot the row RELIGHT_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
-    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
-        raise ValueError(f"new_relight_stats: n_slots is an integer >= 1, got {n_slots!r}")
-    return torch.zeros(int(n_slots), RELIGHT_ROW, dtype=torch.int64, device=device)
+new_relight_stats, relight_stats_to_numpy = _stats_rows("relight", RELIGHT_FIELDS, "the gain and luma sums are in units of RELIGHT_UNIT")
 
 
 def relight_parameters(grid=(8, 8), clip_limit=2.0, max_gain=8.0, white_balance=True) -> dict:
@@ -818,12 +819,6 @@ def relight_parameters(grid=(8, 8), clip_limit=2.0, max_gain=8.0, white_balance=
             raise ValueError(f"relight: grid is an integer or a pair of integers in [1, {RELIGHT_MAX_TILES}], got {grid!r}")
         return int(v)
 
-    def bounded(name, v):
-        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
-        f = float(np.float32(v)) if ok else 0.0
-        if not (ok and RELIGHT_RANGE[0] <= f <= RELIGHT_RANGE[1]):
-            raise ValueError(f"relight: {name} is a number in [1, 64] (also as float32), got {v!r}")
-        return f
     if isinstance(grid, (list, tuple)):
         if len(grid) != 2:
             raise ValueError(f"relight: grid is an integer or a pair of integers in [1, {RELIGHT_MAX_TILES}], got {grid!r}")
@@ -832,8 +827,8 @@ def relight_parameters(grid=(8, 8), clip_limit=2.0, max_gain=8.0, white_balance=
         tiles = (tile_count(grid),) * 2
     if not isinstance(white_balance, (bool, np.bool_)) and not (isinstance(white_balance, (int, np.integer)) and white_balance in (0, 1)):
         raise ValueError(f"relight: white_balance is a bool, got {white_balance!r}")
-    return {"grid": tiles, "clip_limit": bounded("clip_limit", clip_limit), "max_gain": bounded("max_gain", max_gain),
-            "white_balance": bool(white_balance)}
+    return {"grid": tiles, "clip_limit": _number("relight", "clip_limit", clip_limit, *RELIGHT_RANGE),
+            "max_gain": _number("relight", "max_gain", max_gain, *RELIGHT_RANGE), "white_balance": bool(white_balance)}
 
 
 def relight_workspace_bytes(b: int, tiles_y: int, tiles_x: int) -> int:
@@ -853,7 +848,8 @@ def relight(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Opt
     the restored frames go (contiguous, not `image`).  The grid may not have more tiles than the frame has rows or columns.  There
     is no CPU path."""
     p = relight_parameters(grid, clip_limit, max_gain, white_balance)
-    image, b, h, w, m, s, stats, out, gains = _dehaze_buffers("relight", image, stats, cond, mean, std, out, RELIGHT_ROW, new_relight_stats)
+    image, b, h, w, m, s, stats = _restore_frames("relight", image, stats, cond, mean, std, RELIGHT_ROW, new_relight_stats)
+    out, gains = _restore_outputs("relight", image, out)
     ty, tx = p["grid"]
     if ty > h or tx > w:
         raise ValueError(f"relight: a grid of {ty} x {tx} tiles does not fit frames of {h} x {w} pixels (a tile is never empty)")
@@ -865,14 +861,6 @@ def relight(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: Opt
     return out, gains
 
 
-def relight_stats_to_numpy(stats) -> dict:
-    """int64 [..., RELIGHT_ROW] -> {field: int64 [...]} for RELIGHT_FIELDS; the gain and luma sums stay in units of RELIGHT_UNIT."""
-    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
-    if raw.shape[-1] != RELIGHT_ROW:
-        raise ValueError(f"relight rows hold {RELIGHT_ROW} counters, got {raw.shape[-1]}")
-    return {f: raw[..., i] for i, f in enumerate(RELIGHT_FIELDS)}
-
-
 # ------------------------------------------------ rain and snow removal: top-hat mask + masked fill (include/awseg_restore.h, DESIGN 10p)
 DEOCCLUDE_FIELDS = ("frames", "pixels", "seed_pixels", "masked_pixels", "unfilled_pixels", "sum_change", "nonfinite_values")
 DEOCCLUDE_ROW = len(DEOCCLUDE_FIELDS)  # AWSEG_DEOCCLUDE_ROW
@@ -880,30 +868,16 @@ DEOCCLUDE_MAX_DILATE = 2               # AWSEG_DEOCCLUDE_MAX_DILATE
 DEOCCLUDE_UNIT = 2.0 ** -16            # the change sum is int64 in fixed point: exact, order-independent
 DEOCCLUDE_DEFAULTS = {"radius": 9, "threshold": 0.06, "bright_min": 0.5, "dilate": 1}    # the prototype's: a stated choice, not a tuned one
 
-
-def new_deocclude_stats(device, n_slots: int = 1) -> torch.Tensor:
-    """int64 [n_slots, DEOCCLUDE_ROW]: per slot the row DEOCCLUDE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
-    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
-        raise ValueError(f"new_deocclude_stats: n_slots is an integer >= 1, got {n_slots!r}")
-    return torch.zeros(int(n_slots), DEOCCLUDE_ROW, dtype=torch.int64, device=device)
+new_deocclude_stats, deocclude_stats_to_numpy = _stats_rows("deocclude", DEOCCLUDE_FIELDS, "the change sum is in units of DEOCCLUDE_UNIT")
 
 
 def deocclude_parameters(radius=9, threshold=0.06, bright_min=0.5, dilate=1) -> dict:
     """The checked parameters of deocclude(): radius an integer in [1, 15]; threshold a number in (0, 1], bright_min one in [0, 1]
     (also as float32); dilate an integer in [0, 2].  ValueError otherwise."""
-    def integer(name, v, lo, hi):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-            raise ValueError(f"deocclude: {name} is an integer in [{lo}, {hi}], got {v!r}")
-        return int(v)
-
-    def unit(name, v, open_below):
-        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
-        f = float(np.float32(v)) if ok else -1.0
-        if not (ok and (0.0 < f if open_below else 0.0 <= f) and f <= 1.0):
-            raise ValueError(f"deocclude: {name} is a number in {'(' if open_below else '['}0, 1] (also as float32), got {v!r}")
-        return f
-    return {"radius": integer("radius", radius, 1, DEHAZE_MAX_RADIUS), "threshold": unit("threshold", threshold, True),
-            "bright_min": unit("bright_min", bright_min, False), "dilate": integer("dilate", dilate, 0, DEOCCLUDE_MAX_DILATE)}
+    return {"radius": _integer("deocclude", "radius", radius, 1, DEHAZE_MAX_RADIUS),
+            "threshold": _number("deocclude", "threshold", threshold, 0.0, 1.0, open_below=True),
+            "bright_min": _number("deocclude", "bright_min", bright_min, 0.0, 1.0),
+            "dilate": _integer("deocclude", "dilate", dilate, 0, DEOCCLUDE_MAX_DILATE)}
 
 
 def deocclude_workspace_bytes(b: int, h: int, w: int) -> int:
@@ -922,7 +896,8 @@ def deocclude(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: O
     go to a tensor nobody reads.  `mean`, `std`: the loader's normalisation (default: ImageNet's).  `out`, `mask`: where the
     restored frames and the mask go (contiguous; `out` not `image`).  There is no CPU path."""
     p = deocclude_parameters(radius, threshold, bright_min, dilate)
-    image, b, h, w, m, s, stats, out, _ = _dehaze_buffers("deocclude", image, stats, cond, mean, std, out, DEOCCLUDE_ROW, new_deocclude_stats)
+    image, b, h, w, m, s, stats = _restore_frames("deocclude", image, stats, cond, mean, std, DEOCCLUDE_ROW, new_deocclude_stats)
+    out, _ = _restore_outputs("deocclude", image, out)
     if mask is None:
         mask = torch.empty(b, h, w, dtype=torch.uint8, device=image.device)
     if mask.dtype != torch.uint8 or tuple(mask.shape) != (b, h, w) or not mask.is_contiguous() or mask.device != image.device:
@@ -934,14 +909,6 @@ def deocclude(image: torch.Tensor, stats: Optional[torch.Tensor] = None, cond: O
     N.call("awseg_deocclude", N.ptr(image), b, 3, h, w, N.host(m), N.host(s), p["radius"], p["threshold"], p["bright_min"], p["dilate"],
            N.ptr(cond), N.ptr(out), N.ptr(mask), N.ptr(stats), stats.shape[0], N.ptr(ws), N.stream())
     return out, mask
-
-
-def deocclude_stats_to_numpy(stats) -> dict:
-    """int64 [..., DEOCCLUDE_ROW] -> {field: int64 [...]} for DEOCCLUDE_FIELDS; the change sum stays in units of DEOCCLUDE_UNIT."""
-    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
-    if raw.shape[-1] != DEOCCLUDE_ROW:
-        raise ValueError(f"deocclude rows hold {DEOCCLUDE_ROW} counters, got {raw.shape[-1]}")
-    return {f: raw[..., i] for i, f in enumerate(DEOCCLUDE_FIELDS)}
 
 
 # ------------------------------------------------ weather estimate: which front-end a frame needs (include/awseg_restore.h, DESIGN 10q)
@@ -959,13 +926,7 @@ ESTIMATE_EXPECTED_ROUTE = {"clean": "none", "fog": "dark_channel", "night": "cla
 # depends on the resolution (the renderer's drop count does not grow with the frame)
 ESTIMATE_DEFAULTS = {"radius": 7, "threshold": 0.06, "bright_min": 0.5, "cast_max": 0.65, "luma_max": 0.5, "dark_min": 0.47,
                      "seed_min": 0.001}
-
-
-def new_estimate_stats(device, n_slots: int = 1) -> torch.Tensor:
-    """int64 [n_slots, ESTIMATE_ROW]: per slot the row ESTIMATE_FIELDS of include/awseg_restore.h (zeroed: the launches accumulate)."""
-    if isinstance(n_slots, (bool, np.bool_)) or not isinstance(n_slots, (int, np.integer)) or n_slots < 1:
-        raise ValueError(f"new_estimate_stats: n_slots is an integer >= 1, got {n_slots!r}")
-    return torch.zeros(int(n_slots), ESTIMATE_ROW, dtype=torch.int64, device=device)
+new_estimate_stats, estimate_stats_to_numpy = _stats_rows("estimate", ESTIMATE_FIELDS, "the five sums are in units of ESTIMATE_UNIT")
 
 
 def weather_estimate_parameters(radius=7, threshold=0.06, bright_min=0.5, cast_max=0.65, luma_max=0.5, dark_min=0.47,
@@ -973,17 +934,9 @@ def weather_estimate_parameters(radius=7, threshold=0.06, bright_min=0.5, cast_m
     """The checked parameters of weather_estimate(): radius an integer in [1, 15]; threshold a number in (0, 1], bright_min one in
     [0, 1], cast_max in (0, 4], luma_max in (0, 1], dark_min and seed_min in [0, 1) (all also as float32; NaN is refused).
     ValueError otherwise."""
-    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= DEHAZE_MAX_RADIUS:
-        raise ValueError(f"weather_estimate: radius is an integer in [1, {DEHAZE_MAX_RADIUS}], got {radius!r}")
-
-    def number(name, v, lo, hi, open_below=False, open_above=False):
-        ok = not isinstance(v, (bool, np.bool_, str, bytes)) and isinstance(v, (int, float, np.integer, np.floating))
-        f = float(np.float32(v)) if ok else float("nan")
-        if not (ok and (lo < f if open_below else lo <= f) and (f < hi if open_above else f <= hi)):
-            raise ValueError(f"weather_estimate: {name} is a number in {'(' if open_below else '['}{lo:g}, {hi:g}"
-                             f"{')' if open_above else ']'} (also as float32), got {v!r}")
-        return f
-    return {"radius": int(radius), "threshold": number("threshold", threshold, 0.0, 1.0, open_below=True),
+    number = lambda *a, **k: _number("weather_estimate", *a, **k)      # noqa: E731
+    return {"radius": _integer("weather_estimate", "radius", radius, 1, DEHAZE_MAX_RADIUS),
+            "threshold": number("threshold", threshold, 0.0, 1.0, open_below=True),
             "bright_min": number("bright_min", bright_min, 0.0, 1.0), "cast_max": number("cast_max", cast_max, 0.0, 4.0, open_below=True),
             "luma_max": number("luma_max", luma_max, 0.0, 1.0, open_below=True),
             "dark_min": number("dark_min", dark_min, 0.0, 1.0, open_above=True),
@@ -1008,26 +961,9 @@ def weather_estimate(image: torch.Tensor, stats: Optional[torch.Tensor] = None, 
     `mean`, `std`: the loader's normalisation (default: ImageNet's).  `route`, `descriptors`: where the results go (contiguous, on
     the frames' device).  The frames are read only.  There is no CPU path."""
     p = weather_estimate_parameters(radius, threshold, bright_min, cast_max, luma_max, dark_min, seed_min)
-    if image.dim() != 4 or image.dtype != torch.float32 or image.shape[1] != 3:
-        raise ValueError(f"weather_estimate: image is float32 [B, 3, H, W], got {image.dtype} {tuple(image.shape)}")
-    b, _, h, w = (int(d) for d in image.shape)
-    if h < 1 or w < 1:
-        raise ValueError(f"weather_estimate: frames of at least one pixel, got {tuple(image.shape)}")
-    if b > 65535 or h * w >= 2 ** 31:
-        raise ValueError(f"weather_estimate: at most 65535 frames of fewer than 2^31 pixels per launch, got {tuple(image.shape)}")
-    if (mean is None) != (std is None):
-        raise ValueError("weather_estimate: mean and std come together")
-    m, s = _mean_std(mean, std)
-    m, s = m.reshape(-1), s.reshape(-1)
-    if m.size != 3 or s.size != 3 or not np.isfinite(m).all() or not np.isfinite(s).all() or (s <= 0).any():
-        raise ValueError(f"weather_estimate: mean holds 3 finite numbers and std 3 finite numbers > 0, got {mean!r}, {std!r}")
-    if stats is None:
-        stats = new_estimate_stats(image.device, 1)
-    if stats.dim() != 2 or stats.dtype != torch.int64 or stats.shape[0] < 1 or stats.shape[1] != ESTIMATE_ROW or not stats.is_contiguous():
+    image, b, h, w, m, s, stats = _restore_frames("weather_estimate", image, stats, cond, mean, std, ESTIMATE_ROW, new_estimate_stats)
+    if not stats.is_contiguous():                                      # the one entry point that refuses it
         raise ValueError(f"stats must be int64 [slots, {ESTIMATE_ROW}] (new_estimate_stats), got {stats.dtype} {tuple(stats.shape)}")
-    if cond is not None and (cond.dtype != torch.int32 or cond.numel() != b):
-        raise ValueError("cond must be int32 [B]")
-    image = image.contiguous()
     if route is None:
         route = torch.empty(b, dtype=torch.int32, device=image.device)
     if route.dtype != torch.int32 or tuple(route.shape) != (b,) or not route.is_contiguous() or route.device != image.device:
@@ -1046,14 +982,6 @@ def weather_estimate(image: torch.Tensor, stats: Optional[torch.Tensor] = None, 
            p["cast_max"], p["luma_max"], p["dark_min"], p["seed_min"], N.ptr(cond), N.ptr(route), N.ptr(descriptors), N.ptr(stats),
            stats.shape[0], N.ptr(ws), N.stream())
     return route, descriptors
-
-
-def estimate_stats_to_numpy(stats) -> dict:
-    """int64 [..., ESTIMATE_ROW] -> {field: int64 [...]} for ESTIMATE_FIELDS; the five sums stay in units of ESTIMATE_UNIT."""
-    raw = stats.cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats, dtype=np.int64)
-    if raw.shape[-1] != ESTIMATE_ROW:
-        raise ValueError(f"estimate rows hold {ESTIMATE_ROW} counters, got {raw.shape[-1]}")
-    return {f: raw[..., i] for i, f in enumerate(ESTIMATE_FIELDS)}
 
 
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent

@@ -218,69 +218,50 @@ def parse_restoration_grid(text: str):
     return values[0] if len(values) == 1 else values
 
 
+# --restoration-<flag> -> (the --restoration values it needs, its key under evaluation.restoration, what reads its text), in the order
+# the messages name them.  The guided filter's flags pass without --restoration: what they need first is --restoration-refine guided
+RESTORATION_FLAGS = {
+    "route": (("auto",), "route", None), "seed_min": (("auto",), "estimator.seed_min", None),
+    "dark_min": (("auto",), "estimator.dark_min", None), "cast_max": (("auto",), "estimator.cast_max", None),
+    "refine": (("dark_channel",), "refine", None),
+    "guided_radius": (("dark_channel", None), "guided_radius", None), "guided_eps": (("dark_channel", None), "guided_eps", None),
+    "grid": (("clahe",), "grid", parse_restoration_grid), "clip_limit": (("clahe",), "clip_limit", None),
+    "max_gain": (("clahe",), "max_gain", None), "white_balance": (("clahe",), "white_balance", None),
+    "radius": (("tophat", "dark_channel"), "radius", None),
+    "threshold": (("tophat",), "threshold", None), "bright_min": (("tophat",), "bright_min", None), "dilate": (("tophat",), "dilate", None),
+}
+
+
 def apply_restoration_options(args, config) -> None:
-    """--restoration / --restoration-conditions / --restoration-refine / --restoration-guided-* and the flags of --restoration clahe
-    and --restoration tophat, and --restoration auto with its route and estimator flags, into the configuration (the harness
-    checks them)."""
-    estimator = {k: v for k, v in (("seed_min", args.restoration_seed_min), ("dark_min", args.restoration_dark_min),
-                                   ("cast_max", args.restoration_cast_max)) if v is not None}
-    if (estimator or args.restoration_route is not None) and args.restoration != "auto":
-        raise ValueError("--restoration-route, --restoration-seed-min, --restoration-dark-min and --restoration-cast-max need "
-                         "--restoration auto")
-    if args.restoration == "auto":
-        others = ("refine", "guided_radius", "guided_eps", "grid", "clip_limit", "max_gain", "white_balance", "radius", "threshold",
-                  "bright_min", "dilate")
-        given = [f"--restoration-{o.replace('_', '-')}" for o in others if getattr(args, f"restoration_{o}") is not None]
-        if given:
-            raise ValueError(f"{', '.join(given)}: under --restoration auto the methods' parameters are configuration only "
-                             "(evaluation.restoration.dark_channel / .clahe / .tophat)")
-        spec = {"method": "auto", **({} if args.restoration_route is None else {"route": args.restoration_route}),
-                **({"estimator": estimator} if estimator else {})}
-        config.set("evaluation.restoration", spec if len(spec) > 1 else "auto")
-        if args.restoration_conditions is not None:
-            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
-        return
-    tophat = {k: v for k, v in (("threshold", args.restoration_threshold), ("bright_min", args.restoration_bright_min),
-                                ("dilate", args.restoration_dilate)) if v is not None}
-    if tophat and args.restoration != "tophat":
-        raise ValueError("--restoration-threshold, --restoration-bright-min and --restoration-dilate need --restoration tophat")
-    if args.restoration_radius is not None and args.restoration not in ("tophat", "dark_channel"):
-        raise ValueError("--restoration-radius needs --restoration tophat or --restoration dark_channel")
-    if args.restoration == "tophat":
-        if args.restoration_refine is not None or args.restoration_guided_radius is not None or args.restoration_guided_eps is not None:
-            raise ValueError("--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to tophat")
-        if args.restoration_radius is not None:
-            tophat["radius"] = args.restoration_radius
-    relight = {k: v for k, v in (("grid", args.restoration_grid), ("clip_limit", args.restoration_clip_limit),
-                                 ("max_gain", args.restoration_max_gain), ("white_balance", args.restoration_white_balance))
-               if v is not None}
-    if relight and args.restoration != "clahe":
-        raise ValueError("--restoration-grid, --restoration-clip-limit, --restoration-max-gain and --restoration-white-balance need "
-                         "--restoration clahe")
-    if args.restoration == "tophat":
-        config.set("evaluation.restoration", {"method": "tophat", **tophat} if tophat else "tophat")
-        if args.restoration_conditions is not None:
-            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
-        return
-    if args.restoration == "clahe":
-        if args.restoration_refine is not None or args.restoration_guided_radius is not None or args.restoration_guided_eps is not None:
-            raise ValueError("--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to clahe")
-        if "grid" in relight:
-            relight["grid"] = parse_restoration_grid(relight["grid"])
-        config.set("evaluation.restoration", {"method": "clahe", **relight} if relight else "clahe")
-        if args.restoration_conditions is not None:
-            config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
-        return
-    if args.restoration_refine is not None and args.restoration is None:
-        raise ValueError("--restoration-refine needs --restoration dark_channel")
-    guided = {k: v for k, v in (("guided_radius", args.restoration_guided_radius), ("guided_eps", args.restoration_guided_eps))
-              if v is not None}
-    if guided and args.restoration_refine != "guided":
+    """--restoration / --restoration-conditions and the flags of RESTORATION_FLAGS into the configuration (the harness checks them)."""
+    method, option = args.restoration, lambda flag: f"--restoration-{flag.replace('_', '-')}"      # noqa: E731
+    given = {f: getattr(args, f"restoration_{f}") for f in RESTORATION_FLAGS if getattr(args, f"restoration_{f}") is not None}
+    for flag in given:
+        owners = RESTORATION_FLAGS[flag][0]
+        if method in owners:
+            continue
+        if method == "auto":
+            raise ValueError(f"{', '.join(option(f) for f in given if 'auto' not in RESTORATION_FLAGS[f][0])}: under --restoration auto "
+                             "the methods' parameters are configuration only (evaluation.restoration.dark_channel / .clahe / .tophat)")
+        if owners[0] == "dark_channel" and method is not None:
+            raise ValueError(f"--restoration-refine and --restoration-guided-* belong to --restoration dark_channel, not to {method}")
+        names = [option(f) for f, (o, _, _) in RESTORATION_FLAGS.items() if o == owners]
+        raise ValueError(f"{', '.join(names[:-1])}{' and ' if names[1:] else ''}{names[-1]} need{'' if names[1:] else 's'} "
+                         f"{' or '.join('--restoration ' + o for o in owners)}")
+    if given.keys() & {"guided_radius", "guided_eps"} and args.restoration_refine != "guided":
         raise ValueError("--restoration-guided-radius and --restoration-guided-eps need --restoration-refine guided")
-    if args.restoration is not None:
-        spec = {**({} if args.restoration_refine is None else {"refine": args.restoration_refine}), **guided,
-                **({} if args.restoration_radius is None else {"radius": args.restoration_radius})}
-        config.set("evaluation.restoration", spec if spec else args.restoration)
+    if method is not None:
+        spec = {}
+        for flag, value in given.items():
+            _, key, read = RESTORATION_FLAGS[flag]
+            *outer, key = key.split(".")
+            level = spec
+            for name in outer:
+                level = level.setdefault(name, {})
+            level[key] = value if read is None else read(value)
+        if method != "dark_channel":                                   # the dark channel's dict carries no 'method' key
+            spec = {"method": method, **spec}
+        config.set("evaluation.restoration", spec if set(spec) - {"method"} else method)
     if args.restoration_conditions is not None:
         config.set("evaluation.restoration_conditions", [c.strip() for c in args.restoration_conditions.split(",") if c.strip()])
 

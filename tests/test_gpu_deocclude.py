@@ -83,6 +83,51 @@ def test_both_paths_give_the_same_bits(P):
     assert torch.equal(o, a) and torch.equal(om, am) and int(buf[0]) == 0 and int(buf[1 + am.numel():].sum()) == 0
 
 
+_SEAM = {}                                                             # (h, w) -> frames, made once; nothing writes them
+
+
+def seam_frames(h: int, w: int) -> np.ndarray:
+    if (h, w) not in _SEAM:
+        _SEAM[h, w] = D.occluder_batch((2, 3, h, w), 21 + h)
+    return _SEAM[h, w]
+
+
+# The window minimum that awseg_dehaze (256 threads, +inf kept outside the frame), awseg_deocclude and awseg_weather_estimate (512
+# threads, -inf outside) share, where a wrong thread count or flag would show: two tiles down and two across with a ragged last tile,
+# on the 16-byte path (33 x 68) and the scalar path (37 x 70), at the fewest taps (r = 1) and the most (r = 15), two frames into slots
+# 1 and 3.  Not repeated here: deocclude at 37 x 70, r = 15, d = 2, which CASES holds (three frames); the dehazer's own lists hold
+# r = 1 and r = 15 at 31 x 53 and 43 x 140, the estimate's r = 15 at 5 x 9 and 40 x 72.
+SEAM_CASES = [(who, shape, r) for who, shapes, radii in (("dehaze", ((33, 68), (37, 70)), (1, 15)), ("deocclude", ((33, 68),), (1, 15)),
+                                                           ("deocclude", ((37, 70),), (1,)), ("weather_estimate", ((33, 68), (37, 70)), (15,)))
+              for shape in shapes for r in radii]
+
+
+@pytest.mark.parametrize("who,shape,radius", SEAM_CASES, ids=[f"{w} {s[0]} x {s[1]} r={r}" for w, s, r in SEAM_CASES])
+def test_shared_window_minimum_at_ragged_tiles_and_extreme_radii(P, who, shape, radius):
+    from tests import estimate_ref as E
+    from tests import restore_ref as R
+    x, cond = seam_frames(*shape), np.array([0, 2], np.int32)
+    d_x, d_cond = on_device(x), torch.from_numpy(cond).cuda()
+    if who == "dehaze":
+        want = R.dehaze(x, cond=cond, n_slots=4, radius=radius, refine=1)
+        stats = P.ops.new_dehaze_stats("cuda", 4)
+        got = P.ops.dehaze(d_x, stats, d_cond, radius=radius, refine=1)
+    elif who == "deocclude":
+        want = D.deocclude(x, cond=cond, n_slots=4, radius=radius, dilate=2)
+        stats = P.ops.new_deocclude_stats("cuda", 4)
+        got = P.ops.deocclude(d_x, stats, d_cond, radius=radius, dilate=2)
+    else:
+        want = E.estimate(x, cond=cond, n_slots=4, radius=radius)
+        stats = P.ops.new_estimate_stats("cuda", 4)
+        got = P.ops.weather_estimate(d_x, stats, d_cond, radius=radius)
+    torch.cuda.synchronize()
+    print(who, shape, radius, "model", want[-1][0].tolist(), "device", stats[0].cpu().tolist())
+    assert stats.cpu().numpy().tolist() == want[-1].tolist()
+    assert want[-1][1].any() and want[-1][3].any() and not want[-1][2].any()      # slots 1 and 3, and nothing between them
+    for g, w in zip(got, want):
+        assert not differing(g, w), f"output {tuple(w.shape)}: " + differing(g, w)
+
+
 def test_other_parameters_and_normalisations_reach_the_kernel(P):
     x = D.occluder_batch((2, 3, 33, 65), 11)
     mean, std = np.array([0.4, 0.5, 0.45], np.float32), np.array([0.25, 0.2, 0.3], np.float32)
