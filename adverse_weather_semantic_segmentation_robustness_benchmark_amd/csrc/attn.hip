@@ -21,11 +21,9 @@
 // forms bring nothing measurable, so the loop stays scalar.)
 // Block = 128 queries of one (image, head): 4 waves x 32 queries, all waves sharing the K / V^T tiles (32 keys,
 // double-buffered in LDS, register-prefetched one tile ahead).
-#include "awseg_common.h"
+#include "awseg_split.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int AT = 256;          // threads
 #ifndef AWSEG_ATTN_SPLIT_WAVES
@@ -201,52 +199,12 @@ void attention_d32_kernel(const float* __restrict__ q, const float* __restrict__
 // that is guaranteed above 2^-13 (2^-(17 - kTau)) and typically holds above 2^-17.  Below, the absolute floor 2^-25 operand
 // units (f16 subnormals are kept) is worth < 2^-35 of the row maximum instead of < 2^-40: 2 048 such keys together stay
 // below float32 rounding of the row sum.
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int SROW = 72;         // halfs per LDS row: 32 hi | 32 lo | 8 pad  (144 B: conflict-free ds_read_b128)
-constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;
 
-// (a, b) -> packed f16 high parts and packed scaled residuals.  Round-toward-zero is fine: the residual is exact.
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo)
-{
-    const auto hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const h2 hh = __builtin_bit_cast(h2, hp);
-    const float ra = (a - (float)hh.x) * kLoScale, rb = (b - (float)hh.y) * kLoScale;
-    hi = __builtin_bit_cast(unsigned, hp);
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-// the same without scaling the residual: for values whose low part is a normal (or harmlessly subnormal) f16 as is
-// Three instructions (wino_split.hip): v_cvt_pkrtz_f16_f32, then one mixed-precision FMA per value — x * 1.0 + (-hi) with the f16
-// source widened and the sum taken in float32 (exact), rounded to f16 into one half of the destination.  (The plain form is six:
-// two v_cvt_f32_f16, two subtracts, a second pack; the loop is bound by its vector instruction count: -1.6 % on stage 1.)
-// Only the probabilities use it.  Q, K and V keep the x 2048 low parts: unscaled ones are subnormal below |x| = 2^-3, an ABSOLUTE
-// 2^-25 that the tests with a small q against one large k (flat softmax) and with whole tensors at 1e-5 (tiny operands: 5e-6
-// RELATIVE) do not allow — both were tried.
-__device__ __forceinline__ void split_pair_unscaled(float a, float b, unsigned& hi, unsigned& lo)
-{
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"          // the low parts go straight into an MFMA operand register: two wait states hipcc does not pad behind inline asm
-        : "=&v"(lo) : "v"(a), "v"(b), "v"(hi));
-}
-__device__ __forceinline__ void split8_unscaled(const float* x, h8& hi, h8& lo)
-{
-    u32x4 H, L;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { unsigned h, l; split_pair_unscaled(x[2 * i], x[2 * i + 1], h, l); H[i] = h; L[i] = l; }
-    hi = __builtin_bit_cast(h8, H); lo = __builtin_bit_cast(h8, L);
-}
-__device__ __forceinline__ void split8(const float* x, h8& hi, h8& lo)
-{
-    u32x4 H, L;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { unsigned h, l; split_pair(x[2 * i], x[2 * i + 1], h, l); H[i] = h; L[i] = l; }
-    hi = __builtin_bit_cast(h8, H); lo = __builtin_bit_cast(h8, L);
-}
+// The splits are in awseg_split.h.  Q, K and V take split_scaled_rtz (the x 2048 low parts): unscaled ones are subnormal below
+// |x| = 2^-3, an ABSOLUTE 2^-25 that the tests with a small q against one large k (flat softmax) and with whole tensors at 1e-5
+// (tiny operands: 5e-6 RELATIVE) do not allow — both were tried.  Only the probabilities take split_unscaled_mfma (three
+// instructions a pair instead of six; the loop is bound by its vector instruction count: -1.6 % on stage 1).
 // ---- the stale-maximum softmax step shared by both split kernels (see the header): identical arithmetic, identical bits
 constexpr float kTau = 4.0f;                 // headroom of the stale maximum, log2 units
 constexpr float kPre = 15.0f - kTau;         // probability pre-scale exponent of the stale-maximum loop
@@ -320,13 +278,6 @@ __device__ __forceinline__ float amax4(float m, const float4& t)
     return __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fabsf(t.z)), __builtin_fabsf(t.w));
 }
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, bf2));
-}
 __device__ __forceinline__ h8 pack8_bf16(const float* x)
 {
     u32x4 H;
@@ -370,7 +321,7 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
 #pragma unroll
                 for (int i = 0; i < 8; ++i) qmax = __builtin_fmaxf(qmax, __builtin_fabsf(x[i]));
             }
-            split8(x, qh[s], ql[s]);
+            split8_scaled_rtz(x, qh[s], ql[s]);
         }
     }
     // tile staging role of this thread: key = tid / 8, 4 consecutive d = 4c .. 4c+3
@@ -396,13 +347,13 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
             kmax = amax4(kmax, kk4); vmax = amax4(vmax, vv4);
         }
         u32x2 H, L; unsigned hh, ll;
-        split_pair(kk4.x, kk4.y, hh, ll); H[0] = hh; L[0] = ll;
-        split_pair(kk4.z, kk4.w, hh, ll); H[1] = hh; L[1] = ll;
+        split_scaled_rtz(kk4.x, kk4.y, hh, ll); H[0] = hh; L[0] = ll;
+        split_scaled_rtz(kk4.z, kk4.w, hh, ll); H[1] = hh; L[1] = ll;
         *reinterpret_cast<u32x2*>(&sK[buf][wk0]) = H;
         *reinterpret_cast<u32x2*>(&sK[buf][wk0 + 32]) = L;
         unsigned vh01, vl01, vh23, vl23;
-        split_pair(vv4.x, vv4.y, vh01, vl01);
-        split_pair(vv4.z, vv4.w, vh23, vl23);
+        split_scaled_rtz(vv4.x, vv4.y, vh01, vl01);
+        split_scaled_rtz(vv4.z, vv4.w, vh23, vl23);
         unsigned short* sv = reinterpret_cast<unsigned short*>(&sV[buf][wv0]);
         sv[0] = (unsigned short)vh01;            sv[32] = (unsigned short)vl01;
         sv[SROW] = (unsigned short)(vh01 >> 16); sv[SROW + 32] = (unsigned short)(vl01 >> 16);
@@ -495,8 +446,8 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
             continue;
         }
         h8 ph0, pl0, ph1, pl1;
-        split8_unscaled(p, ph0, pl0);
-        split8_unscaled(p + 8, ph1, pl1);
+        split8_unscaled_mfma(p, ph0, pl0);
+        split8_unscaled_mfma(p + 8, ph1, pl1);
         om = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh0, ph0, om, 0, 0, 0);
         oc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl0, ph0, oc, 0, 0, 0);
         om = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh1, ph1, om, 0, 0, 0);
@@ -539,14 +490,6 @@ __device__ __forceinline__ bool attn_split_pass(const float* __restrict__ q, con
     return false;
 }
 
-// exponent e >= 0 with max * 2^-e in [2^13, 2^14) when the maximum (float bits) left the split range, else 0
-__device__ __forceinline__ int guard_exponent(unsigned maxbits)
-{
-    const int ex = (int)(maxbits >> 23) & 0xff;
-    if (maxbits == 0u || ex == 0xff) return 0;               // in range, or Inf / NaN (nothing to rescue: they propagate)
-    return ex - 127 - 13;
-}
-
 __global__ __launch_bounds__(AT, AWSEG_ATTN_SPLIT_WAVES)
 void attention_d32_split_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
                                 float* __restrict__ out, int nq, int nkv, int heads, float scale_log2e, int kvp)
@@ -561,9 +504,8 @@ void attention_d32_split_kernel(const float* __restrict__ q, const float* __rest
         attn_split_pass<false>(q, k, v, out, nq, nkv, heads, scale_log2e, kvp, sK, sV, sMax, one);
         return;
     }
-    const int eq = guard_exponent(sMax[0]), ek = guard_exponent(sMax[1]), ev = guard_exponent(sMax[2]);
-    auto p2 = [](int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); };            // |e| <= 114
-    const attn_scales sc = {p2(-eq), p2(-ek), p2(-ev), p2(eq), p2(ek), p2(ev)};
+    const int eq = norm_exponent_reported_max(sMax[0]), ek = norm_exponent_reported_max(sMax[1]), ev = norm_exponent_reported_max(sMax[2]);
+    const attn_scales sc = {pow2f(-eq), pow2f(-ek), pow2f(-ev), pow2f(eq), pow2f(ek), pow2f(ev)};       // |e| <= 114
     attn_split_pass<true>(q, k, v, out, nq, nkv, heads, scale_log2e, kvp, sK, sV, sMax, sc);
 }
 
@@ -579,12 +521,6 @@ void attention_d32_split_kernel(const float* __restrict__ q, const float* __rest
 // from the maxima when they reach 2^15, exponents left in a table); the query blocks keep the optimistic pass / scaled second pass
 // for q alone.  Same arithmetic per element as attention_d32_split_kernel: same values.
 constexpr int IMG_TILE_HALFS = (TK + D) * SROW;                    // 4 608 halfs
-
-__device__ __forceinline__ uint32_t at_lds_addr(const void* p) { return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p; }
-__device__ __forceinline__ void at_dma16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds_base)
-{
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base) : "m0", "memory");
-}
 
 __global__ __launch_bounds__(AT)
 void attn_kv_image_kernel(const float* __restrict__ k, const float* __restrict__ v, int kvp, int nkv, int heads,
@@ -609,9 +545,8 @@ void attn_kv_image_kernel(const float* __restrict__ k, const float* __restrict__
     if (kmax >= kSplitLimit) atomicMax(&sM[0], __builtin_bit_cast(unsigned, kmax));
     if (vmax >= kSplitLimit) atomicMax(&sM[1], __builtin_bit_cast(unsigned, vmax));
     __syncthreads();
-    const int ek = guard_exponent(sM[0]), ev = guard_exponent(sM[1]);
-    auto p2 = [](int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); };
-    const float sk = p2(-ek), sv = p2(-ev);
+    const int ek = norm_exponent_reported_max(sM[0]), ev = norm_exponent_reported_max(sM[1]);
+    const float sk = pow2f(-ek), sv = pow2f(-ev);
     if (tid == 0) { exps[((size_t)b * heads + h) * 2] = ek; exps[((size_t)b * heads + h) * 2 + 1] = ev; }
     _Float16* base = img + ((size_t)b * heads + h) * ntiles * IMG_TILE_HALFS;
     for (int t = 0; t < ntiles; ++t) {
@@ -621,13 +556,13 @@ void attn_kv_image_kernel(const float* __restrict__ k, const float* __restrict__
         vv4.x *= sv; vv4.y *= sv; vv4.z *= sv; vv4.w *= sv;
         _Float16* T = base + (size_t)t * IMG_TILE_HALFS;
         u32x2 H, L; unsigned hh, ll;
-        split_pair(kk4.x, kk4.y, hh, ll); H[0] = hh; L[0] = ll;
-        split_pair(kk4.z, kk4.w, hh, ll); H[1] = hh; L[1] = ll;
+        split_scaled_rtz(kk4.x, kk4.y, hh, ll); H[0] = hh; L[0] = ll;
+        split_scaled_rtz(kk4.z, kk4.w, hh, ll); H[1] = hh; L[1] = ll;
         *reinterpret_cast<u32x2*>(&T[wk0]) = H;
         *reinterpret_cast<u32x2*>(&T[wk0 + 32]) = L;
         unsigned vh01, vl01, vh23, vl23;
-        split_pair(vv4.x, vv4.y, vh01, vl01);
-        split_pair(vv4.z, vv4.w, vh23, vl23);
+        split_scaled_rtz(vv4.x, vv4.y, vh01, vl01);
+        split_scaled_rtz(vv4.z, vv4.w, vh23, vl23);
         unsigned short* sv16 = reinterpret_cast<unsigned short*>(&T[wv0]);
         sv16[0] = (unsigned short)vh01;            sv16[32] = (unsigned short)vl01;
         sv16[SROW] = (unsigned short)(vh01 >> 16); sv16[SROW + 32] = (unsigned short)(vl01 >> 16);
@@ -663,19 +598,19 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
 #pragma unroll
                 for (int i = 0; i < 8; ++i) qmax = __builtin_fmaxf(qmax, __builtin_fabsf(x[i]));
             }
-            split8(x, qh[s], ql[s]);
+            split8_scaled_rtz(x, qh[s], ql[s]);
         }
     }
     const int ntiles = nkv / TK;
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)img_bh, 0, ntiles * IMG_TILE_HALFS * 2, 0x00020000);
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(at_lds_addr(&sKV[0][0]));
+    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(&sKV[0][0]));
     const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);
     // a tile = nine 1 KB LDS-DMA instructions: wave w issues chunks w and w + 4, wave 0 the ninth
     auto dma_tile = [&](int t, int buf) {
         const uint32_t so = (uint32_t)t * (uint32_t)(IMG_TILE_HALFS * 2), lb = lds0 + (uint32_t)buf * (uint32_t)(IMG_TILE_HALFS * 2);
-        at_dma16(rsrc, (uint32_t)(lane * 16) + wave_u * 1024u, so, lb + wave_u * 1024u);
-        at_dma16(rsrc, (uint32_t)(lane * 16) + (wave_u + 4u) * 1024u, so, lb + (wave_u + 4u) * 1024u);
-        if (wave_u == 0) at_dma16(rsrc, (uint32_t)(lane * 16) + 8192u, so, lb + 8192u);
+        lds_dma16(rsrc, (uint32_t)(lane * 16) + wave_u * 1024u, so, lb + wave_u * 1024u);
+        lds_dma16(rsrc, (uint32_t)(lane * 16) + (wave_u + 4u) * 1024u, so, lb + (wave_u + 4u) * 1024u);
+        if (wave_u == 0) lds_dma16(rsrc, (uint32_t)(lane * 16) + 8192u, so, lb + 8192u);
     };
     dma_tile(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -736,8 +671,8 @@ __device__ __forceinline__ bool attn_split_pass_img(const float* __restrict__ q,
             }
         }
         h8 ph0, pl0, ph1, pl1;
-        split8_unscaled(p, ph0, pl0);
-        split8_unscaled(p + 8, ph1, pl1);
+        split8_unscaled_mfma(p, ph0, pl0);
+        split8_unscaled_mfma(p + 8, ph1, pl1);
         om = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh0, ph0, om, 0, 0, 0);
         oc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl0, ph0, oc, 0, 0, 0);
         om = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh1, ph1, om, 0, 0, 0);
@@ -781,8 +716,7 @@ void attention_d32_split_img_kernel(const float* __restrict__ q, const _Float16*
     if (threadIdx.x < 2) sMax[threadIdx.x] = 0u;                     // ordered by the pass's first barrier
     const _Float16* img_bh = img + ((size_t)b * heads + h) * (size_t)(nkv / TK) * IMG_TILE_HALFS;
     const int ek = exps[((size_t)b * heads + h) * 2], ev = exps[((size_t)b * heads + h) * 2 + 1];
-    auto p2 = [](int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); };
-    attn_scales sc = {1.f, p2(-ek), p2(-ev), 1.f, p2(ek), p2(ev)};
+    attn_scales sc = {1.f, pow2f(-ek), pow2f(-ev), 1.f, pow2f(ek), pow2f(ev)};
     bool redo;
     if ((ek | ev) == 0) redo = attn_split_pass_img<false, true, true>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
     else redo = attn_split_pass_img<true, true, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
@@ -792,8 +726,8 @@ void attention_d32_split_img_kernel(const float* __restrict__ q, const _Float16*
         attn_split_pass_img<false, false, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
         return;
     }
-    const int eq = guard_exponent(sMax[0]);
-    sc.sq = p2(-eq); sc.bq = p2(eq);
+    const int eq = norm_exponent_reported_max(sMax[0]);
+    sc.sq = pow2f(-eq); sc.bq = pow2f(eq);
     attn_split_pass_img<true, false, false>(q, img_bh, out, nq, nkv, heads, scale_log2e, sKV, sMax, sc);
 }
 

@@ -87,6 +87,44 @@ __device__ __forceinline__ void awseg_amax_step(float v, int c, float& best, int
     if (!(v <= best) && !(best != best)) { best = v; bi = c; }
 }
 
+// erf to 1.5e-7 absolute (Abramowitz & Stegun 7.1.26: 1 - (a1 t + ... + a5 t^5) exp(-x^2), t = 1 / (1 + p |x|)) with the hardware
+// reciprocal and exp2: 14 vector instructions, two of them transcendental.  The library erff is ~40 (two range branches, both
+// evaluated and selected): the depthwise 3x3 + GELU kernel of backbone.hip spent 160 of its ~200 instructions per output quad
+// there and was bound by them, not by memory.  GELU error <= 0.5 |x| x 3e-7: two orders inside the 1e-4 gate
+// (AWSEG_GELU_EXACT=1: erff).  backbone.hip and the Mix-FFN tile kernel of mixffn.hip.
+__device__ __forceinline__ float awseg_erf_as(float x)
+{
+    const float ax = __builtin_fabsf(x);
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
+    float p = fmaf(1.061405429f, t, -1.453152027f);
+    p = fmaf(p, t, 1.421413741f);
+    p = fmaf(p, t, -0.284496736f);
+    p = fmaf(p, t, 0.254829592f);
+    p = p * t;
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
+    const float r = fmaf(-p, e, 1.0f);
+    return __builtin_copysignf(r, x);
+}
+// torch GELU (erf form) on the fast erf
+__device__ __forceinline__ float awseg_gelu(float v) { return 0.5f * v * (1.0f + awseg_erf_as(v * 0.70710678118654752440f)); }
+
+// Border indices of the stencil kernels (weather.hip, depth.hip): scipy 'reflect' (d c b a | a b c d | d c b a) ...
+__device__ __forceinline__ int awseg_reflect_sym(int i, int n)
+{
+    if (n == 1) return 0;
+    const int period = 2 * n;
+    i %= period;
+    if (i < 0) i += period;
+    return i < n ? i : period - 1 - i;
+}
+// ... and OpenCV BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba) at any offset (cv::borderInterpolate)
+__device__ __forceinline__ int awseg_reflect_101(int i, int n)
+{
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
+    return i;
+}
+
 // ECE confidence sums in FIXED POINT, units of 2^-30 (metrics.hip, calib.hip): a float32 confidence in [2^-7, 1] is a multiple
 // of 2^-30, so conf * 2^30 is an exact integer and integer sums do not depend on the order of the atomics.
 __device__ __forceinline__ unsigned long long awseg_conf_q30(float conf) { return (unsigned long long)(conf * 1073741824.0f); }

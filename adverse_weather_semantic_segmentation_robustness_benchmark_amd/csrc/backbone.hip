@@ -15,27 +15,10 @@ namespace {
 
 constexpr int kThreads = 256;
 
-// erf to 1.5e-7 absolute (Abramowitz & Stegun 7.1.26: 1 - (a1 t + ... + a5 t^5) exp(-x^2), t = 1 / (1 + p |x|)) with the hardware
-// reciprocal and exp2: 14 vector instructions, two of them transcendental.  The library erff is ~40 (two range branches, both
-// evaluated and selected): the depthwise 3x3 + GELU kernel spent 160 of its ~200 instructions per output quad there and was
-// bound by them, not by memory.  GELU error <= 0.5 |x| x 3e-7: two orders inside the 1e-4 gate (AWSEG_GELU_EXACT=1: erff).
-__device__ __forceinline__ float erf_as(float x)
-{
-    const float ax = __builtin_fabsf(x);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    p = p * t;
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
-    const float r = fmaf(-p, e, 1.0f);
-    return __builtin_copysignf(r, x);
-}
 __device__ __forceinline__ float act1(float v, int act)
 {
     if (act == 1) return v > 0.f ? v : 0.f;
-    if (act == 2) return 0.5f * v * (1.0f + erf_as(v * 0.70710678118654752440f));   // torch GELU (erf form), fast erf
+    if (act == 2) return awseg_gelu(v);                                             // torch GELU (erf form), fast erf (awseg_common.h)
     if (act == 3) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));     // the same with the library erff
     return v;
 }

@@ -35,14 +35,6 @@ constexpr unsigned long long kLow40 = (1ull << 40) - 1;
 // t, s = log2(e)/t (exponent scale; == kLog2e exactly at t = 1), inv = 1/t.  Kernel arguments: wave-uniform scalar loads.
 struct tgrid_consts { float t[kMaxTemps], s[kMaxTemps], inv[kMaxTemps]; };
 
-__device__ __forceinline__ bool is_nan(float v) { return v != v; }
-
-// torch argmax update rule (awseg_amax_step, used by the ensemble statistics with the confusion counts)
-__device__ __forceinline__ void amax_step(float v, int c, float& best, int& bi)
-{
-    if (!(v <= best) && !is_nan(best)) { best = v; bi = c; }
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v)
 {
 #pragma unroll
@@ -135,7 +127,7 @@ void tgrid_kernel(const float* __restrict__ seg1, const float* __restrict__ seg2
                 d[c][j] = rv;
                 if (c == 0) { m[j] = rv; bi[j] = 0; }
                 else if (MODE == 3) { if (rv > m[j]) { m[j] = rv; bi[j] = c; } }   // ece_kernel (metrics.hip)
-                else amax_step(rv, c, m[j], bi[j]);                              // ensemble_stats_kernel (with confusion)
+                else awseg_amax_step(rv, c, m[j], bi[j]);                        // torch's argmax rule: ensemble_stats_kernel (with confusion)
             }
         }
         float dy[PX];

@@ -28,25 +28,12 @@ constexpr int GW = IW + 2, GH = IH + 2;      // gray window: one more pixel for 
 
 struct gauss_taps { double w[2 * FR + 1]; };
 
-__device__ __forceinline__ int reflect_sym(int i, int n)          // scipy 'reflect'
-{
-    if (n == 1) return 0;
-    const int period = 2 * n;
-    i %= period;
-    if (i < 0) i += period;
-    return i < n ? i : period - 1 - i;
-}
-__device__ __forceinline__ int reflect_101(int i, int n)          // BORDER_REFLECT_101, |offset| == 1
+// (scipy 'reflect' and BORDER_REFLECT_101 at any offset: awseg_reflect_sym / awseg_reflect_101 of awseg_common.h)
+__device__ __forceinline__ int reflect_101_step(int i, int n)     // BORDER_REFLECT_101, |offset| == 1: no loop
 {
     if (n == 1) return 0;
     if (i < 0) return -i;
     if (i >= n) return 2 * n - 2 - i;
-    return i;
-}
-__device__ __forceinline__ int reflect_101n(int i, int n)         // BORDER_REFLECT_101, any offset (cv::borderInterpolate)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
     return i;
 }
 __device__ __forceinline__ int gray15(const uint8_t* __restrict__ px)
@@ -79,8 +66,8 @@ __device__ __forceinline__ void stage_gray(const uint8_t* __restrict__ src, int 
 template <int SW>
 __device__ __forceinline__ int abs_laplacian(const uint8_t* s_gray, const gray_win& g, int gy, int gx, int H, int W)
 {
-    const int ym = reflect_101(gy - 1, H) - g.ylo, yp = reflect_101(gy + 1, H) - g.ylo;
-    const int xm = reflect_101(gx - 1, W) - g.xlo, xp = reflect_101(gx + 1, W) - g.xlo;
+    const int ym = reflect_101_step(gy - 1, H) - g.ylo, yp = reflect_101_step(gy + 1, H) - g.ylo;
+    const int xm = reflect_101_step(gx - 1, W) - g.xlo, xp = reflect_101_step(gx + 1, W) - g.xlo;
     const int yc = gy - g.ylo, xc = gx - g.xlo;
     int v = (int)s_gray[ym * SW + xc] + (int)s_gray[yp * SW + xc] + (int)s_gray[yc * SW + xm] + (int)s_gray[yc * SW + xp]
           - 4 * (int)s_gray[yc * SW + xc];
@@ -140,7 +127,7 @@ void depth_estimate_kernel(const uint8_t* __restrict__ imgs, int H, int W, const
         // cells only outputs beyond the image edge would read are not produced (their reflections
         // may fall outside the staged gray window)
         if (y0 - FR + ty > y_last + FR || x0 - FR + tx > x_last + FR) { s_in[i] = 0.0; continue; }
-        int gy = reflect_sym(y0 - FR + ty, H), gx = reflect_sym(x0 - FR + tx, W);
+        int gy = awseg_reflect_sym(y0 - FR + ty, H), gx = awseg_reflect_sym(x0 - FR + tx, W);
         double base = ((double)gy / (double)H) * 0.8 + 0.2;        // :348-349
         if (gy < H / 3) base = 1.0;                                // :353
         if (gy >= H / 2) base = base * 0.5;                        // :354
@@ -216,7 +203,7 @@ void local_contrast_kernel(const uint8_t* __restrict__ imgs, int H, int W, float
         int gy = y0 - 4 + ty, gx = x0 - 4 + tx;
         float v = 0.f;
         if (gy >= -2 && gy < H + 2 && gx >= -2 && gx < W + 2) {        // only positions some in-image mean needs
-            const int ry = reflect_101n(gy, H), rx = reflect_101n(gx, W);
+            const int ry = awseg_reflect_101(gy, H), rx = awseg_reflect_101(gx, W);
             v = (float)gray15(src + ((int64_t)ry * W + rx) * 3) / 255.0f;   // :271-272
         }
         s_g[i] = v;
@@ -250,7 +237,7 @@ void local_contrast_kernel(const uint8_t* __restrict__ imgs, int H, int W, float
         for (int dy = -2; dy <= 2; ++dy)
 #pragma unroll
             for (int dx = -2; dx <= 2; ++dx) {
-                const int ry = reflect_101n(gy + dy, H), rx = reflect_101n(gx + dx, W);   // REFLECT_101 of the deviation map
+                const int ry = awseg_reflect_101(gy + dy, H), rx = awseg_reflect_101(gx + dx, W);   // REFLECT_101 of the deviation map
                 float t = k * s_d[(ry - y0 + 2) * CM + (rx - x0 + 2)];
                 v = v + t;
             }

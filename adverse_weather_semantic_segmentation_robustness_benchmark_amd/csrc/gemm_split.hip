@@ -3,13 +3,11 @@
 // decoder (PKG/models/model.py:349) — the same operator as awseg_gemm_bias_act (gemm.hip, hipBLASLt on the
 // float32-input MFMA), which stays the path for the HBM-bound shapes.
 //
-// v_mfma_f32_32x32x16_f16 issues 16x the multiply-adds per cycle of the float32-input MFMA, and a float32 product is
-// three f16 products once both operands are SPLIT (attn.hip has the same scheme, measured there against float64):
-//     x = xh + xl / 2048,  xh = f16(x),  xl = f16((x - xh) * 2048)            (22 significant bits)
+// SPLIT operands (awseg_split.h has the scheme and the 22-bit claim), here with the SCALED residual and two accumulators:
+//     x = xh + xl / 2048,  xh = f16(x),  xl = f16((x - xh) * 2048)
 //     x * w = xh*wh + (xh*wl + xl*wh) / 2048                                  (+ O(2^-22 |x w|), dropped)
-// Every f16 product is exact in the float32 accumulator and the accumulation itself is float32, so the result differs
-// from a float32 GEMM by operand rounding at 2^-22 instead of 2^-24 — the same order as the difference between two
-// float32 summation orders (tests/test_gpu_kernels.py prices both against float64).
+// — the same order as the difference between two float32 summation orders (tests/test_gpu_kernels.py prices both against
+// float64).
 //   * weights are split once (awseg_gemm_split_weights -> [2][N][K] f16), activations at tile-load time;
 //   * block = 128 x 128 outputs, 8 waves as 4 x 2, each 32 x 64 = 1 x 2 MFMA tiles with a main and a correction
 //     accumulator (64 accumulator registers, 128 VGPRs: four waves per SIMD); K tiles of 32, double-buffered in LDS,
@@ -31,40 +29,15 @@
 //     The guard has a SMALL side too: a tile whose max|x| < 2^-7 (low parts f16 subnormals, the high parts too below 2^-14)
 //     takes the same scaled second pass (tests/test_gpu_split_magnitudes.py).  It is per tile, not per row: a row at 2^-12
 //     in a tile with O(1) rows keeps the optimistic split, accurate relative to the tile's largest products.
-#include "awseg_common.h"
+// (the split itself is split_scaled_rtz of awseg_split.h, which has the scheme and the other flavours side by side)
+#include "awseg_split.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int GT = 512;          // threads of a GEMM block (8 waves)
 constexpr int SWT = 256;         // threads of the weight-split kernel
 constexpr int GKT = 32;          // K tile
 constexpr int GROW = 72;         // halfs per LDS row: 32 hi | 32 lo | 8 pad
-constexpr float kLoScale = 2048.0f, kLoInv = 1.0f / 2048.0f;
-
-__device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo)
-{
-    const auto hp = __builtin_amdgcn_cvt_pkrtz(a, b);
-    const h2 hh = __builtin_bit_cast(h2, hp);
-    const float ra = (a - (float)hh.x) * kLoScale, rb = (b - (float)hh.y) * kLoScale;
-    hi = __builtin_bit_cast(unsigned, hp);
-    lo = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(ra, rb));
-}
-
-// power-of-two scale that brings a maximum magnitude with float bits `maxbits` into [2^13, 2^14): returns e with
-// scaled = v * 2^-e.  Zero / subnormal maxima (and Inf / NaN) leave the tensor unscaled.
-__device__ __forceinline__ int norm_exponent(unsigned maxbits)
-{
-    const int ex = (int)(maxbits >> 23) & 0xff;
-    if (ex == 0 || ex == 0xff) return 0;
-    return ex - 127 - 13;
-}
-__device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }   // -126 <= e <= 127
 
 // trailer of a split-weight buffer (8 uint16 = 16 bytes behind the [2][N][K] halfs): {max|w| bits, 2^ew as float, 0, 0}
 __global__ __launch_bounds__(SWT)
@@ -80,7 +53,7 @@ void weights_absmax_kernel(const float* __restrict__ w, int64_t n_elems, unsigne
 __global__ __launch_bounds__(SWT)
 void split_weights_kernel(const float* __restrict__ w, int64_t n_elems, uint16_t* __restrict__ out, unsigned* __restrict__ trailer)
 {
-    const int e = norm_exponent(trailer[0]);
+    const int e = norm_exponent_any_max(trailer[0]);            // zero / subnormal maxima (and Inf / NaN) leave the tensor unscaled
     // |e| can exceed the exponent range of one float factor (max|w| = 1e-38 -> e = -139): apply it in two halves
     const int e1 = e / 2, e2 = e - e1;
     const float s1 = pow2f(-e1), s2 = pow2f(-e2);
@@ -91,7 +64,7 @@ void split_weights_kernel(const float* __restrict__ w, int64_t n_elems, uint16_t
     if (i >= n_elems) return;
     const float a = w[i] * s1 * s2, b = (i + 1 < n_elems) ? w[i + 1] * s1 * s2 : 0.f;
     unsigned hi, lo;
-    split_pair(a, b, hi, lo);
+    split_scaled_rtz(a, b, hi, lo);
     out[i] = (uint16_t)hi; out[n_elems + i] = (uint16_t)lo;
     if (i + 1 < n_elems) { out[i + 1] = (uint16_t)(hi >> 16); out[n_elems + i + 1] = (uint16_t)(lo >> 16); }
 }
@@ -122,16 +95,7 @@ __device__ __forceinline__ constexpr int acc_row(int r, int hk) { return (r & 3)
 //   <1, 2, 4, 2>: 128 x 128, 64 accumulator registers per lane, four waves per SIMD, two blocks per CU
 //   <2, 2, 2, 4>: 128 x 256, 128 accumulator registers, two waves per SIMD, one block per CU: 25 % fewer operand bytes
 //                 fetched per multiply-add (the measured limit) for the shapes with N >= 256
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-
-// float32 pair -> packed bf16 (round to nearest even: v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned pack_bf16(float a, float b)
-{
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(f2{a, b}, bf2));
-}
-
+//
 // BF16 = true: the same kernel with ONE v_mfma_f32_32x32x16_bf16 per product tile (BASELINE config 5: the bf16 MFMA
 // path): activations are rounded to bf16 when they are staged, weights come as one bf16 plane (awseg_gemm_bf16_weights
 // writes it where the split form keeps its high parts), float32 accumulation and epilogue.  bf16 has float32's exponent
@@ -236,8 +200,8 @@ void gemm_split_kernel(gemm_args a)
             if (scaled) { v.x *= sx; v.y *= sx; v.z *= sx; v.w *= sx; }       // block-uniform branch
             amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v.x)), __builtin_fabsf(v.y));   // v_max3_f32 with |.| modifiers
             amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(v.z)), __builtin_fabsf(v.w));
-            split_pair(v.x, v.y, hh, ll); H[0] = hh; L[0] = ll;
-            split_pair(v.z, v.w, hh, ll); H[1] = hh; L[1] = ll;
+            split_scaled_rtz(v.x, v.y, hh, ll); H[0] = hh; L[0] = ll;
+            split_scaled_rtz(v.z, v.w, hh, ll); H[1] = hh; L[1] = ll;
             *reinterpret_cast<u32x2*>(d) = H;
             *reinterpret_cast<u32x2*>(d + 32) = L;
         }

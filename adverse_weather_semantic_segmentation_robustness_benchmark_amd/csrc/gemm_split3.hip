@@ -23,14 +23,10 @@
 // Operand range: as gemm_split.hip — weights normalised when they are split, activations split optimistically (x 2^4) while
 // the block tracks max|x|; a tile that met |x| >= 2^11, or whose max|x| < 2^-7 (low parts f16 subnormals: the small side), is
 // recomputed with x 2^-e and rescaled in the epilogue.  Per tile, not per row.
-#include "awseg_common.h"
+// The LDS-DMA (lds_dma16) and the split (split_prescaled_rne_mfma) are in awseg_split.h.
+#include "awseg_split.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int G3M_MAX = 256, G3K = 32;     // the tile has 32 WV rows (WV = 8 or 4 waves); one operand's stage: rows x 128 B
 // two stages of two operands + sMax[4]; the four-wave blocks pack the weight stages (64-column tiles: 48 KB a block, THREE blocks per CU)
@@ -42,32 +38,6 @@ constexpr float kActScale0 = 16.0f;
 constexpr int kActExp0 = -4;
 constexpr float kSplitLimit3 = 2048.0f;     // |x| below this splits without loss at scale 2^4 (|x s| < 2^15)
 constexpr float kSmallLimit3 = 0.0078125f;  // a tile whose max|x| is below 2^-7 is redone scaled (small-side guard)
-
-__device__ __forceinline__ float pow2f3(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }
-
-__device__ __forceinline__ uint32_t lds_addr3(const void* p)
-{
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-// 16 bytes per lane global -> LDS through a buffer descriptor: LDS address = m0 + 16 * lane (wave-uniform base), the
-// source address per lane (vector offset; out-of-range lanes read zeros) + a scalar offset
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds_base)
-{
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base) : "m0", "memory");
-}
-
-// two float32 -> packed f16 high parts and packed f16 low parts of (a s, b s): hi = f16(x s) (round to nearest), lo = f16(x s - hi)
-// (exact in float32, then exactly representable while normal).  Four mixed-precision FMAs, no packed-float32 instruction
-// (those cost extra beside MFMAs: MI355X_MICROARCH.md cycle constants).
-__device__ __forceinline__ void split2(float a, float b, float s, unsigned& hi, unsigned& lo)
-{
-    asm("v_fma_mixlo_f16 %0, %2, %4, 0\n\t"
-        "v_fma_mixhi_f16 %0, %3, %4, 0\n\t"
-        "v_fma_mixlo_f16 %1, %2, %4, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, %4, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"          // a vector write needs two wait states before an MFMA reads the register as an operand; hipcc pads only its own instructions
-        : "=&v"(hi), "=&v"(lo) : "v"(a), "v"(b), "s"(s));
-}
 
 #ifdef AWSEG_G3_STAMP
 // tools/scratch/g3_stamps.py: s_memtime stamps of block 0, waves 0 and 4, summed over K tiles:
@@ -104,11 +74,7 @@ struct g3_args {
 // BF16: BASELINE config 5 — ONE v_mfma_f32_32x32x16_bf16 per product tile: the activation fragment is rounded to bf16 (RNE) by the
 // wave that multiplies it, the weights come as a bf16 image [N/256][KB][256][32] (64-byte rows: a 16 KB stage), float32
 // accumulation and epilogue; bf16 has float32's exponent range: no range guard, no scaling.
-typedef __bf16 bf8_3 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf2_3 __attribute__((ext_vector_type(2)));
-typedef float f2_3 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pack_bf16_3(float x, float y) { return __builtin_bit_cast(unsigned, __builtin_convertvector(f2_3{x, y}, bf2_3)); }
-
+//
 // NT: MFMA tiles of 32 columns per wave: block tile 256 x (32 NT) — 8 for N % 256 == 0, 4 for N % 128 == 0, 2 for N % 64 == 0 (the
 // narrow tiles serve HBM-bound shapes: l1 / l2 conv1, MiT projections; the weight image is cut into n-tiles of the same width)
 // WV: waves of a block = 32-row strips of its tile.  8: the 256-row tile, one block per CU (128 KB of LDS).  4: a 128-row tile on
@@ -151,7 +117,7 @@ void gemm_split3_kernel(g3_args a)
     const int KA = DUAL ? a.K1 : a.K;                              // row length of x
     const int kt1 = KA / G3K;                                      // DUAL: K tiles kt >= kt1 come from x2
     int cby[4], cy0[4], cx0[4];                                    // CONV: image row base b * cH, first tap's input row / column of this lane's A rows (< 0: row past M)
-    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr3(smem));
+    const uint32_t lds0 = __builtin_amdgcn_readfirstlane(lds_addr(smem));
     const uint32_t wave_u = __builtin_amdgcn_readfirstlane(wave);   // scalar register: the LDS-DMA base goes through m0
     __amdgpu_buffer_rsrc_t x_rsrc, w_rsrc, x2_rsrc, x3_rsrc, x4_rsrc;
     auto point = [&](int64_t m0, int n0) {
@@ -215,7 +181,7 @@ void gemm_split3_kernel(g3_args a)
                 const int iy = cy0[j] + ky * a.cd, ix = cx0[j] + kx * a.cd;
                 const bool ok = cby[j] >= 0 && (unsigned)iy < (unsigned)a.cH && (unsigned)ix < (unsigned)a.cW;
                 const uint32_t vo = ok ? (uint32_t)((((cby[j] + iy) * a.cW + ix) * a.cpitch + c0) * 4) + a_voff[j] : 0x80000000u;
-                dma16(x_rsrc, vo, 0u, la + (uint32_t)(j * 1024));
+                lds_dma16(x_rsrc, vo, 0u, la + (uint32_t)(j * 1024));
             }
         } else {
         if (DUAL && kt >= kt1) {                                   // (block-uniform)
@@ -224,24 +190,24 @@ void gemm_split3_kernel(g3_args a)
             const uint32_t ko = (uint32_t)__builtin_amdgcn_readfirstlane(((kt - kt1) - piece * kt2) * 128);
             if (piece == 0) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) dma16(x2_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
+                for (int j = 0; j < 4; ++j) lds_dma16(x2_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
             } else if (piece == 1) {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) dma16(x3_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
+                for (int j = 0; j < 4; ++j) lds_dma16(x3_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) dma16(x4_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
+                for (int j = 0; j < 4; ++j) lds_dma16(x4_rsrc, a_voff2[j], ko, la + (uint32_t)(j * 1024));
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dma16(x_rsrc, kt == nkt - 1 ? a_voff_last[j] : a_voff[j], (uint32_t)(kt * 128), la + (uint32_t)(j * 1024));
+            for (int j = 0; j < 4; ++j) lds_dma16(x_rsrc, kt == nkt - 1 ? a_voff_last[j] : a_voff[j], (uint32_t)(kt * 128), la + (uint32_t)(j * 1024));
         }
         }
         {
             const uint32_t lbw = lds0 + (uint32_t)(G3_B0 + stage * G3_BSTAGE) + wave_u * (uint32_t)(NBI * 1024);
             if (NBI_ALL >= WV || (int)wave_u < NBI_ALL) {
 #pragma unroll
-                for (int j = 0; j < NBI; ++j) dma16(w_rsrc, b_voff[j], (uint32_t)(kt * a.img_bn * ROWB), lbw + (uint32_t)(j * 1024));
+                for (int j = 0; j < NBI; ++j) lds_dma16(w_rsrc, b_voff[j], (uint32_t)(kt * a.img_bn * ROWB), lbw + (uint32_t)(j * 1024));
             }
         }
     };
@@ -334,20 +300,20 @@ void gemm_split3_kernel(g3_args a)
                 }
                 u32x4 H, L; unsigned h, l;
                 if (BF16) {
-                    H[0] = pack_bf16_3(p[0], p[1]); H[1] = pack_bf16_3(p[2], p[3]); H[2] = pack_bf16_3(q[0], q[1]); H[3] = pack_bf16_3(q[2], q[3]);
-                    const bf8_3 Ab = __builtin_bit_cast(bf8_3, H);
+                    H[0] = pack_bf16(p[0], p[1]); H[1] = pack_bf16(p[2], p[3]); H[2] = pack_bf16(q[0], q[1]); H[3] = pack_bf16(q[2], q[3]);
+                    const bf8 Ab = __builtin_bit_cast(bf8, H);
 #pragma unroll
-                    for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ab, __builtin_bit_cast(bf8_3, Bh[j]), acc[j], 0, 0, 0);
+                    for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(Ab, __builtin_bit_cast(bf8, Bh[j]), acc[j], 0, 0, 0);
                     continue;
                 }
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(p[0])), __builtin_fabsf(p[1]));
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(p[2])), __builtin_fabsf(p[3]));
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(q[0])), __builtin_fabsf(q[1]));
                 amax = __builtin_fmaxf(__builtin_fmaxf(amax, __builtin_fabsf(q[2])), __builtin_fabsf(q[3]));
-                split2(p[0], p[1], sx, h, l); H[0] = h; L[0] = l;
-                split2(p[2], p[3], sx, h, l); H[1] = h; L[1] = l;
-                split2(q[0], q[1], sx, h, l); H[2] = h; L[2] = l;
-                split2(q[2], q[3], sx, h, l); H[3] = h; L[3] = l;
+                split_prescaled_rne_mfma(p[0], p[1], sx, h, l); H[0] = h; L[0] = l;
+                split_prescaled_rne_mfma(p[2], p[3], sx, h, l); H[1] = h; L[1] = l;
+                split_prescaled_rne_mfma(q[0], q[1], sx, h, l); H[2] = h; L[2] = l;
+                split_prescaled_rne_mfma(q[2], q[3], sx, h, l); H[3] = h; L[3] = l;
                 const h8 Ah = __builtin_bit_cast(h8, H), Al = __builtin_bit_cast(h8, L);
 #pragma unroll
                 for (int j = 0; j < NT; ++j) {
@@ -381,7 +347,7 @@ void gemm_split3_kernel(g3_args a)
             if (ex != 0xff) {                                      // Inf / NaN: nothing to rescue, let them propagate
                 xe = ex - 127 - 13;                                // max|x| * 2^-xe in [2^13, 2^14)
                 xe = xe < -127 ? -127 : xe;
-                sx = pow2f3(-xe);
+                sx = pow2f(-xe);
                 scaled = true; again = true;
             }
         }
@@ -396,7 +362,7 @@ void gemm_split3_kernel(g3_args a)
 
         const int oe = BF16 ? 0 : we + xe;
         const int oe1 = oe / 2, oe2 = oe - oe1;
-        const float os1 = pow2f3(oe1 < -126 ? -126 : (oe1 > 127 ? 127 : oe1)), os2 = pow2f3(oe2 < -126 ? -126 : (oe2 > 127 ? 127 : oe2));
+        const float os1 = pow2f(oe1 < -126 ? -126 : (oe1 > 127 ? 127 : oe1)), os2 = pow2f(oe2 < -126 ? -126 : (oe2 > 127 ? 127 : oe2));
 
         // ---- epilogue: lane = output column n (32 j + li), registers = rows m (32 wave + 8 (r >> 2) + 4 hk + (r & 3)): a store
         // instruction writes two full 128-byte lines.  (The transposed form — lane = row, 16-byte accesses, a quarter of the
@@ -491,7 +457,7 @@ void split3_weights_kernel(const float* __restrict__ w, int n_rows, int k_dim, i
 {
     const int e = (int)trailer[1];
     const int e1 = e / 2, e2 = e - e1;
-    const float s1 = pow2f3(-e1), s2 = pow2f3(-e2);
+    const float s1 = pow2f(-e1), s2 = pow2f(-e2);
     const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 2;        // padded element pair (n, k), (n, k + 1), k < 32 KB
     const int kp = kb * 32;
     if (i >= (int64_t)n_rows * kp) return;
@@ -513,7 +479,7 @@ void bf16_3_weights_kernel(const float* __restrict__ w, int n_rows, int k_dim, i
     if (i >= (int64_t)n_rows * kp) return;
     const int64_t n = i / kp;
     const int k = (int)(i - n * kp);
-    const unsigned pr = pack_bf16_3(k < k_dim ? w[n * k_dim + k] : 0.f, k + 1 < k_dim ? w[n * k_dim + k + 1] : 0.f);
+    const unsigned pr = pack_bf16(k < k_dim ? w[n * k_dim + k] : 0.f, k + 1 < k_dim ? w[n * k_dim + k + 1] : 0.f);
     uint16_t* d = out + (((n / bn) * kb + (k >> 5)) * bn + (n % bn)) * 32 + (k & 31);
     d[0] = (uint16_t)pr; d[1] = (uint16_t)(pr >> 16);
 }

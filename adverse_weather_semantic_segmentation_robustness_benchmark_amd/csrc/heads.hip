@@ -6,7 +6,7 @@
 // with G = the nine 1x1 products W_tap . f at the encoder's resolution (a 2.4 GFLOP GEMM the
 // caller runs once).  The 2.15 GB / image full-resolution 256-channel tensor and 2.47 TFLOP /
 // image of the as-written op never exist; per pixel we spend 36 gathers x Cmid + Cmid x Cout.
-#include "awseg_common.h"
+#include "awseg_split.h"
 #include <cstdlib>
 #include <stdlib.h>
 
@@ -100,7 +100,6 @@ void segformer_head_kernel(const float* __restrict__ g9, int cmid, int h, int w,
 //            the k order is the accumulator's row order and W2 is pre-permuted into registers.
 // Per 32 pixels: 6*OT + 16*OT MFMAs (OT = Cmid/32), i.e. 176 x 64 cycles for Cmid = 256.
 // ---------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 template <int OT, bool CLASSIFY, int NW>
 __global__ __launch_bounds__(NW * 64, NW / 4)
 void head_mfma_kernel(const float* __restrict__ g9, int h, int w, int H, int W, int R,
@@ -439,18 +438,9 @@ void head_mfma_classify_kernel(const float* __restrict__ g9, int h, int w, int H
 // Per 32 pixels: OT * (2..3 + 6) MFMAs of 32 cycles instead of OT * 22 of 64.
 // Operand range: every |T| and every activation a wave converts is tracked (v_max3); a row whose maximum reaches 2^15 — f16
 // would overflow — is recomputed by the same wave on the float32 instruction (the v3 arithmetic, W2 read from memory).
+// The split is split_unscaled_lds of awseg_split.h: the flavour WITHOUT trailing wait states, here also for the operands that stay
+// in registers (T, the horizontal weights, the GEMM-1 accumulators) — kept as found; see the flavour table there.
 // ---------------------------------------------------------------------------------------
-typedef _Float16 hd8 __attribute__((ext_vector_type(8)));
-typedef unsigned hu4 __attribute__((ext_vector_type(4)));
-typedef float hf2 __attribute__((ext_vector_type(2)));
-typedef float hf4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void head_split_pair(float a, float b, unsigned& hi, unsigned& lo)
-{
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(a, b));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(lo) : "v"(a), "v"(b), "v"(hi));
-}
 __device__ __forceinline__ float head_max3(float m, float a, float b)
 {
     float r;
@@ -469,7 +459,7 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
     extern __shared__ float smem[];
     float* Gl = smem;                           // [3][4][9][CM]
     float* s_sh = smem + 108 * CM;              // [OT][2 (hh)][16 (acc reg)]
-    hu4* s_w2 = reinterpret_cast<hu4*>(s_sh + OT * 32);   // [OT][2 (k step)][2 (hi, lo)][64 lanes] x 8 halves
+    u32x4* s_w2 = reinterpret_cast<u32x4*>(s_sh + OT * 32);   // [OT][2 (k step)][2 (hi, lo)][64 lanes] x 8 halves
     float* s_b2 = reinterpret_cast<float*>(s_w2 + OT * 256);   // [32]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int lo = lane & 31, hh = lane >> 5;
@@ -501,11 +491,11 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
             const int row = (j & 3) + 8 * (j >> 2) + 16 * ks + 4 * kk;       // accumulator row of register 8 ks + j
             v[j] = (cls < cout) ? w2[(int64_t)cls * CM + chan(ot, row)] : 0.f;
         }
-        hu4 Hh, Ll; unsigned a, c;
-        head_split_pair(v[0], v[1], a, c); Hh[0] = a; Ll[0] = c;
-        head_split_pair(v[2], v[3], a, c); Hh[1] = a; Ll[1] = c;
-        head_split_pair(v[4], v[5], a, c); Hh[2] = a; Ll[2] = c;
-        head_split_pair(v[6], v[7], a, c); Hh[3] = a; Ll[3] = c;
+        u32x4 Hh, Ll; unsigned a, c;
+        split_unscaled_lds(v[0], v[1], a, c); Hh[0] = a; Ll[0] = c;
+        split_unscaled_lds(v[2], v[3], a, c); Hh[1] = a; Ll[1] = c;
+        split_unscaled_lds(v[4], v[5], a, c); Hh[2] = a; Ll[2] = c;
+        split_unscaled_lds(v[6], v[7], a, c); Hh[3] = a; Ll[3] = c;
         s_w2[((ot * 2 + ks) * 2 + 0) * 64 + ln] = Hh;
         s_w2[((ot * 2 + ks) * 2 + 1) * 64 + ln] = Ll;
     }
@@ -524,12 +514,12 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
         cx[s] = v;
         lbase[s] = (c * 9 + kx) * CM + lo * 4;
     }
-    hu4 cxh, cxl;
+    u32x4 cxh, cxl;
     {
         unsigned a, c;
-        head_split_pair(cx[0], cx[1], a, c); cxh[0] = a; cxl[0] = c;
-        head_split_pair(cx[2], cx[3], a, c); cxh[1] = a; cxl[1] = c;
-        head_split_pair(cx[4], cx[5], a, c); cxh[2] = a; cxl[2] = c;
+        split_unscaled_lds(cx[0], cx[1], a, c); cxh[0] = a; cxl[0] = c;
+        split_unscaled_lds(cx[2], cx[3], a, c); cxh[1] = a; cxl[1] = c;
+        split_unscaled_lds(cx[4], cx[5], a, c); cxh[2] = a; cxl[2] = c;
         // the two spare K slots of the first half-wave carry the BatchNorm shift: B = (1, 1) against A = (shift hi, shift lo)
         cxh[3] = hh == 0 ? 0x3C003C00u : 0u; cxl[3] = 0u;
     }
@@ -545,7 +535,7 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
     const bool cx_exact = __builtin_amdgcn_ballot_w64(((cxl[0] | cxl[1] | cxl[2]) & 0x7FFF7FFFu) != 0u) == 0ull;
     if (tid < 32) s_b2[tid] = tid < cout ? b2[tid] : 0.f;
     __syncthreads();
-#define HMFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(hd8, A), __builtin_bit_cast(hd8, B), C, 0, 0, 0)
+#define HMFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h8, A), __builtin_bit_cast(h8, B), C, 0, 0, 0)
 
     const int64_t HW = (int64_t)H * W;
     for (int ry = wv; ry < R; ry += kT / 64) {
@@ -568,11 +558,11 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
 #pragma unroll
             for (int s = 0; s < 6; ++s) {
                 const float* base = Gl + lbase[s] + gi * 128;
-                hf2 v01 = { 0.f, 0.f }, v23 = { 0.f, 0.f };
+                v2f v01 = { 0.f, 0.f }, v23 = { 0.f, 0.f };
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    const hf4 a = *reinterpret_cast<const hf4*>(base + ub[j]);
-                    const hf2 wj = { lw[j], lw[j] };
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(base + ub[j]);
+                    const v2f wj = { lw[j], lw[j] };
                     v01 = __builtin_elementwise_fma(wj, __builtin_shufflevector(a, a, 0, 1), v01);
                     v23 = __builtin_elementwise_fma(wj, __builtin_shufflevector(a, a, 2, 3), v23);
                 }
@@ -593,17 +583,17 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
         // A operands of the four tiles of a group, already split: th[q] / tl[q] halves 0..5 = slots, 6..7 = shift / zero.
         // A group's operands are produced in three steps (slot pairs) so that the LDS reads and packed FMAs of the NEXT
         // group can sit between the matrix instructions of this one instead of in one exposed block behind them.
-        auto gather_step = [&](int gi, int sp, hu4* th, hu4* tl) {
+        auto gather_step = [&](int gi, int sp, u32x4* th, u32x4* tl) {
             float t[4][2];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
                 const int s = 2 * sp + e;
                 const float* base = Gl + lbase[s] + gi * 128;
-                hf2 v01 = { 0.f, 0.f }, v23 = { 0.f, 0.f };
+                v2f v01 = { 0.f, 0.f }, v23 = { 0.f, 0.f };
 #pragma unroll
                 for (int j = 0; j < 6; ++j) {
-                    const hf4 a = *reinterpret_cast<const hf4*>(base + ub[j]);
-                    const hf2 wj = { lw[j], lw[j] };
+                    const f32x4 a = *reinterpret_cast<const f32x4*>(base + ub[j]);
+                    const v2f wj = { lw[j], lw[j] };
                     v01 = __builtin_elementwise_fma(wj, __builtin_shufflevector(a, a, 0, 1), v01);
                     v23 = __builtin_elementwise_fma(wj, __builtin_shufflevector(a, a, 2, 3), v23);
                 }
@@ -612,12 +602,12 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 unsigned p, r;
-                head_split_pair(t[q][0], t[q][1], p, r);
+                split_unscaled_lds(t[q][0], t[q][1], p, r);
                 th[q][sp] = p; tl[q][sp] = r;
                 amax = head_max3(amax, t[q][0], t[q][1]);
             }
         };
-        auto gemm1 = [&](unsigned shpk, hu4 th, hu4 tl) {
+        auto gemm1 = [&](unsigned shpk, u32x4 th, u32x4 tl) {
             f32x16 a;
 #pragma unroll
             for (int r = 0; r < 16; ++r) a[r] = 0.f;
@@ -628,19 +618,19 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
             return a;
         };
         auto finish = [&](int ot, f32x16& acc) {
-            const hu4* wp = s_w2 + ot * 256 + lane;
-            const hu4 wh0 = wp[0], wl0 = wp[64], wh1 = wp[128], wl1 = wp[192];
+            const u32x4* wp = s_w2 + ot * 256 + lane;
+            const u32x4 wh0 = wp[0], wl0 = wp[64], wh1 = wp[128], wl1 = wp[192];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {                           // one v_max_f32 (fmaxf() adds a canonicalising v_max x, x)
                 float v;
                 asm("v_max_f32 %0, 0, %1" : "=v"(v) : "v"(acc[r]));
                 acc[r] = v;
             }
-            hu4 mh0, ml0, mh1, ml1; unsigned p, q;
+            u32x4 mh0, ml0, mh1, ml1; unsigned p, q;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                head_split_pair(acc[2 * j], acc[2 * j + 1], p, q); mh0[j] = p; ml0[j] = q;
-                head_split_pair(acc[8 + 2 * j], acc[9 + 2 * j], p, q); mh1[j] = p; ml1[j] = q;
+                split_unscaled_lds(acc[2 * j], acc[2 * j + 1], p, q); mh0[j] = p; ml0[j] = q;
+                split_unscaled_lds(acc[8 + 2 * j], acc[9 + 2 * j], p, q); mh1[j] = p; ml1[j] = q;
                 amax = head_max3(amax, acc[2 * j], acc[2 * j + 1]);
                 amax = head_max3(amax, acc[8 + 2 * j], acc[9 + 2 * j]);
             }
@@ -651,7 +641,7 @@ void head_split_classify_kernel(const float* __restrict__ g9, int h, int w, int 
             acc2 = HMFMA(wl1, mh1, acc2);
             acc2 = HMFMA(wh1, ml1, acc2);
         };
-        hu4 oh[2][4], ol[2][4];                                      // operands of the current / next group
+        u32x4 oh[2][4], ol[2][4];                                      // operands of the current / next group
 #pragma unroll
         for (int sp = 0; sp < 3; ++sp) gather_step(0, sp, oh[0], ol[0]);
 #pragma unroll

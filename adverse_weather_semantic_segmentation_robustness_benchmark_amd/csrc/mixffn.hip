@@ -19,55 +19,18 @@
 //     one cross-lane exchange for mean and variance (two-pass, as awseg_layernorm_rows);
 //   * fc1, 32 hidden channels at a time: weights as the row operand, tokens as columns, so a lane ends up with 16 hidden values of
 //     ITS token in 4-channel runs -> + bias -> zero outside the frame (the convolution's padding) -> LDS [token][32];
-//   * depthwise 3x3 + bias + GELU (erf form, the fast erf of backbone.hip) on the inner tokens -> LDS;
+//   * depthwise 3x3 + bias + GELU (erf form, the fast erf of awseg_common.h) on the inner tokens -> LDS;
 //   * fc2 partial sums over those 32 hidden channels, accumulators [C outputs x 32 tokens] per column group;
 //   * epilogue: + bias + residual, inner tokens only.
 // K order of a 16-deep step: K half kh of a lane = channels 16 step + 8 kh .. + 7 (two aligned float4 / one 16-byte f16 run).  The
 // float32 fall-back of fc2 walks the same eight channels two at a time (k = 0 <-> channel e, k = 1 <-> channel 8 + e of the step).
-#include "awseg_common.h"
+// The split is split8_unscaled_mfma_fused of awseg_split.h (operands go straight into MFMA registers), GELU is awseg_gelu.
+#include "awseg_split.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// (a, b) -> packed f16 high parts and packed f16 low parts (wino_split.hip's split_pair)
-__device__ __forceinline__ void mf_split_pair(float x, float y, unsigned& hi, unsigned& lo)
-{
-    asm("v_cvt_pkrtz_f16_f32 %0, %2, %3\n\t"
-        "v_fma_mixlo_f16 %1, %2, 1.0, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"
-        : "=&v"(hi), "=&v"(lo) : "v"(x), "v"(y));
-}
-__device__ __forceinline__ void mf_split8(const float4& p, const float4& q, h8& hi, h8& lo)
-{
-    unsigned h0, h1, h2, h3, l0, l1, l2, l3;
-    mf_split_pair(p.x, p.y, h0, l0); mf_split_pair(p.z, p.w, h1, l1);
-    mf_split_pair(q.x, q.y, h2, l2); mf_split_pair(q.z, q.w, h3, l3);
-    const u32x4 H = {h0, h1, h2, h3}, L = {l0, l1, l2, l3};
-    hi = __builtin_bit_cast(h8, H); lo = __builtin_bit_cast(h8, L);
-}
-
 constexpr int MF_TW = 32, MF_TH = 8, MF_IW = 30, MF_IH = 6;
 constexpr int MF_HS = 36;                    // LDS floats per token row: 32 + 4 (16-byte aligned, conflict-free float4 columns)
-
-__device__ __forceinline__ float mf_erf(float x)
-{
-    // Abramowitz-Stegun 7.1.26 (|error| < 1.5e-7), as backbone.hip's erf_as
-    const float ax = __builtin_fabsf(x);
-    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.0f));
-    float p = fmaf(1.061405429f, t, -1.453152027f);
-    p = fmaf(p, t, 1.421413741f);
-    p = fmaf(p, t, -0.284496736f);
-    p = fmaf(p, t, 0.254829592f);
-    p = p * t;
-    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * ax * ax);
-    const float r = fmaf(-p, e, 1.0f);
-    return __builtin_copysignf(r, x);
-}
-__device__ __forceinline__ float mf_gelu(float v) { return 0.5f * v * (1.0f + mf_erf(v * 0.70710678118654752440f)); }
 
 struct mf_args {
     const float* tok; const float* gamma; const float* beta; float eps;
@@ -131,7 +94,7 @@ void mixffn_kernel(mf_args a)
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int st = 0; st < NS; ++st) mf_split8(y[m][2 * st], y[m][2 * st + 1], yh[m][st], yl[m][st]);
+        for (int st = 0; st < NS; ++st) split8_unscaled_mfma_fused(y[m][2 * st], y[m][2 * st + 1], yh[m][st], yl[m][st]);
 
     f32x16 acc2[2][NN];
 #pragma unroll
@@ -222,7 +185,7 @@ void mixffn_kernel(mf_args a)
                         const float4 v = win[(iy + dy) % 3][dx], w = tap[dy * 3 + dx];
                         acc.x = fmaf(v.x, w.x, acc.x); acc.y = fmaf(v.y, w.y, acc.y); acc.z = fmaf(v.z, w.z, acc.z); acc.w = fmaf(v.w, w.w, acc.w);
                     }
-                const float4 gv = make_float4(mf_gelu(acc.x), mf_gelu(acc.y), mf_gelu(acc.z), mf_gelu(acc.w));
+                const float4 gv = make_float4(awseg_gelu(acc.x), awseg_gelu(acc.y), awseg_gelu(acc.z), awseg_gelu(acc.w));
                 gmax = __builtin_fmaxf(__builtin_fmaxf(gmax, __builtin_fmaxf(__builtin_fabsf(gv.x), __builtin_fabsf(gv.y))),
                                        __builtin_fmaxf(__builtin_fabsf(gv.z), __builtin_fabsf(gv.w)));
                 *reinterpret_cast<float4*>(s_g + ((iy + 1) * MF_TW + dix + 1) * MF_HS + 4 * dq) = gv;
@@ -240,7 +203,7 @@ void mixffn_kernel(mf_args a)
                 for (int m = 0; m < 2; ++m) {
                     const float* gp = s_g + ((2 * wave + m) * MF_TW + col) * MF_HS + 16 * st + 8 * kh;
                     h8 gh, gl;
-                    mf_split8(*reinterpret_cast<const float4*>(gp), *reinterpret_cast<const float4*>(gp + 4), gh, gl);
+                    split8_unscaled_mfma_fused(*reinterpret_cast<const float4*>(gp), *reinterpret_cast<const float4*>(gp + 4), gh, gl);
 #pragma unroll
                     for (int n = 0; n < NN; ++n) {
                         acc2[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[st][n], gh, acc2[m][n], 0, 0, 0);

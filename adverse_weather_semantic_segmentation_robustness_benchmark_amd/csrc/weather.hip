@@ -93,22 +93,6 @@ __device__ __forceinline__ void store_quad(const uint8_t (&res)[12], uint8_t* ds
     }
 }
 
-// scipy 'reflect' (d c b a | a b c d | d c b a)
-__device__ __forceinline__ int reflect_sym(int i, int n)
-{
-    if (n == 1) return 0;
-    int period = 2 * n;
-    i %= period; if (i < 0) i += period;
-    return i < n ? i : period - 1 - i;
-}
-// OpenCV BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba)
-__device__ __forceinline__ int reflect_101(int i, int n)
-{
-    if (n == 1) return 0;
-    while (i < 0 || i >= n) { if (i < 0) i = -i; else i = 2 * n - 2 - i; }
-    return i;
-}
-
 // ------------------------------------------------------------------------------------ A7
 // 4 pixels per lane: 12 B in (3 dwords), three float4 out (one per channel plane).
 // (bodies take their block coordinates as arguments: the same code runs under its own launcher and, kind by kind, inside the ONE
@@ -226,7 +210,7 @@ void fog_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<awseg_f
     // phase 1: depth_base + noise for the tile and its halo (scipy reflect at the image border)
     for (int i = threadIdx.x; i < FIH * FIW; i += kThreads) {
         int ty = i / FIW, tx = i - ty * FIW;
-        int gy = reflect_sym(y0 - FR + ty, H), gx = reflect_sym(x0 - FR + tx, W);
+        int gy = awseg_reflect_sym(y0 - FR + ty, H), gx = awseg_reflect_sym(x0 - FR + tx, W);
         double base = ((double)gy / (double)H) * 100.0;           // preprocessing.py:236
         s_in[i] = base + fog_noise_at<PHILOX>(noise, job.seed, gy, gx, W);
     }
@@ -360,7 +344,7 @@ void fog_fast_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<aw
     if (interior_x) {
         for (int i = threadIdx.x; i < FIH * (FIW / 8); i += kFogFastThreads) {
             const int ty = i / (FIW / 8), to = i - ty * (FIW / 8);
-            const int gy = reflect_sym(y0 - FR + ty, H), gx = x0 - FR + to * 8;      // x0 - 8 is a multiple of 8
+            const int gy = awseg_reflect_sym(y0 - FR + ty, H), gx = x0 - FR + to * 8;      // x0 - 8 is a multiple of 8
             uint32_t r[4]; float n[8];
             awseg_philox::gen(job.seed, (uint64_t)gy * Wo + (gx >> 3), 0x0F06u, r);
 #pragma unroll
@@ -376,7 +360,7 @@ void fog_fast_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<aw
     } else {
         for (int i = threadIdx.x; i < FIH * FIW; i += kFogFastThreads) {
             const int ty = i / FIW, tx = i - ty * FIW;
-            const int gy = reflect_sym(y0 - FR + ty, H), gx = reflect_sym(x0 - FR + tx, W);
+            const int gy = awseg_reflect_sym(y0 - FR + ty, H), gx = awseg_reflect_sym(x0 - FR + tx, W);
             uint32_t r[4]; float n0, n1;
             awseg_philox::gen(job.seed, (uint64_t)gy * Wo + (gx >> 3), 0x0F06u, r);
             const int sel = gx & 7;
@@ -508,7 +492,7 @@ __device__ __forceinline__ void fog_strip_body(const uint8_t* __restrict__ imgs,
     float4* col = s_ring + threadIdx.x;                      // this lane's column: slot s at col[s * 256]
     int pair = -1; uint32_t r[4] = { 0u, 0u, 0u, 0u };
     for (int i = 0; i < rows_out + 2 * FR; ++i) {
-        const int gy = reflect_sym(y0 - FR + i, H);
+        const int gy = awseg_reflect_sym(y0 - FR + i, H);
         uint32_t px0 = 0u, px1 = 0u, px2 = 0u;               // the output row this iteration closes: its source pixels, requested early
         const int oy = y0 + i - 2 * FR;
         if (i >= 2 * FR && own) {
@@ -1031,7 +1015,7 @@ void snow7_tile_kernel(const uint8_t* __restrict__ imgs, int H, int W, job_pack<
     } else {
         for (int i = threadIdx.x; i < sh * sw; i += kSThreads) {
             const int ty = i / sw, tx = i - ty * sw;
-            const int gy = reflect_101(y0 - R + ty, H), gx = reflect_101(x0 - R + tx, W);
+            const int gy = awseg_reflect_101(y0 - R + ty, H), gx = awseg_reflect_101(x0 - R + tx, W);
             const bool cov = ((bits[(int64_t)gy * wd + (gx >> 5)] >> (gx & 31)) & 1u) != 0u;
             const uint8_t* px = src + ((int64_t)gy * W + gx) * 3;
 #pragma unroll
@@ -1168,7 +1152,7 @@ __device__ __forceinline__ void streak_strip_body(const uint8_t* __restrict__ im
 
     uint32_t raw[ND]; uint32_t mlo = 0u, mhi = 0u;
     auto issue = [&](int i) {                                     // loads of input row i (image row reflect(y0 - R + i))
-        const int gy = reflect_101(y0 - R + i, H);
+        const int gy = awseg_reflect_101(y0 - R + i, H);
         if (fast) {
             const uint8_t* rp = src + (int64_t)gy * W * 3;
 #pragma unroll
@@ -1195,10 +1179,10 @@ __device__ __forceinline__ void streak_strip_body(const uint8_t* __restrict__ im
                     win[(R + 3 + j) * 3 + c] = edge_r ? win[(R + 3 - j) * 3 + c] : win[(R + 3 + j) * 3 + c];
                 }
         } else {
-            const int gy = reflect_101(y0 - R + i, H);
+            const int gy = awseg_reflect_101(y0 - R + i, H);
 #pragma unroll
             for (int k = 0; k < NW; ++k) {
-                const int xk = reflect_101(gx - R + k, W);
+                const int xk = awseg_reflect_101(gx - R + k, W);
                 const bool cov = ((bits[(int64_t)gy * wd + (xk >> 5)] >> (xk & 31)) & 1u) != 0u;
                 const uint8_t* px = src + ((int64_t)gy * W + xk) * 3;
 #pragma unroll

@@ -27,13 +27,11 @@
 // was tuned by removing them (DESIGN.md §5a has the measurements and the ablation builds).
 // Epilogues: FULL  out[b,y,x,n] = act(Y + shift[n] (+ residual))            (NHWC)
 //            HEAD1 out[b,y,x]   = sigmoid(b2 + sum_n w2[n] * relu(Y + shift[n]))   (Cout == 64)
-#include "awseg_common.h"
+#include "awseg_split.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int WT = 256;            // threads per block
+constexpr int WT = 256;           // threads per block
 constexpr int TB = 8;              // 8 x 8 tiles per block
 constexpr int NTILE = TB * TB;     // 64
 constexpr int KC = 8;              // input channels per chunk
@@ -58,30 +56,17 @@ __device__ __forceinline__ float act_apply(float v, int act)
     return v;
 }
 
-// LDS-DMA of 16 bytes per lane through a buffer descriptor (buffer_load_dwordx4 ... lds): lane l's bytes land at
-// lds_base + 16*l; per-lane 32-bit byte offset + scalar byte offset, bounds-checked by the hardware (an out-of-range
-// lane reads zeros) — no 64-bit address arithmetic and no zero row for padding pixels.  Issued through inline asm on
-// purpose: the LDS-DMA builtins make hipcc treat every later ds_read as possibly aliasing the DMA's LDS write and
-// wait vmcnt(0) right after the first MFMA of a step, which serialises the copy with the math.  The kernel orders
-// the copy itself: a vmcnt wait before the barrier that ends the step in which the copy was issued.
+// The patch travels by lds_dma16 (awseg_split.h: the hardware range check supplies the zero padding — no zero row for padding
+// pixels).  The kernel orders the copy itself: a vmcnt wait before the barrier that ends the step in which the copy was issued.
 // (Inline asm is only used where its operands come from / go to LDS and plain VALU results: hipcc pads MFMA-result
 // and transcendental-result use hazards only for instructions it emitted itself — see attn.hip.)
-__device__ __forceinline__ void bufdma16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds_base)
-{
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base) : "m0");
-}
 __device__ __forceinline__ void glds_wait() { asm volatile("s_waitcnt vmcnt(0)" : : : "memory"); }
 // the four youngest vector-memory operations (the next chunk's first weight fragments, issued after
 // the step's LDS-DMAs) may stay in flight across the barrier
 __device__ __forceinline__ void glds_wait_keep4() { asm volatile("s_waitcnt vmcnt(4)" : : : "memory"); }
-__device__ __forceinline__ uint32_t lds_addr(const float* p)
-{
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
 
-// two channels per lane as a 2-vector: a - b / a + b compile to ONE v_pk_add_f32.  fp32 MFMA runs at the
+// two channels per lane as a 2-vector (v2f): a - b / a + b compile to ONE v_pk_add_f32.  fp32 MFMA runs at the
 // vector rate — VALU instructions do not hide behind it, every one removed from the loop is MFMA time back.
-typedef float v2f __attribute__((ext_vector_type(2)));
 // (hipcc's pre-emit peephole splits v_pk_add_f32 back into two v_add_f32 when it sits behind an MFMA, assuming
 // the MFMA hides them; inline asm keeps the packed form.)
 __device__ __forceinline__ v2f pk_add(v2f a, v2f b)
@@ -188,7 +173,7 @@ void conv3x3_wino_kernel(wino_args a)
         const uint32_t soff = (uint32_t)((chunk < nchunks ? chunk : nchunks - 1) * KC * 4);
 #pragma unroll
         for (int i = 0; i < 3; ++i)
-            if (i < n_pinstr) bufdma16(x_rsrc, pvoff[i], soff, p_lds + (uint32_t)(buf * P_FLOATS * 4 + i * 4096));
+            if (i < n_pinstr) lds_dma16(x_rsrc, pvoff[i], soff, p_lds + (uint32_t)(buf * P_FLOATS * 4 + i * 4096));
     };
     // transform item of this thread: half hk = wave & 1 (channels 4*cp + 2*hk, +1 = k-steps 2cp, 2cp+1), tile =
     // 32*(wave>>1) + lane/2, cp = lane & 1; validity of its 4 x 4 pixels

@@ -27,18 +27,12 @@
 //   * transform item of a thread = (tile, 4 channels, one V row): one 16-byte read per patch pixel, float32 adds, split,
 //     ds_write_b64.
 // wino8s_kernel is one block per tile; wino8p_kernel the same block made persistent (launch_ws picks by map size).
-#include "awseg_common.h"
+// The split is split_unscaled_lds of awseg_split.h (V goes to LDS); the patches travel by lds_dma16_unfenced, see there.
+#include "awseg_split.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-constexpr int TB = 8;                      // 8 x 8 tiles per block
+constexpr int TB = 8;                     // 8 x 8 tiles per block
 constexpr int NTILE = TB * TB;             // 64
 constexpr int KC = 16;                     // input channels per chunk = one K step of v_mfma_f32_32x32x16_f16
 constexpr int NB = 64;                     // output channels per block
@@ -61,40 +55,7 @@ struct ws_args {
     const float* forms; int fh, fw;
 };
 
-// LDS-DMA of 16 bytes per lane through a buffer descriptor (see wino.hip: inline asm on purpose, hardware range check
-// supplies the zero padding)
-__device__ __forceinline__ void bufdma16(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, uint32_t lds_base)
-{
-    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" : : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_base) : "m0");
-}
 __device__ __forceinline__ void vm_wait_all() { asm volatile("s_waitcnt vmcnt(0)" : : : "memory"); }
-__device__ __forceinline__ uint32_t lds_addr(const void* p)
-{
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const void*)p;
-}
-
-// (a, b) -> packed f16 high parts and packed f16 low parts (a - f16(a), b - f16(b): exact in float32, then rounded to f16)
-// Three instructions: v_cvt_pkrtz_f16_f32, then one mixed-precision FMA per value — v_fma_mixlo/mixhi_f16 computes
-// x * 1.0 + (-hi) with the f16 source widened and the sum taken in float32 (exact: hi is x's leading bits), rounds it to f16
-// and writes one half of the destination.  (The plain form costs six: two v_cvt_f32_f16, two subtracts, a second pack.)
-__device__ __forceinline__ void split_pair(v2f v, unsigned& hi, unsigned& lo)
-{
-    hi = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y));
-    asm("v_fma_mixlo_f16 %0, %1, 1.0, -%3 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %0, %2, 1.0, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]"
-        : "=&v"(lo) : "v"(v.x), "v"(v.y), "v"(hi));
-}
-
-// the same split for values that go STRAIGHT into an MFMA operand register: a vector write needs two wait states before an MFMA
-// reads the register, and hipcc pads only instructions it emitted itself (gemm_split3.hip)
-__device__ __forceinline__ void split_pair_mfma(float x, float y, unsigned& hi, unsigned& lo)
-{
-    asm("v_cvt_pkrtz_f16_f32 %0, %2, %3\n\t"
-        "v_fma_mixlo_f16 %1, %2, 1.0, -%0 op_sel_hi:[0,0,1]\n\t"
-        "v_fma_mixhi_f16 %1, %3, 1.0, -%0 op_sel:[0,0,1] op_sel_hi:[0,0,1]\n\t"
-        "s_nop 1"
-        : "=&v"(hi), "=&v"(lo) : "v"(x), "v"(y));
-}
 
 #ifdef AWSEG_WS_STAMP
 // tools/probe_wino_stamps.hip: s_memtime stamps of block 0
@@ -104,15 +65,6 @@ __device__ unsigned long long g_w8_stamp[2][8];                       // [wave 0
 struct awseg_false { static constexpr bool value = false; };
 struct awseg_true { static constexpr bool value = true; };
 template <int N> struct awseg_int { static constexpr int value = N; };
-
-__device__ __forceinline__ float pow2f(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }   // -126 <= e <= 127
-
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ unsigned pack_bf16(v2f v)
-{
-    typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf2));
-}
 
 // MODE: 0 FULL (NHWC map out), 1 HEAD1 (fused 1x1 + sigmoid, Cout == 64).
 // BF16: the same kernel with ONE v_mfma_f32_32x32x16_bf16 per product tile (BASELINE config 5, the bf16 MFMA path): V is
@@ -224,9 +176,9 @@ void wino8s_kernel(ws_args a)
     auto glds_patch = [&](int chunk, int slot) {
         const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane((chunk < nchunks ? chunk : nchunks - 1) * KC * 4);
         const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p_lds + (uint32_t)(slot * P_BYTES)));
-        bufdma16(x_rsrc, pvoff[0], soff, base);
-        bufdma16(x_rsrc, pvoff[1], soff, base + 8192u);
-        if (three) bufdma16(x_rsrc, pvoff[2], soff, base + 16384u);
+        lds_dma16_unfenced(x_rsrc, pvoff[0], soff, base);
+        lds_dma16_unfenced(x_rsrc, pvoff[1], soff, base + 8192u);
+        if (three) lds_dma16_unfenced(x_rsrc, pvoff[2], soff, base + 16384u);
     };
     // s_waitcnt vmcnt(n + 2 | n + 3): everything but this wave's youngest n register loads and ONE patch's DMA instructions
     auto vm_wait_keep_patch_and = [&](auto NC) {
@@ -315,8 +267,8 @@ void wino8s_kernel(ws_args a)
                         *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
                         continue;
                     }
-                    split_pair(va, h, l); H[0] = h; L[0] = l;
-                    split_pair(vb, h, l); H[1] = h; L[1] = l;
+                    split_unscaled_lds(va.x, va.y, h, l); H[0] = h; L[0] = l;
+                    split_unscaled_lds(vb.x, vb.y, h, l); H[1] = h; L[1] = l;
                     *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
                     *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_lo) = L;
                 }
@@ -743,9 +695,9 @@ void wino8p_kernel(ws_args a)
     auto glds_patch_of = [&](const __amdgpu_buffer_rsrc_t& rsrc, const uint32_t (&pv)[3], int chunk, int slot) {
         const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane((chunk < nchunks ? chunk : nchunks - 1) * KC * 4);
         const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p_lds + (uint32_t)slot_off(slot)));
-        bufdma16(rsrc, pv[0], soff, base);
-        bufdma16(rsrc, pv[1], soff, base + 8192u);
-        if (three) bufdma16(rsrc, pv[2], soff, base + 16384u);
+        lds_dma16_unfenced(rsrc, pv[0], soff, base);
+        lds_dma16_unfenced(rsrc, pv[1], soff, base + 8192u);
+        if (three) lds_dma16_unfenced(rsrc, pv[2], soff, base + 16384u);
     };
     auto glds_patch = [&](int chunk, int slot) { glds_patch_of(x_rsrc, pvoff, chunk, slot); };
     // s_waitcnt vmcnt(n + 2 | n + 3): everything but this wave's youngest n register loads and ONE patch's DMA instructions
@@ -799,7 +751,7 @@ void wino8p_kernel(ws_args a)
         if (wave_u < 4) {
             const uint32_t soff = (uint32_t)__builtin_amdgcn_readfirstlane(chunk * KC * 4);
             const uint32_t base = (uint32_t)__builtin_amdgcn_readfirstlane((int)(p_lds + (uint32_t)(X_BYTES + (chunk % 3) * CF_BYTES)));
-            bufdma16(rsrc, cv, soff, base);
+            lds_dma16_unfenced(rsrc, cv, soff, base);
         }
     };
     // generator thread = (patch row r, position group pg, channel quad q): positions {0, 1, 8, 9, 16, 17}[pg] (the only ones that can
@@ -937,8 +889,8 @@ void wino8p_kernel(ws_args a)
                         *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
                         continue;
                     }
-                    split_pair(va, h, l); H[0] = h; L[0] = l;
-                    split_pair(vb, h, l); H[1] = h; L[1] = l;
+                    split_unscaled_lds(va.x, va.y, h, l); H[0] = h; L[0] = l;
+                    split_unscaled_lds(vb.x, vb.y, h, l); H[1] = h; L[1] = l;
                     *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_hi) = H;
                     *reinterpret_cast<u32x2*>(sV + (vr * 4 + j) * V_POS + vw_lo) = L;
                 }
