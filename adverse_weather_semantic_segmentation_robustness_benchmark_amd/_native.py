@@ -163,6 +163,8 @@ EXTENSION_SIGNATURES = {
     "awseg_weather_estimate_workspace": (c_i64, [c_i64]),
     "awseg_weather_estimate": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_p, c_p, c_p, c_p, c_i,
                                      c_p, c_p]),
+    "awseg_tta_view": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_i64, c_i64, c_i, c_p]),
+    "awseg_tta_accumulate": (c_i, [c_p, c_i64, c_i, c_i64, c_i64, c_p, c_i64, c_i64, c_i, c_f, c_i, c_p]),
 }
 
 

@@ -17,12 +17,12 @@ from pathlib import Path
 CSRC = Path(__file__).resolve().parent
 PKG = CSRC.parent
 LIB = PKG / "libawseg_hip.so"
-SOURCES = ["core.hip", "metrics.hip", "weather.hip", "loss.hip", "heads.hip", "backbone.hip", "depth.hip", "wino.hip", "gemm.hip", "attn.hip", "gemm_split.hip", "gemm_split3.hip", "wino_split.hip", "depthfuse.hip", "mixffn.hip", "dwtrain.hip", "bntrain.hip", "smallops.hip", "calib.hip", "consistency.hip", "deptheval.hip", "failure.hip", "boundary.hip", "bootstrap.hip", "strata.hip", "quality.hip", "segments.hip", "weightgrid.hip", "dehaze.hip", "dehaze_guided.hip", "relight.hip", "deocclude.hip", "estimate.hip"]
+SOURCES = ["core.hip", "metrics.hip", "weather.hip", "loss.hip", "heads.hip", "backbone.hip", "depth.hip", "wino.hip", "gemm.hip", "attn.hip", "gemm_split.hip", "gemm_split3.hip", "wino_split.hip", "depthfuse.hip", "mixffn.hip", "dwtrain.hip", "bntrain.hip", "smallops.hip", "calib.hip", "consistency.hip", "deptheval.hip", "failure.hip", "boundary.hip", "bootstrap.hip", "strata.hip", "quality.hip", "segments.hip", "weightgrid.hip", "dehaze.hip", "dehaze_guided.hip", "relight.hip", "deocclude.hip", "estimate.hip", "tta.hip"]
 ARCH = "gfx950"
 # per-file extras.  wino.hip: the SLP vectoriser packs the scalar inverse transform of the fused-head epilogue into
 # v_pk_add_f32 fed by ~220 v_mov (and spills); the kernel packs by hand where adjacent registers make it free.
 HEADER = PKG.parent / "include" / "awseg.h"
-RESTORE_HEADER = PKG.parent / "include" / "awseg_restore.h"     # the extension entry points (dehaze.hip, dehaze_guided.hip, relight.hip, deocclude.hip, estimate.hip), hashed on their own
+RESTORE_HEADER = PKG.parent / "include" / "awseg_restore.h"     # the extension entry points (dehaze.hip, dehaze_guided.hip, relight.hip, deocclude.hip, estimate.hip, tta.hip), hashed on their own
 
 
 def header_hash(path: Path = HEADER) -> int:

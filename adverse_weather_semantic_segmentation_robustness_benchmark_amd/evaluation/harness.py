@@ -33,7 +33,8 @@ from .metrics import (ConfidenceCalibration, ConfusionAccumulator, RobustnessMet
                       depth_metrics_from_stats,
                       failure_metrics_from_stats, iou_from_counts, guided_metrics_from_stats, quality_metrics_from_stats,
                       relight_metrics_from_stats, restoration_metrics_from_stats, restored_quality_metrics_from_stats,
-                      segment_metrics_from_stats, segment_options, severity_sweep_results, weight_grid_metrics_from_stats)
+                      segment_metrics_from_stats, segment_options, severity_sweep_results, tta_metrics_from_stats,
+                      weight_grid_metrics_from_stats)
 
 logger = logging.getLogger(__name__)
 
@@ -451,6 +452,84 @@ def restoration_option(config, images=None):
     return opt
 
 
+TTA_PRESETS = {"flip": {"scales": [1.0], "flip": True}, "ms_flip": {"scales": [0.5, 0.75, 1.0, 1.25, 1.5], "flip": True}}
+TTA_KEYS = ("scales", "flip")
+TTA_MAX_SCALES = 8
+TTA_SCALE_RANGE = (0.25, 2.0)
+TTA_GRID = 32                                  # a rescaled view's sides are multiples of this, at least two of them
+
+
+def tta_option(config):
+    """`evaluation.tta` (default off): test-time augmentation -- the members' logits averaged over mirrored and
+    rescaled views of every frame, scored a second time.  'flip': scales [1.0] with the mirrored view; 'ms_flip': scales 0.5, 0.75,
+    1.0, 1.25, 1.5, each also mirrored; or a dict with `scales` (1 .. 8 strictly increasing numbers in [0.25, 2]; 1.0 is added when
+    absent; default [1.0]) and `flip` (true or false, default true).  Any other key is refused by name.
+    -> None when absent, else {'scales': [...], 'flip': bool}."""
+    spec = _cfg(config, "evaluation.tta", None)
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        if spec not in TTA_PRESETS:
+            raise ValueError(f"evaluation.tta is {', '.join(map(repr, TTA_PRESETS))} or a dict with keys among {list(TTA_KEYS)}, got {spec!r}")
+        spec = TTA_PRESETS[spec]
+    if not isinstance(spec, dict):
+        raise ValueError(f"evaluation.tta is {', '.join(map(repr, TTA_PRESETS))} or a dict with keys among {list(TTA_KEYS)}, got {spec!r}")
+    unknown = sorted(str(k) for k in set(spec) - set(TTA_KEYS))
+    if unknown:
+        raise ValueError(f"evaluation.tta: unknown key{'s' if unknown[1:] else ''} {', '.join(map(repr, unknown))}; the keys are "
+                         f"{list(TTA_KEYS)}")
+    flip = spec.get("flip", True)
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError(f"evaluation.tta.flip is true or false, got {flip!r}")
+    scales = spec.get("scales", [1.0])
+    lo, hi = TTA_SCALE_RANGE
+    what = (f"evaluation.tta.scales is a list of 1 .. {TTA_MAX_SCALES} strictly increasing numbers in [{lo}, {hi}] (1.0 is added when "
+            f"absent), got {scales!r}")
+    if isinstance(scales, (bool, np.bool_, str, bytes, dict, int, float, np.number)):
+        raise ValueError(what)
+    try:
+        scales = list(scales)
+    except TypeError:
+        raise ValueError(what) from None
+    if not 1 <= len(scales) <= TTA_MAX_SCALES or any(
+            isinstance(v, (bool, np.bool_, str, bytes)) or not isinstance(v, (int, float, np.integer, np.floating))
+            or not lo <= float(v) <= hi for v in scales):                                  # (a NaN fails the comparison)
+        raise ValueError(what)
+    scales = [float(v) for v in scales]
+    if any(b <= a for a, b in zip(scales, scales[1:])):
+        raise ValueError(what)
+    if 1.0 not in scales:
+        scales = sorted(scales + [1.0])
+    if len(scales) == 1 and not flip:
+        raise ValueError("evaluation.tta: scales [1.0] without flip is the plain forward alone: nothing to average")
+    return {"scales": scales, "flip": bool(flip)}
+
+
+def tta_views(option) -> list:
+    """The extra views of an option in the order they run, [(scale, flip)]: ascending scale, unflipped before flipped.  View 0, the
+    plain forward (scale 1, no flip), is not among them: there are 1 + len(...) views in all."""
+    return [(s, f) for s in option["scales"] for f in ((False, True) if option["flip"] else (False,)) if not (s == 1.0 and not f)]
+
+
+def tta_view_size(height: int, width: int, scale: float) -> tuple:
+    """The size of a view: the frame's own at scale 1, else both sides 32 max(2, floor(side scale / 32 + 0.5))."""
+    if scale == 1.0:
+        return int(height), int(width)
+    return tuple(TTA_GRID * max(2, int(np.floor(side * scale / TTA_GRID + 0.5))) for side in (int(height), int(width)))
+
+
+def tta_view_sizes(option, height: int, width: int) -> list:
+    """[(scale, flip, (h, w))] of the extra views for frames of height x width.  Two scales that give one size are refused."""
+    by_size = {}
+    for s in option["scales"]:
+        size = tta_view_size(height, width, s)
+        if size in by_size:
+            raise ValueError(f"evaluation.tta: scales {by_size[size]} and {s} both give views of {size[0]} x {size[1]} pixels from "
+                             f"frames of {height} x {width}")
+        by_size[size] = s
+    return [(s, f, tta_view_size(height, width, s)) for s, f in tta_views(option)]
+
+
 BOOTSTRAP_MAX_REPLICATES = 65536
 
 
@@ -520,6 +599,8 @@ COUNTERS = (
     ("restoration_estimate", ("stats",), None, None, None),
     ("restored_quality", ("stats", "oob"), "terms", check_quality_budget, "a clean-frame row outside the buffer in the image-quality "
                                                                           "counters of the restored frames"),
+    ("tta", ("counts", "oob", "stats"), None, None, "label or prediction map value outside [0, num_classes) in the counters of the "
+                                                    "test-time augmentation"),
     ("bootstrap", ("table", "seen", "slot", "oob"), None, None, None),     # ranks fill disjoint rows: the sum is the union
     ("paired", ("stats", "oob", "sources"), None, None, "prediction map value outside [0, num_classes) in the consistency counters"),
 )
@@ -552,7 +633,8 @@ class EvalState:
 
     def __init__(self, metrics: RobustnessMetrics, conditions, device, num_bins: int = 15, ensemble: bool = False, *,
                  temperature_grid=None, calibration_condition: str = "clean", sweep=None, depth=None, failure: bool = False,
-                 boundary=None, bootstrap=None, change=None, quality=None, segments=None, weight_grid=None, restoration=None):
+                 boundary=None, bootstrap=None, change=None, quality=None, segments=None, weight_grid=None, restoration=None,
+                 tta=None):
         # paired severity sweep (data.loader.SeveritySweep): the condition slots are 'clean' and '<kind>_s<j>' instead of the
         # weather conditions; every counter below uses that one slot list
         self.sweep = sweep
@@ -692,6 +774,16 @@ class EvalState:
         if restoration is not None and self.quality is not None:
             self.restored_quality = {"terms": 0, "stats": ops.new_image_quality_stats(device, 1 + len(conditions)),
                                      "oob": torch.zeros(1, dtype=torch.int64, device=device)}
+        # test-time augmentation (off unless tta = tta_option(config)): a SECOND confusion accumulator over this run's
+        # slots for the view-averaged logits ('oob' is its word, and the consistency pass's), the consistency counters of the averaged
+        # prediction against the plain one (ops.new_consistency_stats), and one more uint8 prediction map ('pred', grow-only).
+        # 'sizes': the views of the frame size seen last
+        self.tta = None
+        if tta is not None:
+            acc = ConfusionAccumulator(metrics.num_classes, list(conditions), device)
+            self.tta = {"scales": [float(v) for v in tta["scales"]], "flip": bool(tta["flip"]), "views": 1 + len(tta_views(tta)),
+                        "acc": acc, "counts": acc.counts, "oob": acc.oob,
+                        "stats": ops.new_consistency_stats(metrics.num_classes, device, 1 + len(conditions)), "pred": None, "sizes": None}
         self.paired = None
         if sweep is not None:
             # clean prediction maps, one uint8 row per source whose clean frame has been seen and whose K x S variants have not all
@@ -923,6 +1015,41 @@ class EvalState:
             ops.combine_argmax_confusion(logits, None, 3, want_logits=False, label=labels.contiguous(), counts=rs["counts"],
                                          oob=rs["oob"], cond=cond)
 
+    def update_tta(self, model, images, labels, cond, members, plain_pred, num_classes: int) -> None:
+        """Test-time augmentation of this batch.  `members`: the plain forward's member logits (one map for a single
+        model), fresh tensors nothing reads any more: they are the accumulators, the first extra view folded in with
+        TTA_SCALE_ADD and the others with TTA_ADD, every view weighing float32(1) / float32(views).  The averaged logits go through
+        the model's own combine into the second accumulator and the TTA prediction map, which is counted against `plain_pred`."""
+        t = self.tta
+        check_frames("tta", images)
+        h, w = int(images.shape[2]), int(images.shape[3])
+        if t["sizes"] is None or t["sizes"][0] != (h, w):
+            t["sizes"] = ((h, w), tta_view_sizes(t, h, w))
+        weight = np.float32(1) / np.float32(t["views"])
+        members = [m if m.is_contiguous() else m.contiguous() for m in members]
+        images = images.contiguous()
+        ensemble = len(members) == 2
+        for i, (_, flip, size) in enumerate(t["sizes"][1]):
+            view = ops.tta_view(images, size, flip)
+            if ensemble:
+                out = model.forward_eval(view, want_logits=False, want_pred=False, want_depth=False, combine=False)
+                logits = [out["segformer_seg"], out["deeplabv3plus_seg"]]
+            else:
+                logits = [model(view)["segmentation"].float()]
+            for l, acc in zip(logits, members):
+                ops.tta_accumulate(l.contiguous(), acc, flip, weight, ops.TTA_SCALE_ADD if i == 0 else ops.TTA_ADD)
+        t["pred"] = _grown(t["pred"], plain_pred.numel(), images.device)
+        pred = t["pred"][:plain_pred.numel()].view(plain_pred.shape)
+        if ensemble:
+            mode, w_, T = model.combine_arguments()
+            ops.combine_argmax_confusion(members[0], members[1], mode, w_, T, want_logits=False, label=labels.contiguous(),
+                                         counts=t["counts"], oob=t["oob"], cond=cond, pred_out=pred)
+        else:
+            ops.combine_argmax_confusion(members[0], None, 3, want_logits=False, label=labels.contiguous(), counts=t["counts"],
+                                         oob=t["oob"], cond=cond, pred_out=pred)
+        rows = torch.arange(images.shape[0], dtype=torch.int32, device=images.device)
+        ops.prediction_consistency(pred, plain_pred, rows, labels, num_classes, t["stats"], t["oob"], cond)
+
     def update_change(self, images, pred, labels, frame_ref, cond, num_classes: int) -> None:
         """A variant batch is split into change strata against its sources' clean frames and counted against their clean maps.
         Runs before update_consistency releases the rows."""
@@ -1088,7 +1215,7 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         sources = [int(s) for s in sources]
         if len(sources) != images.shape[0]:
             raise ValueError(f"{len(sources)} sources for a batch of {images.shape[0]} frames")
-    if pred_out is None and (bd is not None or bs is not None or sg is not None):
+    if pred_out is None and (bd is not None or bs is not None or sg is not None or st.tta is not None):
         pred_out = st.pred_map((images.shape[0],) + tuple(images.shape[2:]), images.device)
     cond = st.acc.cond_ids(conds)
     depth_kw = {}
@@ -1175,6 +1302,9 @@ def eval_batch(model, st: EvalState, images: torch.Tensor, labels: torch.Tensor,
         st.update_consistency(pred_out, labels, sources, rows, cond, metrics.num_classes)
     if st.restoration is not None:                                    # after everything above: one more forward, on the dehazed frames
         st.update_restoration(model, images, labels, kinds, cond, rows)
+    if st.tta is not None:                                            # last: the plain member logits become the accumulators
+        members = [res["segformer_seg"], res["deeplabv3plus_seg"]] if st.auroc is not None else [logits]
+        st.update_tta(model, images, labels, cond, members, pred_out, metrics.num_classes)
     st.samples += images.size(0)
 
 
@@ -1203,7 +1333,8 @@ def evaluate_model(model: torch.nn.Module, test_loader, metrics: RobustnessMetri
                    depth=depth_options(config), failure=failure_option(config),
                    boundary=boundary_option(config), bootstrap=bootstrap, change=change_option(config),
                    quality=quality_options(config), segments=segment_option(config),
-                   weight_grid=weight_grid_option(config, model), restoration=restoration_option(config))
+                   weight_grid=weight_grid_option(config, model), restoration=restoration_option(config),
+                   tta=tta_option(config))
     for batch in test_loader:
         images = batch["image"].to(device)
         labels = batch["label"].to(device)
@@ -1301,6 +1432,12 @@ def finalize(st: EvalState, metrics: RobustnessMetrics) -> Dict[str, Any]:
         if st.restored_quality is not None:
             results.update(restored_quality_metrics_from_stats(st.restored_quality["stats"].cpu().numpy(), q["stats"].cpu().numpy(),
                                                                st.acc.conditions, st.sweep.kinds, st.sweep.levels))
+    if st.tta is not None:
+        t = st.tta
+        results.update(tta_metrics_from_stats(t["counts"].cpu().numpy(), st.acc.counts.cpu().numpy(), t["stats"].cpu().numpy(),
+                                              st.acc.conditions, metrics.num_classes, **sweep_kw,
+                                              degradation=metrics.compute_robustness_degradation_ratio, views=t["views"],
+                                              scales=t["scales"], flip=t["flip"]))
     if "clean" in weather_mious:
         for w in ("fog", "rain", "snow", "night"):
             if w in weather_mious:

@@ -827,6 +827,75 @@ def restoration_metrics_from_stats(restored, plain, stats, conditions: List[str]
     return res
 
 
+def tta_metrics_from_stats(tta_counts, plain_counts, consistency, conditions: List[str], num_classes: int, kinds=None, levels: int = 0,
+                           degradation=None, views=None, scales=None, flip=None) -> Dict[str, Any]:
+    """Result keys of the test-time augmentation.  `tta_counts`, `plain_counts`: the confusion counters int64
+    [1 + len(conditions), C * C] of the view-averaged prediction and of the plain one; `consistency`: int64 [1 + len(conditions),
+    C * C + 4] (ops.new_consistency_stats), the agreement matrix A[plain class, TTA class] over all pixels and the four transition
+    counts over the labelled ones (both right, plain right + TTA wrong, plain wrong + TTA right, both wrong); slot 0 = every frame,
+    slot 1 + k = conditions[k].  Host only, float64 on exact integer sums.  With <n> a condition (under a severity sweep its slots
+    'clean', '<kind>_s<j>', and each '<kind>' from the summed counters of its levels), for every <n> with frames:
+      miou_<n>_tta                       mIoU of the averaged prediction, as miou_<n> is of the plain one
+      tta_gain_<n>                       miou_<n>_tta - miou_<n> on the same frames; not clamped: a loss is negative
+      robustness_degradation_<n>_tta     degradation(miou_clean_tta, miou_<n>_tta), <n> != clean
+      tta_changed_fraction_<n>           1 - trace(A) / sum(A): the share of the pixels whose class the averaging changed
+      tta_fixed_fraction_<n>             plain wrong and TTA right, over the labelled pixels
+      tta_broken_fraction_<n>            plain right and TTA wrong, over the labelled pixels
+    over slot 0: overall_miou_tta, mean_tta_gain (against the plain counters summed over the conditions that have frames),
+    mean_tta_changed_fraction; and, when given, tta_views (float), tta_scales (a list of floats), tta_flip (1.0 or 0.0).
+    A ratio without a denominator is absent, not 0.  degradation: RobustnessMetrics.compute_robustness_degradation_ratio unless
+    given."""
+    conditions, C = list(conditions), int(num_classes)
+    n = 1 + len(conditions)
+    arrays = {}
+    for what, a, width in (("tta", tta_counts, C * C), ("plain", plain_counts, C * C), ("consistency", consistency, C * C + 4)):
+        a = np.asarray(a.cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.int64)
+        if a.shape != (n, width):
+            raise ValueError(f"{what} counters must be int64 [{n}, {width}], got {a.shape}")
+        arrays[what] = a
+    degradation = degradation or RobustnessMetrics().compute_robustness_degradation_ratio
+
+    def miou(counts) -> Optional[float]:
+        return float(iou_from_counts(torch.from_numpy(counts.copy()), C)["mean_iou"]) if counts.sum() > 0 else None
+
+    named = [(name, [1 + k]) for k, name in enumerate(conditions)]
+    for kind in (kinds or []):
+        named.append((kind, [1 + conditions.index(f"{kind}_s{j}") for j in range(1, int(levels) + 1)]))
+    res: Dict[str, Any] = {}
+    same_frames = np.zeros(C * C, dtype=np.int64)                           # plain counters of the conditions that have TTA frames
+    rows = [(None, arrays["tta"][0], None, arrays["consistency"][0])]
+    for name, idx in named:
+        rows.append((name, arrays["tta"][idx].sum(0), arrays["plain"][idx].sum(0), arrays["consistency"][idx].sum(0)))
+        if len(idx) == 1 and arrays["tta"][idx[0]].sum() > 0:
+            same_frames += arrays["plain"][idx[0]]
+    mious = {}
+    for name, t_counts, p_counts, row in rows:
+        t = miou(t_counts)
+        if t is not None:
+            mious[name] = t
+            res["overall_miou_tta" if name is None else f"miou_{name}_tta"] = t
+            p = miou(same_frames if name is None else p_counts)
+            if p is not None:
+                res["mean_tta_gain" if name is None else f"tta_gain_{name}"] = t - p
+        agreement, transitions = row[:C * C].reshape(C, C), row[C * C:]
+        pixels, labelled = int(agreement.sum()), int(transitions.sum())
+        if pixels > 0:
+            res["mean_tta_changed_fraction" if name is None else f"tta_changed_fraction_{name}"] = 1.0 - float(np.trace(agreement)) / pixels
+        if labelled > 0 and name is not None:
+            res[f"tta_fixed_fraction_{name}"] = float(transitions[2]) / labelled
+            res[f"tta_broken_fraction_{name}"] = float(transitions[1]) / labelled
+    for name, t in mious.items():
+        if name is not None and name != "clean" and "clean" in mious:
+            res[f"robustness_degradation_{name}_tta"] = float(degradation(mious["clean"], t))
+    if views is not None:
+        res["tta_views"] = float(views)
+    if scales is not None:
+        res["tta_scales"] = [float(s) for s in scales]
+    if flip is not None:
+        res["tta_flip"] = float(bool(flip))
+    return res
+
+
 def guided_metrics_from_stats(stats, conditions: List[str], kinds=None, levels: int = 0) -> Dict[str, float]:
     """Result keys of the guided-filter refinement from its counters int64 [1 + len(conditions),
     AWSEG_GUIDED_ROW] (include/awseg_restore.h; slot 0 = every restored frame, slot 1 + k = conditions[k]).  Host only, float64 on

@@ -60,9 +60,37 @@ def report_markdown(results: Dict[str, Any], target_metrics: Optional[Dict[str, 
         lines += quality_section(results)
     if "overall_miou_restored" in results:
         lines += restoration_section(results)
+    if "overall_miou_tta" in results:
+        lines += tta_section(results)
     if "bootstrap_replicates" in results:
         lines += bootstrap_section(results)
     return "\n".join(lines)
+
+
+def tta_section(results: Dict[str, Any]) -> list:
+    """Test-time augmentation (evaluation.tta): one line per condition with the mIoU of the plain forward, of the logits averaged
+    over the views, the difference, the share of the pixels whose class the averaging changed, and the shares of the labelled
+    pixels it set right and set wrong."""
+    names = [m.group(1) for k in results for m in [re.match(r"miou_(.+)_tta$", k)] if m]
+
+    def cell(key):
+        return f"{results[key]:.3f}" if key in results else "-"
+    scales = results.get("tta_scales")
+    how = f"{int(results['tta_views'])} views" if "tta_views" in results else "several views"
+    if scales is not None:
+        how += " (scales " + ", ".join(f"{s:g}" for s in scales) + (", each also mirrored left to right" if results.get("tta_flip") else "") + ")"
+    lines = ["", "## Test-Time Augmentation", "",
+             f"Every member's logits averaged over {how} of the same frame, mirrored back and resampled to the frame, then combined "
+             "and scored again (DESIGN.md 10r).  Gain: TTA - plain mIoU on the same frames (negative: the views cost accuracy); "
+             "changed: share of the pixels whose class the averaging changed; fixed / broken: share of the labelled pixels it set "
+             "right / set wrong.", "",
+             "| Condition | Plain mIoU | TTA mIoU | Gain | Changed | Fixed | Broken |", "|---|---|---|---|---|---|---|"]
+    for n in names:
+        lines.append(f"| {n} | {cell(f'miou_{n}')} | {cell(f'miou_{n}_tta')} | {cell(f'tta_gain_{n}')} | "
+                     f"{cell(f'tta_changed_fraction_{n}')} | {cell(f'tta_fixed_fraction_{n}')} | {cell(f'tta_broken_fraction_{n}')} |")
+    lines.append(f"| all | {cell('overall_miou')} | {cell('overall_miou_tta')} | {cell('mean_tta_gain')} | "
+                 f"{cell('mean_tta_changed_fraction')} | - | - |")
+    return lines
 
 
 def restoration_section(results: Dict[str, Any]) -> list:

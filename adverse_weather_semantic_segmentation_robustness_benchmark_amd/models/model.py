@@ -392,7 +392,7 @@ class EnsembleModel(nn.Module):
     def forward_eval(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
                      oob: Optional[torch.Tensor] = None, cond: Optional[torch.Tensor] = None, want_logits: bool = True,
                      want_pred: bool = True, pred_dtype=torch.int64, stats=None, pred_out: Optional[torch.Tensor] = None,
-                     depth_stats=None, want_depth: bool = True) -> Dict[str, torch.Tensor]:
+                     depth_stats=None, want_depth: bool = True, combine: bool = True) -> Dict[str, torch.Tensor]:
         """members -> ONE pass: combine, /temperature, argmax, confusion (slots: overall + condition).
         stats = (edges, ece_bins, auroc_hist, lo, hi): also accumulate the calibration / disagreement statistics in that pass
         when nothing per-pixel is asked for (`self._stats_fused` tells the caller whether it happened).
@@ -400,7 +400,9 @@ class EnsembleModel(nn.Module):
         member logits), else by the combine kernel; it is also returned as res['prediction'].
         depth_stats = (target [B, H, W], cond, stats, min_depth): the depth error sums of the ensemble and of both members against
         `target` are added to `stats` (ops.new_depth_eval_stats) in one pass over the SegFormer map and DeepLab's stride-16 map.
-        want_depth=False: the upsampled and the combined depth map are not written and no depth key is returned."""
+        want_depth=False: the upsampled and the combined depth map are not written and no depth key is returned.
+        combine=False: the members run and nothing else; only their full-resolution logits are returned (the views of the
+        harness's test-time augmentation, which combines their average itself: combine_arguments)."""
         if depth_stats is not None and not self.include_depth:
             raise ValueError("depth_stats needs a model with depth heads (include_depth)")
         # (no channels-last copy of the frames here: both 7x7 stems read the zero-padded 4-channel image that fused._stem_rows builds
@@ -433,12 +435,9 @@ class EnsembleModel(nn.Module):
                     o2 = self.deeplabv3plus(x)
         finally:
             self.deeplabv3plus._defer_depth_upsample = False
-        mode = _STRATEGY.get(self.ensemble_strategy, N.COMBINE_MEAN)
-        # (softmax of the two ensemble weights: once per value of the parameter, not once per use — the combine and the depth combine
-        # of every eval step read the same two floats)
-        w = fused.cached(self, "ens_softmax", [self.ensemble_weights], lambda: F.softmax(self.ensemble_weights, dim=0)) \
-            if mode == N.COMBINE_WEIGHTED else None
-        T = self.temperature if self.temperature_scaling else None
+        if not combine:
+            return {"segformer_seg": o1["segmentation"], "deeplabv3plus_seg": o2["segmentation"]}
+        mode, w, T = self.combine_arguments()
         if (stats is not None and not want_logits and not want_pred and labels is not None and counts is not None
                 and mode in (N.COMBINE_WEIGHTED, N.COMBINE_MEAN) and o1["segmentation"].shape[1] == 19
                 and o1["segmentation"][0, 0].numel() % 4 == 0):
@@ -472,6 +471,15 @@ class EnsembleModel(nn.Module):
             else:
                 res.update(self._combine_depth(o1["depth"], o2["depth"]))
         return res
+
+    def combine_arguments(self):
+        """(mode, softmaxed weights or None, temperature or None): what forward_eval hands the combine kernels."""
+        mode = _STRATEGY.get(self.ensemble_strategy, N.COMBINE_MEAN)
+        # (softmax of the two ensemble weights: once per value of the parameter, not once per use — the combine and the depth combine
+        # of every eval step read the same two floats)
+        w = fused.cached(self, "ens_softmax", [self.ensemble_weights], lambda: F.softmax(self.ensemble_weights, dim=0)) \
+            if mode == N.COMBINE_WEIGHTED else None
+        return mode, w, self.temperature if self.temperature_scaling else None
 
     def _side_stream(self, device):
         key = str(device)                                           # (module-level: a Stream on the module would break copy.deepcopy(model))

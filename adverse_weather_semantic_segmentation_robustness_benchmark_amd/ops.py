@@ -984,6 +984,71 @@ def weather_estimate(image: torch.Tensor, stats: Optional[torch.Tensor] = None, 
     return route, descriptors
 
 
+# ------------------------------------------------ test-time augmentation: views and their average (include/awseg_restore.h)
+TTA_SET, TTA_ADD, TTA_SCALE_ADD = 0, 1, 2      # AWSEG_TTA_SET, AWSEG_TTA_ADD, AWSEG_TTA_SCALE_ADD
+TTA_MODES = {"set": TTA_SET, "add": TTA_ADD, "scale_add": TTA_SCALE_ADD}
+TTA_VIEW_MAX_CHANNELS = 4                      # AWSEG_TTA_VIEW_MAX_CHANNELS
+
+
+def _tta_map(who: str, name: str, t) -> torch.Tensor:
+    if not torch.is_tensor(t) or t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous() or min(t.shape) < 1:
+        got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else repr(t)
+        raise ValueError(f"{who}: {name} is a contiguous float32 [B, C, H, W] tensor of at least one element, got {got}")
+    return t
+
+
+def tta_view(images: torch.Tensor, size, flip: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A view of the frames for test-time augmentation: float32 `images` [B, C <= 4, H, W] resampled bilinearly (align_corners =
+    False) to `size` = (h, w) and then mirrored left to right when `flip`, in the float32 arithmetic include/awseg_restore.h
+    states step by step -> float32 [B, C, h, w].  At the frames' own size the values are copied bit for bit.  `out`: where the
+    view goes (contiguous, not `images`).  There is no CPU path."""
+    images = _tta_map("tta_view", "images", images)
+    b, c, H, W = (int(d) for d in images.shape)
+    if c > TTA_VIEW_MAX_CHANNELS:
+        raise ValueError(f"tta_view: frames of 1 .. {TTA_VIEW_MAX_CHANNELS} channels, got {c}")
+    try:
+        h, w = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"tta_view: size is (height, width), got {size!r}") from None
+    if h < 1 or w < 1:
+        raise ValueError(f"tta_view: size is at least 1 x 1, got {size!r}")
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError(f"tta_view: flip is true or false, got {flip!r}")
+    if out is None:
+        out = torch.empty(b, c, h, w, dtype=torch.float32, device=images.device)
+    out = _tta_map("tta_view", "out", out)
+    if tuple(out.shape) != (b, c, h, w) or out.device != images.device or out.data_ptr() == images.data_ptr():
+        raise ValueError(f"tta_view: out is float32 {(b, c, h, w)} on {images.device} and not the input, got {tuple(out.shape)}")
+    N.call("awseg_tta_view", N.ptr(images), b, c, H, W, N.ptr(out), h, w, int(flip), N.stream())
+    return out
+
+
+def tta_accumulate(logits: torch.Tensor, acc: torch.Tensor, flip: bool, weight: float, mode="add") -> torch.Tensor:
+    """Fold a view's float32 `logits` [B, C, h, w] into the running average `acc` [B, C, H, W], in place: the logits are mirrored
+    back when `flip`, resampled bilinearly (align_corners = False) to the frame's size, multiplied by `weight` and, by `mode`
+    ('set' / TTA_SET: acc = weight U; 'add' / TTA_ADD: acc += weight U; 'scale_add' / TTA_SCALE_ADD: acc = weight acc + weight U)
+    written or added, in the float32 arithmetic include/awseg_restore.h states step by step -> acc.  There is no CPU path."""
+    logits, acc = _tta_map("tta_accumulate", "logits", logits), _tta_map("tta_accumulate", "acc", acc)
+    if tuple(acc.shape[:2]) != tuple(logits.shape[:2]) or acc.device != logits.device:
+        raise ValueError(f"tta_accumulate: logits {tuple(logits.shape)} and acc {tuple(acc.shape)} share batch, channels and device")
+    if acc.data_ptr() == logits.data_ptr():
+        raise ValueError("tta_accumulate: acc must not be the logits")
+    if not isinstance(flip, (bool, np.bool_)):
+        raise ValueError(f"tta_accumulate: flip is true or false, got {flip!r}")
+    m = TTA_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)) or int(m) not in TTA_MODES.values():
+        raise ValueError(f"tta_accumulate: mode is one of {sorted(TTA_MODES)} (TTA_SET, TTA_ADD, TTA_SCALE_ADD), got {mode!r}")
+    with np.errstate(over="ignore"):
+        finite = not isinstance(weight, (bool, np.bool_, str)) and isinstance(weight, (int, float, np.integer, np.floating)) \
+            and bool(np.isfinite(np.float32(weight)))
+    if not finite:
+        raise ValueError(f"tta_accumulate: weight is a finite float32 number, got {weight!r}")
+    b, c, h, w = (int(d) for d in logits.shape)
+    N.call("awseg_tta_accumulate", N.ptr(logits), b, c, h, w, N.ptr(acc), int(acc.shape[2]), int(acc.shape[3]), int(flip),
+           float(np.float32(weight)), int(m), N.stream())
+    return acc
+
+
 ECE_CONF_UNIT = 2.0 ** -30    # the device keeps the confidence sums in fixed point (int64, units of 2^-30): exact, order-independent
 
 

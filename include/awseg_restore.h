@@ -290,6 +290,48 @@ int awseg_weather_estimate(const float* image, int64_t batch, int channels, int6
                            int32_t* route /* [B] */, float* descriptors /* [B][AWSEG_ESTIMATE_DESCRIPTORS] */,
                            int64_t* stats /* [n_slots][AWSEG_ESTIMATE_ROW] */, int n_slots, void* workspace, awseg_stream_t stream);
 
+/* ------------------------------------------------------------------------- *
+ *  Test-time augmentation: the two steps between the forwards of a prediction averaged over mirrored and rescaled views of the
+ *  same frames ("ms+flip")
+ *       replaces nothing: the reference evaluates one view
+ * ------------------------------------------------------------------------- *
+ * Both work on planar float32 maps, source [B, C, h, w] and destination [B, C, H, W], and sample bilinearly with
+ * align_corners = False.  Every step is one float32 operation in the order written, no contraction, so numpy float32 gives the same
+ * bits (this is NOT the fmaf form of awseg_upsample_bilinear, which is pinned to torch's build):
+ *     sy = (float) h / (float) H,  sx = (float) w / (float) W                 (on the host)
+ *     f   = fmaxf(sy * ((float) y + 0.5f) - 0.5f, 0)                          (add, multiply, subtract, max)
+ *     y0  = min((int) f, h - 1);   y1 = y0 + (y0 < h - 1);   ly1 = f - (float) y0;   ly0 = 1.0f - ly1          (columns likewise)
+ *     top = lx0 * v00 + lx1 * v01;   bot = lx0 * v10 + lx1 * v11;   U = ly0 * top + ly1 * bot      (products, then the sum)
+ * with v_ij the source value at (y_i, x_j).  A product whose weight is exactly 0 is replaced by +0.0f: a neighbour that is not
+ * finite and takes no part (the second tap where f is whole, as at the first row and column) does not turn the pixel into NaN.  When
+ * h == H and w == W, U is the source value itself, bit for bit, with no blend at all (so one inf in gives one inf out, and -0 stays).
+ *
+ * awseg_tta_view: dst[b,c,y,x] = U(y, flip ? W - 1 - x : x) of src: the frames resampled to (H, W), then mirrored.  channels in
+ * [1, AWSEG_TTA_VIEW_MAX_CHANNELS].
+ * awseg_tta_accumulate: U(y, x) is the sample at the frame pixel (y, x) of the map L'[r, c] = src[b, ch, r, flip ? w - 1 - c : c]:
+ * the view's logits are mirrored back FIRST and resampled then, interpolate(flip(L)) and not flip(interpolate(L)), which differ in
+ * bits.  Then, each product and each sum rounded on its own:
+ *     AWSEG_TTA_SET        acc = weight * U
+ *     AWSEG_TTA_ADD        acc = acc + weight * U
+ *     AWSEG_TTA_SCALE_ADD  acc = weight * acc + weight * U      (the first extra view folded into the plain logits in place)
+ * One streaming kernel: a lane owns four consecutive destination pixels of a row; 16-byte loads and stores of the destination when
+ * W % 4 == 0 and it is 16-byte aligned, and at equal size of the source too when that is aligned (a mirrored group is one 16-byte
+ * load with its components reversed); scalar accesses otherwise, the same bits either way.  The grid is capped and strided.  No
+ * workspace, no LDS.
+ * AWSEG_EINVAL for a NULL pointer, a size below 1 (batch and channels included), more view channels than
+ * AWSEG_TTA_VIEW_MAX_CHANNELS, flip other than 0 or 1, an unknown mode, a weight that is not finite, or src == dst / src == acc;
+ * AWSEG_EALIGN for a pointer that is not 4-byte aligned (16-byte accesses are used only where the pointers allow them);
+ * AWSEG_ERANGE for a plane of 2^31 pixels or more, or B * C * H * ceil(W / 4) >= 2^31.  Refusals come before any launch. */
+#define AWSEG_TTA_SET                0
+#define AWSEG_TTA_ADD                1
+#define AWSEG_TTA_SCALE_ADD          2
+#define AWSEG_TTA_VIEW_MAX_CHANNELS  4
+int awseg_tta_view(const float* src, int64_t batch, int channels, int64_t src_height, int64_t src_width,
+                   float* dst /* [B,C,height,width] */, int64_t height, int64_t width, int flip, awseg_stream_t stream);
+int awseg_tta_accumulate(const float* src, int64_t batch, int channels, int64_t src_height, int64_t src_width,
+                         float* acc /* [B,C,height,width] */, int64_t height, int64_t width, int flip, float weight, int mode,
+                         awseg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -135,6 +135,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--image-quality-targets", type=str, default=None, metavar="SSIM",
                     help="the SSIM values the mIoU is interpolated at: 1-8 comma-separated numbers in (0, 1), default 0.9,0.75,0.5 "
                          "(sets evaluation.image_quality_targets)")
+    ap.add_argument("--tta", type=str, default=None, choices=("flip", "ms_flip"),
+                    help="test-time augmentation: score the logits averaged over views of every frame a second time; flip: the "
+                         "mirrored view, ms_flip: scales 0.5, 0.75, 1, 1.25, 1.5, each also mirrored (sets evaluation.tta)")
+    ap.add_argument("--tta-scales", type=str, default=None, metavar="A,B,C",
+                    help="the scales of the views, 1 .. 8 increasing numbers in [0.25, 2]; 1 is added when absent (sets "
+                         "evaluation.tta.scales)")
+    ap.add_argument("--tta-no-flip", action="store_true", help="no mirrored views (sets evaluation.tta.flip: false)")
     ap.add_argument("--restoration", type=str, default=None, choices=("dark_channel", "clahe", "tophat", "auto"),
                     help="restore every frame in front of the model and score it a second time: plain and restored mIoU and the gain "
                          "per condition.  dark_channel: dehazing by the dark-channel prior (with the mean transmission); clahe: night "
@@ -232,6 +239,33 @@ RESTORATION_FLAGS = {
 }
 
 
+def parse_tta_scales(text: str):
+    """--tta-scales: comma-separated numbers (the harness checks their range and order)."""
+    try:
+        return [float(v) for v in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--tta-scales takes comma-separated numbers such as 0.5,1,1.5, got {text!r}") from None
+
+
+def apply_tta_options(args, config) -> None:
+    """--tta, --tta-scales and --tta-no-flip into `evaluation.tta` (the harness checks it)."""
+    if args.tta is None and args.tta_scales is None:
+        if args.tta_no_flip:
+            raise ValueError("--tta-no-flip needs --tta-scales: without the mirrored view and without other scales nothing is averaged")
+        return
+    if args.tta is not None and args.tta_scales is None and not args.tta_no_flip:
+        config.set("evaluation.tta", args.tta)
+        return
+    if args.tta == "flip" and args.tta_no_flip:
+        raise ValueError("--tta flip with --tta-no-flip: nothing is averaged")
+    spec = {"flip": not args.tta_no_flip}
+    if args.tta_scales is not None:
+        spec["scales"] = parse_tta_scales(args.tta_scales)
+    elif args.tta == "ms_flip":
+        spec["scales"] = [0.5, 0.75, 1.0, 1.25, 1.5]
+    config.set("evaluation.tta", spec)
+
+
 def apply_restoration_options(args, config) -> None:
     """--restoration / --restoration-conditions and the flags of RESTORATION_FLAGS into the configuration (the harness checks them)."""
     method, option = args.restoration, lambda flag: f"--restoration-{flag.replace('_', '-')}"      # noqa: E731
@@ -299,6 +333,7 @@ def main():
             config.set("evaluation.image_quality_targets", parse_image_quality_targets(args.image_quality_targets))
         apply_bootstrap_options(args, config)
         apply_restoration_options(args, config)
+        apply_tta_options(args, config)
         sev = config.get("evaluation.severities")
         paired = {"weather_schedule": "paired", "severities": sev} if sev is not None else {}
         ds = CityscapesKITTIDataset(data_root=config.get("data.data_root", "data"), split="test",

@@ -429,6 +429,27 @@ def main():
     cases["dwconv3x3_upcat (decoder: up x4 + cat + depthwise)"] = (lambda: ops.dwconv3x3_upcat(a_lo, hi48, w304), "hbm",
                                                                    4.0 * B * ((H // 16) * (W // 16) * 256 + (H // 4) * (W // 4) * (48 + 304)))
 
+    # test-time augmentation (evaluation.tta): the view of the frames and the fold of a view's logits into the running
+    # average, one streaming kernel each.  Bytes: what has to move once (the source read, the destination written, and read too by
+    # the fold).  Each row next to the torch composition it replaces on the same tensors, which makes three passes and two
+    # temporaries of the destination's size.  Scale 1 with flip is the 16-byte mirrored copy; 0.5x logits go up (every source value
+    # is read by about four pixels, through the cache); 1.5x logits come down (2.25 source values per pixel, most of them skipped)
+    interp = torch.nn.functional.interpolate
+    tta_frames = torch.randn(B, 3, H, W, device=dev)
+    tta_w = float(np.float32(1) / np.float32(4))
+    for tag, (vh, vw) in (("scale 1 flip", (H, W)), ("0.5x", (H // 2, W // 2)), ("1.5x", (H * 3 // 2, W * 3 // 2))):
+        tta_out = torch.empty(B, 3, vh, vw, device=dev)
+        cases[f"tta view {tag} ({vh}x{vw}, 3 ch)"] = (lambda vh=vh, vw=vw, o=tta_out: ops.tta_view(tta_frames, (vh, vw), True, out=o),
+                                                        "hbm", 4.0 * 3 * B * (px + vh * vw))
+        cases[f"tta view {tag} [torch interpolate + flip]"] = (
+            lambda vh=vh, vw=vw: interp(tta_frames, size=(vh, vw), mode="bilinear", align_corners=False).flip(-1), "hbm", 4.0 * 3 * B * (px + vh * vw))
+        tta_l = s2 if (vh, vw) == (H, W) else torch.randn(B, C, vh, vw, device=dev)
+        cases[f"tta accumulate {tag} logits ({vh}x{vw} -> {H}x{W}, {C} ch, ADD)"] = (
+            lambda l=tta_l: ops.tta_accumulate(l, s1, True, tta_w, ops.TTA_ADD), "hbm", 4.0 * C * B * (2 * px + vh * vw))
+        cases[f"tta accumulate {tag} logits [torch flip + interpolate + add_]"] = (
+            lambda l=tta_l: s1.add_(interp(l.flip(-1), size=(H, W), mode="bilinear", align_corners=False), alpha=tta_w),
+            "hbm", 4.0 * C * B * (2 * px + vh * vw))
+
     only = [s for s in a.only.split(",") if s]
     rows = []
     for name, (fn, bound, work) in cases.items():
